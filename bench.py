@@ -12,7 +12,12 @@ rank verifies its own batch (independent e-mails: weak scaling, no data-path col
 per-e-mail witnesses (status + the two output hashes, 72 B) of every step are all-gathered over RCCL at the end of the
 timed region when N > 1.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` (the hash / modexp launch —
+A plain run sets up, warms up, times the K steps, writes the last timed step's records if `--dump-outputs DIR` is given
+(DIR/<field>.npy, float64 for the 32-bit words, float32 for the byte arrays) and prints ONE JSON line on rank 0 with the
+headline figure (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) and the run's configuration.
+
+With `--full` the line also carries what takes runs or checks of its own: the records of the timed steps checked against
+what the signer expects, `roofline` (the hash / modexp launch —
 SHA-256 groups beside the RSA roles — HIP-event timed on its slot's stream, with S batches in flight as in the timed
 region; the figures of a batch alone and of the timed region as a whole beside it; the instruction-issue bound that
 actually binds the step beside the HBM fraction the metric asks for), `end_to_end` (the same workload from pageable host
@@ -56,6 +61,12 @@ def parse_args():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): every rank verifies its own batch of the configured size.  strong: ONE batch of the "
                          "configured size, sharded by cumulative bytes over the ranks (ShardedVerifier)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: check the timed steps' records, per-kernel timings and the roofline, the "
+                         "chip-filling SHA-256 launches, the end-to-end and latency legs and the CPU baseline (the --no-* options "
+                         "below and --alone-steps / --cpu-seconds shape these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last timed step (rank 0) as DIR/<field>.npy")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (host-memory entry) and single-e-mail latency legs")
     ap.add_argument("--host-threads", type=int, default=0,
                     help="threads that pack host-entry batches into pinned memory (zke_options.host_threads); 0 = the engine's default (4)")
@@ -325,6 +336,35 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
+    # ---- what the last timed step computed, before any later step reuses its slice
+    if args.dump_outputs and rank == 0:
+        last = (counter[0] - 1) % n_slices
+        arrays = record_arrays(results_all[last * rec_bytes:(last + 1) * rec_bytes].cpu().numpy().view(A.RESULT_DTYPE))
+        if use_dist and last < g_steps:
+            # the witnesses every rank received from the end-of-region all-gather, this step's of each rank: [e-mail, rank]
+            wit = gathered_all.view(world, g_steps, wit_bytes)[:, last].contiguous().cpu().numpy().view(A.WITNESS_DTYPE).T
+            arrays.update({f"witness_{k}": v for k, v in record_arrays(wit).items()})
+        dump_outputs(args.dump_outputs, arrays)
+        stage(f"records of the last timed step written to {args.dump_outputs}")
+
+    step_s = dt / args.steps
+    emails_per_s = world * n * args.steps / dt
+    out = {
+        "metric": "emails verified/sec (witness gen)", "value": round(emails_per_s, 1), "unit": "emails/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "warmup_effective": priming + args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+        "config": {"workload": f"BASELINE configs[1]: batch {n} e-mails, 4 KB body, RSA-2048, DKIM-only verify_email"
+                   if args.workload == "c2" else f"{args.workload}: {cfg}",
+                   "emails_per_step_per_gpu": n, "body_bytes": cfg["body_len"], "mean_hashed_body_bytes": round(wl.body_bytes / n, 1),
+                   "rsa_bits": cfg.get("rsa_bits", 0), "algo": cfg.get("algo", "rsa-sha256"),
+                   "inputs": "HBM-resident raw e-mails", "batches_in_flight": S, "collective": "one RCCL all_gather of every step's 72-B witnesses (status + output hashes of each e-mail) at the end of the timed region" if use_dist else "none"},
+        "hashed_body_GBps": round(wl.body_bytes / step_s / 1e9, 3),
+        "host_submit_ms": round(t_submitted * 1e3, 3),
+        "workload_gen_s": round(gen_s, 2),
+    }
+    if not args.full:
+        return finish(out, rank, use_dist, json_fd)
+
     # ---- correctness of what was timed (outside the timed region)
     nocheck = False
     first_timed = priming + args.warmup
@@ -372,7 +412,6 @@ def main():
     eng.set_timing(False)
     stage("per-kernel timings read (in flight, alone)")
 
-    emails_per_s = world * n * args.steps / dt
     # The SHA-256 body kernel's algorithmic bytes, SURVEY §8(d): every canonical body byte read once + 32 B written per e-mail ...
     body_bytes = wl.body_bytes + 32 * n
     # ... and everything else the hash / modexp launch moves: the header preimages, domains and keys it also hashes (+ 32 B per
@@ -388,7 +427,6 @@ def main():
     prof = load_profile_figures(args, n)
     gbps_of = (lambda nbytes, us: round(nbytes / (us * 1e-6) / 1e9, 3) if us and us > 0 else None)
     frac_of = (lambda g: round(g / HBM_PEAK_GBS, 5) if g is not None else None)
-    step_s = dt / args.steps
     agg_gbs = round(body_bytes / step_s / 1e9, 3)
     fused = (4 * ((n + 63) // 64)) <= 512
     # The bound that binds: instruction issue.  The step's VALU wave-instructions (PMC: SQ_INSTS_VALU summed over the three
@@ -480,23 +518,12 @@ def main():
         sha_sat["pair_kernel"] = saturate(1 << 15, 4096, "sha256_pair_kernel<128> = sha256_pair_group, the timed launch's SHA-256 routine "
                                           "(two waves per 64 messages), at its largest launch: 512 groups")
 
-    out = {
-        "metric": "emails verified/sec (witness gen)", "value": round(emails_per_s, 1), "unit": "emails/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "warmup_effective": priming + args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-        "config": {"workload": f"BASELINE configs[1]: batch {n} e-mails, 4 KB body, RSA-2048, DKIM-only verify_email"
-                   if args.workload == "c2" else f"{args.workload}: {cfg}",
-                   "emails_per_step_per_gpu": n, "body_bytes": cfg["body_len"], "mean_hashed_body_bytes": round(wl.body_bytes / n, 1),
-                   "rsa_bits": cfg.get("rsa_bits", 0), "algo": cfg.get("algo", "rsa-sha256"),
-                   "inputs": "HBM-resident raw e-mails", "batches_in_flight": S, "collective": "one RCCL all_gather of every step's 72-B witnesses (status + output hashes of each e-mail) at the end of the timed region" if use_dist else "none"},
+    out.update({
         "roofline": roof,
-        "hashed_body_GBps": round(wl.body_bytes / step_s / 1e9, 3),
         "kernels_us_in_flight": {k: round(v, 2) for k, v in kern_flight.items()},
         "kernels_us_alone": {k: round(v, 2) for k, v in kern_alone.items()} if kern_alone else None,
-        "host_submit_ms": round(t_submitted * 1e3, 3),
         "sha256_saturated": sha_sat,
-        "workload_gen_s": round(gen_s, 2),
-    }
+    })
 
     # ---- end to end: the same workload from pageable host memory (what a drop-in caller holds: core/src/circuits.rs:9 takes a
     # RAM-resident &Email), zke_verify_batch_async through every slot, H2D and D2H inside the clock; and the latency of ONE call
@@ -547,6 +574,13 @@ def main():
             "single_thread_value": round(one, 1),
         }
         out["gpu_over_cpu"] = round(emails_per_s / allc, 2)
+    finish(out, rank, use_dist, json_fd)
+
+
+def finish(out, rank, use_dist, json_fd):
+    """Rank 0 writes the JSON line; with a process group, every rank drains and meets the others before it goes down."""
+    import torch
+    import torch.distributed as dist
     if rank == 0:
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
@@ -557,6 +591,36 @@ def main():
         torch.cuda.synchronize()
         dist.destroy_process_group()
         stage("process group down")
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def record_arrays(rec) -> dict:
+    """A structured array of records (RESULT_DTYPE / WITNESS_DTYPE) as one float array per field: the 32-bit words as float64
+    (exact), the byte arrays (hashes) as float32 (exact); `reserved` is left out."""
+    out = {}
+    for name in rec.dtype.names:
+        if name == "reserved":
+            continue
+        a = np.asarray(rec[name])
+        out[name] = a.astype(np.float32 if a.dtype == np.uint8 else np.float64)
+    return out
+
+
+def dump_outputs(path: str, arrays: dict):
+    """DIR/<name>.npy for every array.  Above DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of rows is kept of each
+    array (their first axis is the e-mail), and its row indices go to DIR/sample_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        rows = len(next(iter(arrays.values())))
+        keep = max(1, int(rows * DUMP_LIMIT_BYTES // total))
+        idx = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["sample_rows"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), v)
 
 
 def cpu_model() -> str:
@@ -803,6 +867,8 @@ def strong_scaling_main(args, cfgs, rank, local_rank, world, json_fd):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     w = wit.cpu().numpy().view(A.WITNESS_DTYPE)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, record_arrays(w))      # the gathered witnesses of the last step, in batch order
     assert len(w) == cfg["n"] and (w["status"] == 0).all(), "strong-scaling batch: not every e-mail verified"
     if rank == 0:
         n = cfg["n"]

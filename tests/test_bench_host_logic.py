@@ -34,3 +34,27 @@ def test_bench_without_gpu_fails_loudly_and_prints_nothing_on_stdout():
     assert r.returncode != 0
     assert r.stdout == "", r.stdout[-500:]
     assert "needs a GPU" in r.stderr
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_above_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    import zkemail_rs_amd  # noqa: F401
+    from zkemail_rs_amd import _abi as A
+    rec = np.zeros(100, dtype=A.RESULT_DTYPE)
+    rec["status"] = np.arange(100)
+    rec["body_hash"][:, 0] = np.arange(100) % 256
+    arrays = bench.record_arrays(rec)
+    assert "reserved" not in arrays and arrays["status"].dtype == np.float64 and arrays["body_hash"].dtype == np.float32
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert (np.load(tmp_path / "all" / "status.npy") == np.arange(100)).all()
+    assert not (tmp_path / "all" / "sample_rows.npy").exists()
+    # above the limit: the same seeded rows of every array, their indices beside them, from run to run
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", sum(a.nbytes for a in arrays.values()) // 4)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    rows = np.load(tmp_path / "s1" / "sample_rows.npy")
+    assert 0 < len(rows) <= 25 and (rows == np.load(tmp_path / "s2" / "sample_rows.npy")).all()
+    assert (np.load(tmp_path / "s1" / "status.npy") == rows).all()
+    assert (np.load(tmp_path / "s1" / "body_hash.npy")[:, 0] == rows % 256).all()
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) < sum(a.nbytes for a in arrays.values())

@@ -1,5 +1,5 @@
-"""GPU (-m gpu): bench.py's output contract — ONE JSON line with the driver's fields, the `roofline` object of the
-dominant kernel and the `cpu_baseline` object (the oracle timed on this box's cores)."""
+"""GPU (-m gpu): bench.py's output contract — ONE JSON line with the driver's fields; with --full also the `roofline` object
+of the dominant kernel and the `cpu_baseline` object (the oracle timed on this box's cores)."""
 import json
 import os
 import subprocess
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "10",
-                        "--cpu-seconds", "1", "--no-saturated"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--full", "--cpu-seconds", "1", "--no-saturated"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.splitlines()
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]          # ONE line on stdout, the JSON
@@ -63,9 +63,35 @@ def test_bench_exchange_path_through_rccl_on_one_gpu():
     env = dict(os.environ, ZKE_BENCH_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
                MASTER_ADDR="127.0.0.1", MASTER_PORT="29577", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "120", "--warmup", "10",
-                        "--no-cpu", "--no-saturated"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                        "--full", "--no-cpu", "--no-saturated"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.splitlines()
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]          # RCCL's version banner must not land on stdout
     j = json.loads(lines[0])
     assert j["n_gpus"] == 1 and "all_gather" in j["config"]["collective"] and j["value"] > 1e5
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full: the headline fields and nothing that takes runs of its own; --dump-outputs writes the last timed
+    step's records, which are the signer's for every e-mail of the seeded workload (rank 0: seed 1000)."""
+    import numpy as np
+    import synth
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == 30 and j["warmup"] == 5 and j["higher_is_better"] is True and j["dtype"] == "u32"
+    assert j["value"] > 1e5 and abs(j["ms_per_step"] * 1e-3 * j["value"] - 1024) < 1.0
+    for k in ("roofline", "cpu_baseline", "end_to_end", "single_email_latency_us", "sha256_saturated", "kernels_us_alone"):
+        assert k not in j, k
+    wl = synth.make_workload("c2", seed=1000, n=1024, body_len=4096, rsa_bits=2048, n_keys=16)
+    status = np.load(out / "status.npy")
+    assert status.dtype == np.float64 and status.shape == (1024,) and (status == 0).all()
+    for f in ("body_hash", "header_hash"):
+        got = np.load(out / f"{f}.npy")
+        assert got.dtype == np.float32 and got.shape == (1024, 32)
+        assert (got == np.array([list(it[f]) for it in wl.inter], dtype=np.float32)).all(), f
+    assert not (out / "reserved.npy").exists()

@@ -10,7 +10,7 @@
 set -o pipefail
 out=gpurun_out/r03; mkdir -p $out
 export TMPDIR=/tmp
-B="--no-cpu --no-saturated --no-e2e"
+B="--full --no-cpu --no-saturated --no-e2e"
 PMC_I="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES"
 line() { python -c "
 import json,sys
@@ -47,12 +47,12 @@ stalls)   # where a wave's cycles go, per kernel: parked (s_waitcnt / barrier), 
   done
   ;;
 lines)
-  timeout -k 10 500 python bench.py > $out/bench_line.json 2> $out/bench_line.err || { tail -20 $out/bench_line.err; exit 1; }
+  timeout -k 10 500 python bench.py --full > $out/bench_line.json 2> $out/bench_line.err || { tail -20 $out/bench_line.err; exit 1; }
   line $out/bench_line.json default
-  timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_line.json 2> $out/bench_driver_line.err || { tail -20 $out/bench_driver_line.err; exit 1; }
+  timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_driver_line.json 2> $out/bench_driver_line.err || { tail -20 $out/bench_driver_line.err; exit 1; }
   line $out/bench_driver_line.json driver
   for W in c2ragged c2inv; do
-    timeout -k 10 500 python bench.py --workload $W --steps 1000 --warmup 40 --no-saturated > $out/line_$W.json 2> $out/line_$W.err || { tail -20 $out/line_$W.err; exit 1; }
+    timeout -k 10 500 python bench.py --workload $W --steps 1000 --warmup 40 --full --no-saturated > $out/line_$W.json 2> $out/line_$W.err || { tail -20 $out/line_$W.err; exit 1; }
     line $out/line_$W.json $W
   done
   ;;
@@ -70,7 +70,7 @@ c2prof)
   ;;
 satprof)
   rm -rf $out/p_sat $out/pi_sat $out/p_sat_fetch $out/p_sat_write
-  S="--no-cpu --no-e2e --steps 20 --warmup 5 --alone-steps 0"
+  S="--full --no-cpu --no-e2e --steps 20 --warmup 5 --alone-steps 0"
   rocprofv3 --kernel-trace --stats -d $out/p_sat -o run --output-format csv -- python bench.py $S > $out/p_sat.log 2>&1 || { tail -20 $out/p_sat.log; exit 1; }
   grep -E "Name|sha256" $out/p_sat/run_kernel_stats.csv > $out/sha_saturated_kernel_stats.csv; cat $out/sha_saturated_kernel_stats.csv | cut -c1-220
   rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES -d $out/pi_sat -o runc --output-format csv -- python bench.py $S > $out/pi_sat.log 2>&1 || { tail -5 $out/pi_sat.log; exit 1; }
