@@ -187,7 +187,8 @@ typedef struct zke_batch {
   const uint32_t* body_part_ids;   /* [n_body_parts] */
   /* captures of email i, part p (p over header parts then body parts, P = total):
    * strings cap_str_off[ cap_off[i*P+p] .. cap_off[i*P+p+1] ) in cap_blob. */
-  const uint32_t* cap_off;         /* [n*P + 1] or NULL when P == 0 */
+  const uint32_t* cap_off;         /* [n*P + 1], or NULL: no captures.  cap_off[n*P] == 0 (no string anywhere) is the same as
+                                      NULL, and cap_str_off / cap_blob may then be NULL; otherwise both are required */
   const uint32_t* cap_str_off;     /* [n_strings + 1] */
   const uint8_t*  cap_blob;
 } zke_batch;
@@ -281,7 +282,9 @@ typedef struct zke_timings {
 int zke_process_init(uint32_t hw_queues);
 
 int zke_engine_create(const zke_options* opt, zke_engine** out);
-/* Waits for everything in flight; host batches nobody waited for are delivered to their `out` arrays on the way out. */
+/* Waits for everything in flight — batches submitted on a caller's stream included — before it frees anything; host batches
+ * nobody waited for are delivered to their `out` arrays on the way out.  (Building-block launches on a caller's stream,
+ * zke_sha256_batch_device, are not tracked: the caller synchronises them first.) */
 void zke_engine_destroy(zke_engine* e);
 /* The message of the last failed call on this engine by the calling thread ("" if none). */
 const char* zke_last_error(const zke_engine* e);

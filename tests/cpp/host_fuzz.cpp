@@ -5,6 +5,7 @@
 //   * zke_wire_decode: borsh / bincode records cut at every length and with random byte flips;
 //   * CopyPool: several callers at once, odd sizes and alignments, results compared with memcpy (also under -fsanitize=thread);
 //   * zke_abi_encode into buffers of exactly the size it asks for, and one byte less;
+//   * host_batch (the host entries' batch descriptor): both shapes of one batch agree, malformed ones are refused;
 //   * zke_shard_bounds, image_layout, pair_hash on edge sizes.
 // tests/test_host_sanitizers.py builds and runs it.  (The same source with -fsanitize=thread instead: clean as well, run by hand —
 // the second 40 s build is not worth a place in the suite.)
@@ -148,6 +149,90 @@ int main(int argc, char** argv) {
     if (zke_abi_encode(h1, h2, p1.data(), l1.data(), (uint32_t)p1.size(), wm, p2.data(), l2.data(), (uint32_t)p2.size(), exact.data(), exact.size(), &got) != 0 || got != need) { fprintf(stderr, "abi exact\n"); return 1; }
     if (zke_abi_encode(h1, h2, p1.data(), l1.data(), (uint32_t)p1.size(), wm, p2.data(), l2.data(), (uint32_t)p2.size(), tight.data(), tight.size(), &got) != ZKE_E_NOMEM) { fprintf(stderr, "abi tight\n"); return 1; }
     cases++;
+  }
+  // ---- host_batch: the host entries' batch descriptor, packed (zke_batch) and gathered (zke_email_ref[n] + zke_regex_lists), every
+  // array in a heap buffer of exactly its size
+  {
+    const uint32_t n = 6, NP = n * 3;                                                // 2 header parts + 1 body part
+    auto exact = [](const auto& v) { return std::vector<typename std::decay_t<decltype(v)>::value_type>(v.begin(), v.end()); };
+    std::vector<std::vector<uint8_t>> raw(n), dom(n), key(n);
+    std::vector<zke_email_ref> refs(n);
+    for (uint32_t i = 0; i < n; i++) {
+      raw[i].resize(i == 4 ? 0 : 1 + rng() % 700); dom[i].resize(i == 1 ? 0 : 1 + rng() % 20); key[i].resize(1 + rng() % 300);
+      for (auto* v : {&raw[i], &dom[i], &key[i]}) for (auto& c : *v) c = (uint8_t)rng();
+      refs[i] = zke_email_ref{raw[i].data(), raw[i].size(), reinterpret_cast<const char*>(dom[i].data()), dom[i].size(), key[i].data(),
+                              key[i].size(), i % 3, i & 1};
+    }
+    // the same e-mails packed, each blob behind `base` bytes of something else (off[0] = base)
+    auto pack = [&](const std::vector<std::vector<uint8_t>>& v, size_t base, std::vector<uint8_t>& blob, std::vector<uint64_t>& off) {
+      std::vector<uint8_t> b(base, 0xAB);
+      off.assign(n + 1, base);
+      for (uint32_t i = 0; i < n; i++) { b.insert(b.end(), v[i].begin(), v[i].end()); off[i + 1] = b.size(); }
+      blob = exact(b);
+    };
+    std::vector<uint8_t> rb, db, kb, kt(n), xn(n);
+    std::vector<uint64_t> ro, dof, ko;
+    pack(raw, 3, rb, ro); pack(dom, 0, db, dof); pack(key, 17, kb, ko);
+    std::vector<uint32_t> hids{4, 9}, bids{2}, co{0}, so{0};
+    std::vector<uint8_t> cb;
+    for (uint32_t k = 0; k < NP; k++) {
+      for (uint32_t c = 0; c < k % 3; c++) { cb.insert(cb.end(), 1 + rng() % 8, (uint8_t)('a' + c)); so.push_back((uint32_t)cb.size()); }
+      co.push_back((uint32_t)so.size() - 1);
+    }
+    const std::vector<uint32_t> cap_off = exact(co), cap_str_off = exact(so), zeros(NP + 1, 0);
+    const std::vector<uint8_t> cap_blob = exact(cb);
+    std::vector<zke_result> out(n);
+    zke_batch pb{};
+    pb.n = n; pb.raw_blob = rb.data(); pb.raw_off = ro.data(); pb.domain_blob = db.data(); pb.domain_off = dof.data();
+    pb.key_blob = kb.data(); pb.key_off = ko.data(); pb.key_type = kt.data(); pb.ext_null = xn.data();
+    pb.with_regex = 1; pb.n_header_parts = 2; pb.n_body_parts = 1; pb.header_part_ids = hids.data(); pb.body_part_ids = bids.data();
+    pb.cap_off = cap_off.data(); pb.cap_str_off = cap_str_off.data(); pb.cap_blob = cap_blob.data();
+    zke_regex_lists rl{2, hids.data(), 1, bids.data(), cap_off.data(), cap_str_off.data(), cap_blob.data()};
+    auto packed = [&](HostBatch& d) { return host_batch(d, "packed", out.data(), &pb); };
+    auto gathered = [&](HostBatch& d) { return host_batch(d, "gathered", out.data(), refs.data(), n, &rl); };
+    auto refused = [&](int r, const char* what) {
+      if (r != ZKE_E_ARG || !strstr(g_err.c_str(), what)) { fprintf(stderr, "host_batch: '%s' not refused (%d, '%s')\n", what, r, g_err.c_str()); exit(1); }
+      cases++;
+    };
+    // one batch, two shapes: the same totals, capture tables and image layout
+    HostBatch a, b;
+    if (packed(a) || gathered(b)) { fprintf(stderr, "host_batch: a valid batch refused: %s\n", g_err.c_str()); return 1; }
+    if (a.raw_total != ro[n] - 3 || a.raw_total != b.raw_total || a.dom_total != b.dom_total || a.key_total != b.key_total ||
+        a.raw_base != 3 || a.key_base != 17 || b.raw_base || a.cap_words != NP + 1 || a.cap_words != b.cap_words ||
+        a.cap_strs != b.cap_strs || a.cap_bytes != cb.size() || a.cap_bytes != b.cap_bytes || memcmp(&a.L, &b.L, sizeof a.L) ||
+        a.refs || b.refs != refs.data()) { fprintf(stderr, "host_batch: the two shapes of one batch differ\n"); return 1; }
+    // each offset array of the packed shape made decreasing
+    for (std::vector<uint64_t>* off : {&ro, &dof, &ko}) {
+      const std::vector<uint64_t> keep = *off;
+      (*off)[2] = (*off)[3] + 1;
+      refused(packed(a), "non-decreasing");
+      *off = keep;
+    }
+    // capture tables without a string, cap_str_off and cap_blob NULL: no tables, in both shapes
+    pb.cap_off = rl.cap_off = zeros.data(); pb.cap_str_off = rl.cap_str_off = nullptr; pb.cap_blob = rl.cap_blob = nullptr;
+    const ImageLayout none = image_layout(n, b.raw_total, b.dom_total, b.key_total, 0, 0, 0);
+    for (int shape = 0; shape < 2; shape++)
+      if ((shape ? gathered(a) : packed(a)) || a.cap_words || a.b.cap_off || a.b.cap_str_off || memcmp(&a.L, &none, sizeof none)) { fprintf(stderr, "host_batch: string-less tables\n"); return 1; }
+    // ... while tables that hold strings need cap_str_off (and cap_blob)
+    pb.cap_off = rl.cap_off = cap_off.data();
+    pb.cap_blob = rl.cap_blob = cap_blob.data();
+    refused(packed(a), "cap_str_off"); refused(gathered(a), "cap_str_off");
+    pb.cap_str_off = rl.cap_str_off = cap_str_off.data();
+    pb.cap_blob = rl.cap_blob = nullptr;
+    refused(packed(a), "cap_blob"); refused(gathered(a), "cap_blob");
+    pb.cap_blob = rl.cap_blob = cap_blob.data();
+    // gathered: a null buffer with a length, implausible lengths, more than 1 TiB in all
+    for (int k = 0; k < 3; k++) {
+      zke_email_ref keep = refs[3];
+      if (k == 0) refs[3].raw = nullptr; else if (k == 1) refs[3].from_domain = nullptr; else refs[3].key = nullptr;
+      refused(gathered(a), "null buffer");
+      refs[3] = keep;
+      if (k == 0) refs[3].raw_len = (1ull << 40) + 1; else if (k == 1) refs[3].domain_len = (1ull << 32) + 1; else refs[3].key_len = (1ull << 32) + 1;
+      refused(gathered(a), "implausible length");
+      refs[3] = keep;
+    }
+    refs[0].raw_len = refs[1].raw_len = 1ull << 40;
+    refused(gathered(a), "1 TiB");
   }
   // ---- small pure functions on edge sizes
   {

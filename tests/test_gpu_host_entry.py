@@ -209,7 +209,7 @@ def test_length_buckets_across_slot_reuse(oracle):
 
 
 def test_host_offsets_are_checked(oracle):
-    """Offset arrays in host memory are validated before anything is staged (csrc/pipeline.hip.h, check_host_batch): a length
+    """Offset arrays in host memory are validated before anything is staged (csrc/pipeline.hip.h, host_batch): a length
     that comes out negative is ZKE_E_ARG, not a copy outside the blob; the engine stays usable."""
     import zkemail_rs_amd as z
     eng = z.Engine()

@@ -187,7 +187,6 @@ Slot* new_slot(zke_engine* e) {
 }
 void free_slot(Slot* w) {
   if (!w) return;
-  if (w->stream) (void)hipStreamSynchronize(w->stream);
   if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
   for (auto* b : w->all) b->release();
   w->h_image.release(); w->h_results.release();
@@ -198,6 +197,20 @@ void free_slot(Slot* w) {
   if (w->wave_feedback) (void)hipHostFree(w->wave_feedback);
   if (w->stream) (void)hipStreamDestroy(w->stream);
   delete w;
+}
+
+// Wait for everything the engine has in flight: per slot, the event behind its last batch if that ran on a caller's stream, then
+// the slot's own stream — read under the slot's lock, waited for outside it, so that a sync does not hold off the threads that
+// submit to the slot meanwhile; with copy_streams, the copy streams of the host entry's input images as well.
+int drain_engine(zke_engine* e, bool copy_streams) {
+  for (Slot* w : e->slots) {
+    hipStream_t own; hipEvent_t done;
+    { std::lock_guard<std::mutex> g(w->mu); own = w->stream; done = w->last_stream && w->last_stream != w->stream ? w->done : nullptr; }
+    if (done) HIPCHK(e, hipEventSynchronize(done));
+    HIPCHK(e, hipStreamSynchronize(own));
+  }
+  if (copy_streams) for (hipStream_t cs : e->copy_stream) if (cs) HIPCHK(e, hipStreamSynchronize(cs));
+  return 0;
 }
 
 // Which lane-group RSA kernels take part in a batch of n e-mails.  Bit 0: four lanes per signature (moduli <= 2048 bits),
@@ -439,10 +452,10 @@ void zke_engine_destroy(zke_engine* e) {
     std::unique_lock<std::shared_mutex> ex(e->big);
     (void)hipSetDevice(e->device);
     for (Slot* w : e->slots) { std::lock_guard<std::mutex> g(w->mu); (void)retire_host(e, *w); }     // deliver what was never waited for
-    for (Slot* w : e->slots) if (w->stream) (void)hipStreamSynchronize(w->stream);
+    (void)drain_engine(e, true);          // before anything is freed: the verdict launch writes wave_feedback from the device
     for (Slot* w : e->slots) free_slot(w);
     e->slots.clear();
-    for (auto& cs : e->copy_stream) if (cs) { (void)hipStreamSynchronize(cs); (void)hipStreamDestroy(cs); cs = nullptr; }
+    for (auto& cs : e->copy_stream) if (cs) { (void)hipStreamDestroy(cs); cs = nullptr; }
     e->misc.release(); e->key_cache.release();
     for (auto* d : e->dfas) if (d) { d->blob.release(); d->dev.release(); delete d; }
     e->dfas.clear();
@@ -478,14 +491,7 @@ int zke_engine_sync(zke_engine* e) {
   if (!e) return ZKE_E_ARG;
   std::shared_lock<std::shared_mutex> sh(e->big);
   HIPCHK(e, hipSetDevice(e->device));
-  for (Slot* w : e->slots) {
-    // a slot's last batch ran on the slot's own stream, or on a caller's stream with `done` recorded behind it
-    hipStream_t own; hipEvent_t done; bool foreign;
-    { std::lock_guard<std::mutex> g(w->mu); own = w->stream; done = w->done; foreign = w->last_stream && w->last_stream != w->stream; }
-    if (foreign) HIPCHK(e, hipEventSynchronize(done));
-    HIPCHK(e, hipStreamSynchronize(own));
-  }
-  return 0;
+  return drain_engine(e, false);
 }
 
 int zke_set_timing(zke_engine* e, int enabled) {

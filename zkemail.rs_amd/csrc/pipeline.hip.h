@@ -280,6 +280,8 @@ Slot& next_slot(zke_engine* e, uint32_t& index) {
   e->last_slot.store(index, std::memory_order_relaxed);
   return *e->slots[index];
 }
+// tickets: slot index in the low 6 bits (an engine has at most 64 slots), the slot's batch count above
+inline uint64_t make_ticket(uint32_t slot, uint64_t gen) { return (gen << 6) | slot; }
 
 uint64_t batch_clock(const zke_engine* e) {
   if (!(e->strict & ZKE_STRICT_EXPIRY_X)) return 0;
@@ -297,62 +299,119 @@ int retire_host(zke_engine* e, Slot& w) {
   return 0;
 }
 
-// Sizes of a batch handed over as separate e-mails (zke_verify_emails): summed once, by the entry point
-struct RefTotals { uint64_t raw = 0, dom = 0, key = 0; };
+int arg_error(const char* who, const char* what) { g_err = std::string(who) + ": " + what; return ZKE_E_ARG; }
+template <class T> bool rising(const T* off, size_t cnt) { uint64_t bad = 0; for (size_t i = 0; i < cnt; i++) bad |= (uint64_t)(off[i + 1] < off[i]); return !bad; }
+// The part-id lists of a batch (host arrays in every entry) ...
+int check_part_ids(const zke_batch& b, const char* who) {
+  return b.with_regex && ((b.n_header_parts && !b.header_part_ids) || (b.n_body_parts && !b.body_part_ids)) ? arg_error(who, "part-id list is null") : 0;
+}
+// ... and with them the pointers the pipeline reads (device memory; with `host`, the packed host entry's: it also copies the domain
+// and key blobs)
+int check_batch_pointers(const zke_batch* in, const void* out, bool host, const char* who) {
+  if (!in || (in->n && (!out || !in->raw_blob || !in->raw_off || !in->domain_off || !in->key_off || !in->key_type ||
+                        (host && (!in->domain_blob || !in->key_blob)))))
+    return arg_error(who, "null pointer");
+  return check_part_ids(*in, who);
+}
 
-// One host-memory batch into slot w (caller holds its lock): pack -> one H2D -> the launches -> one D2H -> event.
-// refs != nullptr: the e-mails come one by one (zke_email_ref); `in` then carries n only and the offsets are made here.
-int submit_host(zke_engine* e, Slot& w, const zke_batch* in, zke_result* out, bool want_em, bool want_clean,
-                const zke_email_ref* refs = nullptr, const RefTotals* rt = nullptr) {
-  const uint32_t n = in->n;
-  const uint64_t raw_total = refs ? rt->raw : in->raw_off[n] - in->raw_off[0], dom_total = refs ? rt->dom : in->domain_off[n] - in->domain_off[0],
-                 key_total = refs ? rt->key : in->key_off[n] - in->key_off[0];
-  const uint64_t raw_base = refs ? 0 : in->raw_off[0], dom_base = refs ? 0 : in->domain_off[0], key_base = refs ? 0 : in->key_off[0];
-  const uint32_t P = in->with_regex ? in->n_header_parts + in->n_body_parts : 0;
-  const bool caps = P && in->cap_off;
-  const uint32_t n_caps = caps ? in->cap_off[(size_t)n * P] : 0;
-  const uint32_t cap_bytes = caps ? in->cap_str_off[n_caps] : 0;
-  const ImageLayout L = image_layout(n, raw_total, dom_total, key_total, caps ? (size_t)n * P + 1 : 0, caps ? (size_t)n_caps + 1 : 0, cap_bytes);
+// A host batch, checked and measured for the staging image by host_batch(): packed (zke_batch) or gathered (zke_email_ref[n]).
+struct HostBatch {
+  zke_batch b{};                        // n, the regex section, (packed) the caller's blobs and offsets; capture tables only if any
+  const zke_email_ref* refs = nullptr;  // the gathered shape's e-mails (nullptr: packed)
+  uint64_t raw_total = 0, dom_total = 0, key_total = 0, raw_base = 0, dom_base = 0, key_base = 0;   // blob bytes; off[0] of packed offsets
+  size_t cap_words = 0, cap_strs = 0, cap_bytes = 0;      // entries of cap_off and cap_str_off, bytes of cap_blob (0: no tables)
+  ImageLayout L{};
+};
+// Both shapes.  Capture tables: a cap_off whose last entry is 0 holds no string and is no table (cap_str_off, cap_blob unread).
+int measure_host_batch(HostBatch& d, const char* who) {
+  zke_batch& b = d.b;
+  if (d.raw_total > (1ull << 40)) return arg_error(who, "raw e-mails beyond 1 TiB");
+  const size_t NP = b.with_regex ? (size_t)b.n * (b.n_header_parts + b.n_body_parts) : 0;
+  if (NP && b.cap_off) {
+    if (!rising(b.cap_off, NP)) return arg_error(who, "capture offset array is not non-decreasing");
+    if (const uint32_t strs = b.cap_off[NP]) {
+      if (!b.cap_str_off || !b.cap_blob) return arg_error(who, "capture strings without cap_str_off or cap_blob");
+      if (!rising(b.cap_str_off, strs)) return arg_error(who, "capture offset array is not non-decreasing");
+      d.cap_words = NP + 1; d.cap_strs = (size_t)strs + 1; d.cap_bytes = b.cap_str_off[strs];
+    }
+  }
+  if (!d.cap_words) b.cap_off = nullptr, b.cap_str_off = nullptr, b.cap_blob = nullptr;
+  d.L = image_layout(b.n, d.raw_total, d.dom_total, d.key_total, d.cap_words, d.cap_strs, d.cap_bytes);
+  return 0;
+}
+// The packed shape.  Its offsets are in host memory here, so they are checked (three passes over n + 1 words): a negative length
+// would send the staging copy, then the kernels, outside the blobs.  (In device memory they are trusted like the pointers.)
+int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_batch* in) {
+  if (int r = check_batch_pointers(in, out, true, who)) return r;
+  d = HostBatch{*in};
+  if (const uint32_t n = in->n) {
+    if (!(rising(in->raw_off, n) && rising(in->domain_off, n) && rising(in->key_off, n))) return arg_error(who, "offset array is not non-decreasing");
+    d.raw_base = in->raw_off[0]; d.dom_base = in->domain_off[0]; d.key_base = in->key_off[0];
+    d.raw_total = in->raw_off[n] - d.raw_base; d.dom_total = in->domain_off[n] - d.dom_base; d.key_total = in->key_off[n] - d.key_base;
+  }
+  return measure_host_batch(d, who);
+}
+// The gathered shape: the e-mails one by one, lists == nullptr for verify_email.
+int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_email_ref* refs, uint32_t n, const zke_regex_lists* lists) {
+  if (n && (!refs || !out)) return arg_error(who, "null pointer");
+  d = HostBatch{zke_batch{n}, refs};
+  if (lists) {
+    d.b.with_regex = 1; d.b.n_header_parts = lists->n_header_parts; d.b.header_part_ids = lists->header_part_ids;
+    d.b.n_body_parts = lists->n_body_parts; d.b.body_part_ids = lists->body_part_ids;
+    d.b.cap_off = lists->cap_off; d.b.cap_str_off = lists->cap_str_off; d.b.cap_blob = lists->cap_blob;
+  }
+  if (int r = check_part_ids(d.b, who)) return r;
+  for (uint32_t i = 0; i < n; i++) {
+    const zke_email_ref& m = refs[i];
+    if ((m.raw_len && !m.raw) || (m.domain_len && !m.from_domain) || (m.key_len && !m.key)) return arg_error(who, "null buffer with a length");
+    if (m.raw_len > (1ull << 40) || m.domain_len > (1ull << 32) || m.key_len > (1ull << 32)) return arg_error(who, "implausible length");
+    d.raw_total += m.raw_len; d.dom_total += m.domain_len; d.key_total += m.key_len;
+  }
+  return measure_host_batch(d, who);
+}
+
+// One host batch into slot w (caller holds its lock): pack -> one H2D -> the launches -> one D2H -> event.
+int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, bool want_em, bool want_clean) {
+  const uint32_t n = d.b.n;
+  const ImageLayout& L = d.L;
   if (int r = retire_host(e, w)) return r;           // the pinned buffers are about to be overwritten
-  if (int r = ensure_host_buffers(e, w, L.total, n)) return r;      // (a no-op: the entry points have grown every slot's staging)
+  if (int r = ensure_host_buffers(e, w, L.total, n)) return r;      // (a no-op: submit_host_batch has grown every slot's staging)
   uint8_t* hp = w.h_image.as<uint8_t>();
-  if (refs) {
+  if (d.refs) {
     // the CSR arrays are written where they will be read from (prefix sums over the lengths), and every e-mail's three buffers
     // go to their places in the blobs — the pool takes runs of consecutive e-mails (CopyPool::gather)
     uint64_t* ro = reinterpret_cast<uint64_t*>(hp + L.raw_off), *dofs = reinterpret_cast<uint64_t*>(hp + L.dom_off), *ko = reinterpret_cast<uint64_t*>(hp + L.key_off);
     uint8_t* kt = hp + L.key_type, *xn = hp + L.ext_null;
     w.gather.resize((size_t)3 * n);
-    uint64_t r = 0, d = 0, k = 0;
+    uint64_t r = 0, dd = 0, k = 0;
     for (uint32_t i = 0; i < n; i++) {
-      const zke_email_ref& m = refs[i];
-      ro[i] = r; dofs[i] = d; ko[i] = k;
+      const zke_email_ref& m = d.refs[i];
+      ro[i] = r; dofs[i] = dd; ko[i] = k;
       kt[i] = (uint8_t)(m.key_type > ZKE_KEY_OTHER ? ZKE_KEY_OTHER : m.key_type);
       xn[i] = m.external_input_null ? 1 : 0;
       w.gather[i] = CopyPool::Piece{hp + L.raw + r, m.raw, m.raw_len};                       // three runs, each contiguous in the image
-      w.gather[(size_t)n + i] = CopyPool::Piece{hp + L.dom + d, m.from_domain, m.domain_len};
+      w.gather[(size_t)n + i] = CopyPool::Piece{hp + L.dom + dd, m.from_domain, m.domain_len};
       w.gather[2 * (size_t)n + i] = CopyPool::Piece{hp + L.key + k, m.key, m.key_len};
-      r += m.raw_len; d += m.domain_len; k += m.key_len;
+      r += m.raw_len; dd += m.domain_len; k += m.key_len;
     }
-    ro[n] = r; dofs[n] = d; ko[n] = k;
+    ro[n] = r; dofs[n] = dd; ko[n] = k;
     if (e->pool) e->pool->gather(w.gather.data(), w.gather.size());
     else for (const auto& p : w.gather) if (p.n) stage_copy(p.dst, p.src, p.n, ZKE_GATHER_STREAM_FROM);
-    if (caps) {       // the capture tables of a regex batch arrive in zke_batch's form (small)
-      stage_copy(hp + L.cap_off, in->cap_off, ((size_t)n * P + 1) * 4);
-      stage_copy(hp + L.cap_str_off, in->cap_str_off, ((size_t)n_caps + 1) * 4);
-      if (cap_bytes) stage_copy(hp + L.cap_blob, in->cap_blob, cap_bytes);
-    }
   } else {
     // the offsets are copied as they are (the kernels subtract off[0] themselves and the device pointers below are biased
     // by -off[0]): nothing is rebased, nothing is allocated, every byte is written once
-    CopyPool::Piece pc[11] = {
-        {hp + L.raw_off, in->raw_off, (size_t)(n + 1) * 8}, {hp + L.dom_off, in->domain_off, (size_t)(n + 1) * 8},
-        {hp + L.key_off, in->key_off, (size_t)(n + 1) * 8}, {hp + L.key_type, in->key_type, n},
-        {hp + L.ext_null, in->ext_null, in->ext_null ? n : 0u},
-        {hp + L.cap_off, in->cap_off, caps ? ((size_t)n * P + 1) * 4 : 0}, {hp + L.cap_str_off, in->cap_str_off, caps ? ((size_t)n_caps + 1) * 4 : 0},
-        {hp + L.raw, in->raw_blob + in->raw_off[0], (size_t)raw_total}, {hp + L.dom, in->domain_blob + in->domain_off[0], (size_t)dom_total},
-        {hp + L.key, in->key_blob + in->key_off[0], (size_t)key_total}, {hp + L.cap_blob, in->cap_blob, caps ? (size_t)cap_bytes : 0}};
-    if (e->pool) e->pool->copy(pc, 11);
+    CopyPool::Piece pc[8] = {
+        {hp + L.raw_off, d.b.raw_off, (size_t)(n + 1) * 8}, {hp + L.dom_off, d.b.domain_off, (size_t)(n + 1) * 8},
+        {hp + L.key_off, d.b.key_off, (size_t)(n + 1) * 8}, {hp + L.key_type, d.b.key_type, n},
+        {hp + L.ext_null, d.b.ext_null, d.b.ext_null ? n : 0u}, {hp + L.raw, d.b.raw_blob + d.raw_base, (size_t)d.raw_total},
+        {hp + L.dom, d.b.domain_blob + d.dom_base, (size_t)d.dom_total}, {hp + L.key, d.b.key_blob + d.key_base, (size_t)d.key_total}};
+    if (e->pool) e->pool->copy(pc, 8);
     else for (const auto& p : pc) if (p.n) stage_copy(p.dst, p.src, p.n);
+  }
+  if (d.cap_words) {       // the capture tables of a regex batch (small)
+    stage_copy(hp + L.cap_off, d.b.cap_off, d.cap_words * 4);
+    stage_copy(hp + L.cap_str_off, d.b.cap_str_off, d.cap_strs * 4);
+    stage_copy(hp + L.cap_blob, d.b.cap_blob, d.cap_bytes);
   }
   hipStream_t s = w.stream;
   SlotUse use(e, w, s);
@@ -379,19 +438,19 @@ int submit_host(zke_engine* e, Slot& w, const zke_batch* in, zke_result* out, bo
   }
   tm.mark(MK_H2D);
   uint8_t* dp = w.d_image.as<uint8_t>();
-  zke_batch dv = *in;
+  zke_batch dv = d.b;
   dv.raw_off = reinterpret_cast<const uint64_t*>(dp + L.raw_off);
   dv.domain_off = reinterpret_cast<const uint64_t*>(dp + L.dom_off);
   dv.key_off = reinterpret_cast<const uint64_t*>(dp + L.key_off);
-  dv.raw_blob = dp + L.raw - raw_base;
-  dv.domain_blob = dp + L.dom - dom_base;
-  dv.key_blob = dp + L.key - key_base;
+  dv.raw_blob = dp + L.raw - d.raw_base;
+  dv.domain_blob = dp + L.dom - d.dom_base;
+  dv.key_blob = dp + L.key - d.key_base;
   dv.key_type = dp + L.key_type;
-  dv.ext_null = (refs || in->ext_null) ? dp + L.ext_null : nullptr;
-  dv.cap_off = caps ? reinterpret_cast<const uint32_t*>(dp + L.cap_off) : nullptr;
-  dv.cap_str_off = caps ? reinterpret_cast<const uint32_t*>(dp + L.cap_str_off) : nullptr;
-  dv.cap_blob = caps ? dp + L.cap_blob : nullptr;
-  if (int r = run_device_pipeline(e, w, &dv, raw_total, key_total, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean)) return r;
+  dv.ext_null = (d.refs || d.b.ext_null) ? dp + L.ext_null : nullptr;
+  dv.cap_off = d.cap_words ? reinterpret_cast<const uint32_t*>(dp + L.cap_off) : nullptr;
+  dv.cap_str_off = d.cap_words ? reinterpret_cast<const uint32_t*>(dp + L.cap_str_off) : nullptr;
+  dv.cap_blob = d.cap_words ? dp + L.cap_blob : nullptr;
+  if (int r = run_device_pipeline(e, w, &dv, d.raw_total, d.key_total, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean)) return r;
   HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
   tm.mark(MK_D2H);
   HIPCHK(e, hipEventRecord(w.host_done, s));
@@ -409,12 +468,8 @@ int grow_host_staging(zke_engine* e, size_t image, uint32_t n) {
   std::unique_lock<std::shared_mutex> ex(e->big);
   if (image <= e->host_image_cap.load() && n <= e->host_n_cap.load()) return 0;       // another thread grew it meanwhile
   HIPCHK(e, hipSetDevice(e->device));
-  for (Slot* w : e->slots) {
-    std::lock_guard<std::mutex> g(w->mu);
-    if (int r = retire_host(e, *w)) return r;
-    if (w->last_stream && w->last_stream != w->stream) HIPCHK(e, hipEventSynchronize(w->done));
-    HIPCHK(e, hipStreamSynchronize(w->stream));
-  }
+  for (Slot* w : e->slots) { std::lock_guard<std::mutex> g(w->mu); if (int r = retire_host(e, *w)) return r; }
+  if (int r = drain_engine(e, false)) return r;
   for (auto& cs : e->copy_stream)
     if (!cs) HIPCHK(e, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
   const size_t want_image = std::max(image + image / 2, e->host_image_cap.load());
@@ -425,36 +480,66 @@ int grow_host_staging(zke_engine* e, size_t image, uint32_t n) {
   e->host_n_cap = want_n;
   return 0;
 }
-// what one batch needs of the staging (image_layout of its sizes)
-size_t host_image_bytes(const zke_batch* in) {
-  const uint32_t n = in->n;
-  const uint32_t P = in->with_regex ? in->n_header_parts + in->n_body_parts : 0;
-  const bool caps = P && in->cap_off;
-  const uint32_t n_caps = caps ? in->cap_off[(size_t)n * P] : 0;
-  return image_layout(n, in->raw_off[n] - in->raw_off[0], in->domain_off[n] - in->domain_off[0], in->key_off[n] - in->key_off[0],
-                      caps ? (size_t)n * P + 1 : 0, caps ? (size_t)n_caps + 1 : 0, caps ? in->cap_str_off[n_caps] : 0).total;
-}
-
-int check_host_batch(zke_engine* e, const zke_batch* in, zke_result* out, const char* who) {
-  if (!e) return ZKE_E_ARG;
-  if (!in || (in->n && (!out || !in->raw_blob || !in->raw_off || !in->domain_blob || !in->domain_off || !in->key_blob ||
-                        !in->key_off || !in->key_type)))
-    return fail(e, ZKE_E_ARG, who);
-  if (in->with_regex && ((in->n_header_parts && !in->header_part_ids) || (in->n_body_parts && !in->body_part_ids)))
-    return fail(e, ZKE_E_ARG, "part-id list is null");
-  // The offset arrays are in host memory here, so they are checked (three passes over n + 1 words): a length that came out
-  // negative would send the staging copy, and then the kernels, outside the blobs.  (In device memory — zke_verify_batch_device —
-  // they are the caller's to get right, like the pointers themselves.)
-  auto rising = [](const auto* off, size_t cnt) { uint64_t bad = 0; for (size_t i = 0; i < cnt; i++) bad |= (uint64_t)(off[i + 1] < off[i]); return !bad; };
-  if (in->n && !(rising(in->raw_off, in->n) && rising(in->domain_off, in->n) && rising(in->key_off, in->n)))
-    return fail(e, ZKE_E_ARG, "offset array is not non-decreasing");
-  if (in->n && in->raw_off[in->n] - in->raw_off[0] > (1ull << 40)) return fail(e, ZKE_E_ARG, "raw blob beyond 1 TiB");
-  if (in->with_regex && in->cap_off) {
-    const size_t NP = (size_t)in->n * ((size_t)in->n_header_parts + in->n_body_parts);
-    if (NP && (!rising(in->cap_off, NP) || (in->cap_off[NP] && (!in->cap_str_off || !in->cap_blob || !rising(in->cap_str_off, in->cap_off[NP])))))
-      return fail(e, ZKE_E_ARG, "capture offset array is not non-decreasing");
+// Parity intermediates (tests) of the packed batch `in` just delivered from slot w: its scratch copied back, sliced on the host.
+int copy_debug_out(zke_engine* e, Slot& w, const zke_batch& in, const zke_result* out, const zke_debug_out* dbg) {
+  const uint32_t n = in.n;
+  const uint64_t raw_total = in.raw_off[n] - in.raw_off[0];
+  std::vector<EmailMeta> meta(n), meta2;
+  HIPCHK(e, hipMemcpy(meta.data(), w.meta.p, (size_t)n * sizeof(EmailMeta), hipMemcpyDeviceToHost));
+  const size_t scratch_bytes = 2 * (size_t)raw_total + (size_t)(n + 1) * SCR_PER_EMAIL + 256;
+  std::vector<uint8_t> scr(scratch_bytes);
+  HIPCHK(e, hipMemcpy(scr.data(), w.scratch.p, scratch_bytes, hipMemcpyDeviceToHost));
+  std::vector<uint8_t> em, clean;
+  if (dbg->em) { em.resize((size_t)n * 512); HIPCHK(e, hipMemcpy(em.data(), w.em_dbg.p, em.size(), hipMemcpyDeviceToHost)); }
+  if (dbg->clean_body && in.with_regex) {
+    meta2.resize(n);
+    HIPCHK(e, hipMemcpy(meta2.data(), w.meta2.p, (size_t)n * sizeof(EmailMeta), hipMemcpyDeviceToHost));
+    clean.resize((size_t)raw_total + (size_t)(n + 1) * CLEAN_PER_EMAIL + 256);
+    HIPCHK(e, hipMemcpy(clean.data(), w.clean.p, clean.size(), hipMemcpyDeviceToHost));
+  }
+  auto put = [](uint8_t* base, size_t stride, uint32_t i, const uint8_t* src, size_t len) {
+    if (!base) return;
+    memset(base + (size_t)i * stride, 0, stride);
+    memcpy(base + (size_t)i * stride, src, std::min(len, stride));
+  };
+  for (uint32_t i = 0; i < n; i++) {
+    const EmailMeta& m = meta[i];
+    const uint64_t rel = in.raw_off[i] - in.raw_off[0];
+    const uint32_t raw_len = (uint32_t)(in.raw_off[i + 1] - in.raw_off[i]);
+    const uint8_t* regA = scr.data() + host_scratch_off(in.raw_off, i);
+    const uint8_t* regB = regA + (((size_t)raw_len + PRE_SLACK + 15) & ~(size_t)15);
+    const bool hashed = out[i].canon_header_len || out[i].canon_body_len || m.canon_full_len;
+    put(dbg->canon_header, dbg->canon_header_stride, i, regA, hashed ? out[i].canon_header_len : 0);
+    const uint8_t* body = m.body_src_is_raw ? in.raw_blob + in.raw_off[i] + m.body_off : regB;
+    put(dbg->canon_body, dbg->canon_body_stride, i, body, hashed ? m.canon_full_len : 0);
+    if (dbg->canon_body_full_len) dbg->canon_body_full_len[i] = hashed ? m.canon_full_len : 0;
+    if (dbg->rsa_route) dbg->rsa_route[i] = m.rsa_route;
+    if (dbg->em) put(dbg->em, dbg->em_stride, i, em.data() + (size_t)i * 512 + 512 - std::min<uint32_t>(512, e_k(out[i].rsa_bits)),
+                     std::min<uint32_t>(512, e_k(out[i].rsa_bits)));
+    if (dbg->clean_body && in.with_regex && meta2[i].state == ST_CAND)
+      put(dbg->clean_body, dbg->clean_body_stride, i, clean.data() + (rel + (uint64_t)i * CLEAN_PER_EMAIL), meta2[i].hashed_len);
+    else if (dbg->clean_body)
+      put(dbg->clean_body, dbg->clean_body_stride, i, nullptr, 0);
   }
   return 0;
+}
+
+// Every host entry's submission.  With a ticket: asynchronous (zke_batch_wait or the slot's next batch delivers).  Without: delivered
+// before this returns, the parity intermediates (dbg) copied back under the same slot lock — the slot's next batch overwrites them.
+int submit_host_batch(zke_engine* e, const HostBatch& d, zke_result* out, uint64_t* ticket, const zke_debug_out* dbg = nullptr) {
+  const uint32_t n = d.b.n;
+  if (!n && !ticket) return 0;
+  if (n && (d.L.total > e->host_image_cap.load() || n > e->host_n_cap.load())) if (int r = grow_host_staging(e, d.L.total, n)) return r;
+  std::shared_lock<std::shared_mutex> sh(e->big);
+  HIPCHK(e, hipSetDevice(e->device));
+  uint32_t slot;
+  Slot& w = next_slot(e, slot);
+  std::lock_guard<std::mutex> g(w.mu);
+  if (!n) { *ticket = make_ticket(slot, w.host_retired); return 0; }      // nothing to wait for
+  if (int r = submit_host(e, w, d, out, dbg && dbg->em, dbg && dbg->clean_body)) return r;
+  if (ticket) { *ticket = make_ticket(slot, w.host_gen); return 0; }
+  if (int r = retire_host(e, w)) return r;
+  return dbg ? copy_debug_out(e, w, d.b, out, dbg) : 0;
 }
 
 // ---- the DFA registry (dfa_registry.hip.h has the blob parser and the entry type)
@@ -491,10 +576,7 @@ bool dfa_lookup(zke_engine* e, uint64_t h, const uint8_t* fwd, size_t fl, const 
 int dfa_evict_one(zke_engine* e) {
   std::unique_lock<std::shared_mutex> ex(e->big);
   HIPCHK(e, hipSetDevice(e->device));
-  for (Slot* w : e->slots) {
-    if (w->last_stream && w->last_stream != w->stream) HIPCHK(e, hipEventSynchronize(w->done));
-    HIPCHK(e, hipStreamSynchronize(w->stream));
-  }
+  if (int r = drain_engine(e, false)) return r;
   std::unique_lock<std::shared_mutex> rl(e->reg_mu);
   uint32_t victim = 0xFFFFFFFFu;
   uint64_t oldest = ~0ull;
@@ -579,9 +661,6 @@ void dfa_unpin(zke_engine* e, const std::vector<uint32_t>& ids) {
   for (uint32_t id : ids) e->dfas[id]->pins.fetch_sub(1);          // (a pinned entry is neither evicted nor unregistered: it is there)
 }
 
-// tickets: slot index in the low 6 bits (an engine has at most 64 slots), the slot's batch count above
-inline uint64_t make_ticket(uint32_t slot, uint64_t gen) { return (gen << 6) | slot; }
-
 }  // namespace
 
 extern "C" {
@@ -602,10 +681,7 @@ int zke_dfa_unregister(zke_engine* e, uint32_t id) {
   if (!e) return ZKE_E_ARG;
   std::unique_lock<std::shared_mutex> ex(e->big);         // no submission in progress ...
   HIPCHK(e, hipSetDevice(e->device));
-  for (Slot* w : e->slots) {                              // ... and nothing in flight that could still read the tables
-    if (w->last_stream && w->last_stream != w->stream) HIPCHK(e, hipEventSynchronize(w->done));
-    HIPCHK(e, hipStreamSynchronize(w->stream));
-  }
+  if (int r = drain_engine(e, false)) return r;           // ... and nothing in flight that could still read the tables
   std::unique_lock<std::shared_mutex> rl(e->reg_mu);
   if (id >= e->dfas.size() || !e->dfas[id]) return fail(e, ZKE_E_DFA, "zke_dfa_unregister: id is not registered");
   if (e->dfas[id]->pins.load()) return fail(e, ZKE_E_DFA, "zke_dfa_unregister: a zke_verify_email_with_regex call in progress uses this pair");
@@ -672,10 +748,7 @@ int zke_verify_batch_device(zke_engine* e, const zke_batch* in, uint64_t raw_tot
                             zke_result* out_dev, void* stream) {
   (void)domain_total;
   if (!e) return ZKE_E_ARG;
-  if (!in || (in->n && (!out_dev || !in->raw_blob || !in->raw_off || !in->domain_off || !in->key_off || !in->key_type)))
-    return fail(e, ZKE_E_ARG, "zke_verify_batch_device: null pointer");
-  if (in->with_regex && ((in->n_header_parts && !in->header_part_ids) || (in->n_body_parts && !in->body_part_ids)))
-    return fail(e, ZKE_E_ARG, "zke_verify_batch_device: part-id list is null");
+  if (int r = check_batch_pointers(in, out_dev, false, "zke_verify_batch_device")) return r;
   std::shared_lock<std::shared_mutex> sh(e->big);
   HIPCHK(e, hipSetDevice(e->device));
   // Submission slots are taken round-robin: with S slots, S batches are in flight before a workspace is reused.
@@ -753,18 +826,11 @@ int zke_verify_batch_device(zke_engine* e, const zke_batch* in, uint64_t raw_tot
 }
 
 int zke_verify_batch_async(zke_engine* e, const zke_batch* in, zke_result* out, uint64_t* ticket) {
-  if (int r = check_host_batch(e, in, out, "zke_verify_batch_async: null pointer")) return r;
+  if (!e) return ZKE_E_ARG;
+  HostBatch d;
+  if (int r = host_batch(d, "zke_verify_batch_async", out, in)) return r;
   if (!ticket) return fail(e, ZKE_E_ARG, "zke_verify_batch_async: null ticket");
-  if (in->n) { const size_t img = host_image_bytes(in); if (img > e->host_image_cap.load() || in->n > e->host_n_cap.load()) if (int r = grow_host_staging(e, img, in->n)) return r; }
-  std::shared_lock<std::shared_mutex> sh(e->big);
-  HIPCHK(e, hipSetDevice(e->device));
-  uint32_t slot;
-  Slot& w = next_slot(e, slot);
-  std::lock_guard<std::mutex> g(w.mu);
-  if (in->n == 0) { *ticket = make_ticket(slot, w.host_retired); return 0; }      // nothing to wait for
-  if (int r = submit_host(e, w, in, out, false, false)) return r;
-  *ticket = make_ticket(slot, w.host_gen);
-  return 0;
+  return submit_host_batch(e, d, out, ticket);
 }
 
 int zke_batch_wait(zke_engine* e, uint64_t ticket) {
@@ -783,45 +849,10 @@ int zke_batch_wait(zke_engine* e, uint64_t ticket) {
 int zke_verify_emails_with_regex_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_lists* lists,
                                        zke_result* out, uint64_t* ticket) {
   if (!e) return ZKE_E_ARG;
-  if (!ticket || (n && (!emails || !out))) return fail(e, ZKE_E_ARG, "zke_verify_emails_async: null pointer");
-  RefTotals t;
-  for (uint32_t i = 0; i < n; i++) {
-    const zke_email_ref& m = emails[i];
-    if ((m.raw_len && !m.raw) || (m.domain_len && !m.from_domain) || (m.key_len && !m.key)) return fail(e, ZKE_E_ARG, "zke_verify_emails_async: null buffer with a length");
-    if (m.raw_len > (1ull << 40) || m.domain_len > (1ull << 32) || m.key_len > (1ull << 32)) return fail(e, ZKE_E_ARG, "zke_verify_emails_async: implausible length");
-    t.raw += m.raw_len; t.dom += m.domain_len; t.key += m.key_len;
-  }
-  if (t.raw > (1ull << 40)) return fail(e, ZKE_E_ARG, "raw e-mails beyond 1 TiB");
-  zke_batch proto{};
-  proto.n = n;
-  size_t cap_words = 0, cap_strs = 0, cap_bytes = 0;
-  if (lists) {
-    proto.with_regex = 1;
-    proto.n_header_parts = lists->n_header_parts; proto.header_part_ids = lists->header_part_ids;
-    proto.n_body_parts = lists->n_body_parts; proto.body_part_ids = lists->body_part_ids;
-    proto.cap_off = lists->cap_off; proto.cap_str_off = lists->cap_str_off; proto.cap_blob = lists->cap_blob;
-    if ((proto.n_header_parts && !proto.header_part_ids) || (proto.n_body_parts && !proto.body_part_ids)) return fail(e, ZKE_E_ARG, "part-id list is null");
-    const size_t NP = (size_t)n * ((size_t)proto.n_header_parts + proto.n_body_parts);
-    if (NP && proto.cap_off) {
-      auto rising = [](const uint32_t* off, size_t cnt) { uint32_t bad = 0; for (size_t i = 0; i < cnt; i++) bad |= (uint32_t)(off[i + 1] < off[i]); return !bad; };
-      if (!rising(proto.cap_off, NP) || (proto.cap_off[NP] && (!proto.cap_str_off || !proto.cap_blob || !rising(proto.cap_str_off, proto.cap_off[NP]))))
-        return fail(e, ZKE_E_ARG, "capture offset array is not non-decreasing");
-      if (proto.cap_off[NP] == 0) proto.cap_off = nullptr;            // tables without a single string: the same as no tables
-      else { cap_words = NP + 1; cap_strs = (size_t)proto.cap_off[NP] + 1; cap_bytes = proto.cap_str_off[proto.cap_off[NP]]; }
-    } else {
-      proto.cap_off = nullptr;
-    }
-  }
-  if (n) { const size_t img = image_layout(n, t.raw, t.dom, t.key, cap_words, cap_strs, cap_bytes).total; if (img > e->host_image_cap.load() || n > e->host_n_cap.load()) if (int r = grow_host_staging(e, img, n)) return r; }
-  std::shared_lock<std::shared_mutex> sh(e->big);
-  HIPCHK(e, hipSetDevice(e->device));
-  uint32_t slot;
-  Slot& w = next_slot(e, slot);
-  std::lock_guard<std::mutex> g(w.mu);
-  if (n == 0) { *ticket = make_ticket(slot, w.host_retired); return 0; }
-  if (int r = submit_host(e, w, &proto, out, false, false, emails, &t)) return r;
-  *ticket = make_ticket(slot, w.host_gen);
-  return 0;
+  if (!ticket) return fail(e, ZKE_E_ARG, "zke_verify_emails_async: null pointer");
+  HostBatch d;
+  if (int r = host_batch(d, "zke_verify_emails_async", out, emails, n, lists)) return r;
+  return submit_host_batch(e, d, out, ticket);
 }
 
 int zke_verify_emails_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, zke_result* out, uint64_t* ticket) {
@@ -839,88 +870,17 @@ int zke_verify_emails(zke_engine* e, const zke_email_ref* emails, uint32_t n, zk
 }
 
 int zke_verify_batch(zke_engine* e, const zke_batch* in, zke_result* out, zke_debug_out* dbg) {
-  if (int r = check_host_batch(e, in, out, "zke_verify_batch: null pointer")) return r;
-  const uint32_t n = in->n;
-  if (n == 0) return 0;
-  { const size_t img = host_image_bytes(in); if (img > e->host_image_cap.load() || n > e->host_n_cap.load()) if (int r = grow_host_staging(e, img, n)) return r; }
-  std::shared_lock<std::shared_mutex> sh(e->big);
-  HIPCHK(e, hipSetDevice(e->device));
-  uint32_t slot;
-  Slot& w = next_slot(e, slot);
-  std::lock_guard<std::mutex> g(w.mu);
-  const bool want_em = dbg && dbg->em;
-  if (int r = submit_host(e, w, in, out, want_em, dbg && dbg->clean_body)) return r;
-  if (int r = retire_host(e, w)) return r;
-  if (!dbg) return 0;
-
-  // parity intermediates (tests): copy the slot's scratch back and slice it on the host; the slot's lock is still held
-  const uint64_t raw_total = in->raw_off[n] - in->raw_off[0];
-  std::vector<EmailMeta> meta(n), meta2;
-  HIPCHK(e, hipMemcpy(meta.data(), w.meta.p, (size_t)n * sizeof(EmailMeta), hipMemcpyDeviceToHost));
-  const size_t scratch_bytes = 2 * (size_t)raw_total + (size_t)(n + 1) * SCR_PER_EMAIL + 256;
-  std::vector<uint8_t> scr(scratch_bytes);
-  HIPCHK(e, hipMemcpy(scr.data(), w.scratch.p, scratch_bytes, hipMemcpyDeviceToHost));
-  std::vector<uint8_t> em, clean;
-  if (dbg->em) { em.resize((size_t)n * 512); HIPCHK(e, hipMemcpy(em.data(), w.em_dbg.p, em.size(), hipMemcpyDeviceToHost)); }
-  if (dbg->clean_body && in->with_regex) {
-    meta2.resize(n);
-    HIPCHK(e, hipMemcpy(meta2.data(), w.meta2.p, (size_t)n * sizeof(EmailMeta), hipMemcpyDeviceToHost));
-    clean.resize((size_t)raw_total + (size_t)(n + 1) * CLEAN_PER_EMAIL + 256);
-    HIPCHK(e, hipMemcpy(clean.data(), w.clean.p, clean.size(), hipMemcpyDeviceToHost));
-  }
-  auto put = [](uint8_t* base, size_t stride, uint32_t i, const uint8_t* src, size_t len) {
-    if (!base) return;
-    memset(base + (size_t)i * stride, 0, stride);
-    memcpy(base + (size_t)i * stride, src, std::min(len, stride));
-  };
-  for (uint32_t i = 0; i < n; i++) {
-    const EmailMeta& m = meta[i];
-    const uint64_t rel = in->raw_off[i] - in->raw_off[0];
-    const uint32_t raw_len = (uint32_t)(in->raw_off[i + 1] - in->raw_off[i]);
-    const uint8_t* regA = scr.data() + host_scratch_off(in->raw_off, i);
-    const uint8_t* regB = regA + (((size_t)raw_len + PRE_SLACK + 15) & ~(size_t)15);
-    const bool hashed = out[i].canon_header_len || out[i].canon_body_len || m.canon_full_len;
-    put(dbg->canon_header, dbg->canon_header_stride, i, regA, hashed ? out[i].canon_header_len : 0);
-    const uint8_t* body = m.body_src_is_raw ? in->raw_blob + in->raw_off[i] + m.body_off : regB;
-    put(dbg->canon_body, dbg->canon_body_stride, i, body, hashed ? m.canon_full_len : 0);
-    if (dbg->canon_body_full_len) dbg->canon_body_full_len[i] = hashed ? m.canon_full_len : 0;
-    if (dbg->rsa_route) dbg->rsa_route[i] = m.rsa_route;
-    if (dbg->em) put(dbg->em, dbg->em_stride, i, em.data() + (size_t)i * 512 + 512 - std::min<uint32_t>(512, e_k(out[i].rsa_bits)),
-                     std::min<uint32_t>(512, e_k(out[i].rsa_bits)));
-    if (dbg->clean_body && in->with_regex && meta2[i].state == ST_CAND)
-      put(dbg->clean_body, dbg->clean_body_stride, i, clean.data() + (rel + (uint64_t)i * CLEAN_PER_EMAIL), meta2[i].hashed_len);
-    else if (dbg->clean_body)
-      put(dbg->clean_body, dbg->clean_body_stride, i, nullptr, 0);
-  }
-  return 0;
+  if (!e) return ZKE_E_ARG;
+  HostBatch d;
+  if (int r = host_batch(d, "zke_verify_batch", out, in)) return r;
+  return submit_host_batch(e, d, out, nullptr, dbg);
 }
 
-// ---- single-e-mail wrappers: a batch of one (config 1 and API-shape parity)
-namespace {
-struct OneEmail {
-  uint64_t ro[2], dofs[2], ko[2];
-  uint8_t kt, ext;
-  zke_batch b{};
-  OneEmail(const uint8_t* raw, size_t raw_len, const char* from_domain, size_t domain_len, const uint8_t* key, size_t key_len,
-           uint32_t key_type, uint32_t external_input_null)
-      : ro{0, raw_len}, dofs{0, domain_len}, ko{0, key_len}, kt((uint8_t)(key_type > ZKE_KEY_OTHER ? ZKE_KEY_OTHER : key_type)),
-        ext(external_input_null ? 1 : 0) {
-    static const uint8_t dummy = 0;
-    b.n = 1;
-    b.raw_blob = raw ? raw : &dummy; b.raw_off = ro;
-    b.domain_blob = from_domain ? reinterpret_cast<const uint8_t*>(from_domain) : &dummy; b.domain_off = dofs;
-    b.key_blob = key ? key : &dummy; b.key_off = ko;
-    b.key_type = &kt; b.ext_null = &ext;
-  }
-};
-}  // namespace
-
+// ---- single-e-mail wrappers: a batch of one through the gathering entry (config 1 and API-shape parity)
 int zke_verify_email(zke_engine* e, const uint8_t* raw, size_t raw_len, const char* from_domain, size_t domain_len,
                      const uint8_t* key, size_t key_len, uint32_t key_type, uint32_t external_input_null, zke_result* out) {
-  if (!e) return ZKE_E_ARG;
-  if (!out || (raw_len && !raw) || (domain_len && !from_domain) || (key_len && !key)) return fail(e, ZKE_E_ARG, "zke_verify_email: null pointer");
-  OneEmail one(raw, raw_len, from_domain, domain_len, key, key_len, key_type, external_input_null);
-  return zke_verify_batch(e, &one.b, out, nullptr);
+  const zke_email_ref one{raw, raw_len, from_domain, domain_len, key, key_len, key_type, external_input_null};
+  return zke_verify_emails_with_regex(e, &one, 1, nullptr, out);
 }
 
 int zke_verify_email_with_regex(zke_engine* e, const uint8_t* raw, size_t raw_len, const char* from_domain, size_t domain_len,
@@ -928,10 +888,7 @@ int zke_verify_email_with_regex(zke_engine* e, const uint8_t* raw, size_t raw_le
                                 const zke_regex_part* header_parts, uint32_t n_header_parts,
                                 const zke_regex_part* body_parts, uint32_t n_body_parts, zke_result* out) {
   if (!e) return ZKE_E_ARG;
-  if (!out || (raw_len && !raw) || (domain_len && !from_domain) || (key_len && !key) || (n_header_parts && !header_parts) ||
-      (n_body_parts && !body_parts))
-    return fail(e, ZKE_E_ARG, "zke_verify_email_with_regex: null pointer");
-  OneEmail one(raw, raw_len, from_domain, domain_len, key, key_len, key_type, external_input_null);
+  if ((n_header_parts && !header_parts) || (n_body_parts && !body_parts)) return fail(e, ZKE_E_ARG, "zke_verify_email_with_regex: null pointer");
   std::vector<uint32_t> hids, bids, cap_off{0}, str_off{0};
   std::vector<uint8_t> blob;
   // every pair this call registers or finds stays pinned until the batch has run: with the registry at its cap another
@@ -957,13 +914,10 @@ int zke_verify_email_with_regex(zke_engine* e, const uint8_t* raw, size_t raw_le
       cap_off.push_back((uint32_t)str_off.size() - 1);
     }
   }
-  if (blob.empty()) blob.push_back(0);
-  zke_batch& b = one.b;
-  b.with_regex = 1;
-  b.n_header_parts = n_header_parts; b.n_body_parts = n_body_parts;
-  b.header_part_ids = hids.data(); b.body_part_ids = bids.data();
-  b.cap_off = cap_off.data(); b.cap_str_off = str_off.data(); b.cap_blob = blob.data();
-  return zke_verify_batch(e, &b, out, nullptr);
+  if (blob.empty()) blob.push_back(0);          // (captures that are all empty strings still want a blob pointer)
+  const zke_email_ref one{raw, raw_len, from_domain, domain_len, key, key_len, key_type, external_input_null};
+  const zke_regex_lists lists{n_header_parts, hids.data(), n_body_parts, bids.data(), cap_off.data(), str_off.data(), blob.data()};
+  return zke_verify_emails_with_regex(e, &one, 1, &lists, out);
 }
 
 }  // extern "C"

@@ -305,9 +305,6 @@ class Engine:
         return out
 
     # ---- zkemail_core mirror
-    def verify_emails(self, emails: Sequence[Email]) -> np.ndarray:
-        return self.verify_batch(PackedBatch(emails))
-
     def pack_with_regex(self, inputs: Sequence[EmailWithRegex]) -> PackedBatch:
         """All inputs must share one part list (one regex_config per batch); captures are per e-mail."""
         first = inputs[0].regex_info
