@@ -242,7 +242,7 @@ pub fn default_options(device: i32) -> sys::zke_options {
         canon_ignores_l: 0,
         i_must_be_subdomain: 0,
         b_removes_own_span_only: 0,
-        reserved0: 0,
+        sha_mapping: 0,
         now_unix: 0,
         reserved: [0; 4],
     }

@@ -221,7 +221,7 @@ typedef struct zke_options {
                                    thread alone).  zke_verify_batch[_async] only. */
   uint32_t max_dfas;            /* DFA pairs the registry holds before it evicts pairs that zke_verify_email_with_regex registered
                                    on its own (0 = 4096) */
-  /* kernel variants (0 = chosen by batch size; the parity tests force each) */
+  /* kernel variants (0 = chosen by batch size; the parity tests force each; sha_mapping below is one more) */
   uint32_t rsa_lane_groups;     /* 1: never the four- / eight-lanes-per-signature RSA routines; 2: always */
   uint32_t dfa_mapping;         /* 1: one e-mail per lane for every regex part; 2: one e-mail per wave for every part */
   uint32_t replay_graphs;       /* 1: zke_verify_batch_device replays a captured hipGraph when a slot sees the same descriptor
@@ -240,7 +240,9 @@ typedef struct zke_options {
                                             last '@') equals d= or ends with "." d=, case-insensitively (RFC 6376 §3.5) */
   uint32_t b_removes_own_span_only;      /* 0: the raw b= value is removed wherever it occurs in the header (String::replace);
                                             1: only the b= tag's own span is emptied */
-  uint32_t reserved0;
+  /* one more kernel variant, as rsa_lane_groups / dfa_mapping above (0 = chosen by launch size; the parity tests force each) */
+  uint32_t sha_mapping;         /* hash stage — 1: always one wave per 64 messages (for a batch: a hash launch of its own, then the
+                                   RSA roles); 2: always two waves per 64 messages (for a batch: fused with the RSA roles) */
   uint64_t now_unix;            /* the time x= is compared with (enforce_expiry_x); 0 = the host clock at submission */
   uint64_t reserved[4];         /* 0 */
 } zke_options;

@@ -366,15 +366,26 @@ def build_limit_cases() -> List[Case]:
     return cs
 
 
-def multi_signature_case(n_bad: int) -> Case:
-    """n_bad same-domain signatures over a different body (body hash fails), then the good one."""
+_BAD_SIG_CACHE: dict = {}
+
+
+def multi_signature_case(n_bad: int, body: Optional[bytes] = None, spec: Optional[SignSpec] = None, hdr_pad: int = 0) -> Case:
+    """n_bad same-domain signatures over a different body (body hash fails), then the good one.  `body` / `spec`: the good
+    signature's body and SignSpec (default: 333 bytes, relaxed/relaxed rsa-sha256); `hdr_pad`: bytes appended to the signed
+    Subject, which lengthen the header preimage of every signature by as much."""
     k0 = K()
-    hs, body = _hdrs(40), _body(333, 40)
-    raw, inter = sign_email(hs, body, k0, SignSpec())
+    hs = _hdrs(40)
+    if hdr_pad:
+        hs = [(n, v + b"p" * hdr_pad if n == b"Subject" else v) for n, v in hs]
+    if body is None:
+        body = _body(333, 40)
+    raw, inter = sign_email(hs, body, k0, spec or SignSpec())
     prefix = b""
     for j in range(n_bad):
-        raw_bad, _ = sign_email(hs, _body(120 + j, 41 + j), k0, SignSpec(selector=f"old{j}"))
-        prefix += raw_bad[:raw_bad.find(b"Received:")]
+        if (hdr_pad, j) not in _BAD_SIG_CACHE:            # (the failing signatures depend on the headers only)
+            raw_bad, _ = sign_email(hs, _body(120 + j, 41 + j), k0, SignSpec(selector=f"old{j}"))
+            _BAD_SIG_CACHE[(hdr_pad, j)] = raw_bad[:raw_bad.find(b"Received:")]
+        prefix += _BAD_SIG_CACHE[(hdr_pad, j)]
     return Case(f"pass_after_{n_bad}_failed_signatures", Email("example.com", prefix + raw, PublicKey(k0.pkcs1_der)), A.ZKE_OK, None, inter)
 
 

@@ -405,6 +405,30 @@ def test_rsa_quad_kernel_variant_parity():
     assert r.returncode == 0 and "rsa quad ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
+def test_sha_one_wave_kernel_variant_parity():
+    """The one-wave-per-64-messages SHA kernel (csrc/sha256.hip.h, sha256_batch_kernel) and the split hash / RSA launch are chosen
+    for batches of more than 8 192 e-mails; forced on (zke_options.sha_mapping = 1) they must give the oracle's records on the
+    corpus (the rsa-sha1 cases included), the fuzz set, the ragged rsa-sha1 workload, several signature rounds and mixed key types."""
+    import os, subprocess, sys, textwrap
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = textwrap.dedent(f"""
+        import sys
+        sys.path.insert(0, {root!r}); sys.path.insert(0, {os.path.join(root, 'tests')!r})
+        import oracle_lib, cases, test_gpu_verify as t
+        import zkemail_rs_amd as z
+        eng, orc = z.Engine(sha_mapping=1), oracle_lib.load()
+        t.test_case_corpus_parity(eng, orc)
+        for seed in (99, 7, 2026):
+            t.test_mutation_fuzz_parity(eng, orc, seed)
+        t.test_workload_parity(eng, orc, dict(n=150, body_len=9000, rsa_bits=2048, seed=12, ragged=True, invalid_frac=0.15, algo="rsa-sha1"))
+        t.test_signature_rounds(eng, orc)
+        t.test_mixed_key_types_one_batch(eng, orc)
+        print("sha one wave ok")
+    """)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "sha one wave ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 def test_rsa_routing_through_the_key_cache(engine, oracle):
     """The front end routes a signature to the lane-group RSA routine when its key's Montgomery constants are cached (the
     modulus compared limb by limb), else to the one-signature-per-wave routine, which fills the cache.  Fresh keys: the first

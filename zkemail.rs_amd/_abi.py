@@ -206,7 +206,7 @@ class zke_options(C.Structure):
         ("host_threads", C.c_uint32), ("max_dfas", C.c_uint32),
         ("rsa_lane_groups", C.c_uint32), ("dfa_mapping", C.c_uint32), ("replay_graphs", C.c_uint32),
         ("enforce_expiry_x", C.c_uint32), ("canon_takes_verified_signature", C.c_uint32), ("canon_ignores_l", C.c_uint32),
-        ("i_must_be_subdomain", C.c_uint32), ("b_removes_own_span_only", C.c_uint32), ("reserved0", C.c_uint32),
+        ("i_must_be_subdomain", C.c_uint32), ("b_removes_own_span_only", C.c_uint32), ("sha_mapping", C.c_uint32),
         ("now_unix", C.c_uint64), ("reserved", C.c_uint64 * 4),
     ]
 

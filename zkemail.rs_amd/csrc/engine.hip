@@ -56,7 +56,7 @@ struct DevBuf {
 
 inline uint32_t e_k(uint32_t bits) { return (bits + 7) / 8; }
 constexpr int SHA_TILE = 128;                      // bytes of a message per LDS tile (sha256.hip.h)
-constexpr uint32_t SHA_PAIR_MAX_GROUPS = 512;      // launches of up to 32 768 messages use two waves per 64 messages
+constexpr uint32_t SHA_PAIR_MAX_GROUPS = 512;      // launches of up to 32 768 messages use two waves per 64 messages (zke_options.sha_mapping forces either)
 
 }  // namespace
 
@@ -157,12 +157,18 @@ int fail(zke_engine* e, int code, const char* what, hipError_t he = hipSuccess) 
 }
 #define HIPCHK(e, call) do { hipError_t _r = (call); if (_r != hipSuccess) return fail((e), ZKE_E_DEVICE, #call, _r); } while (0)
 
+// Two waves per 64 messages (sha256_pair_group) or one (sha256_batch_kernel) for a hash launch of `groups` groups of 64 messages.
+// zke_options.sha_mapping: 0 = by launch size, 1 always one wave, 2 always two.
+bool sha_takes_pairs(const zke_engine* e, uint32_t groups) {
+  return e->opt.sha_mapping ? e->opt.sha_mapping == 2 : groups <= SHA_PAIR_MAX_GROUPS;
+}
+
 int launch_sha(zke_engine* e, const ShaJob* jobs, uint32_t n, hipStream_t s) {
   if (n == 0) return 0;
   // Few messages: the launch is as long as one wave's chain of compressions, so split the chain over two waves
   // (sha256_pair_kernel).  Many messages: the chip is full and the one-wave kernel does less LDS work per byte.
   const uint32_t groups = (n + 63) / 64;
-  if (groups <= SHA_PAIR_MAX_GROUPS) {
+  if (sha_takes_pairs(e, groups)) {
     hipLaunchKernelGGL(sha256_pair_kernel<SHA_TILE>, dim3(groups), dim3(128), sha256_pair_lds_bytes<SHA_TILE>(), s, jobs, n);
   } else {
     hipLaunchKernelGGL(sha256_batch_kernel<SHA_TILE>, dim3((n + 255) / 256), dim3(256), sha256_lds_bytes<SHA_TILE>(), s, jobs, n);
@@ -268,7 +274,7 @@ int launch_hash_modexp(zke_engine* e, const ShaJob* sha, uint32_t n_sha, const R
   A.g_oct = (route_mask & 2u) ? (n + 15) / 16 : 0;
   A.debug_skip_rsa = e->debug_skip_rsa;
   const uint32_t groups = (n_sha + 63) / 64;
-  if (groups <= SHA_PAIR_MAX_GROUPS) {
+  if (sha_takes_pairs(e, groups)) {
     A.g_sha = groups;
     return launch_stage(e, A, s);
   }
@@ -407,7 +413,7 @@ int zke_engine_create(const zke_options* opt, zke_engine** out) {
   if (opt) e->opt = *opt; else e->opt.device = -1;
   zke_options& o = e->opt;
   if (o.slots == 0) o.slots = 1;
-  if (o.slots > 64 || o.rsa_lane_groups > 2 || o.dfa_mapping > 2) { delete e; return fail(nullptr, ZKE_E_ARG, "zke_options: field out of range"); }
+  if (o.slots > 64 || o.rsa_lane_groups > 2 || o.dfa_mapping > 2 || o.sha_mapping > 2) { delete e; return fail(nullptr, ZKE_E_ARG, "zke_options: field out of range"); }
   o.max_sig_rounds = o.max_sig_rounds ? std::min<uint32_t>(o.max_sig_rounds, ZKE_MAX_HEADERS) : 16u;
   if (o.host_threads == 0) o.host_threads = 4;
   o.host_threads = std::min<uint32_t>(o.host_threads, 64);

@@ -8,8 +8,9 @@
 // from the batch: ONE MESSAGE PER LANE for the compression (64 messages per wavefront,
 // all 64 lanes doing integer VALU work), while the bytes are fetched WAVE-COOPERATIVELY:
 // for each tile of T bytes the 64 lanes read each message's tile with 16-byte
-// lane-contiguous global loads (T/16 lanes cover one message's tile -> 256-byte
-// contiguous segments at T=256), park it in the wave's private LDS slab, and every lane
+// lane-contiguous global loads (T/16 lanes cover one message's tile -> T-byte contiguous
+// segments; the engine compiles T = SHA_TILE = 128: 8 lanes per message, two SHA blocks
+// per tile), park it in the wave's private LDS slab, and every lane
 // then pulls its own message's 64-byte blocks back with ds_read_b128.  Row stride T+16
 // bytes keeps both the ds_write_b128 and the ds_read_b128 phases conflict-free
 // (lane stride = 4 banks mod 64).  No __syncthreads: a wave's LDS operations execute in
@@ -136,7 +137,8 @@ typedef const uint8_t __attribute__((address_space(1)))* gptr_u8;
 typedef uint32_t __attribute__((address_space(1)))* gptr_out32;
 
 // Launch: blockDim = 256 (4 independent waves), grid = ceil(n / 256).
-// LDS: 4 waves * 64 rows * (T + 16) bytes  (T = 256 -> 69,632 B per block).
+// LDS (sha256_lds_bytes): 4 waves * (64 rows * (T + 16) bytes + 64 descriptors * 16 bytes) — 40 960 B per block at the
+// engine's T = SHA_TILE = 128 (engine.hip); 73 728 B at T = 256.
 template <int T>
 __global__ __launch_bounds__(256) void sha256_batch_kernel(const ShaJob* __restrict__ jobs, uint32_t n) {
   static_assert(T % 64 == 0 && T >= 64 && T <= 1024, "tile must be whole SHA blocks");

@@ -149,7 +149,8 @@ class Engine:
 
     def __init__(self, device: int = -1, max_sig_rounds: int = 0, **options):
         """`options`: any other field of ``zke_options`` by name — ``slots``, ``host_threads``, ``disable_key_cache``,
-        ``max_dfas``, the kernel variants ``rsa_lane_groups`` / ``dfa_mapping`` (0 by batch size, 1 / 2 forced),
+        ``max_dfas``, the kernel variants ``rsa_lane_groups`` / ``dfa_mapping`` / ``sha_mapping`` (0 by batch size, 1 / 2 forced;
+        ``sha_mapping`` 1: the hash stage always runs one wave per 64 messages, 2: always two),
         ``replay_graphs``, the strictness flags of ``_abi.STRICT_FLAGS`` and ``now_unix``."""
         self.lib = load_library()
         if not self.lib.zke_device_available():
@@ -157,7 +158,7 @@ class Engine:
         opt = A.zke_options()
         opt.device = device
         opt.max_sig_rounds = max_sig_rounds          # same-domain signatures tried per e-mail (0 = the default, 16)
-        names = {f[0] for f in A.zke_options._fields_} - {"reserved", "reserved0"}
+        names = {f[0] for f in A.zke_options._fields_} - {"reserved"}
         for k, v in options.items():
             if k not in names:
                 raise TypeError(f"zke_options has no field {k!r}")
