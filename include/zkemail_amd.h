@@ -115,7 +115,16 @@ enum {
   ZKE_D_DFA_SPECIAL          = 76, /* the eight special-state bounds */
   ZKE_D_DFA_ACCELS           = 77, /* accelerator count and records */
   ZKE_D_DFA_QUITSET          = 78, /* the 256-bit quit set */
-  ZKE_D_DFA_UNREGISTERED     = 79  /* the part id names no registered pair (never registered, or unregistered since) */
+  ZKE_D_DFA_UNREGISTERED     = 79, /* the part id names no registered pair (never registered, or unregistered since) */
+  /* capture extraction (zke_extract_captures, zke_capture_batch): helpers/src/regex.rs:16-51 */
+  ZKE_D_RE_GROUP_MISSING     = 90, /* a requested group is not in the pattern or took no part in the match ("Capture group not found",
+                                      helpers/src/regex.rs:31); status ZKE_HEADER_REGEX_FAIL / ZKE_BODY_REGEX_FAIL */
+  /* ZKE_UNSUPPORTED, continued */
+  ZKE_D_U_CAPTURE_STATES     = 91, /* the capture program has more than ZKE_CAP_MAX_STATES states or ZKE_CAP_MAX_PROGRAM_GROUPS groups */
+  ZKE_D_U_CAPTURE_SPAN       = 92, /* the match is longer than ZKE_CAP_MAX_SPAN bytes */
+  ZKE_D_U_CAPTURE_WALK       = 93, /* the capture program cannot reproduce the span its DFA pair found (the two were not compiled
+                                      from one pattern, or the walk met a case it does not implement): reported, never guessed */
+  ZKE_D_U_CAPTURE_PROGRAM    = 94  /* the capture program does not decode, or its id is not registered */
 };
 #define ZKE_D_DFA_BWD_OFFSET 10u /* added to ZKE_D_DFA_LABEL .. ZKE_D_DFA_QUITSET when the reverse blob is the one that fails (80..88) */
 
@@ -123,6 +132,12 @@ enum {
 #define ZKE_MAX_TAGS    32u    /* tag-specs per DKIM-Signature */
 #define ZKE_MAX_TAGBUF  2048u  /* bytes of FWS-stripped tag values per DKIM-Signature */
 #define ZKE_MAX_RSA_BYTES 512u /* RSA-4096, the rsa crate's ceiling (rsa 0.9.6 RsaPublicKey::MAX_SIZE) */
+#define ZKE_CAP_MAX_STATES 8192u        /* states of a capture program (zke_capture_register) */
+#define ZKE_CAP_MAX_PROGRAM_GROUPS 32u  /* groups of a capture program, group 0 included */
+#define ZKE_CAP_MAX_GROUPS 16u          /* groups requested per part (zke_capture_part.n_groups) */
+#define ZKE_CAP_MAX_SPAN   4096u        /* bytes of a match whose groups are extracted */
+#define ZKE_CAP_MAX_PARTS  16u          /* parts of one extraction batch */
+#define ZKE_CAPF_NOT_UTF8  1u           /* zke_capture_out.flags: the group's bytes are not valid UTF-8 (the host applies from_utf8_lossy) */
 #define ZKE_KEY_RSA 0u
 #define ZKE_KEY_ED25519 1u
 #define ZKE_KEY_OTHER 2u
@@ -304,7 +319,12 @@ const char* zke_last_error(const zke_engine* e);
  * zke_engine_reserve(e, max_n, max_raw_total, slots, max_regex_parts) raises the slot count to `slots` (1..64) and sizes
  * every slot's workspace for batches of up to max_n e-mails / max_raw_total raw bytes (max_regex_parts > 0: the
  * verify_email_with_regex buffers too), so that no allocation happens in the submit path afterwards.  A larger batch
- * still works: its slot grows (one synchronising reallocation). */
+ * still works: its slot grows (one synchronising reallocation).
+ * With max_regex_parts > 0 every slot also gets the buffers of a capture extraction (zke_extract_captures), whether or not the
+ * caller ever extracts: the spans, flags and tables of max_n e-mails with FOUR requested groups per part and 32 bytes of blob per
+ * group, their pinned twin (host memory), and 34.6 MB of HBM for the reachability rows of capture programs with more than 512
+ * states.  An extraction with more groups per part, or whose caller passes a larger cap_blob, regrows its slot's buffers on first
+ * use (one synchronising reallocation), as a larger batch does. */
 int zke_engine_reserve(zke_engine* e, uint32_t max_n, uint64_t max_raw_total, uint32_t slots, uint32_t max_regex_parts);
 /* The same for the host entry's staging: every slot's pinned input image and record buffer (and their HBM twins) are sized
  * for batches of up to max_n e-mails whose inputs — raw e-mails + from_domains + keys (+ captures) — total max_input_bytes.
@@ -367,6 +387,71 @@ typedef struct zke_regex_lists {
 int zke_verify_emails_with_regex(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_lists* lists, zke_result* out);
 int zke_verify_emails_with_regex_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_lists* lists,
                                        zke_result* out, uint64_t* ticket);
+
+/* ---- capture extraction: the compute half of the reference's input generation (helpers/src/generator.rs:55-87 ->
+ * helpers/src/regex.rs:16-51) — canonicalise, remove the QP soft breaks, require exactly one match per pattern, run the capturing
+ * automaton over the match and turn the groups named by capture_indices into strings.  The DNS key fetch and the file IO stay with
+ * the caller.  A capture program is the pattern's Thompson NFA with its capture states (zkemail_rs_amd.regex_compile.
+ * create_capture_program; layout: DESIGN.md §3), registered once like a DFA pair: validated on the host — every state index, slot
+ * and range — before a table reaches the device, de-duplicated by content.  A program that does not decode, or exceeds
+ * ZKE_CAP_MAX_STATES / ZKE_CAP_MAX_PROGRAM_GROUPS, still gets an id; zke_capture_status says which (0, ZKE_D_U_CAPTURE_PROGRAM,
+ * ZKE_D_U_CAPTURE_STATES) and e-mails that use it report ZKE_UNSUPPORTED with that detail. */
+int zke_capture_register(zke_engine* e, const uint8_t* prog, size_t len, uint32_t* out_id);
+int zke_capture_status(zke_engine* e, uint32_t id, uint32_t* detail);
+int zke_capture_unregister(zke_engine* e, uint32_t id);      /* waits for the batches in flight */
+/* The same check without an engine or a GPU (pure host code): *detail as zke_capture_status reports it. */
+int zke_capture_validate(const uint8_t* prog, size_t len, uint32_t* detail);
+
+typedef struct zke_capture_part {
+  uint32_t dfa_id;                 /* from zke_dfa_register: finds the match */
+  uint32_t prog_id;                /* from zke_capture_register: the same pattern's capture program */
+  uint32_t n_groups;               /* <= ZKE_CAP_MAX_GROUPS */
+  const uint32_t* groups;          /* [n_groups] RegexPattern.capture_indices (group 0 = the whole match) */
+} zke_capture_part;
+
+/* Where the extraction goes: caller-sized buffers, the sizes needed written back (the zke_abi_encode convention).  With G = the
+ * sum of n_groups over the parts and P parts: spans, flags, cap_off and cap_str_off have sizes known up front — n*G*2, n*G, n*P+1
+ * and n*G+1 entries; a call whose buffers are smaller fails at once with ZKE_E_NOMEM and the *_need fields set.  cap_blob's size
+ * depends on the e-mails: when it is too small the call (zke_batch_wait for the asynchronous form) returns ZKE_E_NOMEM, records,
+ * spans, flags and both offset tables are delivered all the same, and cap_blob_need says what a second call needs (a group's bytes
+ * never exceed its match span, so n * G * ZKE_CAP_MAX_SPAN always suffices).  String offsets are 32-bit as in zke_batch: a call with
+ * n * G * ZKE_CAP_MAX_SPAN >= 4 GiB (n * G >= 2^20) is refused with ZKE_E_ARG — split the batch.
+ *   spans  {start, end} per (e-mail, requested group), relative to the part's haystack — the canonical header for header parts,
+ *          the QP-cleaned canonical body for body parts; {0xFFFFFFFF, 0xFFFFFFFF}: no string (the e-mail failed)
+ *   flags  ZKE_CAPF_* per (e-mail, requested group)
+ *   cap_off / cap_str_off / cap_blob   the capture tables exactly as zke_batch / zke_regex_lists take them: raw bytes, no UTF-8
+ *          repair.  An e-mail whose record is not ZKE_OK has no strings. */
+typedef struct zke_capture_out {
+  uint32_t* spans;       size_t spans_cap;         /* capacities in ENTRIES of the array's type */
+  uint8_t*  flags;       size_t flags_cap;
+  uint32_t* cap_off;     size_t cap_off_cap;
+  uint32_t* cap_str_off; size_t cap_str_off_cap;
+  uint8_t*  cap_blob;    size_t cap_blob_cap;
+  size_t spans_need, flags_need, cap_off_need, cap_str_off_need, cap_blob_need;     /* written by the call */
+  size_t n_strings;                                                                 /* entries of cap_str_off in use, minus one */
+} zke_capture_out;
+
+/* verify_email + the extraction over n e-mails that share one part list, on the gathering host entry (same slots, tickets and
+ * zke_batch_wait as zke_verify_emails_async).  Records: DKIM failure -> its usual status; match count != 1 -> ZKE_HEADER_REGEX_FAIL
+ * / ZKE_BODY_REGEX_FAIL + ZKE_D_RE_MATCH_COUNT ("Input doesn't match regex pattern"); a requested group absent or not taking part
+ * -> the same statuses + ZKE_D_RE_GROUP_MISSING; over a limit -> ZKE_UNSUPPORTED + ZKE_D_U_CAPTURE_*.  ONE fold, as
+ * compile_regex_parts walks the parts (helpers/src/regex.rs:21-47: a part's match count, then its groups, then the next part): the
+ * record names the first part in verify order (header parts, then body parts) that fails for any reason — a missing group in part 0
+ * is reported in front of a wrong match count in part 1; regex_part, match_count, match_start, match_end keep their meaning and
+ * are those of the part named.  At most ZKE_CAP_MAX_PARTS parts per call (ZKE_E_ARG beyond).  `caps` (and what it points to) must stay valid until the batch has been waited for. */
+int zke_extract_captures(zke_engine* e, const zke_email_ref* emails, uint32_t n,
+                         const zke_capture_part* header_parts, uint32_t n_header_parts,
+                         const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out, zke_capture_out* caps);
+int zke_extract_captures_async(zke_engine* e, const zke_email_ref* emails, uint32_t n,
+                               const zke_capture_part* header_parts, uint32_t n_header_parts,
+                               const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out, zke_capture_out* caps,
+                               uint64_t* ticket);
+/* Building block: one part over n plain host haystacks hay_blob[hay_off[i] .. hay_off[i+1]) — find the match (exactly one, as
+ * core/src/regex.rs:37 counts), extract the groups.  matches[4*i ..] = {code, count, start, end}: code 0, or the ZKE_D_* that
+ * fails the haystack (ZKE_D_RE_MATCH_COUNT, ZKE_D_RE_QUIT, ZKE_D_RE_GROUP_MISSING, ZKE_D_U_CAPTURE_*; an undecodable DFA pair:
+ * its ZKE_D_DFA_* section).  `caps` as above with P = 1, G = n_groups. */
+int zke_capture_batch(zke_engine* e, uint32_t dfa_id, uint32_t prog_id, const uint32_t* groups, uint32_t n_groups,
+                      const uint8_t* hay_blob, const uint64_t* hay_off, uint32_t n, uint32_t* matches, zke_capture_out* caps);
 
 /* Device-resident batch: every pointer in `in` and `out_dev` is device memory (the part-id lists stay host arrays);
  * `raw_total`, `domain_total`, `key_total` are the blob sizes (the CSR tails), which the

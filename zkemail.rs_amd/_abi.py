@@ -84,6 +84,10 @@ D_U_MIME_DEPTH = 69
 D_DFA_LABEL, D_DFA_ENDIAN_VERSION, D_DFA_FLAGS, D_DFA_TRANSITIONS, D_DFA_START_TABLE = 70, 71, 72, 73, 74
 D_DFA_MATCH_STATES, D_DFA_SPECIAL, D_DFA_ACCELS, D_DFA_QUITSET, D_DFA_UNREGISTERED = 75, 76, 77, 78, 79
 D_DFA_BWD_OFFSET = 10
+D_RE_GROUP_MISSING = 90
+D_U_CAPTURE_STATES, D_U_CAPTURE_SPAN, D_U_CAPTURE_WALK, D_U_CAPTURE_PROGRAM = 91, 92, 93, 94
+CAP_MAX_STATES, CAP_MAX_PROGRAM_GROUPS, CAP_MAX_GROUPS, CAP_MAX_SPAN, CAP_MAX_PARTS = 8192, 32, 16, 4096, 16
+CAPF_NOT_UTF8 = 1
 
 KEY_RSA, KEY_ED25519, KEY_OTHER = 0, 1, 2
 F_HDR_RELAXED, F_BODY_RELAXED, F_HAS_LENGTH, F_SHA1, F_ED25519 = 1, 2, 4, 8, 16
@@ -148,6 +152,22 @@ class zke_regex_part(C.Structure):
     _fields_ = [
         ("fwd", C.c_void_p), ("fwd_len", C.c_size_t), ("bwd", C.c_void_p), ("bwd_len", C.c_size_t),
         ("n_captures", C.c_uint32), ("captures", C.POINTER(C.c_void_p)), ("capture_lens", C.POINTER(C.c_size_t)),
+    ]
+
+
+class zke_capture_part(C.Structure):
+    """One part of an extraction (zke_extract_captures): the DFA pair that finds the match, the capture program, the groups."""
+    _fields_ = [("dfa_id", C.c_uint32), ("prog_id", C.c_uint32), ("n_groups", C.c_uint32), ("groups", C.c_void_p)]
+
+
+class zke_capture_out(C.Structure):
+    """Caller-sized buffers of an extraction; capacities in entries, the sizes needed written back."""
+    _fields_ = [
+        ("spans", C.c_void_p), ("spans_cap", C.c_size_t), ("flags", C.c_void_p), ("flags_cap", C.c_size_t),
+        ("cap_off", C.c_void_p), ("cap_off_cap", C.c_size_t), ("cap_str_off", C.c_void_p), ("cap_str_off_cap", C.c_size_t),
+        ("cap_blob", C.c_void_p), ("cap_blob_cap", C.c_size_t),
+        ("spans_need", C.c_size_t), ("flags_need", C.c_size_t), ("cap_off_need", C.c_size_t), ("cap_str_off_need", C.c_size_t),
+        ("cap_blob_need", C.c_size_t), ("n_strings", C.c_size_t),
     ]
 
 

@@ -168,6 +168,96 @@ uint64_t pair_hash(const uint8_t* fwd, size_t fl, const uint8_t* bwd, size_t bl)
   return run(run(0x243F6A8885A308D3ull, fwd, fl), bwd, bl);
 }
 
+// ---- capture programs (zke_capture_register; layout: DESIGN.md §3, written by regex_compile.create_capture_program)
+struct HostCapture {
+  uint32_t n_states = 0, n_groups = 0, start = 0, n_words = 0;
+  std::vector<uint32_t> table;      // offsets [n_states + 1], then the state words
+  std::vector<uint64_t> eps;        // one bit per state: epsilon state (look / union / capture)
+};
+
+// 0 when the blob is a program the kernels can walk: every offset, state index, slot and byte range is checked here, so the
+// device never indexes outside its tables.  ZKE_D_U_CAPTURE_PROGRAM: malformed; ZKE_D_U_CAPTURE_STATES: well-formed header, too large.
+uint32_t parse_capture_program(const uint8_t* b, size_t n, HostCapture& h) {
+  constexpr uint32_t HW = 8;
+  if (!b || n < HW * 4 || (n & 3)) return ZKE_D_U_CAPTURE_PROGRAM;
+  if (rd32(b) != 0x50434B5Au || rd32(b + 4) != 1) return ZKE_D_U_CAPTURE_PROGRAM;
+  h.n_states = rd32(b + 8); h.n_groups = rd32(b + 12); h.start = rd32(b + 16);
+  const uint32_t flags = rd32(b + 20);
+  h.n_words = rd32(b + 24);
+  if (rd32(b + 28) != 0 || flags > 1 || h.n_states == 0 || h.n_groups == 0 || h.start >= h.n_states) return ZKE_D_U_CAPTURE_PROGRAM;
+  const uint64_t total = (uint64_t)HW + (uint64_t)h.n_states + 1 + h.n_words;
+  if (total * 4 != (uint64_t)n) return ZKE_D_U_CAPTURE_PROGRAM;
+  if (h.n_states > ZKE_CAP_MAX_STATES || h.n_groups > ZKE_CAP_MAX_PROGRAM_GROUPS) return ZKE_D_U_CAPTURE_STATES;
+  const uint32_t N = h.n_states;
+  h.table.resize((size_t)N + 1 + h.n_words);
+  for (size_t i = 0; i < h.table.size(); i++) h.table[i] = rd32(b + 4 * (HW + i));
+  h.eps.assign((N + 63) / 64, 0);
+  const uint32_t* off = h.table.data();
+  const uint32_t* st = off + N + 1;
+  if (off[0] != 0 || off[N] != h.n_words) return ZKE_D_U_CAPTURE_PROGRAM;
+  for (uint32_t q = 0; q < N; q++) {
+    if (off[q + 1] <= off[q] || off[q + 1] > h.n_words) return ZKE_D_U_CAPTURE_PROGRAM;
+    const uint32_t o = off[q], len = off[q + 1] - o, kind = st[o] & 0xff, cnt = st[o] >> 8;
+    switch (kind) {
+      case 0: case 1:                                       // FAIL, MATCH
+        if (cnt || len != 1) return ZKE_D_U_CAPTURE_PROGRAM;
+        break;
+      case 2: case 3: {                                     // RANGE, SPARSE
+        if (cnt == 0 || cnt > 256 || (kind == 2 && cnt != 1) || len != 1 + 2 * cnt) return ZKE_D_U_CAPTURE_PROGRAM;
+        uint32_t floor = 0;
+        for (uint32_t k = 0; k < cnt; k++) {
+          const uint32_t r = st[o + 1 + 2 * k], lo = r & 0xff, hi = (r >> 8) & 0xff;
+          if ((r >> 16) || lo > hi || lo < floor || st[o + 2 + 2 * k] >= N) return ZKE_D_U_CAPTURE_PROGRAM;
+          floor = hi + 1;
+        }
+        break;
+      }
+      case 4: {                                             // LOOK
+        const uint32_t lk = len == 3 ? st[o + 1] : 0;
+        if (cnt || len != 3 || !(lk == 1 || lk == 2 || lk == 4 || lk == 8 || lk == 64 || lk == 128) || st[o + 2] >= N) return ZKE_D_U_CAPTURE_PROGRAM;
+        h.eps[q >> 6] |= 1ull << (q & 63);
+        break;
+      }
+      case 5:                                               // UNION
+        if (len != 1 + cnt) return ZKE_D_U_CAPTURE_PROGRAM;
+        for (uint32_t k = 0; k < cnt; k++) if (st[o + 1 + k] >= N) return ZKE_D_U_CAPTURE_PROGRAM;
+        h.eps[q >> 6] |= 1ull << (q & 63);
+        break;
+      case 6:                                               // CAPTURE
+        if (cnt || len != 3 || st[o + 1] >= 2 * h.n_groups || st[o + 2] >= N) return ZKE_D_U_CAPTURE_PROGRAM;
+        h.eps[q >> 6] |= 1ull << (q & 63);
+        break;
+      default: return ZKE_D_U_CAPTURE_PROGRAM;
+    }
+  }
+  return 0;
+}
+
+// One slot's capture buffer (device; everything in front of `blob` has a pinned twin and comes back as one copy):
+// hdr {strings, blob bytes needed} | codes | spans | flags | cap_off | cap_str_off | tmp | blob
+struct CapLayout {
+  size_t hdr, codes, spans, flags, cap_off, cap_str_off, fixed_end, tmp, blob, total;
+  size_t blob_cap;
+};
+inline CapLayout cap_layout(uint32_t n, uint32_t P, uint32_t G, size_t blob_cap) {
+  CapLayout L{};
+  size_t o = 0;
+  auto put = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 63) & ~(size_t)63; return at; };
+  const size_t NP = (size_t)n * P, NG = (size_t)n * G;
+  L.hdr = put(64); L.codes = put(NP * 4); L.spans = put(NG * 8); L.flags = put(NG); L.cap_off = put((NP + 1) * 4);
+  L.cap_str_off = put((NG + 1) * 4); L.fixed_end = o; L.tmp = put((NP + NG) * 4); L.blob = put(blob_cap + 64); L.total = o;
+  L.blob_cap = blob_cap;
+  return L;
+}
+
+struct RegisteredCapture {
+  uint32_t detail = 0;              // 0, ZKE_D_U_CAPTURE_PROGRAM or ZKE_D_U_CAPTURE_STATES
+  CapProgDev dev{};                 // device pointers into `blob` (detail == 0)
+  DevBuf blob;
+  std::vector<uint8_t> copy;        // the registered bytes: an equal program registered again gets the old id
+  uint64_t hash = 0;
+};
+
 // What a batch needs to know about one regex part, copied out of the registry while its lock is held.
 struct PartInfo {
   const RegexDev* dev = nullptr;      // nullptr: the pair does not deserialise / the id is not registered

@@ -25,6 +25,7 @@
 #include "rsa.hip.h"
 #include "parse.hip.h"
 #include "regex.hip.h"
+#include "capture.hip.h"
 #include "rsa_kernel.hip.h"
 #include "rsa_quad.hip.h"
 #include "fused.hip.h"
@@ -92,8 +93,12 @@ struct Slot {
   uint64_t host_retired = 0;           // ... of which this many have been delivered to their caller's `out`
   zke_result* host_out = nullptr;      // where the pending batch's records go
   uint32_t host_n = 0;
-  DevBuf* all[15] = {&meta, &rsa_jobs, &sha_jobs, &sha_order, &rsa_ok, &em_dbg, &scratch_off, &scratch, &clean, &meta2, &scratch2, &parts,
-                     &pending, &d_image, &d_results};
+  // capture extraction (zke_extract_captures): spans, flags, codes and the three tables in one buffer (CapLayout), the rows of
+  // programs too large for LDS, the pinned twin of everything but the blob, and where the pending batch's extraction goes
+  CapBufs cb;
+  zke_capture_out* cap_out = nullptr;
+  DevBuf* all[17] = {&meta, &rsa_jobs, &sha_jobs, &sha_order, &rsa_ok, &em_dbg, &scratch_off, &scratch, &clean, &meta2, &scratch2, &parts,
+                     &pending, &d_image, &d_results, &cb.cap, &cb.work};
   // hipGraph replay of a batch's kernel sequence (zke_options.replay_graphs).  The graph holds this slot's
   // workspace pointers, so it is valid only while none of them has been reallocated: `generation` counts reallocations.
   hipGraphExec_t graph_exec = nullptr;
@@ -131,6 +136,8 @@ struct zke_engine {
   std::vector<RegisteredDfa*> dfas; // index = id; nullptr = unregistered
   std::unordered_multimap<uint64_t, uint32_t> dfa_index;   // pair_hash -> id
   uint32_t dfa_live = 0;
+  std::vector<RegisteredCapture*> captures;                    // index = id; nullptr = unregistered (under reg_mu, as dfas)
+  std::unordered_multimap<uint64_t, uint32_t> capture_index;   // pair_hash(program, nothing) -> id
   std::atomic<uint64_t> reg_clock{0};
   size_t dfa_lds_attr = 0, dfa_wave_lds_attr = 0;
   CopyPool* pool = nullptr;
@@ -195,7 +202,7 @@ void free_slot(Slot* w) {
   if (!w) return;
   if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
   for (auto* b : w->all) b->release();
-  w->h_image.release(); w->h_results.release();
+  w->h_image.release(); w->h_results.release(); w->cb.h_cap.release();
   for (auto& ev : w->ev) if (ev) (void)hipEventDestroy(ev);
   if (w->done) (void)hipEventDestroy(w->done);
   if (w->host_done) (void)hipEventDestroy(w->host_done);
@@ -465,6 +472,8 @@ void zke_engine_destroy(zke_engine* e) {
     e->misc.release(); e->key_cache.release();
     for (auto* d : e->dfas) if (d) { d->blob.release(); d->dev.release(); delete d; }
     e->dfas.clear();
+    for (auto* c : e->captures) if (c) { c->blob.release(); delete c; }
+    e->captures.clear();
     delete e->pool;
     e->pool = nullptr;
   }

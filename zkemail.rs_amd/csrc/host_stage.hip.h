@@ -228,4 +228,14 @@ inline ImageLayout image_layout(uint32_t n, size_t raw_total, size_t dom_total, 
   return L;
 }
 
+// The buffers of one capture extraction (a slot's, or zke_capture_batch's own): spans, flags, codes and the three tables in one
+// device buffer laid out by `L` (dfa_registry.hip.h, CapLayout), the rows of programs too large for LDS, and the pinned twin of
+// everything in front of the blob.
+struct CapBufs {
+  DevBuf cap, work;
+  PinnedBuf h_cap;
+  CapLayout L{};
+  void release() { cap.release(); work.release(); h_cap.release(); }
+};
+
 }  // namespace

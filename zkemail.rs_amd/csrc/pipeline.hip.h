@@ -69,12 +69,92 @@ int raise_dfa_lds_attrs(zke_engine* e, size_t lds) {
   return 0;
 }
 
+int arg_error(const char* who, const char* what);
+
+// ---- capture extraction behind the regex stage (capture.hip.h)
+// An extraction riding on a regex batch: the parts' programs and requested groups, resolved against the registry.
+struct CaptureReq {
+  uint32_t P = 0, G = 0, n_header_parts = 0;
+  bool needs_work = false;               // some program's rows do not fit LDS
+  CapPartDev part[CAP_MAX_PARTS]{};
+  uint32_t gbase[CAP_MAX_PARTS + 1]{};
+  std::vector<uint32_t> dfa_ids;         // [P] header parts, then body parts
+  uint32_t prog_ids[CAP_MAX_PARTS]{};    // resolved against the registry by capture_resolve, under the engine's `big` lock
+  zke_capture_out* out = nullptr;
+};
+constexpr uint32_t CAP_WORK_WAVES = 256;      // waves of a capture launch whose rows live in the slot's workspace (one slice each)
+
+int ensure_capture_buffers(zke_engine* e, CapBufs& b, uint32_t n, uint32_t P, uint32_t G, size_t blob_cap, bool work) {
+  const CapLayout L = cap_layout(n, P, G, blob_cap);
+  int r = 0;
+  if ((r = b.cap.ensure(L.total)) || (r = b.h_cap.ensure(L.fixed_end)) ||
+      (work && (r = b.work.ensure((size_t)CAP_WORK_WAVES * CAP_WORK_WORDS * 8))))
+    return fail(e, r, "capture workspace allocation");
+  return 0;
+}
+
+// Part p of a request: the requested groups (no registry involved: the sizes of the output follow from these alone) ...
+int capture_part_shape(CaptureReq& q, uint32_t p, uint32_t prog_id, const uint32_t* groups, uint32_t n_groups, const char* who) {
+  if (n_groups > ZKE_CAP_MAX_GROUPS) return arg_error(who, "more than ZKE_CAP_MAX_GROUPS groups requested for a part");
+  if (n_groups && !groups) return arg_error(who, "null group list");
+  CapPartDev& d = q.part[p];
+  d = CapPartDev{};
+  d.code = ZKE_D_U_CAPTURE_PROGRAM;
+  d.n_groups = n_groups; d.gbase = q.gbase[p];
+  for (uint32_t k = 0; k < n_groups; k++) d.groups[k] = groups[k];
+  q.prog_ids[p] = prog_id;
+  q.gbase[p + 1] = q.gbase[p] + n_groups;
+  q.G = q.gbase[p + 1];
+  return 0;
+}
+// ... and the programs' device tables.  The caller holds `big` (shared) from here until the batch is enqueued: unregistering a
+// program takes `big` exclusively and drains the engine before it frees a table, so the pointers copied here stay valid for as
+// long as a launch can read them — the same order in which run_device_pipeline resolves the DFA pairs of a batch.
+void capture_resolve(zke_engine* e, CaptureReq& q) {
+  std::shared_lock<std::shared_mutex> rl(e->reg_mu);
+  q.needs_work = false;
+  for (uint32_t p = 0; p < q.P; p++) {
+    CapPartDev& d = q.part[p];
+    const uint32_t id = q.prog_ids[p];
+    const RegisteredCapture* rc = id < e->captures.size() ? e->captures[id] : nullptr;
+    d.code = rc ? rc->detail : (uint32_t)ZKE_D_U_CAPTURE_PROGRAM;
+    d.prog = CapProgDev{};
+    if (rc && !rc->detail) { d.prog = rc->dev; if (d.prog.words64 > CAP_LDS_WORDS) q.needs_work = true; }
+  }
+}
+
+// The two launches of an extraction: the walk per (e-mail, part), then verdict + tables.  `parts`: the PartRes the search left.
+int launch_capture(zke_engine* e, CapBufs& b, const CaptureReq& q, uint32_t n, bool plain, const DfaArgs& base,
+                   const uint8_t* hay_blob, const uint64_t* hay_off, const PartRes* parts, zke_result* results, hipStream_t s) {
+  const CapLayout& L = b.L;
+  uint8_t* cb = b.cap.as<uint8_t>();
+  CapArgs ca{};
+  ca.plain = plain ? 1u : 0u; ca.n = n; ca.P = q.P; ca.G = q.G; ca.d = base; ca.n_header_parts = q.n_header_parts;
+  ca.hay_blob = hay_blob; ca.hay_off = hay_off; ca.parts = parts;
+  ca.spans = reinterpret_cast<uint32_t*>(cb + L.spans); ca.flags = cb + L.flags; ca.codes = reinterpret_cast<uint32_t*>(cb + L.codes);
+  ca.work = b.work.as<uint64_t>();
+  for (uint32_t p = 0; p < q.P; p++) ca.part[p] = q.part[p];
+  const uint32_t items = n * q.P;
+  const uint32_t grid = std::min<uint32_t>(items, q.needs_work ? CAP_WORK_WAVES : 16384u);
+  if (grid) hipLaunchKernelGGL(capture_kernel, dim3(grid), dim3(64), 0, s, ca);
+  CapGatherArgs ga{};
+  ga.plain = ca.plain; ga.n = n; ga.P = q.P; ga.G = q.G; ga.n_header_parts = q.n_header_parts; ga.d = base;
+  ga.hay_blob = hay_blob; ga.hay_off = hay_off; ga.parts = parts; ga.codes = ca.codes; ga.spans = ca.spans; ga.results = results;
+  ga.cap_off = reinterpret_cast<uint32_t*>(cb + L.cap_off); ga.cap_str_off = reinterpret_cast<uint32_t*>(cb + L.cap_str_off);
+  ga.cap_blob = cb + L.blob; ga.blob_cap = L.blob_cap; ga.hdr = reinterpret_cast<uint64_t*>(cb + L.hdr);
+  ga.tmp = reinterpret_cast<uint32_t*>(cb + L.tmp);
+  for (uint32_t p = 0; p <= q.P; p++) ga.gbase[p] = q.gbase[p];
+  hipLaunchKernelGGL(capture_gather_kernel, dim3(1), dim3(1024), 0, s, ga);
+  HIPCHK(e, hipGetLastError());
+  return 0;
+}
+
 // The device pipeline.  Every pointer in `in` / out_dev is device memory, except the part-id lists (host arrays in both
 // entry points).  Three launches — front end, hash / modexp stage, Ed25519 + verdict (which also runs the later signature
 // rounds of the rare e-mail that needs them) — and, for verify_email_with_regex, the regex stage behind them.
 // Caller holds the slot's lock; everything the call needs is in its arguments or in the slot.
 int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t raw_total, uint64_t key_total, zke_result* out_dev,
-                        hipStream_t s, bool want_em, uint64_t now, bool want_clean = false) {
+                        hipStream_t s, bool want_em, uint64_t now, bool want_clean = false, const CaptureReq* cap = nullptr) {
   const uint32_t n = in->n;
   if (n == 0) return 0;
   const uint32_t n_pad = (n + 63) & ~63u;
@@ -210,6 +290,9 @@ int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t ra
       RegexFinArgs rf{B2, w.parts.as<PartRes>(), in->n_header_parts, in->n_body_parts};
       hipLaunchKernelGGL(regex_finalize_kernel, dim3((n + 255) / 256), dim3(256), 0, s, rf);
     }
+    // capture extraction (zke_extract_captures): two more launches behind the regex verdict, in the slot's capture buffer
+    if (cap)
+      if ((r = launch_capture(e, w.cb, *cap, n, false, base, nullptr, nullptr, w.parts.as<PartRes>(), out_dev, s))) return r;
     tm.mark(MK_DFA);
     HIPCHK(e, hipGetLastError());
   }
@@ -290,12 +373,44 @@ uint64_t batch_clock(const zke_engine* e) {
 
 // Deliver a host batch that was enqueued in this slot and not waited for yet: wait for its D2H, copy the records from the
 // pinned buffer to the caller's `out`.  Caller holds the slot's lock.
-int retire_host(zke_engine* e, Slot& w) {
+// An extraction's tables from the slot's pinned twin (and the blob from HBM) into the caller's zke_capture_out.  Returns
+// ZKE_E_NOMEM when the caller's cap_blob is too small for the strings (everything else is delivered; cap_blob_need says how much).
+int deliver_captures(zke_engine* e, CapBufs& b, zke_capture_out* o, hipStream_t s) {
+  const CapLayout& L = b.L;
+  const uint8_t* hp = b.h_cap.as<uint8_t>();
+  const uint64_t* hdr = reinterpret_cast<const uint64_t*>(hp + L.hdr);
+  const size_t strings = (size_t)hdr[0], bytes = (size_t)hdr[1];
+  memcpy(o->spans, hp + L.spans, o->spans_need * 4);
+  memcpy(o->flags, hp + L.flags, o->flags_need);
+  memcpy(o->cap_off, hp + L.cap_off, o->cap_off_need * 4);
+  memcpy(o->cap_str_off, hp + L.cap_str_off, (strings + 1) * 4);
+  o->n_strings = strings;
+  o->cap_blob_need = bytes;
+  const size_t take = std::min(bytes, L.blob_cap);
+  if (take) {
+    HIPCHK(e, hipMemcpyAsync(o->cap_blob, b.cap.as<uint8_t>() + L.blob, take, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+  }
+  if (bytes > L.blob_cap) return fail(e, ZKE_E_NOMEM, "capture extraction: cap_blob is smaller than the strings (zke_capture_out.cap_blob_need)");
+  return 0;
+}
+
+// `cap_rc` (zke_batch_wait, the synchronous entries): where an extraction's shortfall is reported; a slot that retires a batch
+// nobody waited for has nobody to tell.
+int retire_host(zke_engine* e, Slot& w, int* cap_rc = nullptr) {
   if (w.host_retired == w.host_gen) return 0;
   w.host_retired = w.host_gen;                       // whatever happens below, the batch is no longer pending
+  zke_capture_out* pending_caps = w.cap_out;
+  w.cap_out = nullptr;
   HIPCHK(e, hipEventSynchronize(w.host_done));
   if (w.host_out && w.host_n) memcpy(w.host_out, w.h_results.p, (size_t)w.host_n * sizeof(zke_result));
   w.host_out = nullptr;
+  if (pending_caps) {
+    const std::string keep = g_err;
+    const int r = deliver_captures(e, w.cb, pending_caps, w.stream);
+    if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
+    else if (r) return r;
+  }
   return 0;
 }
 
@@ -318,6 +433,7 @@ int check_batch_pointers(const zke_batch* in, const void* out, bool host, const 
 struct HostBatch {
   zke_batch b{};                        // n, the regex section, (packed) the caller's blobs and offsets; capture tables only if any
   const zke_email_ref* refs = nullptr;  // the gathered shape's e-mails (nullptr: packed)
+  CaptureReq* cap = nullptr;            // zke_extract_captures: the extraction that rides on this (regex) batch
   uint64_t raw_total = 0, dom_total = 0, key_total = 0, raw_base = 0, dom_base = 0, key_base = 0;   // blob bytes; off[0] of packed offsets
   size_t cap_words = 0, cap_strs = 0, cap_bytes = 0;      // entries of cap_off and cap_str_off, bytes of cap_blob (0: no tables)
   ImageLayout L{};
@@ -376,6 +492,10 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   const ImageLayout& L = d.L;
   if (int r = retire_host(e, w)) return r;           // the pinned buffers are about to be overwritten
   if (int r = ensure_host_buffers(e, w, L.total, n)) return r;      // (a no-op: submit_host_batch has grown every slot's staging)
+  if (d.cap) {
+    if (int r = ensure_capture_buffers(e, w.cb, n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap, d.cap->needs_work)) return r;
+    w.cb.L = cap_layout(n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap);
+  }
   uint8_t* hp = w.h_image.as<uint8_t>();
   if (d.refs) {
     // the CSR arrays are written where they will be read from (prefix sums over the lengths), and every e-mail's three buffers
@@ -450,12 +570,14 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   dv.cap_off = d.cap_words ? reinterpret_cast<const uint32_t*>(dp + L.cap_off) : nullptr;
   dv.cap_str_off = d.cap_words ? reinterpret_cast<const uint32_t*>(dp + L.cap_str_off) : nullptr;
   dv.cap_blob = d.cap_words ? dp + L.cap_blob : nullptr;
-  if (int r = run_device_pipeline(e, w, &dv, d.raw_total, d.key_total, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean)) return r;
+  if (int r = run_device_pipeline(e, w, &dv, d.raw_total, d.key_total, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap)) return r;
   HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
+  if (d.cap) HIPCHK(e, hipMemcpyAsync(w.cb.h_cap.p, w.cb.cap.p, w.cb.L.fixed_end, hipMemcpyDeviceToHost, s));
   tm.mark(MK_D2H);
   HIPCHK(e, hipEventRecord(w.host_done, s));
   w.host_gen++;
   w.host_out = out; w.host_n = n;
+  w.cap_out = d.cap ? d.cap->out : nullptr;
   return use.release();
 }
 
@@ -532,13 +654,16 @@ int submit_host_batch(zke_engine* e, const HostBatch& d, zke_result* out, uint64
   if (n && (d.L.total > e->host_image_cap.load() || n > e->host_n_cap.load())) if (int r = grow_host_staging(e, d.L.total, n)) return r;
   std::shared_lock<std::shared_mutex> sh(e->big);
   HIPCHK(e, hipSetDevice(e->device));
+  if (d.cap) capture_resolve(e, *d.cap);             // under `big`: the programs' tables cannot be freed before the batch is enqueued
   uint32_t slot;
   Slot& w = next_slot(e, slot);
   std::lock_guard<std::mutex> g(w.mu);
   if (!n) { *ticket = make_ticket(slot, w.host_retired); return 0; }      // nothing to wait for
   if (int r = submit_host(e, w, d, out, dbg && dbg->em, dbg && dbg->clean_body)) return r;
   if (ticket) { *ticket = make_ticket(slot, w.host_gen); return 0; }
-  if (int r = retire_host(e, w)) return r;
+  int cap_rc = 0;
+  if (int r = retire_host(e, w, &cap_rc)) return r;
+  if (cap_rc) return cap_rc;
   return dbg ? copy_debug_out(e, w, d.b, out, dbg) : 0;
 }
 
@@ -701,6 +826,9 @@ int zke_engine_reserve(zke_engine* e, uint32_t max_n, uint64_t max_raw_total, ui
   if (max_n)
     for (Slot* w : e->slots)
       if (int r = ensure_workspace(e, *w, max_n, max_raw_total, max_regex_parts != 0, max_regex_parts, false)) return r;
+  if (max_n && max_regex_parts)          // the capture workspace: four groups of 32 bytes per part is what a larger extraction regrows from
+    for (Slot* w : e->slots)
+      if (int r = ensure_capture_buffers(e, w->cb, max_n, max_regex_parts, 4 * max_regex_parts, (size_t)max_n * max_regex_parts * 128, true)) return r;
 
   // A stream's hardware queue and the queue's scratch memory (the front end spills a few registers) come into being
   // with the first launch that needs them — milliseconds, and they would land in the first batch of every slot.
@@ -843,7 +971,9 @@ int zke_batch_wait(zke_engine* e, uint64_t ticket) {
   if ((ticket >> 6) > w.host_gen) return fail(e, ZKE_E_ARG, "zke_batch_wait: no such ticket");
   if ((ticket >> 6) <= w.host_retired) return 0;        // delivered already (waited for before, or retired by the slot's next batch)
   HIPCHK(e, hipSetDevice(e->device));
-  return retire_host(e, w);
+  int cap_rc = 0;
+  if (int r = retire_host(e, w, &cap_rc)) return r;
+  return cap_rc;
 }
 
 int zke_verify_emails_with_regex_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_lists* lists,
@@ -918,6 +1048,201 @@ int zke_verify_email_with_regex(zke_engine* e, const uint8_t* raw, size_t raw_le
   const zke_email_ref one{raw, raw_len, from_domain, domain_len, key, key_len, key_type, external_input_null};
   const zke_regex_lists lists{n_header_parts, hids.data(), n_body_parts, bids.data(), cap_off.data(), str_off.data(), blob.data()};
   return zke_verify_emails_with_regex(e, &one, 1, &lists, out);
+}
+
+// ---- capture extraction (include/zkemail_amd.h; kernels: capture.hip.h)
+int zke_capture_validate(const uint8_t* prog, size_t len, uint32_t* detail) {
+  if (!detail || (len && !prog)) return ZKE_E_ARG;
+  HostCapture h;
+  *detail = parse_capture_program(prog, len, h);
+  return 0;
+}
+
+int zke_capture_register(zke_engine* e, const uint8_t* prog, size_t len, uint32_t* out_id) {
+  if (!e || !out_id || (len && !prog)) return ZKE_E_ARG;
+  const uint64_t hsh = pair_hash(prog, len, nullptr, 0);
+  auto lookup = [&]() {
+    auto range = e->capture_index.equal_range(hsh);
+    for (auto it = range.first; it != range.second; ++it) {
+      const RegisteredCapture* c = e->captures[it->second];
+      if (c && c->copy.size() == len && (!len || !memcmp(c->copy.data(), prog, len))) { *out_id = it->second; return true; }
+    }
+    return false;
+  };
+  {
+    std::shared_lock<std::shared_mutex> rl(e->reg_mu);
+    if (lookup()) return 0;
+  }
+  HIPCHK(e, hipSetDevice(e->device));
+  RegisteredCapture* rc = new RegisteredCapture();
+  auto discard = [&]() { rc->blob.release(); delete rc; };
+  rc->copy.assign(prog, prog + len);
+  rc->hash = hsh;
+  HostCapture h;
+  rc->detail = parse_capture_program(prog, len, h);
+  if (!rc->detail) {
+    const size_t tb = (h.table.size() * 4 + 7) & ~(size_t)7, eb = h.eps.size() * 8;
+    if (int r = rc->blob.ensure(tb + eb)) { discard(); return fail(e, r, "hipMalloc"); }
+    hipError_t he = hipMemcpy(rc->blob.p, h.table.data(), h.table.size() * 4, hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMemcpy(rc->blob.as<uint8_t>() + tb, h.eps.data(), eb, hipMemcpyHostToDevice);
+    if (he != hipSuccess) { discard(); return fail(e, ZKE_E_DEVICE, "capture program upload", he); }
+    rc->dev.n_states = h.n_states; rc->dev.n_groups = h.n_groups; rc->dev.start = h.start; rc->dev.words64 = (uint32_t)h.eps.size();
+    rc->dev.off = rc->blob.as<uint32_t>();
+    rc->dev.st = rc->blob.as<uint32_t>() + h.n_states + 1;
+    rc->dev.eps = reinterpret_cast<const uint64_t*>(rc->blob.as<uint8_t>() + tb);
+  }
+  std::unique_lock<std::shared_mutex> rl(e->reg_mu);
+  if (lookup()) { discard(); return 0; }             // another thread was first
+  uint32_t live = 0;
+  for (const auto* c : e->captures) live += c != nullptr;
+  if (live >= e->opt.max_dfas) { discard(); return fail(e, ZKE_E_NOMEM, "capture registry full (zke_options.max_dfas): zke_capture_unregister programs no longer needed"); }
+  uint32_t id = 0;
+  while (id < e->captures.size() && e->captures[id]) id++;
+  if (id == e->captures.size()) e->captures.push_back(nullptr);
+  e->captures[id] = rc;
+  e->capture_index.emplace(hsh, id);
+  *out_id = id;
+  return 0;
+}
+
+int zke_capture_status(zke_engine* e, uint32_t id, uint32_t* detail) {
+  if (!e || !detail) return ZKE_E_ARG;
+  std::shared_lock<std::shared_mutex> rl(e->reg_mu);
+  if (id >= e->captures.size() || !e->captures[id]) return fail(e, ZKE_E_DFA, "zke_capture_status: id is not registered");
+  *detail = e->captures[id]->detail;
+  return 0;
+}
+
+int zke_capture_unregister(zke_engine* e, uint32_t id) {
+  if (!e) return ZKE_E_ARG;
+  std::unique_lock<std::shared_mutex> ex(e->big);         // no submission in progress, nothing in flight that could read the tables
+  HIPCHK(e, hipSetDevice(e->device));
+  if (int r = drain_engine(e, false)) return r;
+  std::unique_lock<std::shared_mutex> rl(e->reg_mu);
+  if (id >= e->captures.size() || !e->captures[id]) return fail(e, ZKE_E_DFA, "zke_capture_unregister: id is not registered");
+  RegisteredCapture* c = e->captures[id];
+  auto range = e->capture_index.equal_range(c->hash);
+  for (auto it = range.first; it != range.second; ++it)
+    if (it->second == id) { e->capture_index.erase(it); break; }
+  c->blob.release();
+  delete c;
+  e->captures[id] = nullptr;
+  return 0;
+}
+
+namespace {
+// the sizes an extraction over n e-mails needs, written back; ZKE_E_NOMEM when a buffer of known size is too small
+int check_capture_out(zke_capture_out* o, uint32_t n, uint32_t P, uint32_t G, const char* who) {
+  if (!o) return arg_error(who, "null zke_capture_out");
+  const size_t NP = (size_t)n * P, NG = (size_t)n * G;
+  o->spans_need = NG * 2; o->flags_need = NG; o->cap_off_need = NP + 1; o->cap_str_off_need = NG + 1;
+  o->cap_blob_need = 0; o->n_strings = 0;
+  // string offsets are 32-bit, as the verify entry's tables are: what n * G spans of ZKE_CAP_MAX_SPAN bytes could not address is refused
+  if ((uint64_t)NG * ZKE_CAP_MAX_SPAN > 0xFFFFFFFFull) return arg_error(who, "n x groups beyond what 32-bit string offsets address (n * G * ZKE_CAP_MAX_SPAN must stay below 4 GiB): split the batch");
+  if (o->spans_cap < o->spans_need || o->flags_cap < o->flags_need || o->cap_off_cap < o->cap_off_need || o->cap_str_off_cap < o->cap_str_off_need) {
+    g_err = std::string(who) + ": a zke_capture_out buffer is smaller than its *_need";
+    return ZKE_E_NOMEM;
+  }
+  if (!o->spans || !o->flags || !o->cap_off || !o->cap_str_off || (o->cap_blob_cap && !o->cap_blob)) return arg_error(who, "null buffer in zke_capture_out");
+  return 0;
+}
+}  // namespace
+
+int zke_extract_captures_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
+                               uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
+                               zke_capture_out* caps, uint64_t* ticket) {
+  static const char who[] = "zke_extract_captures";
+  if (!e) return ZKE_E_ARG;
+  if (!ticket || !caps || (n_header_parts && !header_parts) || (n_body_parts && !body_parts)) return arg_error(who, "null pointer");
+  const uint32_t P = n_header_parts + n_body_parts;
+  if (P == 0 || P > ZKE_CAP_MAX_PARTS || n_header_parts > ZKE_CAP_MAX_PARTS) return arg_error(who, "1 .. ZKE_CAP_MAX_PARTS parts");
+  CaptureReq q;
+  q.P = P; q.n_header_parts = n_header_parts; q.out = caps;
+  q.dfa_ids.resize(P);
+  for (uint32_t p = 0; p < P; p++) {
+    const zke_capture_part& cp = p < n_header_parts ? header_parts[p] : body_parts[p - n_header_parts];
+    q.dfa_ids[p] = cp.dfa_id;
+    if (int r = capture_part_shape(q, p, cp.prog_id, cp.groups, cp.n_groups, who)) return r;
+  }
+  if (int r = check_capture_out(caps, n, P, q.G, who)) return r;
+  zke_regex_lists lists{n_header_parts, q.dfa_ids.data(), n_body_parts, q.dfa_ids.data() + n_header_parts, nullptr, nullptr, nullptr};
+  HostBatch d;
+  if (int r = host_batch(d, who, out, emails, n, &lists)) return r;
+  d.cap = &q;
+  return submit_host_batch(e, d, out, ticket);
+}
+
+int zke_extract_captures(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
+                         uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
+                         zke_capture_out* caps) {
+  uint64_t ticket = 0;
+  if (int r = zke_extract_captures_async(e, emails, n, header_parts, n_header_parts, body_parts, n_body_parts, out, caps, &ticket)) return r;
+  return n ? zke_batch_wait(e, ticket) : 0;
+}
+
+int zke_capture_batch(zke_engine* e, uint32_t dfa_id, uint32_t prog_id, const uint32_t* groups, uint32_t n_groups,
+                      const uint8_t* hay_blob, const uint64_t* hay_off, uint32_t n, uint32_t* matches, zke_capture_out* caps) {
+  static const char who[] = "zke_capture_batch";
+  if (!e) return ZKE_E_ARG;
+  if (!caps || (n && (!hay_off || !matches)) || (n && hay_off[n] > hay_off[0] && !hay_blob)) return arg_error(who, "null pointer");
+  if (n && (!rising(hay_off, n) || hay_off[n] - hay_off[0] > (1ull << 32))) return arg_error(who, "offset array is not non-decreasing, or the haystacks exceed 4 GiB");
+  for (uint32_t i = 0; i < n; i++) if (hay_off[i + 1] - hay_off[i] >= (1ull << 31)) return arg_error(who, "haystack of 2 GiB or more");
+  CaptureReq q;
+  q.P = 1; q.n_header_parts = 1; q.out = caps;
+  if (int r = capture_part_shape(q, 0, prog_id, groups, n_groups, who)) return r;
+  if (int r = check_capture_out(caps, n, 1, q.G, who)) return r;
+  if (n == 0) return 0;
+  std::shared_lock<std::shared_mutex> sh(e->big);      // from the registry lookups to the last launch: no table is freed meanwhile
+  std::lock_guard<std::mutex> g(e->misc_mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  capture_resolve(e, q);
+  PartInfo pi{};
+  {
+    std::shared_lock<std::shared_mutex> rl(e->reg_mu);
+    const RegisteredDfa* rd = dfa_id < e->dfas.size() ? e->dfas[dfa_id] : nullptr;
+    if (rd) { pi.detail = rd->detail; pi.dev = rd->valid ? rd->dev.as<RegexDev>() : nullptr; }
+  }
+  // the building blocks run in buffers of their own on slot 0's stream
+  const uint64_t base0 = hay_off[0], total = hay_off[n] - base0;
+  CapBufs tmp;
+  DevBuf dhay, doff, dparts;
+  std::vector<uint8_t> fixed;
+  int r = 0;
+  hipError_t he = hipSuccess;
+  tmp.L = cap_layout(n, 1, q.G, caps->cap_blob_cap);
+  const CapLayout& L = tmp.L;
+  hipStream_t s = e->stream;
+  auto done = [&](int rc) { dhay.release(); doff.release(); dparts.release(); tmp.release(); return rc; };
+  if ((r = dhay.ensure((size_t)total + 64)) || (r = doff.ensure((size_t)(n + 1) * 8)) || (r = dparts.ensure((size_t)n * sizeof(PartRes))) ||
+      (r = ensure_capture_buffers(e, tmp, n, 1, q.G, caps->cap_blob_cap, q.needs_work)))
+    return done(fail(e, r, "zke_capture_batch: allocation"));
+  std::vector<uint64_t> rel(n + 1);
+  for (uint32_t i = 0; i <= n; i++) rel[i] = hay_off[i] - base0;
+  if (total) he = hipMemcpyAsync(dhay.p, hay_blob + base0, (size_t)total, hipMemcpyHostToDevice, s);
+  if (he == hipSuccess) he = hipMemsetAsync(dhay.as<uint8_t>() + total, 0, 64, s);         // the DFA walk loads 16 bytes at a time
+  if (he == hipSuccess) he = hipMemcpyAsync(doff.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s);
+  if (he != hipSuccess) { (void)hipStreamSynchronize(s); return done(fail(e, ZKE_E_DEVICE, "zke_capture_batch: copy", he)); }
+  CapFindArgs fa{};
+  fa.d.re = pi.dev; fa.d.P = 1; fa.d.out = dparts.as<PartRes>(); fa.d.idle = 0xFFFFFFFFu; fa.d.decode_detail = pi.detail;
+  fa.hay_blob = dhay.as<uint8_t>(); fa.hay_off = doff.as<uint64_t>(); fa.n = n;
+  hipLaunchKernelGGL(capture_find_kernel, dim3((n + 255) / 256), dim3(256), 1024, s, fa);
+  r = launch_capture(e, tmp, q, n, true, DfaArgs{}, fa.hay_blob, fa.hay_off, dparts.as<PartRes>(), nullptr, s);
+  std::vector<PartRes> prs(n);
+  if (!r) {
+    he = hipMemcpyAsync(tmp.h_cap.p, tmp.cap.p, L.fixed_end, hipMemcpyDeviceToHost, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(prs.data(), dparts.p, (size_t)n * sizeof(PartRes), hipMemcpyDeviceToHost, s);
+  }
+  const hipError_t hs = hipStreamSynchronize(s);
+  if (r) return done(r);
+  if (he != hipSuccess || hs != hipSuccess) return done(fail(e, ZKE_E_DEVICE, "zke_capture_batch", he != hipSuccess ? he : hs));
+  const uint32_t* codes = reinterpret_cast<const uint32_t*>(tmp.h_cap.as<uint8_t>() + L.codes);
+  for (uint32_t i = 0; i < n; i++) {
+    const PartRes& pr = prs[i];
+    const bool undecodable = pr.code == PART_DECODE_FAIL;
+    matches[4 * i] = undecodable ? pr.count : (pr.code ? pr.code : codes[i]);
+    matches[4 * i + 1] = undecodable ? 0 : pr.count; matches[4 * i + 2] = pr.start; matches[4 * i + 3] = pr.end;
+  }
+  return done(deliver_captures(e, tmp, caps, s));
 }
 
 }  // extern "C"

@@ -122,6 +122,22 @@ def load_library(path: Optional[str] = None):
     lib.zke_abi_encode.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_size_t),
                                    C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.zke_abi_encode.restype = C.c_int
+    lib.zke_capture_validate.argtypes = [vp, C.c_size_t, u32p]
+    lib.zke_capture_validate.restype = C.c_int
+    lib.zke_capture_register.argtypes = [vp, vp, C.c_size_t, u32p]
+    lib.zke_capture_register.restype = C.c_int
+    lib.zke_capture_status.argtypes = [vp, C.c_uint32, u32p]
+    lib.zke_capture_status.restype = C.c_int
+    lib.zke_capture_unregister.argtypes = [vp, C.c_uint32]
+    lib.zke_capture_unregister.restype = C.c_int
+    cpp, cop = C.POINTER(A.zke_capture_part), C.POINTER(A.zke_capture_out)
+    lib.zke_extract_captures.argtypes = [vp, C.POINTER(A.zke_email_ref), C.c_uint32, cpp, C.c_uint32, cpp, C.c_uint32, vp, cop]
+    lib.zke_extract_captures.restype = C.c_int
+    lib.zke_extract_captures_async.argtypes = [vp, C.POINTER(A.zke_email_ref), C.c_uint32, cpp, C.c_uint32, cpp, C.c_uint32, vp, cop,
+                                               C.POINTER(C.c_uint64)]
+    lib.zke_extract_captures_async.restype = C.c_int
+    lib.zke_capture_batch.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, vp, cop]
+    lib.zke_capture_batch.restype = C.c_int
     lib.zke_version.argtypes = []
     lib.zke_version.restype = C.c_char_p
     lib.zke_device_available.argtypes = []
@@ -140,6 +156,8 @@ EXPORTED_SYMBOLS = [
     "zke_process_init", "zke_abi_version", "zke_engine_reserve_host", "zke_wire_decode", "zke_wire_free", "zke_wire_view",
     "zke_wire_external_input", "zke_verify_wire", "zke_shard_bounds", "zke_status_name", "zke_verify_emails", "zke_verify_emails_async",
     "zke_verify_emails_with_regex", "zke_verify_emails_with_regex_async",
+    "zke_capture_validate", "zke_capture_register", "zke_capture_status", "zke_capture_unregister", "zke_extract_captures",
+    "zke_extract_captures_async", "zke_capture_batch",
 ]
 
 
@@ -171,6 +189,8 @@ class Engine:
             raise EngineError(f"zke_engine_create failed ({rc}): {msg.decode() if msg else ''}")
         self.h = h
         self._dfa_cache: Dict[Tuple[bytes, bytes], int] = {}
+        self._capture_cache: Dict[bytes, int] = {}
+        self._pattern_cache: Dict[Tuple[str, bool], Tuple[A.DFA, int, int]] = {}
 
     def close(self):
         if getattr(self, "h", None):
@@ -210,6 +230,114 @@ class Engine:
     def dfa_unregister(self, dfa_id: int):
         self._check(self.lib.zke_dfa_unregister(self.h, dfa_id), "zke_dfa_unregister")
         self._dfa_cache = {k: v for k, v in self._dfa_cache.items() if v != dfa_id}
+        self._pattern_cache = {k: v for k, v in self._pattern_cache.items() if v[1] != dfa_id}
+
+    # ---- capture extraction (helpers/src/regex.rs:16-51 on the device)
+    def capture_register(self, prog: bytes) -> int:
+        prog = bytes(prog)
+        if prog in self._capture_cache:
+            return self._capture_cache[prog]
+        out = C.c_uint32()
+        buf = np.frombuffer(prog or b"\0", np.uint8)
+        self._check(self.lib.zke_capture_register(self.h, buf.ctypes.data, len(prog), C.byref(out)), "zke_capture_register")
+        self._capture_cache[prog] = out.value
+        return out.value
+
+    def capture_status(self, prog_id: int) -> int:
+        """0, D_U_CAPTURE_PROGRAM (the blob does not decode) or D_U_CAPTURE_STATES (beyond the engine's limits)."""
+        d = C.c_uint32()
+        self._check(self.lib.zke_capture_status(self.h, prog_id, C.byref(d)), "zke_capture_status")
+        return d.value
+
+    def capture_unregister(self, prog_id: int):
+        self._check(self.lib.zke_capture_unregister(self.h, prog_id), "zke_capture_unregister")
+        self._capture_cache = {k: v for k, v in self._capture_cache.items() if v != prog_id}
+        self._pattern_cache = {k: v for k, v in self._pattern_cache.items() if v[2] != prog_id}
+
+    def compile_pattern(self, pattern: str, unicode: bool = True):
+        """(DFA pair, its id, the capture program's id) of a pattern: compiled and registered once per engine."""
+        key = (pattern, bool(unicode))
+        if key not in self._pattern_cache:
+            from . import regex_compile as rc
+            dfa = rc.create_dfa(pattern, unicode=unicode)
+            self._pattern_cache[key] = (dfa, self.dfa_register(dfa.fwd, dfa.bwd),
+                                        self.capture_register(rc.create_capture_program(pattern, unicode=unicode)))
+        return self._pattern_cache[key]
+
+    def _run_captures(self, n: int, P: int, G: int, call, blob_bytes: int):
+        """The caller-sized buffers of a zke_capture_out, one retry with the blob size the engine reports."""
+        NP, NG = n * P, n * G
+        spans = np.zeros(max(NG * 2, 1), np.uint32)
+        flags = np.zeros(max(NG, 1), np.uint8)
+        cap_off = np.zeros(NP + 1, np.uint32)
+        cap_str_off = np.zeros(NG + 1, np.uint32)
+        for attempt in (0, 1):
+            blob = np.zeros(max(blob_bytes, 1), np.uint8)
+            o = A.zke_capture_out()
+            o.spans, o.spans_cap, o.flags, o.flags_cap = spans.ctypes.data, NG * 2, flags.ctypes.data, NG
+            o.cap_off, o.cap_off_cap, o.cap_str_off, o.cap_str_off_cap = cap_off.ctypes.data, NP + 1, cap_str_off.ctypes.data, NG + 1
+            o.cap_blob, o.cap_blob_cap = blob.ctypes.data, blob_bytes
+            rc = call(o)
+            if rc == -3 and attempt == 0 and o.cap_blob_need > blob_bytes:        # ZKE_E_NOMEM: the strings need a larger blob
+                blob_bytes = int(o.cap_blob_need)
+                continue
+            return rc, spans[:NG * 2].reshape(n, G, 2), flags[:NG].reshape(n, G), cap_off, cap_str_off[:int(o.n_strings) + 1], blob[:int(o.cap_blob_need)]
+
+    def capture_batch(self, dfa_id: int, prog_id: int, groups: Sequence[int], haystacks: Sequence[bytes]):
+        """zke_capture_batch: one pattern over plain haystacks.  Returns (matches [n, 4] = code, count, start, end;
+        spans [n, G, 2]; flags [n, G]; strings: per haystack the list of raw group bytes, [] where the haystack failed)."""
+        n, G = len(haystacks), len(groups)
+        blob, off = A._csr(list(haystacks))
+        g = np.array(list(groups), np.uint32)
+        matches = np.zeros((max(n, 1), 4), np.uint32)
+        rc, spans, flags, cap_off, cap_str_off, cblob = self._run_captures(
+            n, 1, G, lambda o: self.lib.zke_capture_batch(self.h, dfa_id, prog_id, g.ctypes.data, G, blob.ctypes.data, off.ctypes.data, n,
+                                                         matches.ctypes.data, C.byref(o)), 32 * n * G)
+        self._check(rc, "zke_capture_batch")
+        raw = cblob.tobytes()
+        strings = [[raw[cap_str_off[k]:cap_str_off[k + 1]] for k in range(cap_off[i], cap_off[i + 1])] for i in range(n)]
+        return matches[:n], spans, flags, strings
+
+    def extract_captures(self, emails: Sequence[Email], regex_config, *, unicode: bool = True):
+        """helpers/src/generator.rs:55-87 without the key fetch: verify_email + canonicalise + QP clean + exactly one match per
+        pattern + the groups named by capture_indices, one batch on the GPU.  `regex_config`: a regex_compile.RegexConfig (or
+        its JSON dict).  Returns (records, regex_infos): regex_infos[i] is the RegexInfo of e-mail i — what
+        compile_regex_parts returns for it — or None where the record is not OK (the reference returns Err / panics there)."""
+        from . import regex_compile as rc
+        if isinstance(regex_config, dict):
+            regex_config = rc.RegexConfig.from_json(regex_config)
+        hp, bp = list(regex_config.header_parts or []), list(regex_config.body_parts or [])
+        comp = [self.compile_pattern(p.pattern, unicode) for p in hp + bp]
+        groups = [np.array(list(p.capture_indices or []), np.uint32) for p in hp + bp]
+        arr = (A.zke_capture_part * max(len(comp), 1))()
+        for k, ((_, dfa_id, prog_id), g) in enumerate(zip(comp, groups)):
+            arr[k].dfa_id, arr[k].prog_id, arr[k].n_groups, arr[k].groups = dfa_id, prog_id, len(g), g.ctypes.data
+        refs = emails if isinstance(emails, A.EmailRefs) else A.EmailRefs(emails)
+        n, P, G = refs.n, len(comp), sum(len(g) for g in groups)
+        out = np.zeros(max(n, 1), dtype=A.RESULT_DTYPE)
+        body = C.cast(C.byref(arr, len(hp) * C.sizeof(A.zke_capture_part)), C.POINTER(A.zke_capture_part))
+        rcode, spans, flags, cap_off, cap_str_off, cblob = self._run_captures(
+            n, P, G, lambda o: self.lib.zke_extract_captures(self.h, refs.arr, n, arr, len(hp), body, len(bp), out.ctypes.data, C.byref(o)),
+            32 * n * G)
+        self._check(rcode, "zke_extract_captures")
+        raw = cblob.tobytes()
+        infos: List[Optional[A.RegexInfo]] = []
+        for i in range(n):
+            if out[i]["status"] != A.ZKE_OK:
+                infos.append(None)
+                continue
+            parts, col = [], 0
+            for p in range(P):
+                strs = []
+                for k in range(cap_off[i * P + p], cap_off[i * P + p + 1]):
+                    b = raw[cap_str_off[k]:cap_str_off[k + 1]]
+                    # regex.rs:35 String::from_utf8_lossy — only the strings the device flagged need the repair
+                    strs.append(b.decode("utf-8", errors="replace") if flags[i, col] & A.CAPF_NOT_UTF8 else b.decode("utf-8"))
+                    col += 1
+                parts.append(CompiledRegex(comp[p][0], strs))
+            infos.append(A.RegexInfo(parts[:len(hp)] if regex_config.header_parts is not None else None,
+                                     parts[len(hp):] if regex_config.body_parts is not None else None))
+        return out[:n], infos
 
     # ---- batches
     def verify_batch_async(self, batch: PackedBatch):
@@ -436,6 +564,19 @@ def verify_email(email: Email) -> EmailVerifierOutput:
 
 def verify_email_with_regex(inp: EmailWithRegex) -> EmailWithRegexVerifierOutput:
     return default_engine().verify_email_with_regex(inp)
+
+
+def generate_email_with_regex_inputs(emails: Sequence[Email], regex_config, *, unicode: bool = True, engine: Optional[Engine] = None):
+    """helpers/src/generator.rs:55-87 generate_email_with_regex_inputs for a batch, minus the DNS key fetch and the file IO: the
+    e-mails (raw bytes, from_domain and key already at hand) and a regex_config in, one EmailWithRegex per e-mail out — values
+    `verify_emails_with_regex` accepts.  Raises VerifyPanic for the first e-mail the reference would have returned an error for
+    ("Input doesn't match regex pattern", "Capture group not found") or panicked on."""
+    eng = engine or default_engine()
+    records, infos = eng.extract_captures(emails, regex_config, unicode=unicode)
+    for i, r in enumerate(records):
+        if r["status"] != A.ZKE_OK:
+            raise VerifyPanic(int(r["status"]), int(r["detail"]), i)
+    return [EmailWithRegex(e, info) for e, info in zip(emails, infos)]
 
 
 def abi_encode_native(email: EmailVerifierOutput, matches: Optional[Sequence[str]] = None) -> bytes:

@@ -39,7 +39,7 @@ class RegexSyntaxError(ValueError):
 # ------------------------------------------------------------------ AST
 @dataclass
 class Node:
-    kind: str                     # lit, cat, alt, rep, empty, group; assertions: start, end, sol, eol, wb, nwb
+    kind: str                     # lit, cat, alt, rep, empty, group (lo = capture index, 0 = non-capturing); assertions: start, end, sol, eol, wb, nwb
     byteset: Optional[FrozenSet[int]] = None
     kids: Optional[List["Node"]] = None
     lo: int = 0
@@ -417,15 +417,17 @@ class _Parser:
                     return None
                 saved = (self.unicode, self.dotall, self.icase, self.multiline)
                 self.flags(m.group(1))                        # (?flags:...) and (?:...)
+                index = 0
                 n = self.alt()
                 self.unicode, self.dotall, self.icase, self.multiline = saved
             else:
                 self.ngroups += 1
+                index = self.ngroups                          # numbered by opening parenthesis, as regex-syntax does
                 n = self.alt()
             if self.peek() != ")":
                 raise RegexSyntaxError("missing )")
             self.eat()
-            return Node("group", kids=[n])
+            return Node("group", kids=[n], lo=index)
         if c == "[":
             return self.cls()
         if c == ".":
@@ -854,6 +856,82 @@ def create_dfa(pattern: str, *, is_utf8: Optional[bool] = None, unicode: bool = 
         fwd=_serialize(fwd, start_kind=0, has_empty=has_empty, is_utf8=is_utf8, always_anchored=anchored),
         bwd=_serialize(rev, start_kind=2, has_empty=has_empty, is_utf8=is_utf8, always_anchored=False),
     )
+
+
+# ------------------------------------------------------------------ capture program ("capture program")
+# The Thompson NFA with its capture states, as a self-describing little-endian blob of u32 words.  The state kinds are the
+# ones of regex_automata::nfa::thompson::State, so that a Rust host can write the same blob from thompson::NFA::states():
+#   header   : magic "ZKCP", version, state count, group count (group 0 included), start state (anchored), flags
+#              (bit 0: Unicode mode), word count of the state section, 0
+#   offsets  : state_count + 1 word offsets into the state section
+#   states   : word 0 = kind | count << 8, then
+#              FAIL, MATCH      nothing
+#              RANGE            lo | hi << 8, next                    (State::ByteRange)
+#              SPARSE           count x (lo | hi << 8, next), sorted, disjoint   (State::Sparse)
+#              LOOK             look, next                            (State::Look; `look` is regex_automata's Look bit)
+#              UNION            count x next, in priority order       (State::Union / BinaryUnion)
+#              CAPTURE          slot, next                            (State::Capture; slot = 2 * group, + 1 for its end)
+CAP_MAGIC = 0x50434B5A
+CAP_VERSION = 1
+CAP_HEADER_WORDS = 8
+CAP_FAIL, CAP_MATCH, CAP_RANGE, CAP_SPARSE, CAP_LOOK, CAP_UNION, CAP_CAPTURE = 0, 1, 2, 3, 4, 5, 6
+CAP_LOOK_BITS = {"start": 1, "end": 2, "sol": 4, "eol": 8, "wb": 64, "nwb": 128}   # Look::{Start, End, StartLF, EndLF, WordAscii, WordAsciiNegate}
+CAP_MAX_STATES = 8192                  # ZKE_CAP_MAX_STATES
+CAP_MAX_PROGRAM_GROUPS = 32            # ZKE_CAP_MAX_PROGRAM_GROUPS (group 0 included)
+
+
+class _CapNFA(_NFA):
+    # one more state kind: ("cap", slot, nxt)
+    def build(self, n: Node, nxt: int) -> int:
+        if n.kind == "group" and n.lo:
+            close = self.add(("cap", 2 * n.lo + 1, nxt))
+            return self.add(("cap", 2 * n.lo, self.build(n.kids[0], close)))
+        return super().build(n, nxt)
+
+
+def _byteset_ranges(bs) -> List[Tuple[int, int]]:
+    return _norm([(b, b) for b in bs])
+
+
+def create_capture_program(pattern: str, *, unicode: bool = True) -> bytes:
+    """The capturing automaton of `pattern` for zke_capture_register: what meta::Regex::captures walks in
+    helpers/src/regex.rs:25-27, restricted to one anchored start — the engine runs it over a span the DFA pair has found.
+    Same syntax and modes as create_dfa.  Size limits (ZKE_CAP_MAX_STATES, ...) are the engine's business: a program beyond
+    them still serialises and is reported when it is used."""
+    parser = _Parser(pattern, unicode=unicode)
+    ast = parser.parse()
+    nfa = _CapNFA()
+    m = nfa.add(("match",))
+    end = nfa.add(("cap", 1, m))
+    body = nfa.build(ast, end)
+    start = nfa.add(("cap", 0, body))
+    offs, words = [], []
+    for t in nfa.st:
+        offs.append(len(words))
+        if t[0] == "match":
+            words.append(CAP_MATCH)
+        elif t[0] == "byte":
+            rs = _byteset_ranges(t[1])
+            if not rs:
+                words.append(CAP_FAIL)
+            elif len(rs) == 1:
+                words += [CAP_RANGE | (1 << 8), rs[0][0] | (rs[0][1] << 8), t[2]]
+            else:
+                words.append(CAP_SPARSE | (len(rs) << 8))
+                for lo, hi in rs:
+                    words += [lo | (hi << 8), t[2]]
+        elif t[0] == "look":
+            words += [CAP_LOOK, CAP_LOOK_BITS[t[1]], t[2]]
+        elif t[0] == "split":
+            words.append(CAP_UNION | (len(t[1]) << 8))
+            words += list(t[1])
+        elif t[0] == "cap":
+            words += [CAP_CAPTURE, t[1], t[2]]
+        else:
+            raise AssertionError(t[0])
+    offs.append(len(words))
+    head = [CAP_MAGIC, CAP_VERSION, len(nfa.st), parser.ngroups + 1, start, 1 if unicode else 0, len(words), 0]
+    return struct.pack(f"<{len(head) + len(offs) + len(words)}I", *(head + offs + words))
 
 
 @dataclass
