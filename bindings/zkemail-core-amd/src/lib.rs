@@ -81,6 +81,26 @@ impl fmt::Display for EngineError {
 
 impl std::error::Error for EngineError {}
 
+/// One DKIM-Signature header as a scan reports it (`zke_sig_info`, the selector as a string: it is ASCII by construction).
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct SigInfo {
+    pub header_index: u32,
+    pub code: u32,
+    pub algo: u32,
+    pub selector: String,
+    pub value_span: (u32, u32),
+}
+
+/// A scan's answer for one e-mail; `sigs` holds the first `max_sigs` headers, the counts are the true ones.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct SigScan {
+    pub status: u32,
+    pub detail: u32,
+    pub n_signatures: u32,
+    pub n_candidates: u32,
+    pub sigs: Vec<SigInfo>,
+}
+
 /// One `Email` as the C side sees it: pointers into its own buffers (valid while the `Email` is borrowed).
 fn email_ref(e: &Email) -> sys::zke_email_ref {
     sys::zke_email_ref {
@@ -501,6 +521,187 @@ impl Engine {
             Err(Panic { status: r.status, detail: r.detail })
         })
     }
+
+    /// `helpers/src/generator.rs:17-30` for a slice (`zke_scan_signatures`): per e-mail `(status, detail, n_signatures,
+    /// n_candidates)` and, for the first `max_sigs` DKIM-Signature headers, `validate_header`'s verdict (`code` 0: a candidate,
+    /// `ZKE_D_NEUTRAL`: another domain's, else why it is refused), `a=` classified and the selector.
+    pub fn scan_signatures(&self, raw_emails: &[&[u8]], from_domains: &[&str], max_sigs: u32) -> Result<Vec<SigScan>, EngineError> {
+        if raw_emails.len() != from_domains.len() {
+            return Err(EngineError { code: sys::ZKE_E_ARG, message: "one from_domain per raw e-mail".into() });
+        }
+        let n = raw_emails.len();
+        let refs: Vec<sys::zke_email_ref> = raw_emails
+            .iter()
+            .zip(from_domains)
+            .map(|(r, d)| sys::zke_email_ref {
+                raw: r.as_ptr(),
+                raw_len: r.len(),
+                from_domain: d.as_ptr().cast(),
+                domain_len: d.len(),
+                key: ptr::null(),
+                key_len: 0,
+                key_type: 0,
+                external_input_null: 0,
+            })
+            .collect();
+        let mut status = vec![0u32; 4 * n + 1];
+        let mut off = vec![0u32; n + 1];
+        let zero = sys::zke_sig_info { header_index: 0, code: 0, algo: 0, sel_off: 0, sel_len: 0, val_start: 0, val_end: 0, reserved: 0 };
+        let mut sigs = vec![zero; n * max_sigs as usize + 1];
+        let mut blob = vec![0u8; n * max_sigs as usize * 32 + 1];
+        for attempt in 0..2 {
+            let mut o = sys::zke_sig_scan {
+                scan_status: status.as_mut_ptr(),
+                scan_status_cap: 4 * n,
+                sig_off: off.as_mut_ptr(),
+                sig_off_cap: n + 1,
+                sigs: sigs.as_mut_ptr(),
+                sigs_cap: n * max_sigs as usize,
+                sel_blob: blob.as_mut_ptr(),
+                sel_blob_cap: blob.len(),
+                scan_status_need: 0,
+                sig_off_need: 0,
+                sigs_need: 0,
+                sel_blob_need: 0,
+                n_sigs: 0,
+            };
+            // SAFETY: every pointer refers into a Vec or slice that outlives the (synchronous) call, with its capacity beside it.
+            let rc = unsafe { sys::zke_scan_signatures(self.raw, refs.as_ptr(), n as u32, max_sigs, &mut o) };
+            if rc == sys::ZKE_E_NOMEM && attempt == 0 && o.sel_blob_need > blob.len() {
+                blob.resize(o.sel_blob_need, 0); // the selectors need a larger blob: once more with the size the engine reports
+                continue;
+            }
+            if rc != 0 {
+                return Err(self.last_error(rc));
+            }
+            break;
+        }
+        Ok((0..n)
+            .map(|i| SigScan {
+                status: status[4 * i],
+                detail: status[4 * i + 1],
+                n_signatures: status[4 * i + 2],
+                n_candidates: status[4 * i + 3],
+                sigs: sigs[off[i] as usize..off[i + 1] as usize]
+                    .iter()
+                    .map(|s| SigInfo {
+                        header_index: s.header_index,
+                        code: s.code,
+                        algo: s.algo,
+                        selector: String::from_utf8_lossy(&blob[s.sel_off as usize..(s.sel_off + s.sel_len) as usize]).into_owned(),
+                        value_span: (s.val_start, s.val_end),
+                    })
+                    .collect(),
+            })
+            .collect())
+    }
+
+    /// `helpers/src/generator.rs:31-45` for a slice (`zke_select_keys`): `candidate_keys[i]` are the keys fetched for e-mail i's
+    /// candidates in the scan's order (`None`: the fetch failed).  Returns the records and, per e-mail, the first key under
+    /// which it verifies (bit 31, `ZKE_SEL_AFTER_UNSUPPORTED`: an earlier candidate is outside what the engine implements) or
+    /// `ZKE_SEL_NONE`.
+    pub fn select_keys(
+        &self,
+        raw_emails: &[&[u8]],
+        from_domains: &[&str],
+        candidate_keys: &[Vec<Option<PublicKey>>],
+    ) -> Result<(Vec<sys::zke_result>, Vec<u32>), EngineError> {
+        let n = raw_emails.len();
+        if from_domains.len() != n || candidate_keys.len() != n {
+            return Err(EngineError { code: sys::ZKE_E_ARG, message: "one from_domain and one candidate list per raw e-mail".into() });
+        }
+        let refs: Vec<sys::zke_email_ref> = raw_emails
+            .iter()
+            .zip(from_domains)
+            .map(|(r, d)| sys::zke_email_ref {
+                raw: r.as_ptr(),
+                raw_len: r.len(),
+                from_domain: d.as_ptr().cast(),
+                domain_len: d.len(),
+                key: ptr::null(),
+                key_len: 0,
+                key_type: 0,
+                external_input_null: 0,
+            })
+            .collect();
+        let mut off: Vec<u32> = vec![0];
+        let mut keys: Vec<sys::zke_key_ref> = Vec::new();
+        for row in candidate_keys {
+            for k in row {
+                keys.push(match k {
+                    Some(k) => sys::zke_key_ref { key: k.key.as_ptr(), key_len: k.key.len(), key_type: key_type_code(&k.key_type) as u32, reserved: 0 },
+                    None => sys::zke_key_ref { key: ptr::null(), key_len: 0, key_type: 0, reserved: 0 },
+                });
+            }
+            off.push(keys.len() as u32);
+        }
+        let mut out = vec![zeroed_result(); n];
+        let mut chosen = vec![sys::ZKE_SEL_NONE; n];
+        // SAFETY: every pointer refers into the arguments or the Vecs above, alive until the synchronous call returns.
+        let rc = unsafe { sys::zke_select_keys(self.raw, refs.as_ptr(), n as u32, off.as_ptr(), keys.as_ptr(), out.as_mut_ptr(), chosen.as_mut_ptr()) };
+        if rc != 0 {
+            return Err(self.last_error(rc));
+        }
+        Ok((out, chosen))
+    }
+
+    /// `helpers/src/generator.rs:11-53 generate_email_inputs` for a slice, with the DNS fetch as the caller's closure:
+    /// `fetch_key(from_domain, selector)` is called once per distinct pair, on the host, between the two GPU calls (`None`: the
+    /// fetch failed).  One `Result` per e-mail: the `Email` carrying the first key under which it verifies, or what the
+    /// reference's `Err` stands for — a `parse_mail` error (the scan's status), "No DKIM signatures found"
+    /// (`ZKE_DKIM_NOT_PASS` / `ZKE_D_NO_SIGNATURE`), "No valid DKIM key found for any signature" (`ZKE_DKIM_NOT_PASS` with the
+    /// last candidate's detail) — or `ZKE_UNSUPPORTED` where the engine cannot give the reference's answer.
+    pub fn generate_email_inputs<F>(
+        &self,
+        from_domains: &[&str],
+        raw_emails: &[&[u8]],
+        mut fetch_key: F,
+        external_inputs: Option<&[Vec<ExternalInput>]>,
+    ) -> Result<Vec<Result<Email, Panic>>, EngineError>
+    where
+        F: FnMut(&str, &str) -> Option<PublicKey>,
+    {
+        let scans = self.scan_signatures(raw_emails, from_domains, sys::ZKE_SCAN_MAX_SIGS)?;
+        let mut cache: std::collections::HashMap<(String, String), Option<PublicKey>> = std::collections::HashMap::new();
+        let mut cands: Vec<Vec<Option<PublicKey>>> = Vec::with_capacity(scans.len());
+        for (sc, dom) in scans.iter().zip(from_domains) {
+            let mut row = Vec::new();
+            for s in sc.sigs.iter().filter(|s| s.code == 0) {
+                let key = (dom.to_string(), s.selector.clone());
+                let k = cache.entry(key).or_insert_with(|| fetch_key(dom, &s.selector));
+                row.push(k.clone());
+            }
+            cands.push(row);
+        }
+        let (recs, chosen) = self.select_keys(raw_emails, from_domains, &cands)?;
+        Ok((0..scans.len())
+            .map(|i| {
+                let sc = &scans[i];
+                if sc.status != sys::ZKE_OK {
+                    return Err(Panic { status: sc.status, detail: sc.detail });
+                }
+                if sc.n_signatures == 0 {
+                    return Err(Panic { status: sys::ZKE_DKIM_NOT_PASS, detail: sys::ZKE_D_NO_SIGNATURE }); // generator.rs:21
+                }
+                if chosen[i] == sys::ZKE_SEL_NONE {
+                    if sc.n_candidates as usize > cands[i].len() {
+                        return Err(Panic { status: sys::ZKE_UNSUPPORTED, detail: sys::ZKE_D_U_TOO_MANY_SIGS }); // the list was cut
+                    }
+                    let status = if recs[i].status == sys::ZKE_UNSUPPORTED { sys::ZKE_UNSUPPORTED } else { sys::ZKE_DKIM_NOT_PASS };
+                    return Err(Panic { status, detail: recs[i].detail }); // generator.rs:52
+                }
+                if chosen[i] & sys::ZKE_SEL_AFTER_UNSUPPORTED != 0 {
+                    return Err(Panic { status: sys::ZKE_UNSUPPORTED, detail: sys::ZKE_D_U_ALGO_ED25519 });
+                }
+                Ok(Email {
+                    from_domain: from_domains[i].to_string(),
+                    raw_email: raw_emails[i].to_vec(),
+                    public_key: cands[i][chosen[i] as usize].clone().expect("a chosen candidate has a key"),
+                    external_inputs: external_inputs.map(|x| x[i].clone()).unwrap_or_default(),
+                })
+            })
+            .collect())
+    }
 }
 
 impl Drop for Engine {
@@ -523,6 +724,24 @@ pub fn verify_email(email: &Email) -> EmailVerifierOutput {
         Err(e) => panic!("{e}"),
         Ok(Err(p)) => panic!("{p}"),
         Ok(Ok(out)) => out,
+    }
+}
+
+/// `zkemail_helpers::generate_email_inputs` (helpers/src/generator.rs:11-53) with the key fetch as a closure instead of the
+/// reference's DNS lookup: `Err` where the reference returns `Err`.
+pub fn generate_email_inputs<F>(
+    from_domain: &str,
+    raw_email: &[u8],
+    fetch_key: F,
+    external_inputs: Option<Vec<ExternalInput>>,
+) -> Result<Email, Panic>
+where
+    F: FnMut(&str, &str) -> Option<PublicKey>,
+{
+    let ext = [external_inputs.unwrap_or_default()];
+    match default_engine().generate_email_inputs(&[from_domain], &[raw_email], fetch_key, Some(&ext)) {
+        Err(e) => panic!("{e}"),
+        Ok(mut v) => v.remove(0),
     }
 }
 

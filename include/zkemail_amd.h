@@ -453,6 +453,81 @@ int zke_extract_captures_async(zke_engine* e, const zke_email_ref* emails, uint3
 int zke_capture_batch(zke_engine* e, uint32_t dfa_id, uint32_t prog_id, const uint32_t* groups, uint32_t n_groups,
                       const uint8_t* hay_blob, const uint64_t* hay_off, uint32_t n, uint32_t* matches, zke_capture_out* caps);
 
+/* ---- DKIM-Signature scan and key selection: the compute on both sides of the caller's DNS fetch in the reference's
+ * generate_email_inputs (helpers/src/generator.rs:11-53).  The fetch itself, like all IO, stays with the caller:
+ *     zke_scan_signatures   raw e-mails + from_domain -> per e-mail every DKIM-Signature header with its validate_header verdict,
+ *                           selector and algorithm                                                   (generator.rs:17-30)
+ *     (the caller resolves selector._domainkey.domain for the candidates)                            (generator.rs:31-34)
+ *     zke_select_keys       per e-mail the candidate keys in -> the first one under which verify_email passes, and that
+ *                           verification's record                                                    (generator.rs:36-45)
+ * Both go through the gathering host entry: same slots, tickets and zke_batch_wait as zke_verify_emails_async. */
+#define ZKE_SCAN_MAX_SIGS 64u           /* records per e-mail a scan lists at most (its max_sigs argument: 1 .. this) */
+#define ZKE_SIG_ALGO_RSA_SHA256     0u  /* zke_sig_info.algo: a= as the front end classifies it */
+#define ZKE_SIG_ALGO_RSA_SHA1       1u
+#define ZKE_SIG_ALGO_ED25519_SHA256 2u
+#define ZKE_SIG_ALGO_OTHER          3u
+#define ZKE_SEL_NONE              4294967295u /* 0xFFFFFFFF; zke_select_keys chosen[i]: no candidate key verifies the e-mail */
+#define ZKE_SEL_AFTER_UNSUPPORTED 2147483648u /* 0x80000000; ... bit 31 beside an index: a candidate in front of the chosen one reported
+                                                 ZKE_UNSUPPORTED and might have passed in the reference: reported, never guessed */
+
+typedef struct zke_sig_info {      /* 32 bytes */
+  uint32_t header_index;           /* index of the header field in the message */
+  uint32_t code;                   /* 0 candidate | ZKE_D_NEUTRAL other domain | ZKE_D_* why validate_header refuses it */
+  uint32_t algo;                   /* ZKE_SIG_ALGO_* ; meaningful when code is 0 or ZKE_D_NEUTRAL */
+  uint32_t sel_off, sel_len;       /* selector bytes in sel_blob; sel_len 0 when there is none */
+  uint32_t val_start, val_end;     /* the header's value in raw_email */
+  uint32_t reserved;
+} zke_sig_info;
+
+/* Where a scan goes: caller-sized buffers, capacities in ENTRIES of the array's type, the sizes needed written back (the
+ * zke_capture_out convention).  scan_status (4 n words) and sig_off (n + 1) have sizes known up front: a call whose buffers are
+ * smaller fails at once with ZKE_E_NOMEM and the *_need fields set.  sigs and sel_blob depend on the e-mails (n * max_sigs
+ * records always suffice): when one of them is too small the call (zke_batch_wait for the asynchronous form) returns ZKE_E_NOMEM,
+ * scan_status and sig_off are delivered all the same — and the records, when only the blob is short — and sigs_need /
+ * sel_blob_need say exactly what a second call needs.
+ *   scan_status  {status, detail, n_signatures, n_candidates} per e-mail.  status ZKE_OK, or ZKE_PARSE_FAIL / ZKE_UNSUPPORTED with
+ *                the detail zke_verify_emails gives the same bytes when parse_mail fails (header block, MIME subparts, more than
+ *                ZKE_MAX_HEADERS fields, KELVIN SIGN in from_domain): such an e-mail lists no signature.  n_signatures counts
+ *                every DKIM-Signature header of the e-mail, n_candidates those with code 0 — also beyond max_sigs: a list that
+ *                was cut shows as n_signatures > sig_off[i + 1] - sig_off[i].
+ *   sig_off      CSR over the records: e-mail i's are sigs[sig_off[i] .. sig_off[i + 1]), file order, the first max_sigs
+ *   sigs         one record per DKIM-Signature header (case-insensitive name), also those the verify path skips.  The engine's
+ *                strictness flags apply as in verification; c=, a= and l= are not part of the filter (generator.rs:25-30)
+ *   sel_blob     the FWS-stripped s= values of the records with code 0 or ZKE_D_NEUTRAL (ASCII, at most ZKE_MAX_TAGBUF bytes each),
+ *                in no particular order: a string is (sel_off, sel_len) */
+typedef struct zke_sig_scan {
+  uint32_t*     scan_status; size_t scan_status_cap;
+  uint32_t*     sig_off;     size_t sig_off_cap;
+  zke_sig_info* sigs;        size_t sigs_cap;
+  uint8_t*      sel_blob;    size_t sel_blob_cap;
+  size_t scan_status_need, sig_off_need, sigs_need, sel_blob_need;      /* written by the call */
+  size_t n_sigs;                                                        /* records delivered = sig_off[n] */
+} zke_sig_scan;
+
+/* zke_email_ref.key, key_len and key_type are ignored (key may be NULL).  max_sigs: 1 .. ZKE_SCAN_MAX_SIGS, and n * max_sigs below
+ * 2^21 (32-bit selector offsets).  `out` and its buffers must stay valid until the batch has been waited for.  One input image
+ * without a key section, one launch (sigscan_kernel), one copy back. */
+int zke_scan_signatures(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t max_sigs, zke_sig_scan* out);
+int zke_scan_signatures_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t max_sigs, zke_sig_scan* out, uint64_t* ticket);
+
+/* One candidate key of zke_select_keys.  key_len == 0: "the fetch failed" (generator.rs:33 `continue`); its record is what
+ * verify_email gives an empty key (ZKE_KEY_DECODE_FAIL) and it never passes. */
+typedef struct zke_key_ref { const uint8_t* key; size_t key_len; uint32_t key_type; uint32_t reserved; } zke_key_ref;
+/* Candidate k of e-mail i is keys[cand_off[i] + k]: the key fetched for the k-th record with code 0 the scan listed
+ * (emails[i].key* are ignored).  cand_off[n + 1] must be non-decreasing (ZKE_E_ARG otherwise, before anything is staged).
+ *   chosen[i]  the smallest k for which verify_email(emails[i] with that key) is ZKE_OK — the reference's rule: verify_email_with_key
+ *              with candidate k's key tries EVERY same-domain signature, so selection is "first key under which the e-mail
+ *              verifies" —, with ZKE_SEL_AFTER_UNSUPPORTED when an earlier candidate's record is ZKE_UNSUPPORTED; ZKE_SEL_NONE when
+ *              none passes.  Test for ZKE_SEL_NONE first; otherwise the index is the low 31 bits.
+ *   out[i]     that verification's whole record (public_key_hash is the chosen key's); when none passes, the record of the
+ *              e-mail's last candidate; with no candidate at all a zeroed record with ZKE_DKIM_NOT_PASS / ZKE_D_NEUTRAL.
+ * All cand_off[n] (e-mail, key) pairs run as ONE batch of the verify pipeline; the fold "first OK per e-mail" happens on the
+ * host when the records arrive (zke_batch_wait).  `out`, `chosen` must stay valid until then; cand_off has been copied. */
+int zke_select_keys(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off,
+                    const zke_key_ref* keys, zke_result* out, uint32_t* chosen);
+int zke_select_keys_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off,
+                          const zke_key_ref* keys, zke_result* out, uint32_t* chosen, uint64_t* ticket);
+
 /* Device-resident batch: every pointer in `in` and `out_dev` is device memory (the part-id lists stay host arrays);
  * `raw_total`, `domain_total`, `key_total` are the blob sizes (the CSR tails), which the
  * host needs for workspace sizing without a device read.  Takes the engine's next submission slot (round-robin),

@@ -8,6 +8,8 @@
 // to std::terminate.
 #pragma once
 #include <cstdint>
+#include <functional>
+#include <map>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -96,6 +98,21 @@ struct VerifyPanic : std::runtime_error {
       : std::runtime_error("zkemail_core panic site status=" + std::to_string(s) + " detail=" + std::to_string(d)),
         status(s), detail(d) {}
 };
+
+// One DKIM-Signature header as a scan reports it (zke_sig_info, the selector as a string).
+struct SigInfo {
+  uint32_t header_index, code, algo;       // code: 0 candidate | ZKE_D_NEUTRAL other domain | ZKE_D_* why validate_header refuses it
+  std::string selector;
+  uint32_t val_start, val_end;             // the header's value in raw_email
+};
+// A scan's answer for one e-mail; `sigs` holds the first max_sigs headers, the counts are the true ones.
+struct SigScan {
+  uint32_t status, detail, n_signatures, n_candidates;
+  std::vector<SigInfo> sigs;
+};
+// The caller's resolver of generate_email_inputs: (from_domain, selector) -> the key, or nullopt when the fetch fails
+// (helpers/src/dkim.rs fetch_dkim_key; DNS stays with the caller).
+using FetchKey = std::function<std::optional<PublicKey>(const std::string& domain, const std::string& selector)>;
 
 class Engine {
  public:
@@ -194,6 +211,106 @@ class Engine {
     return out;
   }
 
+  // helpers/src/generator.rs:17-30 for a batch (zke_scan_signatures): every DKIM-Signature header of every e-mail with
+  // validate_header's verdict, whether d= names from_domain, a= classified and the selector.
+  std::vector<SigScan> scan_signatures(const std::vector<std::vector<uint8_t>>& raw_emails, const std::vector<std::string>& from_domains,
+                                       uint32_t max_sigs = 8) {
+    if (raw_emails.size() != from_domains.size()) throw EngineError("one from_domain per raw e-mail");
+    const uint32_t n = (uint32_t)raw_emails.size();
+    std::vector<zke_email_ref> refs(n);
+    for (uint32_t i = 0; i < n; i++)
+      refs[i] = zke_email_ref{raw_emails[i].data(), raw_emails[i].size(), from_domains[i].data(), from_domains[i].size(), nullptr, 0, 0, 0};
+    std::vector<uint32_t> status((size_t)n * 4 + 1), off((size_t)n + 1);
+    std::vector<zke_sig_info> sigs((size_t)n * max_sigs + 1);
+    std::vector<uint8_t> blob((size_t)n * max_sigs * 32 + 1);
+    zke_sig_scan o{};
+    for (int attempt = 0; attempt < 2; attempt++) {
+      o = zke_sig_scan{status.data(), (size_t)n * 4, off.data(), (size_t)n + 1, sigs.data(), (size_t)n * max_sigs, blob.data(), blob.size(), 0, 0, 0, 0, 0};
+      const int r = zke_scan_signatures(e_, refs.data(), n, max_sigs, &o);
+      if (r == ZKE_E_NOMEM && attempt == 0 && o.sel_blob_need > blob.size()) { blob.resize(o.sel_blob_need); continue; }
+      if (r) throw EngineError("zke_scan_signatures failed: " + std::to_string(r) + " " + zke_last_error(e_));
+      break;
+    }
+    std::vector<SigScan> out(n);
+    for (uint32_t i = 0; i < n; i++) {
+      out[i] = SigScan{status[4 * (size_t)i], status[4 * (size_t)i + 1], status[4 * (size_t)i + 2], status[4 * (size_t)i + 3], {}};
+      for (uint32_t k = off[i]; k < off[i + 1]; k++) {
+        const zke_sig_info& s = sigs[k];
+        out[i].sigs.push_back(SigInfo{s.header_index, s.code, s.algo, std::string(reinterpret_cast<const char*>(blob.data()) + s.sel_off, s.sel_len),
+                                      s.val_start, s.val_end});
+      }
+    }
+    return out;
+  }
+
+  // helpers/src/generator.rs:31-45 for a batch (zke_select_keys): candidate_keys[i] = the keys fetched for e-mail i's candidates
+  // in the scan's order (nullopt: the fetch failed).  Returns the records; chosen[i] = the first key under which e-mail i
+  // verifies (bit 31: ZKE_SEL_AFTER_UNSUPPORTED) or ZKE_SEL_NONE.  The e-mails' own public_key fields are ignored.
+  std::vector<zke_result> select_keys(const std::vector<Email>& emails, const std::vector<std::vector<std::optional<PublicKey>>>& candidate_keys,
+                                      std::vector<uint32_t>& chosen) {
+    if (emails.size() != candidate_keys.size()) throw EngineError("one candidate list per e-mail");
+    const uint32_t n = (uint32_t)emails.size();
+    std::vector<zke_email_ref> refs(n);
+    std::vector<uint32_t> off{0};
+    std::vector<zke_key_ref> keys;
+    for (uint32_t i = 0; i < n; i++) {
+      const Email& em = emails[i];
+      uint32_t ext = 0;
+      for (const auto& x : em.external_inputs) if (!x.value) ext = 1;
+      refs[i] = zke_email_ref{em.raw_email.data(), em.raw_email.size(), em.from_domain.data(), em.from_domain.size(), nullptr, 0, 0, ext};
+      for (const auto& k : candidate_keys[i])
+        keys.push_back(k ? zke_key_ref{k->key.data(), k->key.size(), key_type_code(k->key_type), 0} : zke_key_ref{nullptr, 0, ZKE_KEY_RSA, 0});
+      off.push_back((uint32_t)keys.size());
+    }
+    std::vector<zke_result> out(n);
+    chosen.assign(n, ZKE_SEL_NONE);
+    if (int r = zke_select_keys(e_, refs.data(), n, off.data(), keys.data(), out.data(), chosen.data()))
+      throw EngineError("zke_select_keys failed: " + std::to_string(r) + " " + zke_last_error(e_));
+    return out;
+  }
+
+  // helpers/src/generator.rs:11-53 generate_email_inputs for a batch: scan, `fetch_key` once per distinct (from_domain, selector)
+  // of a candidate, keep the first key under which the e-mail verifies.  Throws VerifyPanic for the first e-mail where the
+  // reference returns Err — a parse_mail error (the scan's status), "No DKIM signatures found" (ZKE_DKIM_NOT_PASS /
+  // ZKE_D_NO_SIGNATURE), "No valid DKIM key found for any signature" (ZKE_DKIM_NOT_PASS with the last candidate's detail) — and
+  // with ZKE_UNSUPPORTED where the engine cannot give the reference's answer.
+  std::vector<Email> generate_email_inputs(const std::vector<std::string>& from_domains, const std::vector<std::vector<uint8_t>>& raw_emails,
+                                           const FetchKey& fetch_key, const std::vector<std::vector<ExternalInput>>* external_inputs = nullptr,
+                                           uint32_t max_sigs = ZKE_SCAN_MAX_SIGS) {
+    const std::vector<SigScan> scans = scan_signatures(raw_emails, from_domains, max_sigs);
+    std::map<std::pair<std::string, std::string>, std::optional<PublicKey>> cache;
+    std::vector<std::vector<std::optional<PublicKey>>> cands(scans.size());
+    std::vector<Email> probe(scans.size());
+    for (size_t i = 0; i < scans.size(); i++) {
+      probe[i] = Email{from_domains[i], raw_emails[i], PublicKey{}, {}};
+      for (const SigInfo& s : scans[i].sigs) {
+        if (s.code != 0) continue;
+        auto key = std::make_pair(from_domains[i], s.selector);
+        auto it = cache.find(key);
+        if (it == cache.end()) it = cache.emplace(key, fetch_key(from_domains[i], s.selector)).first;
+        cands[i].push_back(it->second);
+      }
+    }
+    std::vector<uint32_t> chosen;
+    const std::vector<zke_result> recs = select_keys(probe, cands, chosen);
+    std::vector<Email> out;
+    for (size_t i = 0; i < scans.size(); i++) {
+      const SigScan& sc = scans[i];
+      if (sc.status != ZKE_OK) throw VerifyPanic(sc.status, sc.detail);
+      if (sc.n_signatures == 0) throw VerifyPanic(ZKE_DKIM_NOT_PASS, ZKE_D_NO_SIGNATURE);                       // generator.rs:21
+      if (chosen[i] == ZKE_SEL_NONE) {
+        if (sc.n_candidates > cands[i].size()) throw VerifyPanic(ZKE_UNSUPPORTED, ZKE_D_U_TOO_MANY_SIGS);       // the list was cut
+        throw VerifyPanic(recs[i].status == ZKE_UNSUPPORTED ? ZKE_UNSUPPORTED : ZKE_DKIM_NOT_PASS, recs[i].detail);   // generator.rs:52
+      }
+      if (chosen[i] & ZKE_SEL_AFTER_UNSUPPORTED) throw VerifyPanic(ZKE_UNSUPPORTED, ZKE_D_U_ALGO_ED25519);
+      Email em = probe[i];
+      em.public_key = *cands[i][chosen[i]];
+      if (external_inputs) em.external_inputs = (*external_inputs)[i];
+      out.push_back(std::move(em));
+    }
+    return out;
+  }
+
  private:
   static uint32_t key_type_code(const std::string& t) {
     return t == "rsa" ? ZKE_KEY_RSA : (t == "ed25519" ? ZKE_KEY_ED25519 : ZKE_KEY_OTHER);
@@ -254,6 +371,12 @@ inline Engine& default_engine() {
 inline EmailVerifierOutput verify_email(const Email& email) { return default_engine().verify_email(email); }
 inline EmailWithRegexVerifierOutput verify_email_with_regex(const EmailWithRegex& in) {
   return default_engine().verify_email_with_regex(in);
+}
+// helpers/src/generator.rs:11 generate_email_inputs(from_domain, raw_email, external_inputs) with the key fetch as a callback
+inline Email generate_email_inputs(const std::string& from_domain, const std::vector<uint8_t>& raw_email, const FetchKey& fetch_key,
+                                   std::optional<std::vector<ExternalInput>> external_inputs = std::nullopt) {
+  std::vector<std::vector<ExternalInput>> ext{external_inputs.value_or(std::vector<ExternalInput>{})};
+  return default_engine().generate_email_inputs({from_domain}, {raw_email}, fetch_key, &ext)[0];
 }
 
 }  // namespace zkemail

@@ -171,6 +171,38 @@ class zke_capture_out(C.Structure):
     ]
 
 
+SCAN_MAX_SIGS = 64
+SIG_ALGO_RSA_SHA256, SIG_ALGO_RSA_SHA1, SIG_ALGO_ED25519_SHA256, SIG_ALGO_OTHER = 0, 1, 2, 3
+SEL_NONE, SEL_AFTER_UNSUPPORTED = 0xFFFFFFFF, 0x80000000
+MAX_HEADERS, MAX_TAGS, MAX_TAGBUF = 256, 32, 2048
+
+
+class zke_sig_info(C.Structure):
+    """One DKIM-Signature header of a scan (zke_scan_signatures)."""
+    _fields_ = [("header_index", C.c_uint32), ("code", C.c_uint32), ("algo", C.c_uint32), ("sel_off", C.c_uint32), ("sel_len", C.c_uint32),
+                ("val_start", C.c_uint32), ("val_end", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SIG_INFO_DTYPE = np.dtype([("header_index", "<u4"), ("code", "<u4"), ("algo", "<u4"), ("sel_off", "<u4"), ("sel_len", "<u4"),
+                           ("val_start", "<u4"), ("val_end", "<u4"), ("reserved", "<u4")])
+assert C.sizeof(zke_sig_info) == 32 == SIG_INFO_DTYPE.itemsize
+
+
+class zke_sig_scan(C.Structure):
+    """Caller-sized buffers of a scan; capacities in entries, the sizes needed written back."""
+    _fields_ = [
+        ("scan_status", C.c_void_p), ("scan_status_cap", C.c_size_t), ("sig_off", C.c_void_p), ("sig_off_cap", C.c_size_t),
+        ("sigs", C.c_void_p), ("sigs_cap", C.c_size_t), ("sel_blob", C.c_void_p), ("sel_blob_cap", C.c_size_t),
+        ("scan_status_need", C.c_size_t), ("sig_off_need", C.c_size_t), ("sigs_need", C.c_size_t), ("sel_blob_need", C.c_size_t),
+        ("n_sigs", C.c_size_t),
+    ]
+
+
+class zke_key_ref(C.Structure):
+    """One candidate key of zke_select_keys; key_len 0: the fetch failed."""
+    _fields_ = [("key", C.c_void_p), ("key_len", C.c_size_t), ("key_type", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 STRICT_FLAGS = ("enforce_expiry_x", "canon_takes_verified_signature", "canon_ignores_l", "i_must_be_subdomain",
                 "b_removes_own_span_only")          # zke_options' strictness flags, in ZKE_STRICT_* bit order
 

@@ -68,22 +68,34 @@ def build_oracle(force: bool = False) -> str:
 
 
 CPP_EXAMPLE = os.path.join(ROOT, "tests", "cpp", "mirror_test")
+CPP_SIGSCAN = os.path.join(ROOT, "tests", "cpp", "sigscan_test")
 
 
-def build_cpp_example(force: bool = False) -> str:
-    """The C++ host mirror (include/zkemail_core.hpp) compiled against the built library."""
-    src = os.path.join(ROOT, "tests", "cpp", "mirror_test.cpp")
+def _build_cpp(exe: str, force: bool) -> str:
+    src = exe + ".cpp"
     deps = [src, os.path.join(ROOT, "include", "zkemail_core.hpp"), os.path.join(ROOT, "include", "zkemail_amd.h"), ENGINE_SO]
-    if not force and not _newer(CPP_EXAMPLE, deps):
-        return CPP_EXAMPLE
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), src, "-o", CPP_EXAMPLE,
+    if not force and not _newer(exe, deps):
+        return exe
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), src, "-o", exe,
            "-L", PKG, "-lzkemail_amd", "-L", "/opt/rocm/lib", "-lamdhip64",
            "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)
-        raise RuntimeError("g++ failed building tests/cpp/mirror_test")
-    return CPP_EXAMPLE
+        raise RuntimeError("g++ failed building " + os.path.relpath(exe, ROOT))
+    return exe
+
+
+def build_cpp_example(force: bool = False) -> str:
+    """The C++ host mirror (include/zkemail_core.hpp) compiled against the built library: the verify program, whose path is
+    returned, and the generator program (build_cpp_sigscan)."""
+    build_cpp_sigscan(force)
+    return _build_cpp(CPP_EXAMPLE, force)
+
+
+def build_cpp_sigscan(force: bool = False) -> str:
+    """tests/cpp/sigscan_test: scan_signatures / select_keys / generate_email_inputs of the C++ mirror."""
+    return _build_cpp(CPP_SIGSCAN, force)
 
 
 if __name__ == "__main__":

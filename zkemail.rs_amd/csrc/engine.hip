@@ -26,6 +26,7 @@
 #include "parse.hip.h"
 #include "regex.hip.h"
 #include "capture.hip.h"
+#include "sigscan.hip.h"
 #include "rsa_kernel.hip.h"
 #include "rsa_quad.hip.h"
 #include "fused.hip.h"
@@ -97,8 +98,16 @@ struct Slot {
   // programs too large for LDS, the pinned twin of everything but the blob, and where the pending batch's extraction goes
   CapBufs cb;
   zke_capture_out* cap_out = nullptr;
-  DevBuf* all[17] = {&meta, &rsa_jobs, &sha_jobs, &sha_order, &rsa_ok, &em_dbg, &scratch_off, &scratch, &clean, &meta2, &scratch2, &parts,
-                     &pending, &d_image, &d_results, &cb.cap, &cb.work};
+  // signature scan (zke_scan_signatures): statuses, record slots and selector blob in one buffer (ScanLayout) with its pinned
+  // twin, the header-span overflow area, and where the pending batch's scan goes
+  ScanBufs sb;
+  zke_sig_scan* scan_out = nullptr;
+  // key selection (zke_select_keys): the pending batch's records are folded per e-mail on delivery
+  std::vector<uint32_t> sel_off;       // cand_off of the pending selection (n + 1 entries; empty: the pending batch is no selection)
+  zke_result* sel_out = nullptr;
+  uint32_t* sel_chosen = nullptr;
+  DevBuf* all[19] = {&meta, &rsa_jobs, &sha_jobs, &sha_order, &rsa_ok, &em_dbg, &scratch_off, &scratch, &clean, &meta2, &scratch2, &parts,
+                     &pending, &d_image, &d_results, &cb.cap, &cb.work, &sb.out, &sb.ovf};
   // hipGraph replay of a batch's kernel sequence (zke_options.replay_graphs).  The graph holds this slot's
   // workspace pointers, so it is valid only while none of them has been reallocated: `generation` counts reallocations.
   hipGraphExec_t graph_exec = nullptr;
@@ -202,7 +211,7 @@ void free_slot(Slot* w) {
   if (!w) return;
   if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
   for (auto* b : w->all) b->release();
-  w->h_image.release(); w->h_results.release(); w->cb.h_cap.release();
+  w->h_image.release(); w->h_results.release(); w->cb.h_cap.release(); w->sb.h_out.release();
   for (auto& ev : w->ev) if (ev) (void)hipEventDestroy(ev);
   if (w->done) (void)hipEventDestroy(w->done);
   if (w->host_done) (void)hipEventDestroy(w->host_done);

@@ -238,4 +238,23 @@ struct CapBufs {
   void release() { cap.release(); work.release(); h_cap.release(); }
 };
 
+// The buffers of one signature scan (a slot's): {counter | statuses | record slots | selector blob} in one device buffer with a
+// pinned twin of the same layout — the whole of it comes back as ONE copy —, and the overflow of the header span tables.
+struct ScanLayout { size_t status, recs, blob, blob_cap, total; uint32_t n, max_sigs; };
+inline ScanLayout scan_layout(uint32_t n, uint32_t max_sigs, size_t blob_cap) {
+  ScanLayout L{};
+  L.n = n; L.max_sigs = max_sigs; L.blob_cap = blob_cap;
+  L.status = 64;                                                        // [0, 64): the selector bytes reserved so far
+  L.recs = align_up(L.status + (size_t)n * 16, 64);
+  L.blob = align_up(L.recs + (size_t)n * max_sigs * sizeof(zke_sig_info), 64);
+  L.total = L.blob + blob_cap;
+  return L;
+}
+struct ScanBufs {
+  DevBuf out, ovf;
+  PinnedBuf h_out;
+  ScanLayout L{};
+  void release() { out.release(); ovf.release(); h_out.release(); }
+};
+
 }  // namespace

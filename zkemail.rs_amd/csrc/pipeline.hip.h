@@ -153,6 +153,21 @@ int launch_capture(zke_engine* e, CapBufs& b, const CaptureReq& q, uint32_t n, b
 // entry points).  Three launches — front end, hash / modexp stage, Ed25519 + verdict (which also runs the later signature
 // rounds of the rare e-mail that needs them) — and, for verify_email_with_regex, the regex stage behind them.
 // Caller holds the slot's lock; everything the call needs is in its arguments or in the slot.
+// ---- signature scan and key selection (sigscan.hip.h; include/zkemail_amd.h)
+struct ScanReq { uint32_t max_sigs; zke_sig_scan* out; };
+struct SelectReq { const uint32_t* cand_off; uint32_t n; zke_result* out; uint32_t* chosen; };
+
+// A slot's scan buffers for n e-mails with max_sigs record slots each and blob_cap bytes of selectors.  Grow only: the first scan
+// of a shape allocates, a later one of the same shape does not.
+int ensure_scan_buffers(zke_engine* e, ScanBufs& b, uint32_t n, uint32_t max_sigs, size_t blob_cap) {
+  const ScanLayout L = scan_layout(n, max_sigs, blob_cap);
+  int r = 0;
+  if ((r = b.out.ensure(L.total)) || (r = b.h_out.ensure(L.total)) || (r = b.ovf.ensure((size_t)n * HDR_OVF_BYTES)))
+    return fail(e, r, "signature-scan buffer allocation");
+  b.L = L;
+  return 0;
+}
+
 int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t raw_total, uint64_t key_total, zke_result* out_dev,
                         hipStream_t s, bool want_em, uint64_t now, bool want_clean = false, const CaptureReq* cap = nullptr) {
   const uint32_t n = in->n;
@@ -395,16 +410,70 @@ int deliver_captures(zke_engine* e, CapBufs& b, zke_capture_out* o, hipStream_t 
   return 0;
 }
 
-// `cap_rc` (zke_batch_wait, the synchronous entries): where an extraction's shortfall is reported; a slot that retires a batch
-// nobody waited for has nobody to tell.
+// A scan from the slot's pinned twin into the caller's zke_sig_scan: statuses, the CSR over the record slots in use (the
+// compaction: one memcpy per e-mail), the selector bytes.  ZKE_E_NOMEM when sigs or sel_blob is too small (*_need says how much).
+int deliver_scan(zke_engine* e, const ScanBufs& b, zke_sig_scan* o) {
+  const ScanLayout& S = b.L;
+  const uint8_t* hp = b.h_out.as<uint8_t>();
+  const uint32_t* st = reinterpret_cast<const uint32_t*>(hp + S.status);
+  const zke_sig_info* recs = reinterpret_cast<const zke_sig_info*>(hp + S.recs);
+  const size_t used = *reinterpret_cast<const uint32_t*>(hp);
+  memcpy(o->scan_status, st, (size_t)S.n * 16);
+  size_t total = 0;
+  for (uint32_t i = 0; i < S.n; i++) { o->sig_off[i] = (uint32_t)total; total += std::min(st[4 * (size_t)i + 2], S.max_sigs); }
+  o->sig_off[S.n] = (uint32_t)total;
+  o->sigs_need = total; o->sel_blob_need = used; o->n_sigs = 0;
+  if (total > o->sigs_cap) return fail(e, ZKE_E_NOMEM, "signature scan: sigs is smaller than the records (zke_sig_scan.sigs_need)");
+  for (uint32_t i = 0; i < S.n; i++)
+    if (const uint32_t c = o->sig_off[i + 1] - o->sig_off[i]) memcpy(o->sigs + o->sig_off[i], recs + (size_t)i * S.max_sigs, (size_t)c * sizeof(zke_sig_info));
+  o->n_sigs = total;
+  if (used > S.blob_cap) return fail(e, ZKE_E_NOMEM, "signature scan: sel_blob is smaller than the selectors (zke_sig_scan.sel_blob_need)");
+  if (used) memcpy(o->sel_blob, hp + S.blob, used);
+  return 0;
+}
+
+// A key selection's fold: the records of the (e-mail, candidate) pairs are in the pinned buffer; per e-mail the first ZKE_OK.
+void fold_selection(const zke_result* R, const std::vector<uint32_t>& off, zke_result* out, uint32_t* chosen) {
+  for (size_t i = 0; i + 1 < off.size(); i++) {
+    const uint32_t a = off[i], b = off[i + 1];
+    if (a == b) {
+      memset(&out[i], 0, sizeof(zke_result));
+      out[i].status = ZKE_DKIM_NOT_PASS; out[i].detail = ZKE_D_NEUTRAL;
+      chosen[i] = ZKE_SEL_NONE;
+      continue;
+    }
+    uint32_t pick = ZKE_SEL_NONE, flag = 0;
+    for (uint32_t k = a; k < b; k++) {
+      if (R[k].status == ZKE_OK) { pick = k - a; break; }
+      if (R[k].status == ZKE_UNSUPPORTED) flag = ZKE_SEL_AFTER_UNSUPPORTED;
+    }
+    out[i] = R[pick == ZKE_SEL_NONE ? b - 1 : a + pick];
+    chosen[i] = pick == ZKE_SEL_NONE ? ZKE_SEL_NONE : (pick | flag);
+  }
+}
+
+// `cap_rc` (zke_batch_wait, the synchronous entries): where an extraction's or a scan's shortfall is reported; a slot that retires
+// a batch nobody waited for has nobody to tell.
 int retire_host(zke_engine* e, Slot& w, int* cap_rc = nullptr) {
   if (w.host_retired == w.host_gen) return 0;
   w.host_retired = w.host_gen;                       // whatever happens below, the batch is no longer pending
   zke_capture_out* pending_caps = w.cap_out;
   w.cap_out = nullptr;
+  zke_sig_scan* pending_scan = w.scan_out;
+  w.scan_out = nullptr;
   HIPCHK(e, hipEventSynchronize(w.host_done));
   if (w.host_out && w.host_n) memcpy(w.host_out, w.h_results.p, (size_t)w.host_n * sizeof(zke_result));
   w.host_out = nullptr;
+  if (!w.sel_off.empty()) {
+    fold_selection(w.h_results.as<zke_result>(), w.sel_off, w.sel_out, w.sel_chosen);
+    w.sel_off.clear();
+  }
+  if (pending_scan) {
+    const std::string keep = g_err;
+    const int r = deliver_scan(e, w.sb, pending_scan);
+    if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
+    else if (r) return r;
+  }
   if (pending_caps) {
     const std::string keep = g_err;
     const int r = deliver_captures(e, w.cb, pending_caps, w.stream);
@@ -434,6 +503,8 @@ struct HostBatch {
   zke_batch b{};                        // n, the regex section, (packed) the caller's blobs and offsets; capture tables only if any
   const zke_email_ref* refs = nullptr;  // the gathered shape's e-mails (nullptr: packed)
   CaptureReq* cap = nullptr;            // zke_extract_captures: the extraction that rides on this (regex) batch
+  const ScanReq* scan = nullptr;        // zke_scan_signatures: sigscan_kernel runs instead of the verify pipeline
+  const SelectReq* sel = nullptr;       // zke_select_keys: the batch's entries are (e-mail, candidate key) pairs, folded on delivery
   uint64_t raw_total = 0, dom_total = 0, key_total = 0, raw_base = 0, dom_base = 0, key_base = 0;   // blob bytes; off[0] of packed offsets
   size_t cap_words = 0, cap_strs = 0, cap_bytes = 0;      // entries of cap_off and cap_str_off, bytes of cap_blob (0: no tables)
   ImageLayout L{};
@@ -495,6 +566,10 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   if (d.cap) {
     if (int r = ensure_capture_buffers(e, w.cb, n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap, d.cap->needs_work)) return r;
     w.cb.L = cap_layout(n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap);
+  }
+  if (d.scan) {      // (a selector is at most ZKE_MAX_TAGBUF bytes: a larger blob than that per record slot is never used)
+    const size_t blob = std::min<size_t>(d.scan->out->sel_blob_cap, (size_t)n * d.scan->max_sigs * ZKE_MAX_TAGBUF);
+    if (int r = ensure_scan_buffers(e, w.sb, n, d.scan->max_sigs, blob)) return r;
   }
   uint8_t* hp = w.h_image.as<uint8_t>();
   if (d.refs) {
@@ -570,14 +645,41 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   dv.cap_off = d.cap_words ? reinterpret_cast<const uint32_t*>(dp + L.cap_off) : nullptr;
   dv.cap_str_off = d.cap_words ? reinterpret_cast<const uint32_t*>(dp + L.cap_str_off) : nullptr;
   dv.cap_blob = d.cap_words ? dp + L.cap_blob : nullptr;
+  if (d.scan) {
+    // one launch, no verify workspace: the counter of selector bytes starts at zero, everything comes back as one copy
+    const ScanLayout& S = w.sb.L;
+    uint8_t* so = w.sb.out.as<uint8_t>();
+    HIPCHK(e, hipMemsetAsync(so, 0, 64, s));
+    SigScanArgs sa{};
+    sa.n = n; sa.max_sigs = S.max_sigs;
+    sa.raw = dv.raw_blob; sa.raw_off = dv.raw_off; sa.dom = dv.domain_blob; sa.dom_off = dv.domain_off;
+    sa.strict = e->strict; sa.now = batch_clock(e);
+    sa.status = reinterpret_cast<uint32_t*>(so + S.status);
+    sa.recs = reinterpret_cast<zke_sig_info*>(so + S.recs);
+    sa.sel_blob = so + S.blob; sa.sel_cap = (uint32_t)S.blob_cap;
+    sa.sel_used = reinterpret_cast<uint32_t*>(so);
+    sa.hdr_ovf = w.sb.ovf.as<uint32_t>();
+    hipLaunchKernelGGL(sigscan_kernel, dim3(n), dim3(64), 0, s, sa);
+    HIPCHK(e, hipGetLastError());
+    tm.mark(MK_FRONT); tm.mark(MK_HASH); tm.mark(MK_VERDICT);      // zke_timings.front_end_us is the scan; the other stages are empty
+    HIPCHK(e, hipMemcpyAsync(w.sb.h_out.p, so, S.total, hipMemcpyDeviceToHost, s));
+  } else {
   if (int r = run_device_pipeline(e, w, &dv, d.raw_total, d.key_total, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap)) return r;
   HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
+  }
   if (d.cap) HIPCHK(e, hipMemcpyAsync(w.cb.h_cap.p, w.cb.cap.p, w.cb.L.fixed_end, hipMemcpyDeviceToHost, s));
   tm.mark(MK_D2H);
   HIPCHK(e, hipEventRecord(w.host_done, s));
   w.host_gen++;
-  w.host_out = out; w.host_n = n;
+  w.host_out = (d.scan || d.sel) ? nullptr : out; w.host_n = n;
   w.cap_out = d.cap ? d.cap->out : nullptr;
+  w.scan_out = d.scan ? d.scan->out : nullptr;
+  w.sel_off.clear();
+  if (d.sel) {
+    w.sel_off.resize((size_t)d.sel->n + 1);
+    for (uint32_t i = 0; i <= d.sel->n; i++) w.sel_off[i] = d.sel->cand_off[i] - d.sel->cand_off[0];
+    w.sel_out = d.sel->out; w.sel_chosen = d.sel->chosen;
+  }
   return use.release();
 }
 
@@ -1048,6 +1150,72 @@ int zke_verify_email_with_regex(zke_engine* e, const uint8_t* raw, size_t raw_le
   const zke_email_ref one{raw, raw_len, from_domain, domain_len, key, key_len, key_type, external_input_null};
   const zke_regex_lists lists{n_header_parts, hids.data(), n_body_parts, bids.data(), cap_off.data(), str_off.data(), blob.data()};
   return zke_verify_emails_with_regex(e, &one, 1, &lists, out);
+}
+
+// ---- signature scan and key selection (include/zkemail_amd.h; kernel: sigscan.hip.h)
+int zke_scan_signatures_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t max_sigs, zke_sig_scan* out, uint64_t* ticket) {
+  static const char who[] = "zke_scan_signatures";
+  if (!e) return ZKE_E_ARG;
+  if (!out || !ticket || (n && !emails)) return arg_error(who, "null pointer");
+  if (max_sigs < 1 || max_sigs > ZKE_SCAN_MAX_SIGS) return arg_error(who, "max_sigs must be 1 .. ZKE_SCAN_MAX_SIGS");
+  if ((uint64_t)n * max_sigs >= (1ull << 21)) return arg_error(who, "n * max_sigs must stay below 2^21 (32-bit selector offsets): split the batch");
+  out->scan_status_need = (size_t)n * 4; out->sig_off_need = (size_t)n + 1; out->sigs_need = 0; out->sel_blob_need = 0; out->n_sigs = 0;
+  if (out->scan_status_cap < out->scan_status_need || out->sig_off_cap < out->sig_off_need) {
+    g_err = std::string(who) + ": a zke_sig_scan buffer is smaller than its *_need";
+    return ZKE_E_NOMEM;
+  }
+  if ((n && !out->scan_status) || !out->sig_off || (out->sigs_cap && !out->sigs) || (out->sel_blob_cap && !out->sel_blob))
+    return arg_error(who, "null buffer in zke_sig_scan");
+  out->sig_off[0] = 0;
+  std::vector<zke_email_ref> refs(emails, emails + n);              // the key fields are ignored: the image has no key section
+  for (zke_email_ref& m : refs) { m.key = nullptr; m.key_len = 0; m.key_type = ZKE_KEY_RSA; m.external_input_null = 0; }
+  HostBatch d;
+  if (int r = host_batch(d, who, reinterpret_cast<const zke_result*>(out), refs.data(), n, nullptr)) return r;
+  const ScanReq q{max_sigs, out};
+  d.scan = &q;
+  return submit_host_batch(e, d, nullptr, ticket);
+}
+
+int zke_scan_signatures(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t max_sigs, zke_sig_scan* out) {
+  uint64_t ticket = 0;
+  if (int r = zke_scan_signatures_async(e, emails, n, max_sigs, out, &ticket)) return r;
+  return n ? zke_batch_wait(e, ticket) : 0;
+}
+
+int zke_select_keys_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off, const zke_key_ref* keys,
+                          zke_result* out, uint32_t* chosen, uint64_t* ticket) {
+  static const char who[] = "zke_select_keys";
+  if (!e) return ZKE_E_ARG;
+  if (!ticket || (n && (!emails || !cand_off || !out || !chosen))) return arg_error(who, "null pointer");
+  if (n && !rising(cand_off, n)) return arg_error(who, "cand_off is not non-decreasing");
+  const uint32_t base = n ? cand_off[0] : 0, M = n ? cand_off[n] - base : 0;
+  if (M >> 31) return arg_error(who, "2^31 candidates or more");
+  if (M && !keys) return arg_error(who, "null pointer");
+  // ONE batch of the (e-mail, candidate key) pairs: the raw e-mail and the domain by reference, once per candidate
+  std::vector<zke_email_ref> refs(M);
+  for (uint32_t i = 0; i < n; i++)
+    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; k++) {
+      zke_email_ref& m = refs[k - base];
+      m = emails[i];
+      m.key = keys[k].key; m.key_len = keys[k].key_len; m.key_type = keys[k].key_type;
+    }
+  HostBatch d;
+  if (int r = host_batch(d, who, out, refs.data(), M, nullptr)) return r;
+  if (!M) {            // no candidate anywhere: nothing to run
+    const std::vector<uint32_t> off((size_t)n + 1, 0u);
+    if (n) fold_selection(nullptr, off, out, chosen);
+    return submit_host_batch(e, d, out, ticket);
+  }
+  const SelectReq q{cand_off, n, out, chosen};
+  d.sel = &q;
+  return submit_host_batch(e, d, out, ticket);
+}
+
+int zke_select_keys(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off, const zke_key_ref* keys,
+                    zke_result* out, uint32_t* chosen) {
+  uint64_t ticket = 0;
+  if (int r = zke_select_keys_async(e, emails, n, cand_off, keys, out, chosen, &ticket)) return r;
+  return n ? zke_batch_wait(e, ticket) : 0;
 }
 
 // ---- capture extraction (include/zkemail_amd.h; kernels: capture.hip.h)

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -138,6 +138,15 @@ def load_library(path: Optional[str] = None):
     lib.zke_extract_captures_async.restype = C.c_int
     lib.zke_capture_batch.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, vp, cop]
     lib.zke_capture_batch.restype = C.c_int
+    erp = C.POINTER(A.zke_email_ref)
+    lib.zke_scan_signatures.argtypes = [vp, erp, C.c_uint32, C.c_uint32, C.POINTER(A.zke_sig_scan)]
+    lib.zke_scan_signatures.restype = C.c_int
+    lib.zke_scan_signatures_async.argtypes = [vp, erp, C.c_uint32, C.c_uint32, C.POINTER(A.zke_sig_scan), C.POINTER(C.c_uint64)]
+    lib.zke_scan_signatures_async.restype = C.c_int
+    lib.zke_select_keys.argtypes = [vp, erp, C.c_uint32, vp, C.POINTER(A.zke_key_ref), vp, vp]
+    lib.zke_select_keys.restype = C.c_int
+    lib.zke_select_keys_async.argtypes = [vp, erp, C.c_uint32, vp, C.POINTER(A.zke_key_ref), vp, vp, C.POINTER(C.c_uint64)]
+    lib.zke_select_keys_async.restype = C.c_int
     lib.zke_version.argtypes = []
     lib.zke_version.restype = C.c_char_p
     lib.zke_device_available.argtypes = []
@@ -158,7 +167,51 @@ EXPORTED_SYMBOLS = [
     "zke_verify_emails_with_regex", "zke_verify_emails_with_regex_async",
     "zke_capture_validate", "zke_capture_register", "zke_capture_status", "zke_capture_unregister", "zke_extract_captures",
     "zke_extract_captures_async", "zke_capture_batch",
+    "zke_scan_signatures", "zke_scan_signatures_async", "zke_select_keys", "zke_select_keys_async",
 ]
+
+
+class SigInfo(NamedTuple):
+    """One DKIM-Signature header as zke_scan_signatures reports it (zke_sig_info, the selector as bytes)."""
+    header_index: int
+    code: int                      # 0 candidate | D_NEUTRAL other domain | D_* why validate_header refuses it
+    algo: int                      # SIG_ALGO_*; meaningful when code is 0 or D_NEUTRAL
+    selector: bytes
+    value_span: Tuple[int, int]    # the header's value in raw_email
+
+
+class SigScan(NamedTuple):
+    """A scan's answer for one e-mail: (status, detail, sigs) and the true counts (sigs holds the first max_sigs)."""
+    status: int
+    detail: int
+    sigs: List[SigInfo]
+    n_signatures: int = 0
+    n_candidates: int = 0
+
+
+class _ScanBuffers:
+    """The caller-sized buffers of one zke_sig_scan (kept alive until the batch has been waited for)."""
+
+    def __init__(self, n: int, max_sigs: int, blob_bytes: int):
+        self.n = n
+        self.status = np.zeros((max(n, 1), 4), np.uint32)
+        self.sig_off = np.zeros(n + 1, np.uint32)
+        self.sigs = np.zeros(max(n * max_sigs, 1), A.SIG_INFO_DTYPE)
+        self.blob = np.zeros(max(blob_bytes, 1), np.uint8)
+        o = self.c = A.zke_sig_scan()
+        o.scan_status, o.scan_status_cap, o.sig_off, o.sig_off_cap = self.status.ctypes.data, 4 * n, self.sig_off.ctypes.data, n + 1
+        o.sigs, o.sigs_cap, o.sel_blob, o.sel_blob_cap = self.sigs.ctypes.data, n * max_sigs, self.blob.ctypes.data, blob_bytes
+
+    def result(self) -> List[SigScan]:
+        blob = self.blob.tobytes()
+        out = []
+        for i in range(self.n):
+            st = self.status[i]
+            sigs = [SigInfo(int(r["header_index"]), int(r["code"]), int(r["algo"]),
+                            blob[int(r["sel_off"]):int(r["sel_off"]) + int(r["sel_len"])], (int(r["val_start"]), int(r["val_end"])))
+                    for r in self.sigs[int(self.sig_off[i]):int(self.sig_off[i + 1])]]
+            out.append(SigScan(int(st[0]), int(st[1]), sigs, int(st[2]), int(st[3])))
+        return out
 
 
 class Engine:
@@ -338,6 +391,79 @@ class Engine:
             infos.append(A.RegexInfo(parts[:len(hp)] if regex_config.header_parts is not None else None,
                                      parts[len(hp):] if regex_config.body_parts is not None else None))
         return out[:n], infos
+
+    # ---- DKIM-Signature scan and key selection (helpers/src/generator.rs:11-53 around the caller's DNS fetch)
+    @staticmethod
+    def _scan_refs(raw_emails: Sequence[bytes], from_domains: Sequence[str]) -> "A.EmailRefs":
+        if len(raw_emails) != len(from_domains):
+            raise ValueError("one from_domain per raw e-mail")
+        return A.EmailRefs([Email(d, bytes(r), A.PublicKey(b"")) for r, d in zip(raw_emails, from_domains)])
+
+    def scan_signatures(self, raw_emails: Sequence[bytes], from_domains: Sequence[str], max_sigs: int = 8, *, blob_bytes: Optional[int] = None) -> List[SigScan]:
+        """zke_scan_signatures: per e-mail (status, detail, [SigInfo]) — every DKIM-Signature header with validate_header's verdict,
+        whether d= names from_domain (code 0), a= classified and the selector; plus the true counts n_signatures / n_candidates
+        (the list holds the first `max_sigs`).  `blob_bytes`: the selector buffer's size (default 32 bytes per record slot; the
+        call is repeated once with the size the engine reports when that is too small)."""
+        refs = self._scan_refs(raw_emails, from_domains)
+        n = refs.n
+        blob_bytes = 32 * n * max_sigs if blob_bytes is None else blob_bytes
+        for attempt in (0, 1):
+            b = _ScanBuffers(n, max_sigs, blob_bytes)
+            rc = self.lib.zke_scan_signatures(self.h, refs.arr, n, max_sigs, C.byref(b.c))
+            if rc == -3 and attempt == 0 and b.c.sel_blob_need > blob_bytes:           # ZKE_E_NOMEM: the selectors need a larger blob
+                blob_bytes = int(b.c.sel_blob_need)
+                continue
+            self._check(rc, "zke_scan_signatures")
+            return b.result()
+
+    def scan_signatures_async(self, raw_emails: Sequence[bytes], from_domains: Sequence[str], max_sigs: int = 8, *, blob_bytes: Optional[int] = None):
+        """zke_scan_signatures_async: (ticket, pending); ``pending.result()`` is valid once ``wait(ticket)`` has returned."""
+        refs = self._scan_refs(raw_emails, from_domains)
+        b = _ScanBuffers(refs.n, max_sigs, 32 * refs.n * max_sigs if blob_bytes is None else blob_bytes)
+        b.refs = refs
+        t = C.c_uint64()
+        self._check(self.lib.zke_scan_signatures_async(self.h, refs.arr, refs.n, max_sigs, C.byref(b.c), C.byref(t)), "zke_scan_signatures_async")
+        return t.value, b
+
+    @staticmethod
+    def _key_refs(candidate_keys):
+        flat = [k for ks in candidate_keys for k in ks]
+        off = np.zeros(len(candidate_keys) + 1, np.uint32)
+        off[1:] = np.cumsum([len(ks) for ks in candidate_keys])
+        arr = (A.zke_key_ref * max(len(flat), 1))()
+        keep = []
+        for j, k in enumerate(flat):
+            kb = bytes(k.key) if k is not None else b""
+            keep.append(kb)
+            arr[j].key = C.cast(C.c_char_p(kb), C.c_void_p).value if kb else None
+            arr[j].key_len = len(kb)
+            arr[j].key_type = A.key_type_code(k.key_type) if k is not None else A.KEY_RSA
+        return off, arr, keep
+
+    def select_keys(self, emails, candidate_keys: Sequence[Sequence[Optional["A.PublicKey"]]]):
+        """zke_select_keys: candidate_keys[i] = the keys fetched for e-mail i's candidates, in the scan's order (None or an empty
+        key: the fetch failed).  Returns (records, chosen): chosen[i] = the first key under which the e-mail verifies (bit 31,
+        _abi.SEL_AFTER_UNSUPPORTED: an earlier candidate was outside what the engine implements) or _abi.SEL_NONE; records[i] = that
+        verification's record.  The e-mails' own public_key fields are ignored."""
+        refs = emails if isinstance(emails, A.EmailRefs) else A.EmailRefs(emails)
+        if refs.n != len(candidate_keys):
+            raise ValueError("one candidate list per e-mail")
+        off, arr, keep = self._key_refs(candidate_keys)
+        out = np.zeros(max(refs.n, 1), dtype=A.RESULT_DTYPE)
+        chosen = np.zeros(max(refs.n, 1), np.uint32)
+        self._check(self.lib.zke_select_keys(self.h, refs.arr, refs.n, off.ctypes.data, arr, out.ctypes.data, chosen.ctypes.data), "zke_select_keys")
+        return out[:refs.n], chosen[:refs.n]
+
+    def select_keys_async(self, emails, candidate_keys):
+        """zke_select_keys_async: (ticket, records, chosen), valid once ``wait(ticket)`` has returned."""
+        refs = emails if isinstance(emails, A.EmailRefs) else A.EmailRefs(emails)
+        off, arr, keep = self._key_refs(candidate_keys)
+        out = np.zeros(max(refs.n, 1), dtype=A.RESULT_DTYPE)
+        chosen = np.zeros(max(refs.n, 1), np.uint32)
+        t = C.c_uint64()
+        self._check(self.lib.zke_select_keys_async(self.h, refs.arr, refs.n, off.ctypes.data, arr, out.ctypes.data, chosen.ctypes.data, C.byref(t)),
+                    "zke_select_keys_async")
+        return t.value, out[:refs.n], chosen[:refs.n]
 
     # ---- batches
     def verify_batch_async(self, batch: PackedBatch):
@@ -577,6 +703,64 @@ def generate_email_with_regex_inputs(emails: Sequence[Email], regex_config, *, u
         if r["status"] != A.ZKE_OK:
             raise VerifyPanic(int(r["status"]), int(r["detail"]), i)
     return [EmailWithRegex(e, info) for e, info in zip(emails, infos)]
+
+
+NO_SIGNATURES = "No DKIM signatures found"                         # helpers/src/generator.rs:21
+NO_VALID_KEY = "No valid DKIM key found for any signature"        # helpers/src/generator.rs:52
+
+
+def generate_email_inputs(from_domains: Sequence[str], raw_emails: Sequence[bytes],
+                          fetch_key: Callable[[str, bytes], Optional["A.PublicKey"]],
+                          external_inputs: Optional[Sequence[Optional[Sequence["A.ExternalInput"]]]] = None, *,
+                          max_sigs: int = A.SCAN_MAX_SIGS, engine: Optional[Engine] = None) -> List[Email]:
+    """helpers/src/generator.rs:11-53 generate_email_inputs for a batch: scan the DKIM-Signature headers on the GPU, ask
+    `fetch_key(from_domain, selector)` — the caller's resolver, the only place network code would live; called once per distinct
+    pair, on the host, between the two GPU calls; None: the fetch failed — for the key of every candidate, and keep the first key
+    under which the e-mail verifies.  Returns one Email per e-mail.  Raises VerifyPanic (its ``reason`` holds the reference's text)
+    for the first e-mail where the reference returns Err: a parse_mail error, "No DKIM signatures found", "No valid DKIM key found
+    for any signature".  An e-mail whose answer the engine cannot give (ZKE_UNSUPPORTED) raises too, with that status."""
+    eng = engine or default_engine()
+    n = len(raw_emails)
+    scans = eng.scan_signatures(raw_emails, from_domains, max_sigs)
+    cache: Dict[Tuple[str, bytes], Optional[A.PublicKey]] = {}
+    cands: List[List[Optional[A.PublicKey]]] = []
+    for dom, sc in zip(from_domains, scans):
+        row = []
+        for sig in sc.sigs:
+            if sig.code != 0:
+                continue
+            k = (dom, sig.selector)
+            if k not in cache:
+                cache[k] = fetch_key(dom, sig.selector)
+            row.append(cache[k])
+        cands.append(row)
+    probe = [Email(d, bytes(r), A.PublicKey(b"")) for d, r in zip(from_domains, raw_emails)]
+    records, chosen = eng.select_keys(probe, cands)
+
+    def err(status, detail, i, reason):
+        e = VerifyPanic(status, detail, i)
+        e.reason = reason
+        e.args = (f"email {i}: {reason} ({A.STATUS_NAMES.get(status, status)}, detail {detail})",)
+        return e
+
+    out = []
+    for i, sc in enumerate(scans):
+        if sc.status != A.ZKE_OK:
+            raise err(sc.status, sc.detail, i, "parse_mail failed" if sc.status == A.ZKE_PARSE_FAIL else "outside what the engine implements")
+        if sc.n_signatures == 0:
+            raise err(A.ZKE_DKIM_NOT_PASS, A.D_NO_SIGNATURE, i, NO_SIGNATURES)
+        if sc.n_candidates > len(cands[i]) and int(chosen[i]) == A.SEL_NONE:
+            raise err(A.ZKE_UNSUPPORTED, A.D_U_TOO_MANY_SIGS, i, f"more than {max_sigs} DKIM-Signature headers: the list was cut before a key passed")
+        if int(chosen[i]) == A.SEL_NONE:
+            r = records[i]
+            st = int(r["status"]) if int(r["status"]) == A.ZKE_UNSUPPORTED else A.ZKE_DKIM_NOT_PASS
+            raise err(st, int(r["detail"]), i, NO_VALID_KEY)
+        if int(chosen[i]) & A.SEL_AFTER_UNSUPPORTED:
+            raise err(A.ZKE_UNSUPPORTED, A.D_U_ALGO_ED25519, i, "a candidate in front of the passing key is outside what the engine implements")
+        key = cands[i][int(chosen[i])]
+        ext = list(external_inputs[i] or []) if external_inputs is not None else []
+        out.append(Email(from_domains[i], bytes(raw_emails[i]), A.PublicKey(bytes(key.key), key.key_type), ext))
+    return out
 
 
 def abi_encode_native(email: EmailVerifierOutput, matches: Optional[Sequence[str]] = None) -> bytes:
