@@ -91,6 +91,21 @@ pub struct SigInfo {
     pub value_span: (u32, u32),
 }
 
+/// One DKIM key record as a decode reports it (`zke_key_info`, the key as bytes): `code` 0 and the key, or `ZKE_D_KEYREC_*`.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct KeyInfo {
+    pub code: u32,
+    pub key_type: u32,
+    pub key: Vec<u8>,
+}
+
+impl KeyInfo {
+    /// `Email.public_key` of a record that decoded.
+    pub fn public_key(&self) -> PublicKey {
+        PublicKey { key: self.key.clone(), key_type: if self.key_type == sys::ZKE_KEY_ED25519 { "ed25519".into() } else { "rsa".into() } }
+    }
+}
+
 /// A scan's answer for one e-mail; `sigs` holds the first `max_sigs` headers, the counts are the true ones.
 #[derive(Debug, Clone, PartialEq, Eq)]
 pub struct SigScan {
@@ -704,6 +719,168 @@ impl Engine {
     }
 }
 
+/// The records of one call as `zke_keyrec_ref[m]` and the buffers of its `zke_keyrec_out` (3/4 of the records' bytes hold every key).
+struct KeyrecCall {
+    refs: Vec<sys::zke_keyrec_ref>,
+    infos: Vec<sys::zke_key_info>,
+    keys: Vec<u8>,
+}
+
+impl KeyrecCall {
+    fn new(records: &[Option<&[u8]>]) -> Self {
+        let refs: Vec<sys::zke_keyrec_ref> = records
+            .iter()
+            .map(|r| match r {
+                Some(r) if !r.is_empty() => sys::zke_keyrec_ref { txt: r.as_ptr(), len: r.len() },
+                _ => sys::zke_keyrec_ref { txt: ptr::null(), len: 0 },
+            })
+            .collect();
+        let total: usize = refs.iter().map(|r| r.len).sum();
+        let infos = vec![sys::zke_key_info { code: 0, key_type: 0, key_off: 0, key_len: 0 }; records.len() + 1];
+        KeyrecCall { refs, infos, keys: vec![0u8; total * 3 / 4 + 1] }
+    }
+
+    fn out(&mut self) -> sys::zke_keyrec_out {
+        sys::zke_keyrec_out {
+            infos: self.infos.as_mut_ptr(),
+            infos_cap: self.refs.len(),
+            keys: self.keys.as_mut_ptr(),
+            keys_cap: self.keys.len(),
+            infos_need: 0,
+            keys_need: 0,
+        }
+    }
+
+    fn result(&self) -> Vec<KeyInfo> {
+        self.infos[..self.refs.len()]
+            .iter()
+            .map(|f| KeyInfo { code: f.code, key_type: f.key_type, key: self.keys[f.key_off as usize..(f.key_off + f.key_len) as usize].to_vec() })
+            .collect()
+    }
+}
+
+impl Engine {
+    /// `helpers/src/dkim.rs:67-111` for a slice (`zke_decode_key_records`): what a resolver returns -> the (key, key_type) pair of
+    /// `Email.public_key`.  `mode`: `ZKE_KEYREC_DNS` (the TXT record of RFC 6376 3.6.1) or `ZKE_KEYREC_ARCHIVE` (the archive's value
+    /// as dkim.rs reads it); `None` or an empty record: the fetch failed.
+    pub fn decode_key_records(&self, records: &[Option<&[u8]>], mode: u32) -> Result<Vec<KeyInfo>, EngineError> {
+        let mut call = KeyrecCall::new(records);
+        let mut out = call.out();
+        // SAFETY: every pointer refers into `records` or `call`, alive until the synchronous call returns.
+        let rc = unsafe { sys::zke_decode_key_records(self.raw, call.refs.as_ptr(), call.refs.len() as u32, mode, &mut out) };
+        if rc != 0 {
+            return Err(self.last_error(rc));
+        }
+        Ok(call.result())
+    }
+
+    /// `zke_select_keys_from_records`: `select_keys` with the resolver's raw answers in place of keys; the records are decoded on
+    /// the GPU in front of the verify launches and the decoded keys stay in HBM on their way there.  Returns the records, `chosen`
+    /// and, per e-mail, what each candidate decoded to.
+    pub fn select_keys_from_records(
+        &self,
+        raw_emails: &[&[u8]],
+        from_domains: &[&str],
+        candidate_records: &[Vec<Option<Vec<u8>>>],
+        mode: u32,
+    ) -> Result<(Vec<sys::zke_result>, Vec<u32>, Vec<Vec<KeyInfo>>), EngineError> {
+        let n = raw_emails.len();
+        if from_domains.len() != n || candidate_records.len() != n {
+            return Err(EngineError { code: sys::ZKE_E_ARG, message: "one from_domain and one candidate list per raw e-mail".into() });
+        }
+        let refs: Vec<sys::zke_email_ref> = raw_emails
+            .iter()
+            .zip(from_domains)
+            .map(|(r, d)| sys::zke_email_ref {
+                raw: r.as_ptr(),
+                raw_len: r.len(),
+                from_domain: d.as_ptr().cast(),
+                domain_len: d.len(),
+                key: ptr::null(),
+                key_len: 0,
+                key_type: 0,
+                external_input_null: 0,
+            })
+            .collect();
+        let mut off: Vec<u32> = vec![0];
+        let mut flat: Vec<Option<&[u8]>> = Vec::new();
+        for row in candidate_records {
+            flat.extend(row.iter().map(|r| r.as_deref()));
+            off.push(flat.len() as u32);
+        }
+        let mut call = KeyrecCall::new(&flat);
+        let mut keys_out = call.out();
+        let mut out = vec![zeroed_result(); n];
+        let mut chosen = vec![sys::ZKE_SEL_NONE; n];
+        // SAFETY: every pointer refers into the arguments, `call` or the Vecs above, alive until the synchronous call returns.
+        let rc = unsafe {
+            sys::zke_select_keys_from_records(self.raw, refs.as_ptr(), n as u32, off.as_ptr(), call.refs.as_ptr(), mode, out.as_mut_ptr(), chosen.as_mut_ptr(), &mut keys_out)
+        };
+        if rc != 0 {
+            return Err(self.last_error(rc));
+        }
+        let all = call.result();
+        let infos = (0..n).map(|i| all[off[i] as usize..off[i + 1] as usize].to_vec()).collect();
+        Ok((out, chosen, infos))
+    }
+
+    /// `generate_email_inputs` with the resolver's RAW answers: `fetch_record(from_domain, selector)` returns the TXT record of
+    /// `selector._domainkey.from_domain` (its character-strings joined) or the archive's value, `None` when the fetch failed.
+    /// "Raw e-mails + the records in, `Email` values out": the caller is left with network code only.
+    pub fn generate_email_inputs_from_records<F>(
+        &self,
+        from_domains: &[&str],
+        raw_emails: &[&[u8]],
+        mut fetch_record: F,
+        mode: u32,
+        external_inputs: Option<&[Vec<ExternalInput>]>,
+    ) -> Result<Vec<Result<Email, Panic>>, EngineError>
+    where
+        F: FnMut(&str, &str) -> Option<Vec<u8>>,
+    {
+        let scans = self.scan_signatures(raw_emails, from_domains, sys::ZKE_SCAN_MAX_SIGS)?;
+        let mut cache: std::collections::HashMap<(String, String), Option<Vec<u8>>> = std::collections::HashMap::new();
+        let mut cands: Vec<Vec<Option<Vec<u8>>>> = Vec::with_capacity(scans.len());
+        for (sc, dom) in scans.iter().zip(from_domains) {
+            let mut row = Vec::new();
+            for s in sc.sigs.iter().filter(|s| s.code == 0) {
+                let key = (dom.to_string(), s.selector.clone());
+                let k = cache.entry(key).or_insert_with(|| fetch_record(dom, &s.selector));
+                row.push(k.clone());
+            }
+            cands.push(row);
+        }
+        let (recs, chosen, infos) = self.select_keys_from_records(raw_emails, from_domains, &cands, mode)?;
+        Ok((0..scans.len())
+            .map(|i| {
+                let sc = &scans[i];
+                if sc.status != sys::ZKE_OK {
+                    return Err(Panic { status: sc.status, detail: sc.detail });
+                }
+                if sc.n_signatures == 0 {
+                    return Err(Panic { status: sys::ZKE_DKIM_NOT_PASS, detail: sys::ZKE_D_NO_SIGNATURE }); // generator.rs:21
+                }
+                if chosen[i] == sys::ZKE_SEL_NONE {
+                    if sc.n_candidates as usize > cands[i].len() {
+                        return Err(Panic { status: sys::ZKE_UNSUPPORTED, detail: sys::ZKE_D_U_TOO_MANY_SIGS }); // the list was cut
+                    }
+                    let status = if recs[i].status == sys::ZKE_UNSUPPORTED { sys::ZKE_UNSUPPORTED } else { sys::ZKE_DKIM_NOT_PASS };
+                    return Err(Panic { status, detail: recs[i].detail }); // generator.rs:52
+                }
+                if chosen[i] & sys::ZKE_SEL_AFTER_UNSUPPORTED != 0 {
+                    return Err(Panic { status: sys::ZKE_UNSUPPORTED, detail: sys::ZKE_D_U_ALGO_ED25519 });
+                }
+                Ok(Email {
+                    from_domain: from_domains[i].to_string(),
+                    raw_email: raw_emails[i].to_vec(),
+                    public_key: infos[i][chosen[i] as usize].public_key(),
+                    external_inputs: external_inputs.map(|x| x[i].clone()).unwrap_or_default(),
+                })
+            })
+            .collect())
+    }
+}
+
 impl Drop for Engine {
     fn drop(&mut self) {
         // SAFETY: the handle came from zke_engine_create and is destroyed once.
@@ -740,6 +917,25 @@ where
 {
     let ext = [external_inputs.unwrap_or_default()];
     match default_engine().generate_email_inputs(&[from_domain], &[raw_email], fetch_key, Some(&ext)) {
+        Err(e) => panic!("{e}"),
+        Ok(mut v) => v.remove(0),
+    }
+}
+
+/// `generate_email_inputs` with the resolver's raw answer (TXT record or archive value) in place of the key: what
+/// `helpers/src/dkim.rs:67-111` does with it runs on the GPU.
+pub fn generate_email_inputs_from_records<F>(
+    from_domain: &str,
+    raw_email: &[u8],
+    fetch_record: F,
+    mode: u32,
+    external_inputs: Option<Vec<ExternalInput>>,
+) -> Result<Email, Panic>
+where
+    F: FnMut(&str, &str) -> Option<Vec<u8>>,
+{
+    let ext = [external_inputs.unwrap_or_default()];
+    match default_engine().generate_email_inputs_from_records(&[from_domain], &[raw_email], fetch_record, mode, Some(&ext)) {
         Err(e) => panic!("{e}"),
         Ok(mut v) => v.remove(0),
     }

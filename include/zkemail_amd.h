@@ -124,7 +124,23 @@ enum {
   ZKE_D_U_CAPTURE_SPAN       = 92, /* the match is longer than ZKE_CAP_MAX_SPAN bytes */
   ZKE_D_U_CAPTURE_WALK       = 93, /* the capture program cannot reproduce the span its DFA pair found (the two were not compiled
                                       from one pattern, or the walk met a case it does not implement): reported, never guessed */
-  ZKE_D_U_CAPTURE_PROGRAM    = 94  /* the capture program does not decode, or its id is not registered */
+  ZKE_D_U_CAPTURE_PROGRAM    = 94, /* the capture program does not decode, or its id is not registered */
+  /* DKIM key records (zke_decode_key_records, zke_select_keys_from_records): helpers/src/dkim.rs:67-111 / RFC 6376 3.6.1.
+   * zke_key_info.code: why a record yields no key.  100..109 */
+  ZKE_D_KEYREC_NO_KEY        = 100, /* no p= in the record, the record ends with "p=", p= is empty (revoked), or the record is empty
+                                       (the fetch failed)                                              dkim.rs:69-72, :92-94 */
+  ZKE_D_KEYREC_B64           = 101, /* p= is not padded base64 STANDARD with zero trailing bits       dkim.rs:97, :104 */
+  ZKE_D_KEYREC_TYPE          = 102, /* k= is neither "rsa" nor "ed25519" ("Unsupported key type")     dkim.rs:110 */
+  ZKE_D_KEYREC_DER           = 103, /* k=rsa: neither a DER SubjectPublicKeyInfo (rsaEncryption, NULL parameter, 0 unused bits)
+                                       nor a DER PKCS#1 RSAPublicKey                                   dkim.rs:98-99 */
+  ZKE_D_KEYREC_RANGE         = 104, /* k=rsa: modulus > 4096 bits, e < 2 or e > 2^33-1 (as ZKE_D_KEY_RANGE) */
+  ZKE_D_KEYREC_ED25519_LEN   = 105, /* k=ed25519: the decoded key is not 32 bytes                     dkim.rs:105-107 */
+  ZKE_D_KEYREC_VERSION       = 106, /* ZKE_KEYREC_DNS: v= is not the first tag, or is not "DKIM1" */
+  ZKE_D_KEYREC_SYNTAX        = 107, /* ZKE_KEYREC_DNS: the record is no tag-list, or holds a byte >= 0x80 */
+  ZKE_D_KEYREC_NON_ASCII_EDGE = 108, /* ZKE_KEYREC_ARCHIVE: a ';'-separated part begins or ends, after ASCII trimming, with a byte
+                                       >= 0x80: str::trim trims Unicode white space there, the engine trims ASCII only.  "Cannot
+                                       answer", never a guess */
+  ZKE_D_KEYREC_TOO_LONG      = 109  /* the record is longer than ZKE_KEYREC_MAX_BYTES */
 };
 #define ZKE_D_DFA_BWD_OFFSET 10u /* added to ZKE_D_DFA_LABEL .. ZKE_D_DFA_QUITSET when the reverse blob is the one that fails (80..88) */
 
@@ -527,6 +543,59 @@ int zke_select_keys(zke_engine* e, const zke_email_ref* emails, uint32_t n, cons
                     const zke_key_ref* keys, zke_result* out, uint32_t* chosen);
 int zke_select_keys_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off,
                           const zke_key_ref* keys, zke_result* out, uint32_t* chosen, uint64_t* ticket);
+
+/* ---- DKIM key records: what a resolver returns ("v=DKIM1; k=rsa; p=MIGfMA0G...") -> the (key, key_type) pair that
+ * Email.public_key and zke_select_keys take.  The reference does this at helpers/src/dkim.rs:67-111: split at ';', k= and p=,
+ * base64, SubjectPublicKeyInfo or PKCS#1 in, PKCS#1 out (public_key_hash is SHA-256 of exactly those bytes, circuits.rs:17).
+ * One record per wavefront (keyrec_kernel, csrc/keyrec.hip.h).  A canonical SubjectPublicKeyInfo carries its PKCS#1 key as its
+ * tail and DER admits one encoding per value, so the re-encoding is "validate, then take the slice".
+ *   ZKE_KEYREC_ARCHIVE  dkim.rs:67-111 restated: value.split(';').map(str::trim); a part that starts with "k=" / "p=" (case-
+ *                       sensitive) sets the type / the key text, the last such part wins, nothing inside a value is stripped; an
+ *                       empty type is "rsa"; base64 0.22 STANDARD (padding required, trailing bits zero, no white space).
+ *                       Trimming is ASCII (\t \n \v \f \r space): ZKE_D_KEYREC_NON_ASCII_EDGE where Unicode trimming could differ.
+ *   ZKE_KEYREC_DNS      the TXT record of RFC 6376 3.6.1, in the tag-list grammar of the signature parser (the last tag of a name
+ *                       wins; what follows the last well-formed tag-spec is not read): FWS around names and values and inside p=
+ *                       and k= is removed; v=, when present, is the first tag and "DKIM1"; k= absent or empty is "rsa"; p= is
+ *                       required, empty means revoked; h= s= t= n= are ignored.  From the key text on as above.  This is this
+ *                       engine's reading: the reference's DNS path is cfdkim's retrieve_public_key, which is not vendored
+ *                       (parity unpinned).  A TXT answer of several character-strings is joined by the caller first.
+ * For k=rsa: from_public_key_der, then from_pkcs1_der, then RsaPublicKey::new's range (<= 4096 bits, 2 <= e <= 2^33-1); for
+ * k=ed25519 exactly 32 bytes (whether they are a curve point is decided at verification, as in the reference). */
+#define ZKE_KEYREC_ARCHIVE 0u
+#define ZKE_KEYREC_DNS     1u
+#define ZKE_KEYREC_MAX_BYTES 4096u      /* longest record read (an RSA-4096 SubjectPublicKeyInfo is 736 characters) */
+typedef struct zke_keyrec_ref { const uint8_t* txt; size_t len; } zke_keyrec_ref;    /* len == 0: the fetch failed (generator.rs:33) */
+typedef struct zke_key_info {      /* 16 bytes */
+  uint32_t code;                   /* 0: a key | ZKE_D_KEYREC_* */
+  uint32_t key_type;               /* ZKE_KEY_RSA / ZKE_KEY_ED25519 as far as the record got (ZKE_KEY_OTHER with ZKE_D_KEYREC_TYPE) */
+  uint32_t key_off, key_len;       /* the key in zke_keyrec_out.keys: PKCS#1 DER or 32 raw bytes; key_len 0 unless code is 0 */
+} zke_key_info;
+/* Where the keys go: caller-sized buffers, capacities in ENTRIES, the sizes needed written back (the zke_sig_scan convention).
+ * infos (m entries) has a size known up front: too small fails at once with ZKE_E_NOMEM and infos_need set.  keys depends on the
+ * records (3/4 of the records' bytes always suffice): when it is too small the call (zke_batch_wait for the asynchronous form)
+ * returns ZKE_E_NOMEM, infos is delivered all the same (key_off as it will be) and keys_need says what a second call needs. */
+typedef struct zke_keyrec_out {
+  zke_key_info* infos; size_t infos_cap;
+  uint8_t*      keys;  size_t keys_cap;
+  size_t infos_need, keys_need;            /* written by the call */
+} zke_keyrec_out;
+/* The building block: one image of m records, one launch, infos and key bytes back in one copy.  `out` and its buffers must stay
+ * valid until the batch has been waited for; the records have been read when the call returns.  Same slots, tickets and
+ * zke_batch_wait as zke_verify_emails_async. */
+int zke_decode_key_records(zke_engine* e, const zke_keyrec_ref* recs, uint32_t m, uint32_t mode, zke_keyrec_out* out);
+int zke_decode_key_records_async(zke_engine* e, const zke_keyrec_ref* recs, uint32_t m, uint32_t mode, zke_keyrec_out* out, uint64_t* ticket);
+/* zke_select_keys with records in place of keys: candidate k of e-mail i is recs[cand_off[i] + k].  The decode launch runs on the
+ * batch's slot in front of the front end and leaves the candidates' keys as a packed CSR in HBM, where the verify launches read
+ * them: the decoded keys do not visit the host on their way to verification.  A candidate whose record yields no key gets the
+ * record verify_email gives an empty RSA key (ZKE_KEY_DECODE_FAIL) and never passes.  chosen, out and the fold on delivery are
+ * zke_select_keys'.  keys_out delivers every candidate's info and bytes (cand_off[n] - cand_off[0] infos), so that the caller
+ * builds Email.public_key from the chosen one.  Checked before anything is staged: null pointers, cand_off order, mode, and
+ * ZKE_E_NOMEM with infos_need set. */
+int zke_select_keys_from_records(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off,
+                                 const zke_keyrec_ref* recs, uint32_t mode, zke_result* out, uint32_t* chosen, zke_keyrec_out* keys_out);
+int zke_select_keys_from_records_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off,
+                                       const zke_keyrec_ref* recs, uint32_t mode, zke_result* out, uint32_t* chosen,
+                                       zke_keyrec_out* keys_out, uint64_t* ticket);
 
 /* Device-resident batch: every pointer in `in` and `out_dev` is device memory (the part-id lists stay host arrays);
  * `raw_total`, `domain_total`, `key_total` are the blob sizes (the CSR tails), which the

@@ -113,6 +113,15 @@ struct SigScan {
 // The caller's resolver of generate_email_inputs: (from_domain, selector) -> the key, or nullopt when the fetch fails
 // (helpers/src/dkim.rs fetch_dkim_key; DNS stays with the caller).
 using FetchKey = std::function<std::optional<PublicKey>(const std::string& domain, const std::string& selector)>;
+// One DKIM key record as a decode reports it (zke_key_info, the key as bytes): code 0 and the key, or ZKE_D_KEYREC_* and none.
+struct KeyInfo {
+  uint32_t code, key_type;                 // key_type: ZKE_KEY_* as far as the record got
+  std::vector<uint8_t> key;                // PKCS#1 DER or 32 raw bytes
+  PublicKey public_key() const { return PublicKey{key, key_type == ZKE_KEY_ED25519 ? "ed25519" : "rsa"}; }
+};
+// The resolver of generate_email_inputs_from_records: (from_domain, selector) -> the RAW answer — the TXT record of
+// selector._domainkey.domain (its character-strings joined) or the archive's value —, or nullopt when the fetch fails.
+using FetchRecord = std::function<std::optional<std::string>(const std::string& domain, const std::string& selector)>;
 
 class Engine {
  public:
@@ -293,25 +302,121 @@ class Engine {
     }
     std::vector<uint32_t> chosen;
     const std::vector<zke_result> recs = select_keys(probe, cands, chosen);
+    return emails_of_selection(scans, probe, recs, chosen, external_inputs, [&](size_t i) { return cands[i].size(); },
+                               [&](size_t i, uint32_t k) { return *cands[i][k]; });
+  }
+
+  // helpers/src/dkim.rs:67-111 for a batch (zke_decode_key_records): what a resolver returns -> the (key, key_type) pair of
+  // Email.public_key.  mode: ZKE_KEYREC_DNS (RFC 6376 3.6.1 TXT record) or ZKE_KEYREC_ARCHIVE (the archive's value as dkim.rs reads
+  // it); nullopt or an empty record: the fetch failed.
+  std::vector<KeyInfo> decode_key_records(const std::vector<std::optional<std::string>>& records, uint32_t mode = ZKE_KEYREC_DNS) {
+    KeyrecCall c(records);
+    if (int r = zke_decode_key_records(e_, c.refs.data(), (uint32_t)c.refs.size(), mode, &c.out))
+      throw EngineError("zke_decode_key_records failed: " + std::to_string(r) + " " + zke_last_error(e_));
+    return c.result();
+  }
+
+  // zke_select_keys_from_records: select_keys with the resolver's raw answers in place of keys; the records are decoded on the GPU in
+  // front of the verify launches.  infos[i][k]: what candidate k of e-mail i decoded to.
+  std::vector<zke_result> select_keys_from_records(const std::vector<Email>& emails, const std::vector<std::vector<std::optional<std::string>>>& candidate_records,
+                                                   std::vector<uint32_t>& chosen, std::vector<std::vector<KeyInfo>>& infos, uint32_t mode = ZKE_KEYREC_DNS) {
+    if (emails.size() != candidate_records.size()) throw EngineError("one candidate list per e-mail");
+    const uint32_t n = (uint32_t)emails.size();
+    std::vector<zke_email_ref> refs(n);
+    std::vector<uint32_t> off{0};
+    std::vector<std::optional<std::string>> flat;
+    for (uint32_t i = 0; i < n; i++) {
+      const Email& em = emails[i];
+      uint32_t ext = 0;
+      for (const auto& x : em.external_inputs) if (!x.value) ext = 1;
+      refs[i] = zke_email_ref{em.raw_email.data(), em.raw_email.size(), em.from_domain.data(), em.from_domain.size(), nullptr, 0, 0, ext};
+      flat.insert(flat.end(), candidate_records[i].begin(), candidate_records[i].end());
+      off.push_back((uint32_t)flat.size());
+    }
+    KeyrecCall c(flat);
+    std::vector<zke_result> out(n);
+    chosen.assign(n, ZKE_SEL_NONE);
+    if (int r = zke_select_keys_from_records(e_, refs.data(), n, off.data(), c.refs.data(), mode, out.data(), chosen.data(), &c.out))
+      throw EngineError("zke_select_keys_from_records failed: " + std::to_string(r) + " " + zke_last_error(e_));
+    const std::vector<KeyInfo> all = c.result();
+    infos.assign(n, {});
+    for (uint32_t i = 0; i < n; i++) infos[i].assign(all.begin() + off[i], all.begin() + off[i + 1]);
+    return out;
+  }
+
+  // generate_email_inputs with the resolver's RAW answers: "raw e-mails + the records in, Email values out" — the caller is left
+  // with network code only.  Errors as generate_email_inputs.
+  std::vector<Email> generate_email_inputs_from_records(const std::vector<std::string>& from_domains, const std::vector<std::vector<uint8_t>>& raw_emails,
+                                                        const FetchRecord& fetch_record, uint32_t mode = ZKE_KEYREC_DNS,
+                                                        const std::vector<std::vector<ExternalInput>>* external_inputs = nullptr,
+                                                        uint32_t max_sigs = ZKE_SCAN_MAX_SIGS) {
+    const std::vector<SigScan> scans = scan_signatures(raw_emails, from_domains, max_sigs);
+    std::map<std::pair<std::string, std::string>, std::optional<std::string>> cache;
+    std::vector<std::vector<std::optional<std::string>>> cands(scans.size());
+    std::vector<Email> probe(scans.size());
+    for (size_t i = 0; i < scans.size(); i++) {
+      probe[i] = Email{from_domains[i], raw_emails[i], PublicKey{}, {}};
+      for (const SigInfo& s : scans[i].sigs) {
+        if (s.code != 0) continue;
+        auto key = std::make_pair(from_domains[i], s.selector);
+        auto it = cache.find(key);
+        if (it == cache.end()) it = cache.emplace(key, fetch_record(from_domains[i], s.selector)).first;
+        cands[i].push_back(it->second);
+      }
+    }
+    std::vector<uint32_t> chosen;
+    std::vector<std::vector<KeyInfo>> infos;
+    const std::vector<zke_result> recs = select_keys_from_records(probe, cands, chosen, infos, mode);
+    return emails_of_selection(scans, probe, recs, chosen, external_inputs, [&](size_t i) { return cands[i].size(); },
+                               [&](size_t i, uint32_t k) { return infos[i][k].public_key(); });
+  }
+
+ private:
+  // generator.rs:36-52 over a selection's answer: one Email per e-mail under key_of(i, chosen[i]), or the reference's Err
+  template <class Count, class KeyOf>
+  static std::vector<Email> emails_of_selection(const std::vector<SigScan>& scans, const std::vector<Email>& probe, const std::vector<zke_result>& recs,
+                                                const std::vector<uint32_t>& chosen, const std::vector<std::vector<ExternalInput>>* external_inputs,
+                                                Count n_cands, KeyOf key_of) {
     std::vector<Email> out;
     for (size_t i = 0; i < scans.size(); i++) {
       const SigScan& sc = scans[i];
       if (sc.status != ZKE_OK) throw VerifyPanic(sc.status, sc.detail);
       if (sc.n_signatures == 0) throw VerifyPanic(ZKE_DKIM_NOT_PASS, ZKE_D_NO_SIGNATURE);                       // generator.rs:21
       if (chosen[i] == ZKE_SEL_NONE) {
-        if (sc.n_candidates > cands[i].size()) throw VerifyPanic(ZKE_UNSUPPORTED, ZKE_D_U_TOO_MANY_SIGS);       // the list was cut
+        if (sc.n_candidates > n_cands(i)) throw VerifyPanic(ZKE_UNSUPPORTED, ZKE_D_U_TOO_MANY_SIGS);            // the list was cut
         throw VerifyPanic(recs[i].status == ZKE_UNSUPPORTED ? ZKE_UNSUPPORTED : ZKE_DKIM_NOT_PASS, recs[i].detail);   // generator.rs:52
       }
       if (chosen[i] & ZKE_SEL_AFTER_UNSUPPORTED) throw VerifyPanic(ZKE_UNSUPPORTED, ZKE_D_U_ALGO_ED25519);
       Email em = probe[i];
-      em.public_key = *cands[i][chosen[i]];
+      em.public_key = key_of(i, chosen[i]);
       if (external_inputs) em.external_inputs = (*external_inputs)[i];
       out.push_back(std::move(em));
     }
     return out;
   }
-
- private:
+  // The records of one call as zke_keyrec_ref[m] and the buffers of its zke_keyrec_out (3/4 of the records' bytes hold every key)
+  struct KeyrecCall {
+    std::vector<zke_keyrec_ref> refs;
+    std::vector<zke_key_info> infos;
+    std::vector<uint8_t> keys;
+    zke_keyrec_out out{};
+    explicit KeyrecCall(const std::vector<std::optional<std::string>>& records) {
+      size_t total = 0;
+      for (const auto& r : records) {
+        refs.push_back(r && !r->empty() ? zke_keyrec_ref{reinterpret_cast<const uint8_t*>(r->data()), r->size()} : zke_keyrec_ref{nullptr, 0});
+        total += refs.back().len;
+      }
+      infos.resize(records.size() + 1);
+      keys.resize(total * 3 / 4 + 1);
+      out.infos = infos.data(); out.infos_cap = records.size(); out.keys = keys.data(); out.keys_cap = keys.size();
+    }
+    std::vector<KeyInfo> result() const {
+      std::vector<KeyInfo> v;
+      for (size_t i = 0; i < refs.size(); i++)
+        v.push_back(KeyInfo{infos[i].code, infos[i].key_type, std::vector<uint8_t>(keys.begin() + infos[i].key_off, keys.begin() + infos[i].key_off + infos[i].key_len)});
+      return v;
+    }
+  };
   static uint32_t key_type_code(const std::string& t) {
     return t == "rsa" ? ZKE_KEY_RSA : (t == "ed25519" ? ZKE_KEY_ED25519 : ZKE_KEY_OTHER);
   }
@@ -377,6 +482,12 @@ inline Email generate_email_inputs(const std::string& from_domain, const std::ve
                                    std::optional<std::vector<ExternalInput>> external_inputs = std::nullopt) {
   std::vector<std::vector<ExternalInput>> ext{external_inputs.value_or(std::vector<ExternalInput>{})};
   return default_engine().generate_email_inputs({from_domain}, {raw_email}, fetch_key, &ext)[0];
+}
+// ... and with the resolver's raw answer (TXT record or archive value) in place of the key: dkim.rs:67-111 runs on the GPU
+inline Email generate_email_inputs_from_records(const std::string& from_domain, const std::vector<uint8_t>& raw_email, const FetchRecord& fetch_record,
+                                                uint32_t mode = ZKE_KEYREC_DNS, std::optional<std::vector<ExternalInput>> external_inputs = std::nullopt) {
+  std::vector<std::vector<ExternalInput>> ext{external_inputs.value_or(std::vector<ExternalInput>{})};
+  return default_engine().generate_email_inputs_from_records({from_domain}, {raw_email}, fetch_record, mode, &ext)[0];
 }
 
 }  // namespace zkemail

@@ -203,6 +203,35 @@ class zke_key_ref(C.Structure):
     _fields_ = [("key", C.c_void_p), ("key_len", C.c_size_t), ("key_type", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# DKIM key records (zke_decode_key_records, zke_select_keys_from_records)
+KEYREC_ARCHIVE, KEYREC_DNS = 0, 1
+KEYREC_MAX_BYTES = 4096
+(D_KEYREC_NO_KEY, D_KEYREC_B64, D_KEYREC_TYPE, D_KEYREC_DER, D_KEYREC_RANGE, D_KEYREC_ED25519_LEN, D_KEYREC_VERSION, D_KEYREC_SYNTAX,
+ D_KEYREC_NON_ASCII_EDGE, D_KEYREC_TOO_LONG) = range(100, 110)
+KEYREC_NAMES = {0: "ok", 100: "no key", 101: "base64", 102: "unsupported key type", 103: "DER", 104: "range", 105: "Ed25519 length",
+                106: "version", 107: "tag-list syntax", 108: "non-ASCII edge", 109: "record too long"}
+
+
+class zke_keyrec_ref(C.Structure):
+    """One record of zke_decode_key_records; len 0: the fetch failed."""
+    _fields_ = [("txt", C.c_void_p), ("len", C.c_size_t)]
+
+
+class zke_key_info(C.Structure):
+    """What one record decodes to."""
+    _fields_ = [("code", C.c_uint32), ("key_type", C.c_uint32), ("key_off", C.c_uint32), ("key_len", C.c_uint32)]
+
+
+KEY_INFO_DTYPE = np.dtype([("code", "<u4"), ("key_type", "<u4"), ("key_off", "<u4"), ("key_len", "<u4")])
+assert C.sizeof(zke_key_info) == 16 == KEY_INFO_DTYPE.itemsize
+
+
+class zke_keyrec_out(C.Structure):
+    """Caller-sized buffers of a decode; capacities in entries, the sizes needed written back."""
+    _fields_ = [("infos", C.c_void_p), ("infos_cap", C.c_size_t), ("keys", C.c_void_p), ("keys_cap", C.c_size_t),
+                ("infos_need", C.c_size_t), ("keys_need", C.c_size_t)]
+
+
 STRICT_FLAGS = ("enforce_expiry_x", "canon_takes_verified_signature", "canon_ignores_l", "i_must_be_subdomain",
                 "b_removes_own_span_only")          # zke_options' strictness flags, in ZKE_STRICT_* bit order
 

@@ -69,6 +69,7 @@ def build_oracle(force: bool = False) -> str:
 
 CPP_EXAMPLE = os.path.join(ROOT, "tests", "cpp", "mirror_test")
 CPP_SIGSCAN = os.path.join(ROOT, "tests", "cpp", "sigscan_test")
+CPP_KEYREC = os.path.join(ROOT, "tests", "cpp", "keyrec_test")
 
 
 def _build_cpp(exe: str, force: bool) -> str:
@@ -88,14 +89,20 @@ def _build_cpp(exe: str, force: bool) -> str:
 
 def build_cpp_example(force: bool = False) -> str:
     """The C++ host mirror (include/zkemail_core.hpp) compiled against the built library: the verify program, whose path is
-    returned, and the generator program (build_cpp_sigscan)."""
+    returned, the generator program (build_cpp_sigscan) and the key-record program (build_cpp_keyrec)."""
     build_cpp_sigscan(force)
+    build_cpp_keyrec(force)
     return _build_cpp(CPP_EXAMPLE, force)
 
 
 def build_cpp_sigscan(force: bool = False) -> str:
     """tests/cpp/sigscan_test: scan_signatures / select_keys / generate_email_inputs of the C++ mirror."""
     return _build_cpp(CPP_SIGSCAN, force)
+
+
+def build_cpp_keyrec(force: bool = False) -> str:
+    """tests/cpp/keyrec_test: decode_key_records / generate_email_inputs_from_records of the C++ mirror."""
+    return _build_cpp(CPP_KEYREC, force)
 
 
 if __name__ == "__main__":

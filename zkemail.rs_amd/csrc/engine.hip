@@ -27,6 +27,7 @@
 #include "regex.hip.h"
 #include "capture.hip.h"
 #include "sigscan.hip.h"
+#include "keyrec.hip.h"
 #include "rsa_kernel.hip.h"
 #include "rsa_quad.hip.h"
 #include "fused.hip.h"
@@ -106,8 +107,12 @@ struct Slot {
   std::vector<uint32_t> sel_off;       // cand_off of the pending selection (n + 1 entries; empty: the pending batch is no selection)
   zke_result* sel_out = nullptr;
   uint32_t* sel_chosen = nullptr;
-  DevBuf* all[19] = {&meta, &rsa_jobs, &sha_jobs, &sha_order, &rsa_ok, &em_dbg, &scratch_off, &scratch, &clean, &meta2, &scratch2, &parts,
-                     &pending, &d_image, &d_results, &cb.cap, &cb.work, &sb.out, &sb.ovf};
+  // key records (zke_decode_key_records, zke_select_keys_from_records): infos and decoded keys in one buffer (KeyrecLayout) with its
+  // pinned twin, the packed key section the front end reads, and where the pending batch's infos and keys go
+  KeyrecBufs kb;
+  zke_keyrec_out* keyrec_out = nullptr;
+  DevBuf* all[21] = {&meta, &rsa_jobs, &sha_jobs, &sha_order, &rsa_ok, &em_dbg, &scratch_off, &scratch, &clean, &meta2, &scratch2, &parts,
+                     &pending, &d_image, &d_results, &cb.cap, &cb.work, &sb.out, &sb.ovf, &kb.out, &kb.pack};
   // hipGraph replay of a batch's kernel sequence (zke_options.replay_graphs).  The graph holds this slot's
   // workspace pointers, so it is valid only while none of them has been reallocated: `generation` counts reallocations.
   hipGraphExec_t graph_exec = nullptr;
@@ -211,7 +216,7 @@ void free_slot(Slot* w) {
   if (!w) return;
   if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
   for (auto* b : w->all) b->release();
-  w->h_image.release(); w->h_results.release(); w->cb.h_cap.release(); w->sb.h_out.release();
+  w->h_image.release(); w->h_results.release(); w->cb.h_cap.release(); w->sb.h_out.release(); w->kb.h_out.release();
   for (auto& ev : w->ev) if (ev) (void)hipEventDestroy(ev);
   if (w->done) (void)hipEventDestroy(w->done);
   if (w->host_done) (void)hipEventDestroy(w->host_done);

@@ -257,4 +257,24 @@ struct ScanBufs {
   void release() { out.release(); ovf.release(); h_out.release(); }
 };
 
+// The buffers of one key-record decode (a slot's): {infos | decoded keys at their records' offsets} in one device buffer with a pinned
+// twin — ONE copy back —, and, for zke_select_keys_from_records, the key section the front end reads: {key_off | key_type | packed blob}.
+struct KeyrecLayout { size_t keys, total; uint32_t m; size_t p_type, p_blob, p_total; };
+inline KeyrecLayout keyrec_layout(uint32_t m, size_t rec_total) {
+  KeyrecLayout L{};
+  L.m = m;
+  L.keys = align_up((size_t)m * sizeof(zke_key_info), 64);
+  L.total = L.keys + rec_total;
+  L.p_type = align_up(((size_t)m + 1) * 8, 64);
+  L.p_blob = align_up(L.p_type + m, 64);
+  L.p_total = L.p_blob + rec_total + 64;               // (a decoded key is shorter than its record; the kernels read 16 bytes at a time)
+  return L;
+}
+struct KeyrecBufs {
+  DevBuf out, pack;
+  PinnedBuf h_out;
+  KeyrecLayout L{};
+  void release() { out.release(); pack.release(); h_out.release(); }
+};
+
 }  // namespace

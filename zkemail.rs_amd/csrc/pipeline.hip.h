@@ -156,6 +156,19 @@ int launch_capture(zke_engine* e, CapBufs& b, const CaptureReq& q, uint32_t n, b
 // ---- signature scan and key selection (sigscan.hip.h; include/zkemail_amd.h)
 struct ScanReq { uint32_t max_sigs; zke_sig_scan* out; };
 struct SelectReq { const uint32_t* cand_off; uint32_t n; zke_result* out; uint32_t* chosen; };
+// ---- key records (keyrec.hip.h).  Alone: the batch's "raw e-mails" are the records, keyrec_kernel runs instead of the verify
+// pipeline.  With a SelectReq: the image's key section holds the records, and the decode + pack launches in front of the front end
+// replace it by the decoded keys (zke_select_keys_from_records).
+struct KeyrecReq { uint32_t mode; zke_keyrec_out* out; };
+
+int ensure_keyrec_buffers(zke_engine* e, KeyrecBufs& b, uint32_t m, size_t rec_total, bool pack) {
+  const KeyrecLayout L = keyrec_layout(m, rec_total);
+  int r = 0;
+  if ((r = b.out.ensure(L.total)) || (r = b.h_out.ensure(L.total)) || (pack && (r = b.pack.ensure(L.p_total))))
+    return fail(e, r, "key-record buffer allocation");
+  b.L = L;
+  return 0;
+}
 
 // A slot's scan buffers for n e-mails with max_sigs record slots each and blob_cap bytes of selectors.  Grow only: the first scan
 // of a shape allocates, a later one of the same shape does not.
@@ -432,6 +445,27 @@ int deliver_scan(zke_engine* e, const ScanBufs& b, zke_sig_scan* o) {
   return 0;
 }
 
+// A decode from the slot's pinned twin into the caller's zke_keyrec_out: the infos with key_off rewritten to the packed offsets,
+// the key bytes compacted (one memcpy per key).  ZKE_E_NOMEM when keys is too small (keys_need says how much).
+int deliver_keyrec(zke_engine* e, const KeyrecBufs& b, zke_keyrec_out* o) {
+  const KeyrecLayout& K = b.L;
+  const uint8_t* hp = b.h_out.as<uint8_t>();
+  const zke_key_info* src = reinterpret_cast<const zke_key_info*>(hp);
+  size_t total = 0;
+  for (uint32_t i = 0; i < K.m; i++) {
+    zke_key_info f = src[i];
+    if (f.code) f.key_len = 0;
+    f.key_off = (uint32_t)total;
+    total += f.key_len;
+    o->infos[i] = f;
+  }
+  o->keys_need = total;
+  if (total > o->keys_cap) return fail(e, ZKE_E_NOMEM, "key records: keys is smaller than the decoded keys (zke_keyrec_out.keys_need)");
+  for (uint32_t i = 0; i < K.m; i++)
+    if (o->infos[i].key_len) memcpy(o->keys + o->infos[i].key_off, hp + K.keys + src[i].key_off, o->infos[i].key_len);
+  return 0;
+}
+
 // A key selection's fold: the records of the (e-mail, candidate) pairs are in the pinned buffer; per e-mail the first ZKE_OK.
 void fold_selection(const zke_result* R, const std::vector<uint32_t>& off, zke_result* out, uint32_t* chosen) {
   for (size_t i = 0; i + 1 < off.size(); i++) {
@@ -461,6 +495,8 @@ int retire_host(zke_engine* e, Slot& w, int* cap_rc = nullptr) {
   w.cap_out = nullptr;
   zke_sig_scan* pending_scan = w.scan_out;
   w.scan_out = nullptr;
+  zke_keyrec_out* pending_keyrec = w.keyrec_out;
+  w.keyrec_out = nullptr;
   HIPCHK(e, hipEventSynchronize(w.host_done));
   if (w.host_out && w.host_n) memcpy(w.host_out, w.h_results.p, (size_t)w.host_n * sizeof(zke_result));
   w.host_out = nullptr;
@@ -471,6 +507,12 @@ int retire_host(zke_engine* e, Slot& w, int* cap_rc = nullptr) {
   if (pending_scan) {
     const std::string keep = g_err;
     const int r = deliver_scan(e, w.sb, pending_scan);
+    if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
+    else if (r) return r;
+  }
+  if (pending_keyrec) {
+    const std::string keep = g_err;
+    const int r = deliver_keyrec(e, w.kb, pending_keyrec);
     if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
     else if (r) return r;
   }
@@ -505,6 +547,7 @@ struct HostBatch {
   CaptureReq* cap = nullptr;            // zke_extract_captures: the extraction that rides on this (regex) batch
   const ScanReq* scan = nullptr;        // zke_scan_signatures: sigscan_kernel runs instead of the verify pipeline
   const SelectReq* sel = nullptr;       // zke_select_keys: the batch's entries are (e-mail, candidate key) pairs, folded on delivery
+  const KeyrecReq* keyrec = nullptr;    // key records: decoded instead of the verify pipeline, or (with sel) in front of it
   uint64_t raw_total = 0, dom_total = 0, key_total = 0, raw_base = 0, dom_base = 0, key_base = 0;   // blob bytes; off[0] of packed offsets
   size_t cap_words = 0, cap_strs = 0, cap_bytes = 0;      // entries of cap_off and cap_str_off, bytes of cap_blob (0: no tables)
   ImageLayout L{};
@@ -571,6 +614,8 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
     const size_t blob = std::min<size_t>(d.scan->out->sel_blob_cap, (size_t)n * d.scan->max_sigs * ZKE_MAX_TAGBUF);
     if (int r = ensure_scan_buffers(e, w.sb, n, d.scan->max_sigs, blob)) return r;
   }
+  if (d.keyrec)
+    if (int r = ensure_keyrec_buffers(e, w.kb, n, (size_t)(d.sel ? d.key_total : d.raw_total), d.sel != nullptr)) return r;
   uint8_t* hp = w.h_image.as<uint8_t>();
   if (d.refs) {
     // the CSR arrays are written where they will be read from (prefix sums over the lengths), and every e-mail's three buffers
@@ -663,15 +708,44 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
     HIPCHK(e, hipGetLastError());
     tm.mark(MK_FRONT); tm.mark(MK_HASH); tm.mark(MK_VERDICT);      // zke_timings.front_end_us is the scan; the other stages are empty
     HIPCHK(e, hipMemcpyAsync(w.sb.h_out.p, so, S.total, hipMemcpyDeviceToHost, s));
+  } else if (d.keyrec && !d.sel) {
+    // one launch over the records (the image's raw section), infos and keys back as one copy
+    const KeyrecLayout& K = w.kb.L;
+    uint8_t* ko = w.kb.out.as<uint8_t>();
+    const KeyrecArgs ka{n, d.keyrec->mode, dv.raw_blob, dv.raw_off, reinterpret_cast<zke_key_info*>(ko), ko + K.keys};
+    hipLaunchKernelGGL(keyrec_kernel, dim3(n), dim3(64), 0, s, ka);
+    HIPCHK(e, hipGetLastError());
+    tm.mark(MK_FRONT); tm.mark(MK_HASH); tm.mark(MK_VERDICT);      // zke_timings.front_end_us is the decode; the other stages are empty
+    HIPCHK(e, hipMemcpyAsync(w.kb.h_out.p, ko, K.total, hipMemcpyDeviceToHost, s));
   } else {
-  if (int r = run_device_pipeline(e, w, &dv, d.raw_total, d.key_total, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap)) return r;
+  uint64_t key_hint = d.key_total;
+  if (d.keyrec) {
+    // the image's key section holds the candidates' RECORDS: decode them, then scan the lengths and gather the keys into the
+    // packed CSR the front end reads — three small launches, the keys never leave HBM
+    const KeyrecLayout& K = w.kb.L;
+    uint8_t* ko = w.kb.out.as<uint8_t>();
+    uint8_t* pk = w.kb.pack.as<uint8_t>();
+    const KeyrecArgs ka{n, d.keyrec->mode, dv.key_blob, dv.key_off, reinterpret_cast<zke_key_info*>(ko), ko + K.keys};
+    hipLaunchKernelGGL(keyrec_kernel, dim3(n), dim3(64), 0, s, ka);
+    const KeyrecPackArgs pa{n, ka.infos, ka.keys, reinterpret_cast<uint64_t*>(pk), pk + K.p_type, pk + K.p_blob};
+    hipLaunchKernelGGL(keyrec_pack_kernel, dim3(1), dim3(64), 0, s, pa);
+    hipLaunchKernelGGL(keyrec_gather_kernel, dim3(n), dim3(64), 0, s, pa);
+    HIPCHK(e, hipGetLastError());
+    dv.key_blob = pa.key_blob; dv.key_off = pa.key_off; dv.key_type = pa.key_type;
+    // (run_device_pipeline reads "the keys average more than an RSA-2048 key's 270 bytes" from the total: a 2048-bit
+    // SubjectPublicKeyInfo record is about 410 characters, a 3072-bit one 580)
+    key_hint = d.key_total > (uint64_t)n * 480 ? (uint64_t)n * 273 : 0;
+  }
+  if (int r = run_device_pipeline(e, w, &dv, d.raw_total, key_hint, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap)) return r;
   HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
+  if (d.keyrec) HIPCHK(e, hipMemcpyAsync(w.kb.h_out.p, w.kb.out.p, w.kb.L.total, hipMemcpyDeviceToHost, s));
   }
   if (d.cap) HIPCHK(e, hipMemcpyAsync(w.cb.h_cap.p, w.cb.cap.p, w.cb.L.fixed_end, hipMemcpyDeviceToHost, s));
   tm.mark(MK_D2H);
   HIPCHK(e, hipEventRecord(w.host_done, s));
   w.host_gen++;
-  w.host_out = (d.scan || d.sel) ? nullptr : out; w.host_n = n;
+  w.host_out = (d.scan || d.sel || d.keyrec) ? nullptr : out; w.host_n = n;
+  w.keyrec_out = d.keyrec ? d.keyrec->out : nullptr;
   w.cap_out = d.cap ? d.cap->out : nullptr;
   w.scan_out = d.scan ? d.scan->out : nullptr;
   w.sel_off.clear();
@@ -1215,6 +1289,81 @@ int zke_select_keys(zke_engine* e, const zke_email_ref* emails, uint32_t n, cons
                     zke_result* out, uint32_t* chosen) {
   uint64_t ticket = 0;
   if (int r = zke_select_keys_async(e, emails, n, cand_off, keys, out, chosen, &ticket)) return r;
+  return n ? zke_batch_wait(e, ticket) : 0;
+}
+
+// ---- key records (include/zkemail_amd.h; kernels: keyrec.hip.h)
+namespace {
+// The checks both entries share, before anything is staged; fills the needs.  A record longer than ZKE_KEYREC_MAX_BYTES is not
+// read: one byte more than the limit is staged, which is all the kernel needs to say so.
+int keyrec_args(const char* who, const zke_keyrec_ref* recs, uint32_t m, uint32_t mode, zke_keyrec_out* out) {
+  if (!out || (m && !recs)) return arg_error(who, "null pointer");
+  if (mode != ZKE_KEYREC_ARCHIVE && mode != ZKE_KEYREC_DNS) return arg_error(who, "mode must be ZKE_KEYREC_ARCHIVE or ZKE_KEYREC_DNS");
+  if (m >= (1u << 19)) return arg_error(who, "2^19 records or more (32-bit key offsets): split the batch");
+  for (uint32_t i = 0; i < m; i++)
+    if (recs[i].len && !recs[i].txt) return arg_error(who, "null buffer with a length");
+  out->infos_need = m; out->keys_need = 0;
+  if (out->infos_cap < m) { g_err = std::string(who) + ": zke_keyrec_out.infos is smaller than infos_need"; return ZKE_E_NOMEM; }
+  if ((m && !out->infos) || (out->keys_cap && !out->keys)) return arg_error(who, "null buffer in zke_keyrec_out");
+  return 0;
+}
+inline size_t keyrec_staged(size_t len) { return std::min<size_t>(len, (size_t)ZKE_KEYREC_MAX_BYTES + 1); }
+}  // namespace
+
+int zke_decode_key_records_async(zke_engine* e, const zke_keyrec_ref* recs, uint32_t m, uint32_t mode, zke_keyrec_out* out, uint64_t* ticket) {
+  static const char who[] = "zke_decode_key_records";
+  if (!e) return ZKE_E_ARG;
+  if (!ticket) return arg_error(who, "null pointer");
+  if (int r = keyrec_args(who, recs, m, mode, out)) return r;
+  std::vector<zke_email_ref> refs(m);                 // the records travel as the image's raw section: no domains, no keys
+  for (uint32_t i = 0; i < m; i++) { refs[i] = zke_email_ref{}; refs[i].raw = recs[i].txt; refs[i].raw_len = keyrec_staged(recs[i].len); }
+  HostBatch d;
+  if (int r = host_batch(d, who, reinterpret_cast<const zke_result*>(out), refs.data(), m, nullptr)) return r;
+  const KeyrecReq q{mode, out};
+  d.keyrec = &q;
+  return submit_host_batch(e, d, nullptr, ticket);
+}
+
+int zke_decode_key_records(zke_engine* e, const zke_keyrec_ref* recs, uint32_t m, uint32_t mode, zke_keyrec_out* out) {
+  uint64_t ticket = 0;
+  if (int r = zke_decode_key_records_async(e, recs, m, mode, out, &ticket)) return r;
+  return m ? zke_batch_wait(e, ticket) : 0;
+}
+
+int zke_select_keys_from_records_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off,
+                                       const zke_keyrec_ref* recs, uint32_t mode, zke_result* out, uint32_t* chosen,
+                                       zke_keyrec_out* keys_out, uint64_t* ticket) {
+  static const char who[] = "zke_select_keys_from_records";
+  if (!e) return ZKE_E_ARG;
+  if (!ticket || !keys_out || (n && (!emails || !cand_off || !out || !chosen))) return arg_error(who, "null pointer");
+  if (n && !rising(cand_off, n)) return arg_error(who, "cand_off is not non-decreasing");
+  const uint32_t base = n ? cand_off[0] : 0, M = n ? cand_off[n] - base : 0;
+  if (int r = keyrec_args(who, recs ? recs + base : nullptr, M, mode, keys_out)) return r;
+  // ONE batch of the (e-mail, candidate) pairs, as zke_select_keys; the key section of its image holds the candidates' records
+  std::vector<zke_email_ref> refs(M);
+  for (uint32_t i = 0; i < n; i++)
+    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; k++) {
+      zke_email_ref& m = refs[k - base];
+      m = emails[i];
+      m.key = recs[k].txt; m.key_len = keyrec_staged(recs[k].len); m.key_type = ZKE_KEY_RSA;
+    }
+  HostBatch d;
+  if (int r = host_batch(d, who, out, refs.data(), M, nullptr)) return r;
+  if (!M) {            // no candidate anywhere: nothing to run
+    const std::vector<uint32_t> off((size_t)n + 1, 0u);
+    if (n) fold_selection(nullptr, off, out, chosen);
+    return submit_host_batch(e, d, out, ticket);
+  }
+  const SelectReq q{cand_off, n, out, chosen};
+  const KeyrecReq kq{mode, keys_out};
+  d.sel = &q; d.keyrec = &kq;
+  return submit_host_batch(e, d, out, ticket);
+}
+
+int zke_select_keys_from_records(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off,
+                                 const zke_keyrec_ref* recs, uint32_t mode, zke_result* out, uint32_t* chosen, zke_keyrec_out* keys_out) {
+  uint64_t ticket = 0;
+  if (int r = zke_select_keys_from_records_async(e, emails, n, cand_off, recs, mode, out, chosen, keys_out, &ticket)) return r;
   return n ? zke_batch_wait(e, ticket) : 0;
 }
 

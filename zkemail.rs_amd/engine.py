@@ -147,6 +147,15 @@ def load_library(path: Optional[str] = None):
     lib.zke_select_keys.restype = C.c_int
     lib.zke_select_keys_async.argtypes = [vp, erp, C.c_uint32, vp, C.POINTER(A.zke_key_ref), vp, vp, C.POINTER(C.c_uint64)]
     lib.zke_select_keys_async.restype = C.c_int
+    krp, kop = C.POINTER(A.zke_keyrec_ref), C.POINTER(A.zke_keyrec_out)
+    lib.zke_decode_key_records.argtypes = [vp, krp, C.c_uint32, C.c_uint32, kop]
+    lib.zke_decode_key_records.restype = C.c_int
+    lib.zke_decode_key_records_async.argtypes = [vp, krp, C.c_uint32, C.c_uint32, kop, C.POINTER(C.c_uint64)]
+    lib.zke_decode_key_records_async.restype = C.c_int
+    lib.zke_select_keys_from_records.argtypes = [vp, erp, C.c_uint32, vp, krp, C.c_uint32, vp, vp, kop]
+    lib.zke_select_keys_from_records.restype = C.c_int
+    lib.zke_select_keys_from_records_async.argtypes = [vp, erp, C.c_uint32, vp, krp, C.c_uint32, vp, vp, kop, C.POINTER(C.c_uint64)]
+    lib.zke_select_keys_from_records_async.restype = C.c_int
     lib.zke_version.argtypes = []
     lib.zke_version.restype = C.c_char_p
     lib.zke_device_available.argtypes = []
@@ -168,6 +177,7 @@ EXPORTED_SYMBOLS = [
     "zke_capture_validate", "zke_capture_register", "zke_capture_status", "zke_capture_unregister", "zke_extract_captures",
     "zke_extract_captures_async", "zke_capture_batch",
     "zke_scan_signatures", "zke_scan_signatures_async", "zke_select_keys", "zke_select_keys_async",
+    "zke_decode_key_records", "zke_decode_key_records_async", "zke_select_keys_from_records", "zke_select_keys_from_records_async",
 ]
 
 
@@ -212,6 +222,45 @@ class _ScanBuffers:
                     for r in self.sigs[int(self.sig_off[i]):int(self.sig_off[i + 1])]]
             out.append(SigScan(int(st[0]), int(st[1]), sigs, int(st[2]), int(st[3])))
         return out
+
+
+class KeyInfo(NamedTuple):
+    """One DKIM key record as zke_decode_key_records reports it (zke_key_info, the key as bytes)."""
+    code: int                      # 0 a key | D_KEYREC_* why the record yields none
+    key_type: int                  # KEY_RSA / KEY_ED25519 as far as the record got (KEY_OTHER with D_KEYREC_TYPE)
+    key: bytes                     # PKCS#1 DER or 32 raw bytes; b"" unless code is 0
+
+    def public_key(self) -> "A.PublicKey":
+        """Email.public_key of a record that decoded."""
+        return A.PublicKey(self.key, "ed25519" if self.key_type == A.KEY_ED25519 else "rsa")
+
+
+class _KeyrecBuffers:
+    """The records of one call as zke_keyrec_ref[m] and the caller-sized buffers of its zke_keyrec_out (kept alive until the batch
+    has been waited for).  None stands for an empty record: the fetch failed."""
+
+    def __init__(self, records: Sequence[Optional[bytes]], keys_bytes: Optional[int] = None, off=None):
+        self.m = m = len(records)
+        self.off = off                           # cand_off of a selection: result() is then one list per e-mail
+        self._keep = [bytes(r) if r else b"" for r in records]
+        self.arr = (A.zke_keyrec_ref * max(m, 1))()
+        for j, r in enumerate(self._keep):
+            self.arr[j].txt = C.cast(C.c_char_p(r), C.c_void_p).value if r else None
+            self.arr[j].len = len(r)
+        if keys_bytes is None:                   # 3/4 of the records' bytes always suffice
+            keys_bytes = sum(min(len(r), A.KEYREC_MAX_BYTES) for r in self._keep) * 3 // 4
+        self.infos = np.zeros(max(m, 1), A.KEY_INFO_DTYPE)
+        self.keys = np.zeros(max(keys_bytes, 1), np.uint8)
+        o = self.c = A.zke_keyrec_out()
+        o.infos, o.infos_cap, o.keys, o.keys_cap = self.infos.ctypes.data, m, self.keys.ctypes.data, keys_bytes
+
+    def result(self):
+        blob = self.keys.tobytes()
+        flat = [KeyInfo(int(f["code"]), int(f["key_type"]), blob[int(f["key_off"]):int(f["key_off"]) + int(f["key_len"])])
+                for f in self.infos[:self.m]]
+        if self.off is None:
+            return flat
+        return [flat[int(self.off[i]):int(self.off[i + 1])] for i in range(len(self.off) - 1)]
 
 
 class Engine:
@@ -465,6 +514,49 @@ class Engine:
                     "zke_select_keys_async")
         return t.value, out[:refs.n], chosen[:refs.n]
 
+    # ---- DKIM key records (helpers/src/dkim.rs:67-111: what the resolver returns -> Email.public_key)
+    def decode_key_records(self, records: Sequence[Optional[bytes]], mode: int = A.KEYREC_DNS, *, keys_bytes: Optional[int] = None) -> List[KeyInfo]:
+        """zke_decode_key_records: one KeyInfo per record (None or b"": the fetch failed).  `mode`: _abi.KEYREC_DNS, the TXT record
+        of RFC 6376 3.6.1, or _abi.KEYREC_ARCHIVE, the archive value as helpers/src/dkim.rs:67-111 reads it.  `keys_bytes`: the
+        key buffer's size (default: 3/4 of the records' bytes, which always suffices)."""
+        b = _KeyrecBuffers(records, keys_bytes)
+        self._check(self.lib.zke_decode_key_records(self.h, b.arr, b.m, mode, C.byref(b.c)), "zke_decode_key_records")
+        return b.result()
+
+    def decode_key_records_async(self, records: Sequence[Optional[bytes]], mode: int = A.KEYREC_DNS, *, keys_bytes: Optional[int] = None):
+        """zke_decode_key_records_async: (ticket, pending); ``pending.result()`` is valid once ``wait(ticket)`` has returned."""
+        b = _KeyrecBuffers(records, keys_bytes)
+        t = C.c_uint64()
+        self._check(self.lib.zke_decode_key_records_async(self.h, b.arr, b.m, mode, C.byref(b.c), C.byref(t)), "zke_decode_key_records_async")
+        return t.value, b
+
+    def select_keys_from_records(self, emails, candidate_records: Sequence[Sequence[Optional[bytes]]], mode: int = A.KEYREC_DNS):
+        """zke_select_keys_from_records: select_keys with the resolver's raw answers in place of keys — candidate_records[i] = the
+        records fetched for e-mail i's candidates, in the scan's order (None or b"": the fetch failed).  The records are decoded on
+        the GPU in front of the verify launches; the decoded keys stay in HBM on their way there.  Returns (records, chosen, infos):
+        infos[i][k] = the KeyInfo of e-mail i's candidate k, from which Email.public_key of the chosen one is built."""
+        refs = emails if isinstance(emails, A.EmailRefs) else A.EmailRefs(emails)
+        if refs.n != len(candidate_records):
+            raise ValueError("one candidate list per e-mail")
+        t, out, chosen, pend = self.select_keys_from_records_async(refs, candidate_records, mode)
+        self.wait(t)
+        return out, chosen, pend.result()
+
+    def select_keys_from_records_async(self, emails, candidate_records, mode: int = A.KEYREC_DNS):
+        """zke_select_keys_from_records_async: (ticket, records, chosen, pending), valid once ``wait(ticket)`` has returned;
+        ``pending.result()`` is the per-e-mail lists of KeyInfo."""
+        refs = emails if isinstance(emails, A.EmailRefs) else A.EmailRefs(emails)
+        off = np.zeros(len(candidate_records) + 1, np.uint32)
+        off[1:] = np.cumsum([len(r) for r in candidate_records])
+        b = _KeyrecBuffers([r for row in candidate_records for r in row], off=off)
+        b.refs = refs
+        out = np.zeros(max(refs.n, 1), dtype=A.RESULT_DTYPE)
+        chosen = np.zeros(max(refs.n, 1), np.uint32)
+        t = C.c_uint64()
+        self._check(self.lib.zke_select_keys_from_records_async(self.h, refs.arr, refs.n, off.ctypes.data, b.arr, mode, out.ctypes.data,
+                                                                chosen.ctypes.data, C.byref(b.c), C.byref(t)), "zke_select_keys_from_records_async")
+        return t.value, out[:refs.n], chosen[:refs.n], b
+
     # ---- batches
     def verify_batch_async(self, batch: PackedBatch):
         """zke_verify_batch_async: returns (ticket, records); the records are valid once ``wait(ticket)`` has returned.
@@ -709,21 +801,11 @@ NO_SIGNATURES = "No DKIM signatures found"                         # helpers/src
 NO_VALID_KEY = "No valid DKIM key found for any signature"        # helpers/src/generator.rs:52
 
 
-def generate_email_inputs(from_domains: Sequence[str], raw_emails: Sequence[bytes],
-                          fetch_key: Callable[[str, bytes], Optional["A.PublicKey"]],
-                          external_inputs: Optional[Sequence[Optional[Sequence["A.ExternalInput"]]]] = None, *,
-                          max_sigs: int = A.SCAN_MAX_SIGS, engine: Optional[Engine] = None) -> List[Email]:
-    """helpers/src/generator.rs:11-53 generate_email_inputs for a batch: scan the DKIM-Signature headers on the GPU, ask
-    `fetch_key(from_domain, selector)` — the caller's resolver, the only place network code would live; called once per distinct
-    pair, on the host, between the two GPU calls; None: the fetch failed — for the key of every candidate, and keep the first key
-    under which the e-mail verifies.  Returns one Email per e-mail.  Raises VerifyPanic (its ``reason`` holds the reference's text)
-    for the first e-mail where the reference returns Err: a parse_mail error, "No DKIM signatures found", "No valid DKIM key found
-    for any signature".  An e-mail whose answer the engine cannot give (ZKE_UNSUPPORTED) raises too, with that status."""
-    eng = engine or default_engine()
-    n = len(raw_emails)
+def _scan_candidates(eng, from_domains, raw_emails, fetch, max_sigs):
+    """The scan and the resolver loop: `fetch(from_domain, selector)` once per distinct pair -> (scans, per-e-mail answers)."""
     scans = eng.scan_signatures(raw_emails, from_domains, max_sigs)
-    cache: Dict[Tuple[str, bytes], Optional[A.PublicKey]] = {}
-    cands: List[List[Optional[A.PublicKey]]] = []
+    cache: Dict[Tuple[str, bytes], object] = {}
+    cands: List[list] = []
     for dom, sc in zip(from_domains, scans):
         row = []
         for sig in sc.sigs:
@@ -731,12 +813,14 @@ def generate_email_inputs(from_domains: Sequence[str], raw_emails: Sequence[byte
                 continue
             k = (dom, sig.selector)
             if k not in cache:
-                cache[k] = fetch_key(dom, sig.selector)
+                cache[k] = fetch(dom, sig.selector)
             row.append(cache[k])
         cands.append(row)
-    probe = [Email(d, bytes(r), A.PublicKey(b"")) for d, r in zip(from_domains, raw_emails)]
-    records, chosen = eng.select_keys(probe, cands)
+    return scans, cands
 
+
+def _emails_of_selection(from_domains, raw_emails, external_inputs, max_sigs, scans, cands, records, chosen, key_of) -> List[Email]:
+    """generator.rs:36-52 over a selection's answer: one Email per e-mail under `key_of(i, k)`, or the reference's Err."""
     def err(status, detail, i, reason):
         e = VerifyPanic(status, detail, i)
         e.reason = reason
@@ -757,10 +841,44 @@ def generate_email_inputs(from_domains: Sequence[str], raw_emails: Sequence[byte
             raise err(st, int(r["detail"]), i, NO_VALID_KEY)
         if int(chosen[i]) & A.SEL_AFTER_UNSUPPORTED:
             raise err(A.ZKE_UNSUPPORTED, A.D_U_ALGO_ED25519, i, "a candidate in front of the passing key is outside what the engine implements")
-        key = cands[i][int(chosen[i])]
+        key = key_of(i, int(chosen[i]))
         ext = list(external_inputs[i] or []) if external_inputs is not None else []
         out.append(Email(from_domains[i], bytes(raw_emails[i]), A.PublicKey(bytes(key.key), key.key_type), ext))
     return out
+
+
+def generate_email_inputs(from_domains: Sequence[str], raw_emails: Sequence[bytes],
+                          fetch_key: Callable[[str, bytes], Optional["A.PublicKey"]],
+                          external_inputs: Optional[Sequence[Optional[Sequence["A.ExternalInput"]]]] = None, *,
+                          max_sigs: int = A.SCAN_MAX_SIGS, engine: Optional[Engine] = None) -> List[Email]:
+    """helpers/src/generator.rs:11-53 generate_email_inputs for a batch: scan the DKIM-Signature headers on the GPU, ask
+    `fetch_key(from_domain, selector)` — the caller's resolver, the only place network code would live; called once per distinct
+    pair, on the host, between the two GPU calls; None: the fetch failed — for the key of every candidate, and keep the first key
+    under which the e-mail verifies.  Returns one Email per e-mail.  Raises VerifyPanic (its ``reason`` holds the reference's text)
+    for the first e-mail where the reference returns Err: a parse_mail error, "No DKIM signatures found", "No valid DKIM key found
+    for any signature".  An e-mail whose answer the engine cannot give (ZKE_UNSUPPORTED) raises too, with that status."""
+    eng = engine or default_engine()
+    scans, cands = _scan_candidates(eng, from_domains, raw_emails, fetch_key, max_sigs)
+    probe = [Email(d, bytes(r), A.PublicKey(b"")) for d, r in zip(from_domains, raw_emails)]
+    records, chosen = eng.select_keys(probe, cands)
+    return _emails_of_selection(from_domains, raw_emails, external_inputs, max_sigs, scans, cands, records, chosen, lambda i, k: cands[i][k])
+
+
+def generate_email_inputs_from_records(from_domains: Sequence[str], raw_emails: Sequence[bytes],
+                                       fetch_record: Callable[[str, bytes], Optional[bytes]],
+                                       external_inputs: Optional[Sequence[Optional[Sequence["A.ExternalInput"]]]] = None, *,
+                                       mode: int = A.KEYREC_DNS, max_sigs: int = A.SCAN_MAX_SIGS, engine: Optional[Engine] = None) -> List[Email]:
+    """generate_email_inputs with the resolver's RAW answers: `fetch_record(from_domain, selector)` returns the TXT record of
+    selector._domainkey.from_domain as bytes (the character-strings of a multi-string answer joined; `mode` = _abi.KEYREC_DNS) or
+    the archive's `value` (_abi.KEYREC_ARCHIVE), None when the fetch failed.  Turning the record into the (key, key_type) pair —
+    helpers/src/dkim.rs:67-111: base64, SubjectPublicKeyInfo or PKCS#1 in, PKCS#1 out — happens on the GPU in front of the verify
+    launches (zke_select_keys_from_records); the caller is left with network code only.  Errors as generate_email_inputs."""
+    eng = engine or default_engine()
+    scans, cands = _scan_candidates(eng, from_domains, raw_emails, fetch_record, max_sigs)
+    probe = [Email(d, bytes(r), A.PublicKey(b"")) for d, r in zip(from_domains, raw_emails)]
+    records, chosen, infos = eng.select_keys_from_records(probe, cands, mode)
+    return _emails_of_selection(from_domains, raw_emails, external_inputs, max_sigs, scans, cands, records, chosen,
+                                lambda i, k: infos[i][k].public_key())
 
 
 def abi_encode_native(email: EmailVerifierOutput, matches: Optional[Sequence[str]] = None) -> bytes:
