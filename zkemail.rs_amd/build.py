@@ -44,7 +44,7 @@ def build_engine(force: bool = False, verbose: bool = False) -> str:
            "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-Wall", "-Wno-unused-function",
            "-o", ENGINE_SO] + srcs
     if verbose:
-        cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
+        cmd[1:1] = ["-Rpass-analysis=kernel-resource-usage", "-DZKE_LIST_GROUP_KERNELS"]     # rsa_group_kernel<4> / <8> listed too
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)

@@ -30,11 +30,15 @@ struct StageArgs {
 
 constexpr uint32_t QUAD_LDS_DWORDS = 16 * (4 * QL + 4), OCT_LDS_DWORDS = 8 * (8 * QL + 4);      // per wave
 
+// Waves per SIMD of the hash / modexp launch.  The kernel needs 153 registers (the SHA-256 pair routine's), which would let
+// three waves share a SIMD; ZKE_STAGE_WAVES is both the least the compiler must allow AND the most the hardware may place
+// (amdgpu_waves_per_eu(min, max): the register count is raised to what max waves leave each other), so that the occupancy
+// is chosen here and not by whatever the register allocation happens to come to.  2 or 3; the A/B is profiles/limb29_bench_ab.txt.
 #ifndef ZKE_STAGE_WAVES
-#define ZKE_STAGE_WAVES 2        // waves per SIMD the hash / modexp launch is compiled for
+#define ZKE_STAGE_WAVES 2
 #endif
 template <int T>
-__global__ __launch_bounds__(128, ZKE_STAGE_WAVES) void hash_modexp_kernel(StageArgs A) {
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(ZKE_STAGE_WAVES, ZKE_STAGE_WAVES))) void hash_modexp_kernel(StageArgs A) {
   static_assert(sha256_pair_lds_bytes<T>() >= 2 * 4 * QUAD_LDS_DWORDS && sha256_pair_lds_bytes<T>() >= 2 * 4 * OCT_LDS_DWORDS,
                 "the RSA roles borrow the launch's LDS");
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];

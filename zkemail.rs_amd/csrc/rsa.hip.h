@@ -42,6 +42,11 @@ enum : uint32_t {
   RSA_F_OCT = 8,                // ... rsa_group_kernel<8> (eight lanes per signature: moduli of 2049..4096 bits)
 };
 
+// The limb layout of the lane-group routine (rsa_quad.hip.h), here because the cache entry holds a constant in it.
+constexpr int QL = 18;                       // limbs per lane
+constexpr int QBITS = 29;                    // bits per limb
+constexpr uint32_t QMASK = (1u << QBITS) - 1u;
+
 // Per-key Montgomery constants, cached across e-mails and batches (one table per engine = per device, shared by all
 // submission slots).  Keyed by the MODULUS itself: the slot comes from a hash of its two low limbs and a hit needs all
 // limbs equal, so a lookup is exact and needs nothing but the decoded key — the front end does it (parse.hip.h) and
@@ -55,9 +60,10 @@ struct KeyCacheEntry {
   uint32_t pad;
   uint32_t mod[128];            // the modulus, little-endian 32-bit limbs (zero above `bits`)
   uint32_t rr[128];             // R^2 mod n, limb q*64+lane
-  uint32_t rr28[152];           // rsa_quad.hip.h: 2^4256 mod n as 76 limbs of 28 bits (512..2048 bits), 2^8512 mod n as 152 (..4096)
+  uint32_t rrq[8 * QL];         // rsa_quad.hip.h: R'^2 mod n in that routine's limbs: 4 QL of them for R' = 2^(QBITS QL 4) (512..2048 bits),
+                                // 8 QL for R' = 2^(QBITS QL 8) (..4096)
 };
-static_assert(sizeof(KeyCacheEntry) == 1648, "KeyCacheEntry layout");
+static_assert(sizeof(KeyCacheEntry) == 4 * (4 + 128 + 128 + 8 * QL), "KeyCacheEntry layout");
 constexpr uint32_t KEY_CACHE_SLOTS = 4096;
 __host__ __device__ inline uint32_t key_cache_slot(uint32_t n0, uint32_t n1) { return (n0 * 0x9E3779B1u + n1 * 0x85EBCA77u) >> 20; }   // 12 bits
 static_assert(KEY_CACHE_SLOTS == (1u << 12), "key_cache_slot yields 12 bits");

@@ -139,16 +139,18 @@ __device__ __forceinline__ bool rsa_wave(const RsaJob* __restrict__ jobs, uint32
 #pragma unroll
           for (int q = 0; q < NL; q++) st_agent(&E->rr[q * 64 + lane], rr.v[q]);
           if (bits >= 512) {
-            // R'^2 mod n for the 28-bit radix of rsa_quad.hip.h (R' = 2^(532 G): 2^2128 for four lanes, 2^4256 for eight):
+            // R'^2 mod n for the QBITS-bit radix of rsa_quad.hip.h (R' = 2^(QBITS QL G): 2^2088 for four lanes, 2^4176 for eight):
             // two more products with R = 2^(2048 NL): mont(R^2, 2^c) = 2^c R, mont(R^2, 2^c R) = 2^c R^2 with
-            // c = 2 (532 G - 2048 NL) = 160 / 320; then limb t = bits [28 t, 28 t + 28)
+            // c = 2 (QBITS QL G - 2048 NL) = 80 / 160; then limb t = bits [QBITS t, QBITS t + QBITS)
+            constexpr uint32_t C = 2u * ((uint32_t)QBITS * QL * 4 * NL - 2048u * NL);
+            static_assert(C == (NL == 1 ? 80u : 160u) && C < 2048u * NL, "2^c is an operand below R");
             Big<NL> cc, z, r2;
 #pragma unroll
-            for (int q = 0; q < NL; q++) cc.v[q] = (q == 0 && lane == (NL == 1 ? 5 : 10)) ? 1u : 0u;
+            for (int q = 0; q < NL; q++) cc.v[q] = (q == 0 && lane == (int)(C >> 5)) ? (1u << (C & 31)) : 0u;
             mont_mul<NL>(z, rr, cc, nn, ninv, lane);
             mont_mul<NL>(r2, rr, z, nn, ninv, lane);
-            for (uint32_t t0 = 0; t0 < 64u * (NL + 1); t0 += 64) {
-              const uint32_t t = t0 + (uint32_t)lane, bit = 28u * t, w = bit >> 5;
+            for (uint32_t t0 = 0; t0 < 64u * (NL + 1); t0 += 64) {        // 64 (NL + 1) >= 4 QL NL limbs
+              const uint32_t t = t0 + (uint32_t)lane, bit = (uint32_t)QBITS * t, w = bit >> 5;
               uint32_t lo = 0, hi = 0;
 #pragma unroll
               for (int q = 0; q < NL; q++) {                       // 32-bit limb w lives in v[w >> 6] of lane w & 63
@@ -157,8 +159,8 @@ __device__ __forceinline__ bool rsa_wave(const RsaJob* __restrict__ jobs, uint32
                 if ((w >> 6) == (uint32_t)q) lo = l0;
                 if (((w + 1) >> 6) == (uint32_t)q) hi = l1;
               }
-              const uint32_t v = (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (bit & 31)) & 0x0FFFFFFFu;
-              if (t < 76u * NL) st_agent(&E->rr28[t], v);
+              const uint32_t v = (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (bit & 31)) & QMASK;      // 31 + QBITS <= 64
+              if (t < (uint32_t)(4 * QL) * NL) st_agent(&E->rrq[t], v);
             }
           }
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the entry has reached the coherence point ...

@@ -1,39 +1,46 @@
 // rsa_quad.hip.h — RSA verification with FOUR LANES PER SIGNATURE (16 signatures per wavefront) for moduli of up
 // to 2048 bits and e = 65537: the same rsa 0.9.6 / num-bigint-dig operation as rsa.hip.h (call site
-// core/src/email.rs:31-33; RFC 8017 §8.2.2, §9.2), 4.6 k instead of 12.0 k VALU instructions per signature (measured).
+// core/src/email.rs:31-33; RFC 8017 §8.2.2, §9.2), at about a third of the VALU instructions per signature of the
+// one-signature-per-wave routine (DESIGN.md §5 has the measured counts).
 //
 // Why.  The path is VALU-issue bound and the one-limb-per-lane kernel spends 9 instructions per
 // limb and CIOS step: two multiplies, and seven to read the multiplier digit, form the quotient digit, shift the
-// accumulator one lane down and keep its carries.  Here a number is 76 limbs of 28 bits, 19 consecutive limbs per
-// lane, four lanes (one DPP quad) per signature:
-//   * products of 28-bit limbs are < 2^56, and a register holds at most 38 of them in its life as a column, so
-//     every column is a plain 64-bit accumulator: ONE v_mad_u64_u32 per limb product, no carry instructions;
-//   * the accumulator is a window of 38 columns per lane addressed at compile time (column k + r for limb k at
-//     step r of a block of 19 steps), so nothing is shifted inside a block; the per-step cross-lane work is two
-//     quad broadcasts (multiplier digit, quotient digit) for 38 multiplies;
-//   * every 19 steps the reduced low half of a lane's window (zero in lane 0) moves one lane down and the high half
-//     becomes the low half: 19 quad rotations + 19 additions per 722 multiplies;
-//   * R = 2^2128 > 4n, so values stay in [0, 2n) without any conditional subtraction; carries are normalised once per
-//     product (limbs <= 2^28), exactly only for the final result.
-// 55 instructions per step for 16 signatures instead of 9 per step for one.  Moduli of 2049..4096 bits run the same
-// code with eight lanes per signature (152 limbs, R = 2^4256, eight blocks of 19 steps).
+// accumulator one lane down and keep its carries.  Here a number is G * QL limbs of QBITS bits (QL = 18, QBITS = 29:
+// 72 limbs for G = 4), QL consecutive limbs per lane, four lanes (one DPP quad) per signature:
+//   * operand limbs are <= 2^QBITS, so a product is <= 2^58, and a register holds 2 QL = 36 of them in its life as a
+//     column (QL as a high column of one block, QL as a low column of the next; half of them a * b, half m * n), plus at most
+//     two carries < 2^35 (one when it is the first high column, one when the column below it is reduced) and one received
+//     limb < 2^QBITS at the hand-over: 36 * 2^58 + 2^36 + 2^29 < 2^63.2, so every column is a plain 64-bit accumulator: ONE
+//     v_mad_u64_u32 per limb product, no carry instructions.  (QL = 18 is what lets 29 bits fit: 2 QL * 2^(2 QBITS) must stay
+//     below 2^64; 30-bit limbs would overflow a column after 16 products);
+//   * the accumulator is a window of 2 QL columns per lane addressed at compile time (column k + r for limb k at
+//     step r of a block of QL steps), so nothing is shifted inside a block; the per-step cross-lane work is two
+//     quad broadcasts (multiplier digit, quotient digit) for 2 QL = 36 multiplies;
+//   * every QL steps the reduced low half of a lane's window (zero in lane 0) moves one lane down and the high half
+//     becomes the low half: QL quad rotations + QL additions per 2 QL^2 = 648 multiplies;
+//   * R = 2^(QBITS QL G) = 2^2088 > 2^40 n >= 4n, so values stay in [0, 2n) without any conditional subtraction; carries
+//     are normalised once per product (limbs <= 2^QBITS), exactly only for the final result.
+// A Montgomery product is 2 (QL G)^2 = 10 368 multiplies for 16 signatures; a block of QL steps compiles to 828 VALU
+// instructions, 648 of them multiplies — 46 per step for 16 signatures instead of 9 per step for one.  Moduli of 2049..4096 bits run the same
+// code with eight lanes per signature (144 limbs, R = 2^4176, eight blocks of QL steps).
 //
-// R^2 mod n for this radix (2^4256 mod n; 2^8512 mod n for eight lanes) comes from the key cache.  The front end looks a
-// decoded key up there (by modulus: exact) and routes the e-mail's signatures here (RSA_F_QUAD / RSA_F_OCT) when the
+// R^2 mod n for this radix (2^(2 * 2088) mod n; 2^(2 * 4176) mod n for eight lanes) comes from the key cache.  The front end
+// looks a decoded key up there (by modulus: exact) and routes the e-mail's signatures here (RSA_F_QUAD / RSA_F_OCT) when the
 // entry exists and e = 65537; a key seen for the first time — and other exponents, keys whose cache slot belongs to
 // another key — goes to the one-signature-per-wave routine, which fills the entry (two more 32-bit-radix Montgomery
-// products turn 2^4096 mod n into 2^4256 mod n).  Signatures rsa 0.9.6 rejects before the arithmetic are rejected here too.  The algorithm and its register bounds are modelled with
-// Python integers in tests/test_rsa_group_model.py.
+// products turn 2^(2 * 2048) mod n into 2^(2 * 2088) mod n).  Signatures rsa 0.9.6 rejects before the arithmetic are rejected
+// here too.  The algorithm and its register bounds are modelled with Python integers in tests/test_rsa_group_model29.py.
 #pragma once
 #include "rsa_kernel.hip.h"
 
 namespace zke {
 
-constexpr int QL = 19;                       // limbs per lane
-constexpr uint32_t QMASK = 0x0FFFFFFFu;
-struct QBig { uint32_t v[QL]; };             // lane p of the group: limbs 19p .. 19p+18
+// QL = 18 limbs per lane, QBITS = 29 bits per limb, QMASK: rsa.hip.h (KeyCacheEntry holds R^2 mod n in this layout)
+static_assert(2 * QL < (1 << (64 - 2 * QBITS)), "2 QL products of <= 2^(2 QBITS) and their carries (< one product more) must fit a 64-bit column");
+static_assert(4 * QL * QBITS >= 2048 + 2 && 8 * QL * QBITS >= 4096 + 2, "R > 4n for four lanes (<= 2048 bits) and eight (<= 4096)");
+struct QBig { uint32_t v[QL]; };             // lane p of the group: limbs QL p .. QL p + QL - 1
 
-// Lane groups of G = 4 (one DPP quad: 76 limbs, moduli <= 2048 bits) or G = 8 (half a DPP row: 152 limbs, <= 4096 bits).
+// Lane groups of G = 4 (one DPP quad: 72 limbs, moduli <= 2048 bits) or G = 8 (half a DPP row: 144 limbs, <= 4096 bits).
 // (bound_ctrl on the full-mask moves: lanes without a source read 0 and the destination needs no initial value)
 template <int G> __device__ __forceinline__ uint32_t g_bcast0(uint32_t x) {        // lane 0 of the group to all of it
   uint32_t q = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x00 /*quad_perm:[0,0,0,0]*/, 0xf, 0xf, true);
@@ -51,8 +58,8 @@ template <int G> __device__ __forceinline__ uint32_t g_fromprev(uint32_t x) {   
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111 /*row_shr:1*/, 0xf, 0xf, true);
 }
 
-// W = (a * b + sum_i m_i * n * 2^(28 i)) / 2^(532 G) as 19 lazy 64-bit columns per lane (column j of lane p: limb 19p + j).
-// A register holds at most 38 products (< 2^56 each) in its life as a high and then a low column: no overflow.
+// W = (a * b + sum_i m_i * n * 2^(QBITS i)) / 2^(QBITS QL G) as QL lazy 64-bit columns per lane (column j of lane p: limb QL p + j).
+// A register holds at most 2 QL = 36 products (<= 2^58 each) in its life as a high and then a low column: no overflow.
 template <int G>
 __device__ __forceinline__ void qmont_columns(uint64_t (&W)[2 * QL], const QBig& a, const QBig& b, const QBig& n, uint32_t ninv, int p) {
 #pragma unroll
@@ -60,20 +67,20 @@ __device__ __forceinline__ void qmont_columns(uint64_t (&W)[2 * QL], const QBig&
   QBig B = b;
 #pragma unroll 1
   for (int blk = 0; blk < G; blk++) {
-    // 19 steps: multiplier digits 19 blk + r, held by lane 0 of the group after blk rotations of B
+    // QL steps: multiplier digits QL blk + r, held by lane 0 of the group after blk rotations of B
 #pragma unroll
     for (int r = 0; r < QL; r++) {
       const uint32_t bd = g_bcast0<G>(B.v[r]);
 #pragma unroll
-      for (int k = 0; k < QL; k++)           // column r + 18 is touched here for the first time in this block (r > 0)
+      for (int k = 0; k < QL; k++)           // column r + QL - 1 is touched here for the first time in this block (r > 0)
         W[k + r] = (uint64_t)a.v[k] * bd + ((k == QL - 1 && r > 0) ? 0ull : W[k + r]);
       const uint32_t m = g_bcast0<G>(((uint32_t)W[r] * ninv) & QMASK);       // lane 0's column r is the lowest live limb
 #pragma unroll
       for (int k = 0; k < QL; k++) W[k + r] = (uint64_t)n.v[k] * m + W[k + r];
-      W[r + 1] += W[r] >> 28;              // lane 0: the column is now a multiple of 2^28; other lanes: a partial carry
+      W[r + 1] += W[r] >> QBITS;           // lane 0: the column is now a multiple of 2^QBITS; other lanes: a partial carry (< 2^35)
       W[r] &= QMASK;
     }
-    // the window moves up 19 limbs: finished low columns go one lane down (lane 0's are zero and reach the top lane)
+    // the window moves up QL limbs: finished low columns go one lane down (lane 0's are zero and reach the top lane)
 #pragma unroll
     for (int j = 0; j < QL; j++) {
       const uint32_t recv = g_rotdown<G>((uint32_t)W[j], p);
@@ -84,7 +91,7 @@ __device__ __forceinline__ void qmont_columns(uint64_t (&W)[2 * QL], const QBig&
   }
 }
 
-// columns -> limbs.  CROSS cross-lane passes: 1 leaves limbs <= 2^28 (good enough as an operand), G - 1 is exact.
+// columns -> limbs.  CROSS cross-lane passes: 1 leaves limbs <= 2^QBITS (good enough as an operand), G - 1 is exact.
 template <int G, int CROSS>
 __device__ __forceinline__ void qnorm(QBig& out, const uint64_t (&W)[2 * QL], int p) {
   uint64_t c = 0;
@@ -92,27 +99,37 @@ __device__ __forceinline__ void qnorm(QBig& out, const uint64_t (&W)[2 * QL], in
   for (int j = 0; j < QL; j++) {
     const uint64_t t = W[j] + c;
     out.v[j] = (uint32_t)t & QMASK;
-    c = t >> 28;
+    c = t >> QBITS;                                             // t < 2^64: c < 2^35
   }
-  uint32_t clo = (uint32_t)c, chi = (uint32_t)(c >> 32);       // < 2^37 out of the local pass
+  uint32_t clo = (uint32_t)c, chi = (uint32_t)(c >> 32);       // < 2^35 out of the local pass
 #pragma unroll
   for (int pass = 0; pass < CROSS; pass++) {
     uint32_t ilo = g_fromprev<G>(clo), ihi = g_fromprev<G>(chi);
     if (p == 0) { ilo = 0; ihi = 0; }
     const uint64_t t0 = (uint64_t)out.v[0] + (((uint64_t)ihi << 32) | ilo);
     out.v[0] = (uint32_t)t0 & QMASK;
-    uint32_t c32 = (uint32_t)(t0 >> 28);
+    uint32_t c32 = (uint32_t)(t0 >> QBITS);                    // t0 < 2^29 + 2^35: c32 < 2^7 (first pass), then 0 or 1
 #pragma unroll
     for (int j = 1; j < QL; j++) {
       const uint32_t t = out.v[j] + c32;
       out.v[j] = t & QMASK;
-      c32 = t >> 28;
+      c32 = t >> QBITS;
     }
     clo = c32; chi = 0;                                         // 0 or 1 from here on
   }
   uint32_t last = g_fromprev<G>(clo);
   if (p == 0) last = 0;
   out.v[0] += last;                                             // value-preserving; zero after G - 1 passes
+}
+
+// bits [QBITS t, QBITS t + QBITS) of a big-endian 512-byte field (RsaJob.mod / .sig)
+__device__ __forceinline__ uint32_t qlimb_of(const uint8_t* field, uint32_t t) {
+  typedef uint64_t __attribute__((aligned(1))) u64_unaligned;
+  const uint32_t bit = (uint32_t)QBITS * t, o = bit >> 3;              // little-endian byte o = field[511 - o]
+  if (o >= 512) return 0;                                              // beyond 4096 bits
+  const uint32_t oo = o > 504 ? 504u : o;                              // the top limbs: read the field's first 8 bytes and shift
+  const uint64_t v = __builtin_bswap64(*(const u64_unaligned*)(field + 504 - oo)) >> (8 * (o - oo));
+  return (uint32_t)(v >> (bit & 7)) & QMASK;                           // 7 + QBITS <= 64 - 8 * (o - oo) bits of v, or zeros above the field
 }
 
 // One wave: NG = 64 / G signatures.  job0 = the wave's first job.  Llimb: NG x (G * QL + 4) dwords of LDS private to the wave.
@@ -136,65 +153,67 @@ __device__ __forceinline__ void rsa_group_wave(const RsaJob* __restrict__ jobs, 
   if (job < n) flags = J->flags;
   const bool act = (flags & MY_FLAG) != 0;
   if (__ballot(act) == 0) return;
-  // NG signatures share one long dependency chain (~95 k instructions for G = 4): served round-robin with the short waves
+  // NG signatures share one long dependency chain (~65 k instructions for G = 4): served round-robin with the short waves
   // of other batches it would stretch several times over and hold its whole batch back; the others have parallel slack.
   __builtin_amdgcn_s_setprio(ZKE_QUAD_PRIO);
 
-  QBig nn, s, rr;
+  // (the signature and the cached constant are operands of one product each: they are read where they are used — s twice — and
+  // hold no registers through the seventeen products between: 36 loads per lane, once per signature)
+  const KeyCacheEntry* E = cache;
+  QBig nn, acc;
 #pragma unroll
-  for (int j = 0; j < QL; j++) { nn.v[j] = 0; s.v[j] = 0; rr.v[j] = 0; }
+  for (int j = 0; j < QL; j++) { nn.v[j] = 0; acc.v[j] = 0; }
   uint32_t ninv = 0, kbytes = 0;
   if (act) {
-    typedef uint64_t __attribute__((aligned(1))) u64_unaligned;
-    auto limb_of = [&](const uint8_t* field, uint32_t t) -> uint32_t {     // bits [28 t, 28 t + 28) of a big-endian 512-byte field
-      const uint32_t bit = 28u * t, o = bit >> 3;                          // little-endian byte o = field[511 - o]
-      if (o >= 512) return 0;                                              // beyond 4096 bits
-      const uint32_t oo = o > 504 ? 504u : o;                              // the top limbs: read the field's first 8 bytes and shift
-      const uint64_t v = __builtin_bswap64(*(const u64_unaligned*)(field + 504 - oo)) >> (8 * (o - oo));
-      return (uint32_t)(v >> (bit & 7)) & QMASK;
-    };
     // the front end found this modulus in the cache (all limbs compared) before it set MY_FLAG; entries are immutable
     const uint32_t n0 = __builtin_bswap32(*(const uint32_t*)(J->mod + 508)), n1 = __builtin_bswap32(*(const uint32_t*)(J->mod + 504));
-    const KeyCacheEntry* E = cache + key_cache_slot(n0, n1);
+    E = cache + key_cache_slot(n0, n1);
 #pragma unroll
     for (int j = 0; j < QL; j++) {
-      nn.v[j] = limb_of(J->mod, QL * p + j);
-      s.v[j] = limb_of(J->sig, QL * p + j);
-      rr.v[j] = ld_agent(&E->rr28[QL * p + j]);
+      nn.v[j] = qlimb_of(J->mod, QL * p + j);
+      acc.v[j] = qlimb_of(J->sig, QL * p + j);
     }
     ninv = ld_agent(&E->ninv) & QMASK;
     kbytes = J->k;
   }
+  bool take = act;                            // the signature takes part in the arithmetic
   {
     // rsa 0.9.6 rejects a signature whose length is not the modulus length, or with s >= n, before any arithmetic:
     // such a job runs with s = 0, whose EM = 0 has no EMSA shape (em_ok = 0, an all-zero EM block, as the wave path leaves).
     // s >= n: per lane the sign of the highest differing limb; the highest lane of the group that differs decides.
     int c = 0;
 #pragma unroll
-    for (int j = QL - 1; j >= 0; j--) c = c != 0 ? c : (int)(s.v[j] > nn.v[j]) - (int)(s.v[j] < nn.v[j]);
+    for (int j = QL - 1; j >= 0; j--) c = c != 0 ? c : (int)(acc.v[j] > nn.v[j]) - (int)(acc.v[j] < nn.v[j]);
     const uint64_t gmask0 = (G == 4 ? 0xFull : 0xFFull);
     const uint64_t gtg = (__ballot(c > 0) >> (G * grp)) & gmask0, ltg = (__ballot(c < 0) >> (G * grp)) & gmask0;
     const bool reject = act && (J->sig_len != kbytes || gtg >= ltg);
     if (reject) {
+      take = false;
 #pragma unroll
-      for (int j = 0; j < QL; j++) s.v[j] = 0;
+      for (int j = 0; j < QL; j++) acc.v[j] = 0;
     }
   }
 
   // s^65537 in 18 products: s R (into the Montgomery domain), sixteen squarings -> s^65536 R, and the last product takes
   // the PLAIN s: (s^65536 R) s / R = s^65537 — out of the domain without a nineteenth product by one.  That value is
-  // < n + n^2 / R (a < 2n, s < n, R > 2^80 n): one conditional subtraction makes it exact.
-  QBig acc = s;
+  // < n + n^2 / R (a < 2n, s < n, R > 2^40 n): one conditional subtraction makes it exact.
   uint64_t W[2 * QL];
 #pragma unroll 1
   for (int step = 0; step < 17; step++) {
-    QBig b;
+    QBig b = acc;
+    if (step == 0) {
 #pragma unroll
-    for (int j = 0; j < QL; j++) b.v[j] = step == 0 ? rr.v[j] : acc.v[j];
+      for (int j = 0; j < QL; j++) b.v[j] = act ? ld_agent(&E->rrq[QL * p + j]) : 0u;
+    }
     qmont_columns<G>(W, acc, b, nn, ninv, p);
     qnorm<G, 1>(acc, W, p);
   }
-  qmont_columns<G>(W, acc, s, nn, ninv, p);
+  {
+    QBig s;
+#pragma unroll
+    for (int j = 0; j < QL; j++) s.v[j] = take ? qlimb_of(J->sig, QL * p + j) : 0u;
+    qmont_columns<G>(W, acc, s, nn, ninv, p);
+  }
   qnorm<G, G - 1>(acc, W, p);                 // exact limbs
   {
     // acc >= n?  Per lane the sign of the highest differing limb; the highest differing lane of the group decides, and the
@@ -231,8 +250,8 @@ __device__ __forceinline__ void rsa_group_wave(const RsaJob* __restrict__ jobs, 
     uint8_t* tail = meta ? reinterpret_cast<uint8_t*>(meta[job].em_tail) : nullptr;
     for (uint32_t u = 0; u < 64; u++) {
       const uint32_t i = G * u + (uint32_t)p;                    // little-endian byte index: 64 G bytes per group
-      const uint32_t t = (8 * i) / 28, sh = 8 * i - 28 * t;
-      const uint64_t two = (uint64_t)Llimb[grp][t] | ((uint64_t)Llimb[grp][t + 1] << 28);
+      const uint32_t t = (8 * i) / QBITS, sh = 8 * i - QBITS * t;   // t + 1 <= LIMBS - 1; the + 4 words stay as zeroed padding
+      const uint64_t two = (uint64_t)Llimb[grp][t] | ((uint64_t)Llimb[grp][t + 1] << QBITS);
       const uint32_t got = (uint32_t)(two >> sh) & 0xff;
       if (i < hl) {
         if (tail) tail[i] = (uint8_t)got;                        // little-endian limb image: byte i of EM counted from its end
@@ -265,5 +284,12 @@ __global__ __launch_bounds__(64) void rsa_group_kernel(const RsaJob* __restrict_
   __shared__ uint32_t Llimb[NG * (LIMBS + 4)];
   rsa_group_wave<G>(jobs, n, blockIdx.x * NG, Llimb, hash_base, hash_stride, ok_out, em_out, cache, meta);
 }
+
+// (not launched by the engine, which runs the routine inside hash_modexp_kernel: instantiated only for the compiler's resource
+// remarks — build.py's verbose build defines ZKE_LIST_GROUP_KERNELS — to show the routine's own register footprint)
+#ifdef ZKE_LIST_GROUP_KERNELS
+template __global__ void rsa_group_kernel<4>(const RsaJob*, uint32_t, const uint8_t*, size_t, uint32_t*, uint8_t*, const KeyCacheEntry*, EmailMeta*);
+template __global__ void rsa_group_kernel<8>(const RsaJob*, uint32_t, const uint8_t*, size_t, uint32_t*, uint8_t*, const KeyCacheEntry*, EmailMeta*);
+#endif
 
 }  // namespace zke
