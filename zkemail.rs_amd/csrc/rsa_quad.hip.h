@@ -17,19 +17,21 @@
 //     step r of a block of QL steps), so nothing is shifted inside a block; the per-step cross-lane work is two
 //     quad broadcasts (multiplier digit, quotient digit) for 2 QL = 36 multiplies;
 //   * every QL steps the reduced low half of a lane's window (zero in lane 0) moves one lane down and the high half
-//     becomes the low half: QL quad rotations + QL additions per 2 QL^2 = 648 multiplies;
+//     becomes the low half: QL quad rotations + QL additions per 2 QL^2 = 648 multiplies; the masks to QBITS bits (quotient
+//     digit, finished column) ride on DPP moves for four lanes (v_and_b32_dpp);
 //   * R = 2^(QBITS QL G) = 2^2088 > 2^40 n >= 4n, so values stay in [0, 2n) without any conditional subtraction; carries
 //     are normalised once per product (limbs <= 2^QBITS), exactly only for the final result.
-// A Montgomery product is 2 (QL G)^2 = 10 368 multiplies for 16 signatures; a block of QL steps compiles to 828 VALU
-// instructions, 648 of them multiplies — 46 per step for 16 signatures instead of 9 per step for one.  Moduli of 2049..4096 bits run the same
-// code with eight lanes per signature (144 limbs, R = 2^4176, eight blocks of QL steps).
+// A Montgomery product is 2 (QL G)^2 = 10 368 multiplies for 16 signatures; a block of QL steps compiles to 792 VALU
+// instructions, 648 of them multiplies — 44 per step for 16 signatures instead of 9 per step for one (profiles/rsa_trim_static.txt).
+// Moduli of 2049..4096 bits run the same code with eight lanes per signature (144 limbs, R = 2^4176, eight blocks of QL steps, 936 each).
 //
 // R^2 mod n for this radix (2^(2 * 2088) mod n; 2^(2 * 4176) mod n for eight lanes) comes from the key cache.  The front end
 // looks a decoded key up there (by modulus: exact) and routes the e-mail's signatures here (RSA_F_QUAD / RSA_F_OCT) when the
 // entry exists and e = 65537; a key seen for the first time — and other exponents, keys whose cache slot belongs to
 // another key — goes to the one-signature-per-wave routine, which fills the entry (two more 32-bit-radix Montgomery
 // products turn 2^(2 * 2048) mod n into 2^(2 * 2088) mod n).  Signatures rsa 0.9.6 rejects before the arithmetic are rejected
-// here too.  The algorithm and its register bounds are modelled with Python integers in tests/test_rsa_group_model29.py.
+// here too.  The algorithm and its register bounds are modelled with Python integers in tests/test_rsa_group_model29.py, the
+// deferred masks and the limb classes of the EMSA check in tests/test_rsa_group_trim_model.py.
 #pragma once
 #include "rsa_kernel.hip.h"
 
@@ -58,12 +60,29 @@ template <int G> __device__ __forceinline__ uint32_t g_fromprev(uint32_t x) {   
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111 /*row_shr:1*/, 0xf, 0xf, true);
 }
 
+// QMASK in a VGPR the compiler cannot turn back into a literal: an `and` whose other operand comes out of a full-mask DPP move
+// then folds into that move (v_and_b32_dpp; DPP encodings take no literal operand).
+__device__ __forceinline__ uint32_t qmask_vgpr() {
+  uint32_t qm = QMASK;
+  asm("" : "+v"(qm));
+  return qm;
+}
+
 // W = (a * b + sum_i m_i * n * 2^(QBITS i)) / 2^(QBITS QL G) as QL lazy 64-bit columns per lane (column j of lane p: limb QL p + j).
 // A register holds at most 2 QL = 36 products (<= 2^58 each) in its life as a high and then a low column: no overflow.
+//   * The quotient digit is masked BEHIND its broadcast: the 32-bit product travels, every lane keeps QBITS bits of it.
+//   * A finished column r is not masked in the step.  After the step it is read twice more: `>> QBITS` for the carry (the whole
+//     column, as before) and, at the hand-over, its low 32 bits by the lane below — which masks what it receives to QBITS bits.
+//     Both are the values a masked column would give; the register is overwritten right after (W[j] = W[QL + j] + recv).  So the
+//     column bound is untouched: still at most 2 QL products, two carries and one received limb <= 2^QBITS - 1 per register.
+//   With the mask in a VGPR both `and`s fold into their DPP moves for four lanes (v_and_b32_dpp): 792 VALU per block instead of 828.
+// (The four blocks written out, each reading its digit from lane blk of b with one quad_perm move and no rotating copy B, are 786
+// per block and as fast alone, but 25 KB of code: in flight they give back the gain — profiles/rsa_trim_bench_ab.txt.)
 template <int G>
 __device__ __forceinline__ void qmont_columns(uint64_t (&W)[2 * QL], const QBig& a, const QBig& b, const QBig& n, uint32_t ninv, int p) {
 #pragma unroll
   for (int j = 0; j < 2 * QL; j++) W[j] = 0;
+  const uint32_t qm = qmask_vgpr();
   QBig B = b;
 #pragma unroll 1
   for (int blk = 0; blk < G; blk++) {
@@ -74,16 +93,15 @@ __device__ __forceinline__ void qmont_columns(uint64_t (&W)[2 * QL], const QBig&
 #pragma unroll
       for (int k = 0; k < QL; k++)           // column r + QL - 1 is touched here for the first time in this block (r > 0)
         W[k + r] = (uint64_t)a.v[k] * bd + ((k == QL - 1 && r > 0) ? 0ull : W[k + r]);
-      const uint32_t m = g_bcast0<G>(((uint32_t)W[r] * ninv) & QMASK);       // lane 0's column r is the lowest live limb
+      const uint32_t m = g_bcast0<G>((uint32_t)W[r] * ninv) & qm;           // lane 0's column r is the lowest live limb
 #pragma unroll
       for (int k = 0; k < QL; k++) W[k + r] = (uint64_t)n.v[k] * m + W[k + r];
       W[r + 1] += W[r] >> QBITS;           // lane 0: the column is now a multiple of 2^QBITS; other lanes: a partial carry (< 2^35)
-      W[r] &= QMASK;
     }
-    // the window moves up QL limbs: finished low columns go one lane down (lane 0's are zero and reach the top lane)
+    // the window moves up QL limbs: finished low columns go one lane down (lane 0's are zero mod 2^QBITS and reach the top lane)
 #pragma unroll
     for (int j = 0; j < QL; j++) {
-      const uint32_t recv = g_rotdown<G>((uint32_t)W[j], p);
+      const uint32_t recv = g_rotdown<G>((uint32_t)W[j], p) & qm;
       W[j] = W[QL + j] + recv;
     }
 #pragma unroll
@@ -235,7 +253,7 @@ __device__ __forceinline__ void rsa_group_wave(const RsaJob* __restrict__ jobs, 
     }
   }
 
-  // EMSA-PKCS1-v1_5 (rsa 0.9.6 pkcs1v15_sign_unpad), byte by byte through LDS: the structure in front of the digest is
+  // EMSA-PKCS1-v1_5 (rsa 0.9.6 pkcs1v15_sign_unpad), limb compares and a byte walk through LDS: the structure in front of the digest is
   // checked here; the digest bytes are compared now (hash_base) or handed to verdict_kernel (meta)
 #pragma unroll
   for (int j = 0; j < QL; j++) Llimb[grp][QL * p + j] = acc.v[j];
@@ -248,18 +266,40 @@ __device__ __forceinline__ void rsa_group_wave(const RsaJob* __restrict__ jobs, 
   if (act) {
     const uint32_t* hw = hash_base ? (const uint32_t*)(hash_base + (size_t)job * hash_stride) : nullptr;
     uint8_t* tail = meta ? reinterpret_cast<uint8_t*>(meta[job].em_tail) : nullptr;
-    for (uint32_t u = 0; u < 64; u++) {
-      const uint32_t i = G * u + (uint32_t)p;                    // little-endian byte index: 64 G bytes per group
-      const uint32_t t = (8 * i) / QBITS, sh = 8 * i - QBITS * t;   // t + 1 <= LIMBS - 1; the + 4 words stay as zeroed padding
-      const uint64_t two = (uint64_t)Llimb[grp][t] | ((uint64_t)Llimb[grp][t + 1] << QBITS);
-      const uint32_t got = (uint32_t)(two >> sh) & 0xff;
-      if (i < hl) {
-        if (tail) tail[i] = (uint8_t)got;                        // little-endian limb image: byte i of EM counted from its end
-        if (hw) tail_bad = tail_bad || got != emsa_byte(i, kbytes, hw, sha1);
-      } else {
-        bad = bad || got != emsa_byte(i, kbytes, nullptr, sha1);
+    // Almost all of EM's bytes are the FF run (little-endian bytes [tLen + 1, k - 2)) or the zeros at and above k, whose
+    // value depends on nothing but their position: a limb that lies wholly inside the run must be all ones, one wholly at or
+    // above bit 8k must be zero — QL compares per lane on the registers — and the byte walk visits only the bytes of the other
+    // limbs: the digest, DigestInfo, the 00 separator and the limb that straddles that edge at the bottom, and the limbs
+    // around 01 and the top 00.  emsa_byte stays the judge of every byte walked, the single statement of the padding.
+    // (k < tLen + 11 makes the ranges meaningless: that verdict is refused below whatever they give, and the walk stays
+    // inside the 64 G bytes.)  tests/test_rsa_group_trim_model.py has the classifier for every k.
+    const uint32_t tlen = sha1 ? 35u : 51u;
+    const uint32_t ff_lo = (8 * (tlen + 1) + QBITS - 1) / QBITS, ff_hi = (8 * (kbytes - 2)) / QBITS;
+    const uint32_t z_lo = (8 * kbytes + QBITS - 1) / QBITS;
+#pragma unroll
+    for (int j = 0; j < QL; j++) {
+      const uint32_t t = QL * (uint32_t)p + j;
+      if (t >= ff_lo && t < ff_hi) bad = bad || acc.v[j] != QMASK;
+      else if (t >= z_lo) bad = bad || acc.v[j] != 0;
+    }
+    const uint32_t walk_lo = (QBITS * ff_lo + 7) / 8, walk_hi = (QBITS * ff_hi) / 8;
+    const uint32_t walk_top = (QBITS * z_lo + 7) / 8, walk_end = walk_top < 64u * G ? walk_top : 64u * G;
+    // the bottom stretch and the top one; parity / debug, where every byte is written out, keeps the full walk instead
+#pragma unroll 1
+    for (int part = 0; part < (em_out ? 1 : 2); part++) {
+      const uint32_t from = part == 1 ? walk_hi : 0u, to = em_out ? 64u * G : part == 0 ? walk_lo : walk_end;
+      for (uint32_t i = from + (uint32_t)p; i < to; i += G) {        // little-endian byte index, the group's lanes side by side
+        const uint32_t t = (8 * i) / QBITS, sh = 8 * i - QBITS * t;   // t + 1 <= LIMBS - 1; the + 4 words stay as zeroed padding
+        const uint64_t two = (uint64_t)Llimb[grp][t] | ((uint64_t)Llimb[grp][t + 1] << QBITS);
+        const uint32_t got = (uint32_t)(two >> sh) & 0xff;
+        if (i < hl) {
+          if (tail) tail[i] = (uint8_t)got;                        // little-endian limb image: byte i of EM counted from its end
+          if (hw) tail_bad = tail_bad || got != emsa_byte(i, kbytes, hw, sha1);
+        } else {
+          bad = bad || got != emsa_byte(i, kbytes, nullptr, sha1);
+        }
+        if (em_out) em_out[(size_t)job * 512 + 511 - i] = (uint8_t)got;
       }
-      if (em_out) em_out[(size_t)job * 512 + 511 - i] = (uint8_t)got;
     }
     if (em_out && G == 4) {
 #pragma unroll
