@@ -76,3 +76,64 @@ def build_vectors(seed: int = 7, n_valid: int = 24):
     for enc in ((1 | (1 << 255)).to_bytes(32, "little"), ((ed.P - 1) | (1 << 255)).to_bytes(32, "little")):
         out.append((enc, msg, sig, expect(enc, msg, sig)))
     return out
+
+
+def build_edge_vectors(seed: int = 8):
+    """-> list of (label, [(key, msg, sig, expected), ...]): one verify call per entry, equal-length messages within it.
+    Message lengths 1..32, S at and around its boundaries, and the launch shapes of the 16-signatures-per-wave kernel:
+    partial waves, waves whose other quads leave early, a wave that leaves as a whole, and the replicated tail."""
+    rng = np.random.default_rng(seed)
+    out = []
+
+    def rb(k):
+        return rng.integers(0, 256, k, dtype=np.uint8).tobytes()
+
+    def expect(key, msg, sig):
+        if not ed.key_decodes(key):
+            return 0
+        return 2 if ed.verify_strict(key, msg, sig) else 1
+
+    def vec(key, msg, sig):
+        return (key, msg, sig, expect(key, msg, sig))
+
+    def with_s(sig, S):
+        return sig[:32] + S.to_bytes(32, "little")
+
+    # message length: a valid signature, and the same signature over a message with its last byte changed
+    for ml in range(1, 33):
+        sd, msg = rb(32), rb(ml)
+        pk, sig = ed.public_key(sd), ed.sign(sd, msg)
+        out.append(("msg_len %d" % ml, [vec(pk, msg, sig), vec(pk, msg[:-1] + bytes([msg[-1] ^ 0x40]), sig)]))
+        assert [v[3] for v in out[-1][1]] == [2, 1]
+
+    # S boundaries on an otherwise valid signature
+    sd, msg = rb(32), rb(32)
+    pk, sig = ed.public_key(sd), ed.sign(sd, msg)
+    S = int.from_bytes(sig[32:], "little")
+    wraps = [vec(pk, msg, with_s(sig, S + k * ed.L)) for k in range(1, (2 ** 256 - 1 - S) // ed.L + 1)]
+    assert len(wraps) >= 14 and all(v[3] == 1 for v in wraps)
+    out.append(("S + kL", wraps))
+    out.append(("S boundaries", [vec(pk, msg, sig)] +
+                [vec(pk, msg, with_s(sig, s)) for s in (ed.L - 1, ed.L, ed.L + 1, 0, 2 ** 252, 2 ** 255, 2 ** 256 - 1)]))
+
+    # launch shapes
+    good = []
+    for _ in range(33):
+        sd, m = rb(32), rb(32)
+        good.append((ed.public_key(sd), m, ed.sign(sd, m), 2))
+    for n in (1, 15, 16, 17, 33):
+        out.append(("n = %d, all valid" % n, good[:n]))
+    nokey = []
+    while len(nokey) < 16:
+        k = rb(32)
+        if not ed.key_decodes(k):
+            nokey.append((k, rb(32), rb(64), 0))
+    early = [(k, m, with_s(s, int.from_bytes(s[32:], "little") + ed.L), 1) for k, m, s, _ in good[:16]]
+    for name, fill in (("keys that do not decode", nokey), ("S >= L", early)):
+        for j in range(16):
+            out.append(("one valid signature at quad %d among %s" % (j, name), fill[:j] + [good[j]] + fill[j + 1:]))
+    out.append(("a wave of early-outs, then a wave of valid signatures", nokey[:8] + early[8:] + good[16:32]))
+    bad16 = (good[15][0], good[15][1], good[16][2], 1)           # the 16th carries the 17th's signature
+    out.append(("17 signatures, the 16th invalid, the last valid", good[:15] + [bad16, good[16]]))
+    assert expect(*bad16[:3]) == 1
+    return out

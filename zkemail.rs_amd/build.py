@@ -70,6 +70,7 @@ def build_oracle(force: bool = False) -> str:
 CPP_EXAMPLE = os.path.join(ROOT, "tests", "cpp", "mirror_test")
 CPP_SIGSCAN = os.path.join(ROOT, "tests", "cpp", "sigscan_test")
 CPP_KEYREC = os.path.join(ROOT, "tests", "cpp", "keyrec_test")
+ED_PROBE = os.path.join(ROOT, "tests", "cpp", "ed_probe")
 
 
 def _build_cpp(exe: str, force: bool) -> str:
@@ -89,9 +90,12 @@ def _build_cpp(exe: str, force: bool) -> str:
 
 def build_cpp_example(force: bool = False) -> str:
     """The C++ host mirror (include/zkemail_core.hpp) compiled against the built library: the verify program, whose path is
-    returned, the generator program (build_cpp_sigscan) and the key-record program (build_cpp_keyrec)."""
+    returned, the generator program (build_cpp_sigscan) and the key-record program (build_cpp_keyrec); and the Ed25519 probe
+    (build_ed_probe), which needs no library."""
     build_cpp_sigscan(force)
     build_cpp_keyrec(force)
+    if os.path.exists(ED_PROBE + ".hip"):       # test infrastructure that lives in tests/: a tree whose tests/ does not carry the probe
+        build_ed_probe(force)                   # has nothing that runs it, and the three programs below do not depend on it
     return _build_cpp(CPP_EXAMPLE, force)
 
 
@@ -103,6 +107,25 @@ def build_cpp_sigscan(force: bool = False) -> str:
 def build_cpp_keyrec(force: bool = False) -> str:
     """tests/cpp/keyrec_test: decode_key_records / generate_email_inputs_from_records of the C++ mirror."""
     return _build_cpp(CPP_KEYREC, force)
+
+
+def build_ed_probe(force: bool = False) -> str:
+    """tests/cpp/ed_probe: the device routines of csrc/ed25519.hip.h, one per case of a tape (tests/ed_field_cases.py).  A stand-alone
+    HIP program compiled from the product header with the engine's target and optimisation flags; it does not link the library.
+    Called directly (tests/test_gpu_ed_field.py) it raises when the source is missing."""
+    src = ED_PROBE + ".hip"
+    if not os.path.exists(src):
+        raise RuntimeError("tests/cpp/ed_probe.hip is missing")
+    deps = [src] + [d for d in _deps(CSRC) if d.endswith(".h")] + _deps(os.path.join(ROOT, "include"))
+    if not force and not _newer(ED_PROBE, deps):
+        return ED_PROBE
+    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
+           "-Wall", "-Wno-unused-function", "-o", ED_PROBE, src]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout + r.stderr)
+        raise RuntimeError("hipcc failed building tests/cpp/ed_probe")
+    return ED_PROBE
 
 
 if __name__ == "__main__":
