@@ -6,11 +6,14 @@
 //   * CopyPool: several callers at once, odd sizes and alignments, results compared with memcpy (also under -fsanitize=thread);
 //   * zke_abi_encode into buffers of exactly the size it asks for, and one byte less;
 //   * host_batch (the host entries' batch descriptor): both shapes of one batch agree, malformed ones are refused;
+//   * deliver_scan and fold_selection (what a retired scan / key selection hands its caller): random results in the device layout
+//     into exact-size caller buffers, every capacity from none to plenty;
 //   * zke_shard_bounds, image_layout, pair_hash on edge sizes.
 // tests/test_host_sanitizers.py builds and runs it.  (The same source with -fsanitize=thread instead: clean as well, run by hand —
 // the second 40 s build is not worth a place in the suite.)
 #include "../../zkemail.rs_amd/csrc/engine.hip"
 
+#include <array>
 #include <random>
 #include <thread>
 
@@ -233,6 +236,74 @@ int main(int argc, char** argv) {
     }
     refs[0].raw_len = refs[1].raw_len = 1ull << 40;
     refused(gathered(a), "1 TiB");
+  }
+  // ---- deliver_scan: random scans in the device layout (the pinned twin is an exact-size heap vector, as every caller buffer is);
+  // sigs and sel_blob each at no capacity, one short, exact and generous
+  for (int it = 0; it < 150; it++) {
+    const uint32_t n = 1 + (uint32_t)(rng() % 9), max_sigs = 1 + (uint32_t)(rng() % 5);
+    std::vector<uint32_t> st(4 * (size_t)n), want_off(n + 1, 0);
+    for (uint32_t i = 0; i < n; i++) {
+      st[4 * i] = (uint32_t)(rng() % 3); st[4 * i + 1] = (uint32_t)rng(); st[4 * i + 3] = (uint32_t)(rng() % 4);
+      st[4 * i + 2] = rng() % 3 == 0 ? 0u : (uint32_t)(rng() % (max_sigs + 3));                 // n_signatures: also beyond max_sigs
+      want_off[i + 1] = want_off[i] + std::min(st[4 * i + 2], max_sigs);
+    }
+    const size_t total = want_off[n], used = rng() % 4 == 0 ? 0 : (size_t)(rng() % (40 * (size_t)n * max_sigs));
+    std::vector<zke_sig_info> recs((size_t)n * max_sigs);
+    for (auto& r : recs) { uint8_t* p = reinterpret_cast<uint8_t*>(&r); for (size_t k = 0; k < sizeof r; k++) p[k] = (uint8_t)rng(); }
+    std::vector<uint8_t> sel(used);
+    for (auto& c : sel) c = (uint8_t)rng();
+    for (size_t sigs_cap : {(size_t)0, total ? total - 1 : 0, total, total + 3})
+      for (size_t blob_cap : {(size_t)0, used ? used - 1 : 0, used, used + 9}) {
+        ScanBufs b;
+        b.L = scan_layout(n, max_sigs, std::min<size_t>(blob_cap, (size_t)n * max_sigs * ZKE_MAX_TAGBUF));      // as submit_host sizes it
+        std::vector<uint8_t> twin(b.L.total, 0xEE);
+        const uint32_t used32 = (uint32_t)used;
+        memcpy(twin.data(), &used32, 4);
+        memcpy(twin.data() + b.L.status, st.data(), st.size() * 4);
+        memcpy(twin.data() + b.L.recs, recs.data(), recs.size() * sizeof(zke_sig_info));
+        if (std::min(used, b.L.blob_cap)) memcpy(twin.data() + b.L.blob, sel.data(), std::min(used, b.L.blob_cap));
+        b.h_out.p = twin.data(); b.h_out.cap = twin.size();
+        std::vector<uint32_t> status(4 * (size_t)n, 7u), off(n + 1, 7u);
+        std::vector<zke_sig_info> sigs(sigs_cap);
+        std::vector<uint8_t> blob(blob_cap, 0xCC);
+        zke_sig_scan o{status.data(), status.size(), off.data(), off.size(), sigs_cap ? sigs.data() : nullptr, sigs_cap,
+                       blob_cap ? blob.data() : nullptr, blob_cap, 4 * (size_t)n, (size_t)n + 1, 99, 99, 99};
+        zke_engine eng;
+        const int r = deliver_scan(&eng, b, &o);
+        b.h_out.p = nullptr; b.h_out.cap = 0;
+        const bool sigs_short = sigs_cap < total, blob_short = blob_cap < used;
+        bool ok = r == (sigs_short || blob_short ? ZKE_E_NOMEM : 0) && o.sigs_need == total && o.sel_blob_need == used && off == want_off &&
+                  status == st && o.n_sigs == (sigs_short ? 0 : total);
+        for (uint32_t i = 0; ok && !sigs_short && i < n; i++)
+          ok = want_off[i + 1] == want_off[i] ||
+               !memcmp(sigs.data() + want_off[i], recs.data() + (size_t)i * max_sigs, (want_off[i + 1] - want_off[i]) * sizeof(zke_sig_info));
+        if (ok && !r && used) ok = !memcmp(blob.data(), sel.data(), used);
+        if (!ok) { fprintf(stderr, "deliver_scan: n %u max_sigs %u sigs %zu/%zu blob %zu/%zu -> %d\n", n, max_sigs, sigs_cap, total, blob_cap, used, r); return 1; }
+        cases++;
+      }
+  }
+  // ---- fold_selection against its rule restated: the first ZKE_OK record of a row wins, flagged when a ZKE_UNSUPPORTED one precedes
+  // it; no ZKE_OK: the row's last record, ZKE_SEL_NONE; an empty row: a zeroed record, ZKE_DKIM_NOT_PASS / ZKE_D_NEUTRAL, ZKE_SEL_NONE
+  for (int it = 0; it < 400; it++) {
+    const uint32_t n = (uint32_t)(rng() % 12);
+    std::vector<uint32_t> off(n + 1, 0);
+    for (uint32_t i = 0; i < n; i++) off[i + 1] = off[i] + (rng() % 3 == 0 ? 0u : (uint32_t)(rng() % 5));
+    std::vector<zke_result> R(off[n]), out(n), want(n);
+    std::vector<uint32_t> chosen(n, 7u), want_chosen(n);
+    for (auto& x : R) {
+      uint8_t* p = reinterpret_cast<uint8_t*>(&x); for (size_t k = 0; k < sizeof x; k++) p[k] = (uint8_t)rng();
+      x.status = std::array<uint32_t, 4>{ZKE_OK, ZKE_UNSUPPORTED, ZKE_DKIM_NOT_PASS, ZKE_KEY_DECODE_FAIL}[rng() % 4];
+    }
+    for (uint32_t i = 0; i < n; i++) {
+      uint32_t k = off[i], flag = 0;
+      for (; k < off[i + 1] && R[k].status != ZKE_OK; k++) if (R[k].status == ZKE_UNSUPPORTED) flag = ZKE_SEL_AFTER_UNSUPPORTED;
+      want_chosen[i] = k < off[i + 1] ? ((k - off[i]) | flag) : ZKE_SEL_NONE;
+      if (off[i] == off[i + 1]) { memset(&want[i], 0, sizeof want[i]); want[i].status = ZKE_DKIM_NOT_PASS; want[i].detail = ZKE_D_NEUTRAL; }
+      else want[i] = R[k < off[i + 1] ? k : off[i + 1] - 1];
+    }
+    fold_selection(R.data(), off, out.data(), chosen.data());
+    if (chosen != want_chosen || (n && memcmp(out.data(), want.data(), n * sizeof(zke_result)))) { fprintf(stderr, "fold_selection differs from its rule\n"); return 1; }
+    cases++;
   }
   // ---- small pure functions on edge sizes
   {

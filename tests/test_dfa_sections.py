@@ -154,7 +154,7 @@ def test_unregister_and_registry_cap(oracle):
 def test_per_email_regex_calls_from_four_threads_through_a_full_registry():
     """96 distinct pairs through a registry of 64 from four threads at once: registrations evict each other's pairs all the
     time and ids change hands, yet every call must be checked against ITS pattern — the pairs of a call in progress are pinned
-    (csrc/pipeline.hip.h, dfa_register_impl / dfa_unpin).  Pattern k matches one six-byte window of the subject and the
+    (csrc/registry.hip.h, dfa_register_impl / dfa_unpin).  Pattern k matches one six-byte window of the subject and the
     call's capture is that window: under any other pattern of the set the capture is contained in no match (regex.rs:41-47)
     and the call panics."""
     import threading

@@ -209,7 +209,7 @@ def test_length_buckets_across_slot_reuse(oracle):
 
 
 def test_host_offsets_are_checked(oracle):
-    """Offset arrays in host memory are validated before anything is staged (csrc/pipeline.hip.h, host_batch): a length
+    """Offset arrays in host memory are validated before anything is staged (csrc/host_entry.hip.h, host_batch): a length
     that comes out negative is ZKE_E_ARG, not a copy outside the blob; the engine stays usable."""
     import zkemail_rs_amd as z
     eng = z.Engine()
@@ -345,3 +345,61 @@ def test_engine_lifecycle_returns_its_memory(oracle):
     eng.close()
     for _, rec in pend:
         assert_records_equal(rec, want, None, "delivered by zke_engine_destroy")
+
+
+def test_unwaited_batches_with_short_buffers_are_retired_by_the_next_batch():
+    """One slot; a scan, a key-record decode and an extraction are submitted asynchronously, each with its variable-size buffer too
+    small (sel_blob, keys, cap_blob of capacity 0), and never waited for.  The slot's next batch retires each: that batch is not
+    disturbed (it returns 0, its record is right), the unwaited batch's fixed-size outputs are there with the exact *_need, and
+    the shortfall — which had nobody to be told to — does not come back from a later wait on the old ticket."""
+    import base64
+    import re
+    import zkemail_rs_amd as z
+    from zkemail_rs_amd.engine import _KeyrecBuffers, _ScanBuffers
+    c = [x for x in cases.build_cases() if x.status == A.ZKE_OK][0]
+    key = c.email.public_key.key
+    subject = re.findall(rb"subject:([^\r\n]+)\r\n", c.inter["canon_header"])
+    assert len(subject) == 1
+    eng = z.Engine(slots=1)
+    try:
+        def next_batch_retires(ticket):
+            got = eng.verify_emails([c.email])
+            assert int(got[0]["status"]) == c.status == A.ZKE_OK
+            assert (bytes(got[0]["from_domain_hash"]), bytes(got[0]["public_key_hash"])) == cases.expected_witness(c)
+            assert bytes(got[0]["body_hash"]) == c.inter["body_hash"] and bytes(got[0]["header_hash"]) == c.inter["header_hash"]
+            assert eng.lib.zke_batch_wait(eng.h, ticket) == 0
+
+        # a scan whose selector blob holds nothing
+        t, sb = eng.scan_signatures_async([c.email.raw_email], [c.email.from_domain], 8, blob_bytes=0)
+        next_batch_retires(t)
+        assert [int(x) for x in sb.status[0]] == [A.ZKE_OK, 0, 1, 1] and [int(x) for x in sb.sig_off] == [0, 1]
+        assert (int(sb.c.sigs_need), int(sb.c.n_sigs), int(sb.c.sel_blob_need)) == (1, 1, len("sel1"))
+        assert (int(sb.sigs[0]["code"]), int(sb.sigs[0]["sel_len"])) == (0, len("sel1"))
+        # a decode of the e-mail's key record whose key buffer holds nothing
+        kb = _KeyrecBuffers([b"v=DKIM1; k=rsa; p=" + base64.b64encode(key)], 0)
+        tk = C.c_uint64()
+        assert eng.lib.zke_decode_key_records_async(eng.h, kb.arr, kb.m, A.KEYREC_DNS, C.byref(kb.c), C.byref(tk)) == 0
+        next_batch_retires(tk.value)
+        assert (int(kb.c.infos_need), int(kb.c.keys_need)) == (1, len(key))
+        assert [int(kb.infos[0][f]) for f in ("code", "key_type", "key_off", "key_len")] == [0, A.KEY_RSA, 0, len(key)]
+        # an extraction of one header pattern's one group whose string blob holds nothing
+        _, dfa_id, prog_id = eng.compile_pattern(synth.HEADER_PATTERNS[1][0], False)
+        group = np.array([1], np.uint32)
+        part = (A.zke_capture_part * 1)()
+        part[0].dfa_id, part[0].prog_id, part[0].n_groups, part[0].groups = dfa_id, prog_id, 1, group.ctypes.data
+        refs = A.EmailRefs([c.email])
+        out = np.zeros(1, dtype=A.RESULT_DTYPE)
+        spans, flags, cap_off, cap_str_off = np.zeros(2, np.uint32), np.full(1, 9, np.uint8), np.full(2, 9, np.uint32), np.full(2, 9, np.uint32)
+        o = A.zke_capture_out()
+        o.spans, o.spans_cap, o.flags, o.flags_cap = spans.ctypes.data, 2, flags.ctypes.data, 1
+        o.cap_off, o.cap_off_cap, o.cap_str_off, o.cap_str_off_cap = cap_off.ctypes.data, 2, cap_str_off.ctypes.data, 2
+        o.cap_blob, o.cap_blob_cap = None, 0
+        tc = C.c_uint64()
+        assert eng.lib.zke_extract_captures_async(eng.h, refs.arr, 1, part, 1, part, 0, out.ctypes.data, C.byref(o), C.byref(tc)) == 0
+        next_batch_retires(tc.value)
+        assert int(out[0]["status"]) == A.ZKE_OK and bytes(out[0]["header_hash"]) == c.inter["header_hash"]
+        assert (int(o.n_strings), int(o.cap_blob_need)) == (1, len(subject[0]))
+        assert [int(x) for x in cap_off] == [0, 1] and [int(x) for x in cap_str_off] == [0, len(subject[0])] and int(flags[0]) == 0
+        assert int(spans[1]) - int(spans[0]) == len(subject[0])
+    finally:
+        eng.close()

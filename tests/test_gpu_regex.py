@@ -62,7 +62,7 @@ def test_regex_status_paths_parity(engine, oracle):
 
 
 def test_blobs_written_by_regex_automata_itself_deserialise(engine, oracle):
-    """The engine's parse_dfa_blob (dense::DFA::from_bytes restated, csrc/pipeline.hip.h) on the two dense DFAs that
+    """The engine's parse_dfa_blob (dense::DFA::from_bytes restated, csrc/dfa_registry.hip.h) on the two dense DFAs that
     regex-automata itself serialised (tests/golden/regex_automata_ws_anchored_*.dfa, tests/test_regex_automata_blobs.py):
     they register as valid — an e-mail using them does NOT report ZKE_DFA_DECODE_FAIL (the pair is anchored-only, so the
     search itself stops at the start state; engine and oracle agree on what that is) — while the same bytes with three flag

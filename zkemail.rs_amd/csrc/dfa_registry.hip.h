@@ -1,5 +1,5 @@
 // dfa_registry.hip.h — host side of zke_dfa_register: the regex-automata 0.4.9 dense-DFA wire format (little-endian,
-// version 2) restated as dense::DFA::from_bytes reads it, and the engine's registry of parsed pairs.
+// version 2) restated as dense::DFA::from_bytes reads it, and the entry types of the engine's registries (registry.hip.h).
 // Replaces the per-e-mail from_bytes of core/src/regex.rs:32-33.  Included by engine.hip (single translation unit).
 #pragma once
 

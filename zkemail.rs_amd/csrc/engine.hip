@@ -137,7 +137,7 @@ struct zke_engine {
 #ifndef ZKE_COPY_STREAMS
 #define ZKE_COPY_STREAMS 2
 #endif
-  hipStream_t copy_stream[ZKE_COPY_STREAMS]{};   // host batches' input images cross PCIe on these streams, in turn (pipeline.hip.h).  Created
+  hipStream_t copy_stream[ZKE_COPY_STREAMS]{};   // host batches' input images cross PCIe on these streams, in turn (host_entry.hip.h).  Created
                                                  // with the host entry's first batch, not with the engine: every stream takes part in HIP's
                                                  // mapping of streams onto hardware queues, and an engine that only ever sees device-resident
                                                  // batches must not pay for two it never uses (22 slots + 2: 23 M e-mails/s instead of 31 M)
@@ -320,6 +320,8 @@ int set_kernel_attrs(zke_engine* e) {
 }  // namespace
 
 #include "pipeline.hip.h"
+#include "registry.hip.h"
+#include "host_entry.hip.h"
 #include "wire.hip.h"
 
 extern "C" {
@@ -684,6 +686,72 @@ int zke_ed25519_verify_batch(zke_engine* e, const uint8_t* keys, const uint8_t* 
   if (he != hipSuccess) return fail(e, ZKE_E_DEVICE, "ed25519 batch", he);
   if (hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "ed25519 batch sync", hs);
   return 0;
+}
+
+// ---- capture extraction over haystacks of the caller's (registry.hip.h; checks and delivery: host_entry.hip.h)
+int zke_capture_batch(zke_engine* e, uint32_t dfa_id, uint32_t prog_id, const uint32_t* groups, uint32_t n_groups,
+                      const uint8_t* hay_blob, const uint64_t* hay_off, uint32_t n, uint32_t* matches, zke_capture_out* caps) {
+  static const char who[] = "zke_capture_batch";
+  if (!e) return ZKE_E_ARG;
+  if (!caps || (n && (!hay_off || !matches)) || (n && hay_off[n] > hay_off[0] && !hay_blob)) return arg_error(who, "null pointer");
+  if (n && (!rising(hay_off, n) || hay_off[n] - hay_off[0] > (1ull << 32))) return arg_error(who, "offset array is not non-decreasing, or the haystacks exceed 4 GiB");
+  for (uint32_t i = 0; i < n; i++) if (hay_off[i + 1] - hay_off[i] >= (1ull << 31)) return arg_error(who, "haystack of 2 GiB or more");
+  CaptureReq q;
+  q.P = 1; q.n_header_parts = 1; q.out = caps;
+  if (int r = capture_part_shape(q, 0, prog_id, groups, n_groups, who)) return r;
+  if (int r = check_capture_out(caps, n, 1, q.G, who)) return r;
+  if (n == 0) return 0;
+  std::shared_lock<std::shared_mutex> sh(e->big);      // from the registry lookups to the last launch: no table is freed meanwhile
+  std::lock_guard<std::mutex> g(e->misc_mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  capture_resolve(e, q);
+  PartInfo pi{};
+  {
+    std::shared_lock<std::shared_mutex> rl(e->reg_mu);
+    const RegisteredDfa* rd = dfa_id < e->dfas.size() ? e->dfas[dfa_id] : nullptr;
+    if (rd) { pi.detail = rd->detail; pi.dev = rd->valid ? rd->dev.as<RegexDev>() : nullptr; }
+  }
+  // the building blocks run in buffers of their own on slot 0's stream
+  const uint64_t base0 = hay_off[0], total = hay_off[n] - base0;
+  CapBufs tmp;
+  DevBuf dhay, doff, dparts;
+  std::vector<uint8_t> fixed;
+  int r = 0;
+  hipError_t he = hipSuccess;
+  tmp.L = cap_layout(n, 1, q.G, caps->cap_blob_cap);
+  const CapLayout& L = tmp.L;
+  hipStream_t s = e->stream;
+  auto done = [&](int rc) { dhay.release(); doff.release(); dparts.release(); tmp.release(); return rc; };
+  if ((r = dhay.ensure((size_t)total + 64)) || (r = doff.ensure((size_t)(n + 1) * 8)) || (r = dparts.ensure((size_t)n * sizeof(PartRes))) ||
+      (r = ensure_capture_buffers(e, tmp, n, 1, q.G, caps->cap_blob_cap, q.needs_work)))
+    return done(fail(e, r, "zke_capture_batch: allocation"));
+  std::vector<uint64_t> rel(n + 1);
+  for (uint32_t i = 0; i <= n; i++) rel[i] = hay_off[i] - base0;
+  if (total) he = hipMemcpyAsync(dhay.p, hay_blob + base0, (size_t)total, hipMemcpyHostToDevice, s);
+  if (he == hipSuccess) he = hipMemsetAsync(dhay.as<uint8_t>() + total, 0, 64, s);         // the DFA walk loads 16 bytes at a time
+  if (he == hipSuccess) he = hipMemcpyAsync(doff.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s);
+  if (he != hipSuccess) { (void)hipStreamSynchronize(s); return done(fail(e, ZKE_E_DEVICE, "zke_capture_batch: copy", he)); }
+  CapFindArgs fa{};
+  fa.d.re = pi.dev; fa.d.P = 1; fa.d.out = dparts.as<PartRes>(); fa.d.idle = 0xFFFFFFFFu; fa.d.decode_detail = pi.detail;
+  fa.hay_blob = dhay.as<uint8_t>(); fa.hay_off = doff.as<uint64_t>(); fa.n = n;
+  hipLaunchKernelGGL(capture_find_kernel, dim3((n + 255) / 256), dim3(256), 1024, s, fa);
+  r = launch_capture(e, tmp, q, n, true, DfaArgs{}, fa.hay_blob, fa.hay_off, dparts.as<PartRes>(), nullptr, s);
+  std::vector<PartRes> prs(n);
+  if (!r) {
+    he = hipMemcpyAsync(tmp.h_cap.p, tmp.cap.p, L.fixed_end, hipMemcpyDeviceToHost, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(prs.data(), dparts.p, (size_t)n * sizeof(PartRes), hipMemcpyDeviceToHost, s);
+  }
+  const hipError_t hs = hipStreamSynchronize(s);
+  if (r) return done(r);
+  if (he != hipSuccess || hs != hipSuccess) return done(fail(e, ZKE_E_DEVICE, "zke_capture_batch", he != hipSuccess ? he : hs));
+  const uint32_t* codes = reinterpret_cast<const uint32_t*>(tmp.h_cap.as<uint8_t>() + L.codes);
+  for (uint32_t i = 0; i < n; i++) {
+    const PartRes& pr = prs[i];
+    const bool undecodable = pr.code == PART_DECODE_FAIL;
+    matches[4 * i] = undecodable ? pr.count : (pr.code ? pr.code : codes[i]);
+    matches[4 * i + 1] = undecodable ? 0 : pr.count; matches[4 * i + 2] = pr.start; matches[4 * i + 3] = pr.end;
+  }
+  return done(deliver_captures(e, tmp, caps, s));
 }
 
 }  // extern "C"

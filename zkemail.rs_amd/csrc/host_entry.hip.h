@@ -1,0 +1,793 @@
+// host_entry.hip.h — the entries whose batch lies in host memory: the batch descriptor and its checks, the packed image into a
+// slot (host_stage.hip.h), upload, launches (pipeline.hip.h), delivery into the caller's buffers.  Stands for the reference's
+// callers, `&[Email]` into verify_email / verify_email_with_regex (core/src/circuits.rs:9-68), and for what comes before a key is
+// known: scan, key records, selection, captures.  Included by engine.hip behind pipeline.hip.h and registry.hip.h (one translation unit).
+#pragma once
+
+#ifndef ZKE_HOST_COPY_STREAM
+#define ZKE_HOST_COPY_STREAM 1     // 0: every input image is copied on its slot's own stream
+#endif
+
+namespace {
+
+inline uint64_t host_scratch_off(const uint64_t* raw_off, uint32_t i) { return scratch_offset(raw_off[i] - raw_off[0], i); }
+
+// Host-entry buffers of one slot: the packed input image (pinned and in HBM) and the records (HBM and pinned).
+int ensure_host_buffers(zke_engine* e, Slot& w, size_t image_bytes, uint32_t n) {
+  int r = 0;
+  if ((r = w.h_image.ensure(image_bytes)) || (r = w.d_image.ensure(image_bytes)) ||
+      (r = w.h_results.ensure((size_t)n * sizeof(zke_result))) || (r = w.d_results.ensure((size_t)n * sizeof(zke_result))))
+    return fail(e, r, "host-entry staging allocation");
+  return 0;
+}
+
+// ---- signature scan and key selection (sigscan.hip.h; include/zkemail_amd.h)
+struct ScanReq { uint32_t max_sigs; zke_sig_scan* out; };
+struct SelectReq { const uint32_t* cand_off; uint32_t n; zke_result* out; uint32_t* chosen; };
+// ---- key records (keyrec.hip.h).  Alone: the batch's "raw e-mails" are the records, keyrec_kernel runs instead of the verify
+// pipeline.  With a SelectReq: the image's key section holds the records, and the decode + pack launches in front of the front end
+// replace it by the decoded keys (zke_select_keys_from_records).
+struct KeyrecReq { uint32_t mode; zke_keyrec_out* out; };
+
+int ensure_keyrec_buffers(zke_engine* e, KeyrecBufs& b, uint32_t m, size_t rec_total, bool pack) {
+  const KeyrecLayout L = keyrec_layout(m, rec_total);
+  int r = 0;
+  if ((r = b.out.ensure(L.total)) || (r = b.h_out.ensure(L.total)) || (pack && (r = b.pack.ensure(L.p_total))))
+    return fail(e, r, "key-record buffer allocation");
+  b.L = L;
+  return 0;
+}
+
+// A slot's scan buffers for n e-mails with max_sigs record slots each and blob_cap bytes of selectors.  Grow only: the first scan
+// of a shape allocates, a later one of the same shape does not.
+int ensure_scan_buffers(zke_engine* e, ScanBufs& b, uint32_t n, uint32_t max_sigs, size_t blob_cap) {
+  const ScanLayout L = scan_layout(n, max_sigs, blob_cap);
+  int r = 0;
+  if ((r = b.out.ensure(L.total)) || (r = b.h_out.ensure(L.total)) || (r = b.ovf.ensure((size_t)n * HDR_OVF_BYTES)))
+    return fail(e, r, "signature-scan buffer allocation");
+  b.L = L;
+  return 0;
+}
+
+// An extraction's tables from the slot's pinned twin (and the blob from HBM) into the caller's zke_capture_out.  Returns
+// ZKE_E_NOMEM when the caller's cap_blob is too small for the strings (everything else is delivered; cap_blob_need says how much).
+int deliver_captures(zke_engine* e, CapBufs& b, zke_capture_out* o, hipStream_t s) {
+  const CapLayout& L = b.L;
+  const uint8_t* hp = b.h_cap.as<uint8_t>();
+  const uint64_t* hdr = reinterpret_cast<const uint64_t*>(hp + L.hdr);
+  const size_t strings = (size_t)hdr[0], bytes = (size_t)hdr[1];
+  memcpy(o->spans, hp + L.spans, o->spans_need * 4);
+  memcpy(o->flags, hp + L.flags, o->flags_need);
+  memcpy(o->cap_off, hp + L.cap_off, o->cap_off_need * 4);
+  memcpy(o->cap_str_off, hp + L.cap_str_off, (strings + 1) * 4);
+  o->n_strings = strings;
+  o->cap_blob_need = bytes;
+  const size_t take = std::min(bytes, L.blob_cap);
+  if (take) {
+    HIPCHK(e, hipMemcpyAsync(o->cap_blob, b.cap.as<uint8_t>() + L.blob, take, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+  }
+  if (bytes > L.blob_cap) return fail(e, ZKE_E_NOMEM, "capture extraction: cap_blob is smaller than the strings (zke_capture_out.cap_blob_need)");
+  return 0;
+}
+
+// A scan from the slot's pinned twin into the caller's zke_sig_scan: statuses, the CSR over the record slots in use (the
+// compaction: one memcpy per e-mail), the selector bytes.  ZKE_E_NOMEM when sigs or sel_blob is too small (*_need says how much).
+int deliver_scan(zke_engine* e, const ScanBufs& b, zke_sig_scan* o) {
+  const ScanLayout& S = b.L;
+  const uint8_t* hp = b.h_out.as<uint8_t>();
+  const uint32_t* st = reinterpret_cast<const uint32_t*>(hp + S.status);
+  const zke_sig_info* recs = reinterpret_cast<const zke_sig_info*>(hp + S.recs);
+  const size_t used = *reinterpret_cast<const uint32_t*>(hp);
+  memcpy(o->scan_status, st, (size_t)S.n * 16);
+  size_t total = 0;
+  for (uint32_t i = 0; i < S.n; i++) { o->sig_off[i] = (uint32_t)total; total += std::min(st[4 * (size_t)i + 2], S.max_sigs); }
+  o->sig_off[S.n] = (uint32_t)total;
+  o->sigs_need = total; o->sel_blob_need = used; o->n_sigs = 0;
+  if (total > o->sigs_cap) return fail(e, ZKE_E_NOMEM, "signature scan: sigs is smaller than the records (zke_sig_scan.sigs_need)");
+  for (uint32_t i = 0; i < S.n; i++)
+    if (const uint32_t c = o->sig_off[i + 1] - o->sig_off[i]) memcpy(o->sigs + o->sig_off[i], recs + (size_t)i * S.max_sigs, (size_t)c * sizeof(zke_sig_info));
+  o->n_sigs = total;
+  if (used > S.blob_cap) return fail(e, ZKE_E_NOMEM, "signature scan: sel_blob is smaller than the selectors (zke_sig_scan.sel_blob_need)");
+  if (used) memcpy(o->sel_blob, hp + S.blob, used);
+  return 0;
+}
+
+// A decode from the slot's pinned twin into the caller's zke_keyrec_out: the infos with key_off rewritten to the packed offsets,
+// the key bytes compacted (one memcpy per key).  ZKE_E_NOMEM when keys is too small (keys_need says how much).
+int deliver_keyrec(zke_engine* e, const KeyrecBufs& b, zke_keyrec_out* o) {
+  const KeyrecLayout& K = b.L;
+  const uint8_t* hp = b.h_out.as<uint8_t>();
+  const zke_key_info* src = reinterpret_cast<const zke_key_info*>(hp);
+  size_t total = 0;
+  for (uint32_t i = 0; i < K.m; i++) {
+    zke_key_info f = src[i];
+    if (f.code) f.key_len = 0;
+    f.key_off = (uint32_t)total;
+    total += f.key_len;
+    o->infos[i] = f;
+  }
+  o->keys_need = total;
+  if (total > o->keys_cap) return fail(e, ZKE_E_NOMEM, "key records: keys is smaller than the decoded keys (zke_keyrec_out.keys_need)");
+  for (uint32_t i = 0; i < K.m; i++)
+    if (o->infos[i].key_len) memcpy(o->keys + o->infos[i].key_off, hp + K.keys + src[i].key_off, o->infos[i].key_len);
+  return 0;
+}
+
+// A key selection's fold: the records of the (e-mail, candidate) pairs are in the pinned buffer; per e-mail the first ZKE_OK.
+void fold_selection(const zke_result* R, const std::vector<uint32_t>& off, zke_result* out, uint32_t* chosen) {
+  for (size_t i = 0; i + 1 < off.size(); i++) {
+    const uint32_t a = off[i], b = off[i + 1];
+    if (a == b) {
+      memset(&out[i], 0, sizeof(zke_result));
+      out[i].status = ZKE_DKIM_NOT_PASS; out[i].detail = ZKE_D_NEUTRAL;
+      chosen[i] = ZKE_SEL_NONE;
+      continue;
+    }
+    uint32_t pick = ZKE_SEL_NONE, flag = 0;
+    for (uint32_t k = a; k < b; k++) {
+      if (R[k].status == ZKE_OK) { pick = k - a; break; }
+      if (R[k].status == ZKE_UNSUPPORTED) flag = ZKE_SEL_AFTER_UNSUPPORTED;
+    }
+    out[i] = R[pick == ZKE_SEL_NONE ? b - 1 : a + pick];
+    chosen[i] = pick == ZKE_SEL_NONE ? ZKE_SEL_NONE : (pick | flag);
+  }
+}
+
+// Deliver a host batch that was enqueued in this slot and not waited for yet: wait for its D2H, copy the records from the
+// pinned buffer to the caller's `out`.  Caller holds the slot's lock.
+// `cap_rc` (zke_batch_wait, the synchronous entries): where an extraction's or a scan's shortfall is reported; a slot that retires
+// a batch nobody waited for has nobody to tell.
+int retire_host(zke_engine* e, Slot& w, int* cap_rc = nullptr) {
+  if (w.host_retired == w.host_gen) return 0;
+  w.host_retired = w.host_gen;                       // whatever happens below, the batch is no longer pending
+  zke_capture_out* pending_caps = w.cap_out;
+  w.cap_out = nullptr;
+  zke_sig_scan* pending_scan = w.scan_out;
+  w.scan_out = nullptr;
+  zke_keyrec_out* pending_keyrec = w.keyrec_out;
+  w.keyrec_out = nullptr;
+  HIPCHK(e, hipEventSynchronize(w.host_done));
+  if (w.host_out && w.host_n) memcpy(w.host_out, w.h_results.p, (size_t)w.host_n * sizeof(zke_result));
+  w.host_out = nullptr;
+  if (!w.sel_off.empty()) {
+    fold_selection(w.h_results.as<zke_result>(), w.sel_off, w.sel_out, w.sel_chosen);
+    w.sel_off.clear();
+  }
+  if (pending_scan) {
+    const std::string keep = g_err;
+    const int r = deliver_scan(e, w.sb, pending_scan);
+    if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
+    else if (r) return r;
+  }
+  if (pending_keyrec) {
+    const std::string keep = g_err;
+    const int r = deliver_keyrec(e, w.kb, pending_keyrec);
+    if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
+    else if (r) return r;
+  }
+  if (pending_caps) {
+    const std::string keep = g_err;
+    const int r = deliver_captures(e, w.cb, pending_caps, w.stream);
+    if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
+    else if (r) return r;
+  }
+  return 0;
+}
+
+int arg_error(const char* who, const char* what) { g_err = std::string(who) + ": " + what; return ZKE_E_ARG; }
+template <class T> bool rising(const T* off, size_t cnt) { uint64_t bad = 0; for (size_t i = 0; i < cnt; i++) bad |= (uint64_t)(off[i + 1] < off[i]); return !bad; }
+// The part-id lists of a batch (host arrays in every entry) ...
+int check_part_ids(const zke_batch& b, const char* who) {
+  return b.with_regex && ((b.n_header_parts && !b.header_part_ids) || (b.n_body_parts && !b.body_part_ids)) ? arg_error(who, "part-id list is null") : 0;
+}
+// ... and with them the pointers the pipeline reads (device memory; with `host`, the packed host entry's: it also copies the domain
+// and key blobs)
+int check_batch_pointers(const zke_batch* in, const void* out, bool host, const char* who) {
+  if (!in || (in->n && (!out || !in->raw_blob || !in->raw_off || !in->domain_off || !in->key_off || !in->key_type ||
+                        (host && (!in->domain_blob || !in->key_blob)))))
+    return arg_error(who, "null pointer");
+  return check_part_ids(*in, who);
+}
+
+// A host batch, checked and measured for the staging image by host_batch(): packed (zke_batch) or gathered (zke_email_ref[n]).
+struct HostBatch {
+  zke_batch b{};                        // n, the regex section, (packed) the caller's blobs and offsets; capture tables only if any
+  const zke_email_ref* refs = nullptr;  // the gathered shape's e-mails (nullptr: packed)
+  CaptureReq* cap = nullptr;            // zke_extract_captures: the extraction that rides on this (regex) batch
+  const ScanReq* scan = nullptr;        // zke_scan_signatures: sigscan_kernel runs instead of the verify pipeline
+  const SelectReq* sel = nullptr;       // zke_select_keys: the batch's entries are (e-mail, candidate key) pairs, folded on delivery
+  const KeyrecReq* keyrec = nullptr;    // key records: decoded instead of the verify pipeline, or (with sel) in front of it
+  uint64_t raw_total = 0, dom_total = 0, key_total = 0, raw_base = 0, dom_base = 0, key_base = 0;   // blob bytes; off[0] of packed offsets
+  size_t cap_words = 0, cap_strs = 0, cap_bytes = 0;      // entries of cap_off and cap_str_off, bytes of cap_blob (0: no tables)
+  ImageLayout L{};
+};
+// Both shapes.  Capture tables: a cap_off whose last entry is 0 holds no string and is no table (cap_str_off, cap_blob unread).
+int measure_host_batch(HostBatch& d, const char* who) {
+  zke_batch& b = d.b;
+  if (d.raw_total > (1ull << 40)) return arg_error(who, "raw e-mails beyond 1 TiB");
+  const size_t NP = b.with_regex ? (size_t)b.n * (b.n_header_parts + b.n_body_parts) : 0;
+  if (NP && b.cap_off) {
+    if (!rising(b.cap_off, NP)) return arg_error(who, "capture offset array is not non-decreasing");
+    if (const uint32_t strs = b.cap_off[NP]) {
+      if (!b.cap_str_off || !b.cap_blob) return arg_error(who, "capture strings without cap_str_off or cap_blob");
+      if (!rising(b.cap_str_off, strs)) return arg_error(who, "capture offset array is not non-decreasing");
+      d.cap_words = NP + 1; d.cap_strs = (size_t)strs + 1; d.cap_bytes = b.cap_str_off[strs];
+    }
+  }
+  if (!d.cap_words) b.cap_off = nullptr, b.cap_str_off = nullptr, b.cap_blob = nullptr;
+  d.L = image_layout(b.n, d.raw_total, d.dom_total, d.key_total, d.cap_words, d.cap_strs, d.cap_bytes);
+  return 0;
+}
+// The packed shape.  Its offsets are in host memory here, so they are checked (three passes over n + 1 words): a negative length
+// would send the staging copy, then the kernels, outside the blobs.  (In device memory they are trusted like the pointers.)
+int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_batch* in) {
+  if (int r = check_batch_pointers(in, out, true, who)) return r;
+  d = HostBatch{*in};
+  if (const uint32_t n = in->n) {
+    if (!(rising(in->raw_off, n) && rising(in->domain_off, n) && rising(in->key_off, n))) return arg_error(who, "offset array is not non-decreasing");
+    d.raw_base = in->raw_off[0]; d.dom_base = in->domain_off[0]; d.key_base = in->key_off[0];
+    d.raw_total = in->raw_off[n] - d.raw_base; d.dom_total = in->domain_off[n] - d.dom_base; d.key_total = in->key_off[n] - d.key_base;
+  }
+  return measure_host_batch(d, who);
+}
+// The gathered shape: the e-mails one by one, lists == nullptr for verify_email.
+int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_email_ref* refs, uint32_t n, const zke_regex_lists* lists) {
+  if (n && (!refs || !out)) return arg_error(who, "null pointer");
+  d = HostBatch{zke_batch{n}, refs};
+  if (lists) {
+    d.b.with_regex = 1; d.b.n_header_parts = lists->n_header_parts; d.b.header_part_ids = lists->header_part_ids;
+    d.b.n_body_parts = lists->n_body_parts; d.b.body_part_ids = lists->body_part_ids;
+    d.b.cap_off = lists->cap_off; d.b.cap_str_off = lists->cap_str_off; d.b.cap_blob = lists->cap_blob;
+  }
+  if (int r = check_part_ids(d.b, who)) return r;
+  for (uint32_t i = 0; i < n; i++) {
+    const zke_email_ref& m = refs[i];
+    if ((m.raw_len && !m.raw) || (m.domain_len && !m.from_domain) || (m.key_len && !m.key)) return arg_error(who, "null buffer with a length");
+    if (m.raw_len > (1ull << 40) || m.domain_len > (1ull << 32) || m.key_len > (1ull << 32)) return arg_error(who, "implausible length");
+    d.raw_total += m.raw_len; d.dom_total += m.domain_len; d.key_total += m.key_len;
+  }
+  return measure_host_batch(d, who);
+}
+
+// One host batch into slot w (caller holds its lock): pack -> one H2D -> the launches -> one D2H -> event.
+int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, bool want_em, bool want_clean) {
+  const uint32_t n = d.b.n;
+  const ImageLayout& L = d.L;
+  if (int r = retire_host(e, w)) return r;           // the pinned buffers are about to be overwritten
+  if (int r = ensure_host_buffers(e, w, L.total, n)) return r;      // (a no-op: submit_host_batch has grown every slot's staging)
+  if (d.cap) {
+    if (int r = ensure_capture_buffers(e, w.cb, n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap, d.cap->needs_work)) return r;
+    w.cb.L = cap_layout(n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap);
+  }
+  if (d.scan) {      // (a selector is at most ZKE_MAX_TAGBUF bytes: a larger blob than that per record slot is never used)
+    const size_t blob = std::min<size_t>(d.scan->out->sel_blob_cap, (size_t)n * d.scan->max_sigs * ZKE_MAX_TAGBUF);
+    if (int r = ensure_scan_buffers(e, w.sb, n, d.scan->max_sigs, blob)) return r;
+  }
+  if (d.keyrec)
+    if (int r = ensure_keyrec_buffers(e, w.kb, n, (size_t)(d.sel ? d.key_total : d.raw_total), d.sel != nullptr)) return r;
+  uint8_t* hp = w.h_image.as<uint8_t>();
+  if (d.refs) {
+    // the CSR arrays are written where they will be read from (prefix sums over the lengths), and every e-mail's three buffers
+    // go to their places in the blobs — the pool takes runs of consecutive e-mails (CopyPool::gather)
+    uint64_t* ro = reinterpret_cast<uint64_t*>(hp + L.raw_off), *dofs = reinterpret_cast<uint64_t*>(hp + L.dom_off), *ko = reinterpret_cast<uint64_t*>(hp + L.key_off);
+    uint8_t* kt = hp + L.key_type, *xn = hp + L.ext_null;
+    w.gather.resize((size_t)3 * n);
+    uint64_t r = 0, dd = 0, k = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      const zke_email_ref& m = d.refs[i];
+      ro[i] = r; dofs[i] = dd; ko[i] = k;
+      kt[i] = (uint8_t)(m.key_type > ZKE_KEY_OTHER ? ZKE_KEY_OTHER : m.key_type);
+      xn[i] = m.external_input_null ? 1 : 0;
+      w.gather[i] = CopyPool::Piece{hp + L.raw + r, m.raw, m.raw_len};                       // three runs, each contiguous in the image
+      w.gather[(size_t)n + i] = CopyPool::Piece{hp + L.dom + dd, m.from_domain, m.domain_len};
+      w.gather[2 * (size_t)n + i] = CopyPool::Piece{hp + L.key + k, m.key, m.key_len};
+      r += m.raw_len; dd += m.domain_len; k += m.key_len;
+    }
+    ro[n] = r; dofs[n] = dd; ko[n] = k;
+    if (e->pool) e->pool->gather(w.gather.data(), w.gather.size());
+    else for (const auto& p : w.gather) if (p.n) stage_copy(p.dst, p.src, p.n, ZKE_GATHER_STREAM_FROM);
+  } else {
+    // the offsets are copied as they are (the kernels subtract off[0] themselves and the device pointers below are biased
+    // by -off[0]): nothing is rebased, nothing is allocated, every byte is written once
+    CopyPool::Piece pc[8] = {
+        {hp + L.raw_off, d.b.raw_off, (size_t)(n + 1) * 8}, {hp + L.dom_off, d.b.domain_off, (size_t)(n + 1) * 8},
+        {hp + L.key_off, d.b.key_off, (size_t)(n + 1) * 8}, {hp + L.key_type, d.b.key_type, n},
+        {hp + L.ext_null, d.b.ext_null, d.b.ext_null ? n : 0u}, {hp + L.raw, d.b.raw_blob + d.raw_base, (size_t)d.raw_total},
+        {hp + L.dom, d.b.domain_blob + d.dom_base, (size_t)d.dom_total}, {hp + L.key, d.b.key_blob + d.key_base, (size_t)d.key_total}};
+    if (e->pool) e->pool->copy(pc, 8);
+    else for (const auto& p : pc) if (p.n) stage_copy(p.dst, p.src, p.n);
+  }
+  if (d.cap_words) {       // the capture tables of a regex batch (small)
+    stage_copy(hp + L.cap_off, d.b.cap_off, d.cap_words * 4);
+    stage_copy(hp + L.cap_str_off, d.b.cap_str_off, d.cap_strs * 4);
+    stage_copy(hp + L.cap_blob, d.b.cap_blob, d.cap_bytes);
+  }
+  hipStream_t s = w.stream;
+  SlotUse use(e, w, s);
+  if (int r = use.acquire()) return r;
+  StageTimer tm(e, &w, s);
+  tm.mark(MK_START);
+  if (ZKE_HOST_COPY_STREAM && L.total >= (256u << 10)) {
+    // The image crosses PCIe on one of the engine's TWO copy streams, taken in turn, and the slot's stream waits for it.  Issued
+    // on the slots' own 22 streams the input copies moved 31 GB/s in aggregate — one DMA engine's rate —, on one copy stream the
+    // same; on two, 48 GB/s = 84 % of the link (122 us per 1 024-e-mail batch instead of 186; three streams: 141 us, four: worse).
+    // Nothing on the device has to be waited for first: the slot's previous host batch — the only earlier user of d_image — was
+    // retired on the host before the image was packed.  (Small images stay on the slot's stream: the cross-stream event costs a
+    // single e-mail 16 us of latency and buys nothing.)
+    std::lock_guard<std::mutex> cg(e->copy_mu);
+    hipStream_t cs = e->copy_stream[e->copy_turn++ % ZKE_COPY_STREAMS];
+    HIPCHK(e, hipMemcpyAsync(w.d_image.p, hp, L.total, hipMemcpyHostToDevice, cs));
+    HIPCHK(e, hipEventRecord(w.h2d_done, cs));
+    HIPCHK(e, hipStreamWaitEvent(s, w.h2d_done, 0));
+  } else {
+    HIPCHK(e, hipMemcpyAsync(w.d_image.p, hp, L.total, hipMemcpyHostToDevice, s));
+  }
+  tm.mark(MK_H2D);
+  uint8_t* dp = w.d_image.as<uint8_t>();
+  zke_batch dv = d.b;
+  dv.raw_off = reinterpret_cast<const uint64_t*>(dp + L.raw_off);
+  dv.domain_off = reinterpret_cast<const uint64_t*>(dp + L.dom_off);
+  dv.key_off = reinterpret_cast<const uint64_t*>(dp + L.key_off);
+  dv.raw_blob = dp + L.raw - d.raw_base;
+  dv.domain_blob = dp + L.dom - d.dom_base;
+  dv.key_blob = dp + L.key - d.key_base;
+  dv.key_type = dp + L.key_type;
+  dv.ext_null = (d.refs || d.b.ext_null) ? dp + L.ext_null : nullptr;
+  dv.cap_off = d.cap_words ? reinterpret_cast<const uint32_t*>(dp + L.cap_off) : nullptr;
+  dv.cap_str_off = d.cap_words ? reinterpret_cast<const uint32_t*>(dp + L.cap_str_off) : nullptr;
+  dv.cap_blob = d.cap_words ? dp + L.cap_blob : nullptr;
+  if (d.scan) {
+    // one launch, no verify workspace: the counter of selector bytes starts at zero, everything comes back as one copy
+    const ScanLayout& S = w.sb.L;
+    uint8_t* so = w.sb.out.as<uint8_t>();
+    HIPCHK(e, hipMemsetAsync(so, 0, 64, s));
+    SigScanArgs sa{};
+    sa.n = n; sa.max_sigs = S.max_sigs;
+    sa.raw = dv.raw_blob; sa.raw_off = dv.raw_off; sa.dom = dv.domain_blob; sa.dom_off = dv.domain_off;
+    sa.strict = e->strict; sa.now = batch_clock(e);
+    sa.status = reinterpret_cast<uint32_t*>(so + S.status);
+    sa.recs = reinterpret_cast<zke_sig_info*>(so + S.recs);
+    sa.sel_blob = so + S.blob; sa.sel_cap = (uint32_t)S.blob_cap;
+    sa.sel_used = reinterpret_cast<uint32_t*>(so);
+    sa.hdr_ovf = w.sb.ovf.as<uint32_t>();
+    hipLaunchKernelGGL(sigscan_kernel, dim3(n), dim3(64), 0, s, sa);
+    HIPCHK(e, hipGetLastError());
+    tm.mark(MK_FRONT); tm.mark(MK_HASH); tm.mark(MK_VERDICT);      // zke_timings.front_end_us is the scan; the other stages are empty
+    HIPCHK(e, hipMemcpyAsync(w.sb.h_out.p, so, S.total, hipMemcpyDeviceToHost, s));
+  } else if (d.keyrec && !d.sel) {
+    // one launch over the records (the image's raw section), infos and keys back as one copy
+    const KeyrecLayout& K = w.kb.L;
+    uint8_t* ko = w.kb.out.as<uint8_t>();
+    const KeyrecArgs ka{n, d.keyrec->mode, dv.raw_blob, dv.raw_off, reinterpret_cast<zke_key_info*>(ko), ko + K.keys};
+    hipLaunchKernelGGL(keyrec_kernel, dim3(n), dim3(64), 0, s, ka);
+    HIPCHK(e, hipGetLastError());
+    tm.mark(MK_FRONT); tm.mark(MK_HASH); tm.mark(MK_VERDICT);      // zke_timings.front_end_us is the decode; the other stages are empty
+    HIPCHK(e, hipMemcpyAsync(w.kb.h_out.p, ko, K.total, hipMemcpyDeviceToHost, s));
+  } else {
+  uint64_t key_hint = d.key_total;
+  if (d.keyrec) {
+    // the image's key section holds the candidates' RECORDS: decode them, then scan the lengths and gather the keys into the
+    // packed CSR the front end reads — three small launches, the keys never leave HBM
+    const KeyrecLayout& K = w.kb.L;
+    uint8_t* ko = w.kb.out.as<uint8_t>();
+    uint8_t* pk = w.kb.pack.as<uint8_t>();
+    const KeyrecArgs ka{n, d.keyrec->mode, dv.key_blob, dv.key_off, reinterpret_cast<zke_key_info*>(ko), ko + K.keys};
+    hipLaunchKernelGGL(keyrec_kernel, dim3(n), dim3(64), 0, s, ka);
+    const KeyrecPackArgs pa{n, ka.infos, ka.keys, reinterpret_cast<uint64_t*>(pk), pk + K.p_type, pk + K.p_blob};
+    hipLaunchKernelGGL(keyrec_pack_kernel, dim3(1), dim3(64), 0, s, pa);
+    hipLaunchKernelGGL(keyrec_gather_kernel, dim3(n), dim3(64), 0, s, pa);
+    HIPCHK(e, hipGetLastError());
+    dv.key_blob = pa.key_blob; dv.key_off = pa.key_off; dv.key_type = pa.key_type;
+    // (run_device_pipeline reads "the keys average more than an RSA-2048 key's 270 bytes" from the total: a 2048-bit
+    // SubjectPublicKeyInfo record is about 410 characters, a 3072-bit one 580)
+    key_hint = d.key_total > (uint64_t)n * 480 ? (uint64_t)n * 273 : 0;
+  }
+  if (int r = run_device_pipeline(e, w, &dv, d.raw_total, key_hint, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap)) return r;
+  HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
+  if (d.keyrec) HIPCHK(e, hipMemcpyAsync(w.kb.h_out.p, w.kb.out.p, w.kb.L.total, hipMemcpyDeviceToHost, s));
+  }
+  if (d.cap) HIPCHK(e, hipMemcpyAsync(w.cb.h_cap.p, w.cb.cap.p, w.cb.L.fixed_end, hipMemcpyDeviceToHost, s));
+  tm.mark(MK_D2H);
+  HIPCHK(e, hipEventRecord(w.host_done, s));
+  w.host_gen++;
+  w.host_out = (d.scan || d.sel || d.keyrec) ? nullptr : out; w.host_n = n;
+  w.keyrec_out = d.keyrec ? d.keyrec->out : nullptr;
+  w.cap_out = d.cap ? d.cap->out : nullptr;
+  w.scan_out = d.scan ? d.scan->out : nullptr;
+  w.sel_off.clear();
+  if (d.sel) {
+    w.sel_off.resize((size_t)d.sel->n + 1);
+    for (uint32_t i = 0; i <= d.sel->n; i++) w.sel_off[i] = d.sel->cand_off[i] - d.sel->cand_off[0];
+    w.sel_out = d.sel->out; w.sel_chosen = d.sel->chosen;
+  }
+  return use.release();
+}
+
+// The host entry's staging of EVERY slot, sized for images of `image` bytes and n records.  Pinned memory that comes into being
+// while other slots' copies are in flight copies at a fraction of the link's rate for the rest of its life (measured: slots that
+// allocated their staging lazily, one by one under traffic, moved 9 GB/s in aggregate; the same buffers allocated together in a
+// quiet moment 31 GB/s) — so growth is a stop-the-world event: no submission in progress (`big` exclusive), every pending host
+// batch delivered, every stream drained, then all slots at once, with headroom so that it stays rare.
+int grow_host_staging(zke_engine* e, size_t image, uint32_t n) {
+  std::unique_lock<std::shared_mutex> ex(e->big);
+  if (image <= e->host_image_cap.load() && n <= e->host_n_cap.load()) return 0;       // another thread grew it meanwhile
+  HIPCHK(e, hipSetDevice(e->device));
+  for (Slot* w : e->slots) { std::lock_guard<std::mutex> g(w->mu); if (int r = retire_host(e, *w)) return r; }
+  if (int r = drain_engine(e, false)) return r;
+  for (auto& cs : e->copy_stream)
+    if (!cs) HIPCHK(e, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+  const size_t want_image = std::max(image + image / 2, e->host_image_cap.load());
+  const uint32_t want_n = std::max<uint32_t>(n + n / 2, e->host_n_cap.load());
+  for (Slot* w : e->slots)
+    if (int r = ensure_host_buffers(e, *w, want_image, want_n)) return r;
+  e->host_image_cap = want_image;
+  e->host_n_cap = want_n;
+  return 0;
+}
+// Parity intermediates (tests) of the packed batch `in` just delivered from slot w: its scratch copied back, sliced on the host.
+int copy_debug_out(zke_engine* e, Slot& w, const zke_batch& in, const zke_result* out, const zke_debug_out* dbg) {
+  const uint32_t n = in.n;
+  const uint64_t raw_total = in.raw_off[n] - in.raw_off[0];
+  std::vector<EmailMeta> meta(n), meta2;
+  HIPCHK(e, hipMemcpy(meta.data(), w.meta.p, (size_t)n * sizeof(EmailMeta), hipMemcpyDeviceToHost));
+  const size_t scratch_bytes = 2 * (size_t)raw_total + (size_t)(n + 1) * SCR_PER_EMAIL + 256;
+  std::vector<uint8_t> scr(scratch_bytes);
+  HIPCHK(e, hipMemcpy(scr.data(), w.scratch.p, scratch_bytes, hipMemcpyDeviceToHost));
+  std::vector<uint8_t> em, clean;
+  if (dbg->em) { em.resize((size_t)n * 512); HIPCHK(e, hipMemcpy(em.data(), w.em_dbg.p, em.size(), hipMemcpyDeviceToHost)); }
+  if (dbg->clean_body && in.with_regex) {
+    meta2.resize(n);
+    HIPCHK(e, hipMemcpy(meta2.data(), w.meta2.p, (size_t)n * sizeof(EmailMeta), hipMemcpyDeviceToHost));
+    clean.resize((size_t)raw_total + (size_t)(n + 1) * CLEAN_PER_EMAIL + 256);
+    HIPCHK(e, hipMemcpy(clean.data(), w.clean.p, clean.size(), hipMemcpyDeviceToHost));
+  }
+  auto put = [](uint8_t* base, size_t stride, uint32_t i, const uint8_t* src, size_t len) {
+    if (!base) return;
+    memset(base + (size_t)i * stride, 0, stride);
+    memcpy(base + (size_t)i * stride, src, std::min(len, stride));
+  };
+  for (uint32_t i = 0; i < n; i++) {
+    const EmailMeta& m = meta[i];
+    const uint64_t rel = in.raw_off[i] - in.raw_off[0];
+    const uint32_t raw_len = (uint32_t)(in.raw_off[i + 1] - in.raw_off[i]);
+    const uint8_t* regA = scr.data() + host_scratch_off(in.raw_off, i);
+    const uint8_t* regB = regA + (((size_t)raw_len + PRE_SLACK + 15) & ~(size_t)15);
+    const bool hashed = out[i].canon_header_len || out[i].canon_body_len || m.canon_full_len;
+    put(dbg->canon_header, dbg->canon_header_stride, i, regA, hashed ? out[i].canon_header_len : 0);
+    const uint8_t* body = m.body_src_is_raw ? in.raw_blob + in.raw_off[i] + m.body_off : regB;
+    put(dbg->canon_body, dbg->canon_body_stride, i, body, hashed ? m.canon_full_len : 0);
+    if (dbg->canon_body_full_len) dbg->canon_body_full_len[i] = hashed ? m.canon_full_len : 0;
+    if (dbg->rsa_route) dbg->rsa_route[i] = m.rsa_route;
+    if (dbg->em) put(dbg->em, dbg->em_stride, i, em.data() + (size_t)i * 512 + 512 - std::min<uint32_t>(512, e_k(out[i].rsa_bits)),
+                     std::min<uint32_t>(512, e_k(out[i].rsa_bits)));
+    if (dbg->clean_body && in.with_regex && meta2[i].state == ST_CAND)
+      put(dbg->clean_body, dbg->clean_body_stride, i, clean.data() + (rel + (uint64_t)i * CLEAN_PER_EMAIL), meta2[i].hashed_len);
+    else if (dbg->clean_body)
+      put(dbg->clean_body, dbg->clean_body_stride, i, nullptr, 0);
+  }
+  return 0;
+}
+
+// Every host entry's submission.  With a ticket: asynchronous (zke_batch_wait or the slot's next batch delivers).  Without: delivered
+// before this returns, the parity intermediates (dbg) copied back under the same slot lock — the slot's next batch overwrites them.
+int submit_host_batch(zke_engine* e, const HostBatch& d, zke_result* out, uint64_t* ticket, const zke_debug_out* dbg = nullptr) {
+  const uint32_t n = d.b.n;
+  if (!n && !ticket) return 0;
+  if (n && (d.L.total > e->host_image_cap.load() || n > e->host_n_cap.load())) if (int r = grow_host_staging(e, d.L.total, n)) return r;
+  std::shared_lock<std::shared_mutex> sh(e->big);
+  HIPCHK(e, hipSetDevice(e->device));
+  if (d.cap) capture_resolve(e, *d.cap);             // under `big`: the programs' tables cannot be freed before the batch is enqueued
+  uint32_t slot;
+  Slot& w = next_slot(e, slot);
+  std::lock_guard<std::mutex> g(w.mu);
+  if (!n) { *ticket = make_ticket(slot, w.host_retired); return 0; }      // nothing to wait for
+  if (int r = submit_host(e, w, d, out, dbg && dbg->em, dbg && dbg->clean_body)) return r;
+  if (ticket) { *ticket = make_ticket(slot, w.host_gen); return 0; }
+  int cap_rc = 0;
+  if (int r = retire_host(e, w, &cap_rc)) return r;
+  if (cap_rc) return cap_rc;
+  return dbg ? copy_debug_out(e, w, d.b, out, dbg) : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zke_engine_reserve_host(zke_engine* e, uint32_t max_n, uint64_t max_input_bytes) {
+  if (!e) return ZKE_E_ARG;
+  // offsets, key types and 64-byte alignment on top of the blobs (image_layout)
+  const size_t image = (size_t)max_input_bytes + (size_t)(max_n + 1) * 24 + 2 * (size_t)max_n + 16 * 64 + 4 * 64;
+  if (image <= e->host_image_cap.load() && max_n <= e->host_n_cap.load()) return 0;
+  return grow_host_staging(e, image, max_n);
+}
+
+int zke_verify_batch_async(zke_engine* e, const zke_batch* in, zke_result* out, uint64_t* ticket) {
+  if (!e) return ZKE_E_ARG;
+  HostBatch d;
+  if (int r = host_batch(d, "zke_verify_batch_async", out, in)) return r;
+  if (!ticket) return fail(e, ZKE_E_ARG, "zke_verify_batch_async: null ticket");
+  return submit_host_batch(e, d, out, ticket);
+}
+
+int zke_batch_wait(zke_engine* e, uint64_t ticket) {
+  if (!e) return ZKE_E_ARG;
+  std::shared_lock<std::shared_mutex> sh(e->big);
+  const uint32_t slot = (uint32_t)(ticket & 63);
+  if (slot >= e->slots.size()) return fail(e, ZKE_E_ARG, "zke_batch_wait: no such ticket");
+  Slot& w = *e->slots[slot];
+  std::lock_guard<std::mutex> g(w.mu);
+  if ((ticket >> 6) > w.host_gen) return fail(e, ZKE_E_ARG, "zke_batch_wait: no such ticket");
+  if ((ticket >> 6) <= w.host_retired) return 0;        // delivered already (waited for before, or retired by the slot's next batch)
+  HIPCHK(e, hipSetDevice(e->device));
+  int cap_rc = 0;
+  if (int r = retire_host(e, w, &cap_rc)) return r;
+  return cap_rc;
+}
+
+int zke_verify_emails_with_regex_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_lists* lists,
+                                       zke_result* out, uint64_t* ticket) {
+  if (!e) return ZKE_E_ARG;
+  if (!ticket) return fail(e, ZKE_E_ARG, "zke_verify_emails_async: null pointer");
+  HostBatch d;
+  if (int r = host_batch(d, "zke_verify_emails_async", out, emails, n, lists)) return r;
+  return submit_host_batch(e, d, out, ticket);
+}
+
+int zke_verify_emails_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, zke_result* out, uint64_t* ticket) {
+  return zke_verify_emails_with_regex_async(e, emails, n, nullptr, out, ticket);
+}
+
+int zke_verify_emails_with_regex(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_lists* lists, zke_result* out) {
+  uint64_t ticket = 0;
+  if (int r = zke_verify_emails_with_regex_async(e, emails, n, lists, out, &ticket)) return r;
+  return n ? zke_batch_wait(e, ticket) : 0;
+}
+
+int zke_verify_emails(zke_engine* e, const zke_email_ref* emails, uint32_t n, zke_result* out) {
+  return zke_verify_emails_with_regex(e, emails, n, nullptr, out);
+}
+
+int zke_verify_batch(zke_engine* e, const zke_batch* in, zke_result* out, zke_debug_out* dbg) {
+  if (!e) return ZKE_E_ARG;
+  HostBatch d;
+  if (int r = host_batch(d, "zke_verify_batch", out, in)) return r;
+  return submit_host_batch(e, d, out, nullptr, dbg);
+}
+
+// ---- single-e-mail wrappers: a batch of one through the gathering entry (config 1 and API-shape parity)
+int zke_verify_email(zke_engine* e, const uint8_t* raw, size_t raw_len, const char* from_domain, size_t domain_len,
+                     const uint8_t* key, size_t key_len, uint32_t key_type, uint32_t external_input_null, zke_result* out) {
+  const zke_email_ref one{raw, raw_len, from_domain, domain_len, key, key_len, key_type, external_input_null};
+  return zke_verify_emails_with_regex(e, &one, 1, nullptr, out);
+}
+
+int zke_verify_email_with_regex(zke_engine* e, const uint8_t* raw, size_t raw_len, const char* from_domain, size_t domain_len,
+                                const uint8_t* key, size_t key_len, uint32_t key_type, uint32_t external_input_null,
+                                const zke_regex_part* header_parts, uint32_t n_header_parts,
+                                const zke_regex_part* body_parts, uint32_t n_body_parts, zke_result* out) {
+  if (!e) return ZKE_E_ARG;
+  if ((n_header_parts && !header_parts) || (n_body_parts && !body_parts)) return fail(e, ZKE_E_ARG, "zke_verify_email_with_regex: null pointer");
+  std::vector<uint32_t> hids, bids, cap_off{0}, str_off{0};
+  std::vector<uint8_t> blob;
+  // every pair this call registers or finds stays pinned until the batch has run: with the registry at its cap another
+  // thread's registration evicts the least recently used transient pair and the id is handed out again
+  struct Pins { zke_engine* e; std::vector<uint32_t> ids; ~Pins() { if (!ids.empty()) dfa_unpin(e, ids); } } pinned{e, {}};
+  for (int side = 0; side < 2; side++) {
+    const zke_regex_part* parts = side ? body_parts : header_parts;
+    const uint32_t np = side ? n_body_parts : n_header_parts;
+    for (uint32_t k = 0; k < np; k++) {
+      const zke_regex_part& p = parts[k];
+      if ((p.fwd_len && !p.fwd) || (p.bwd_len && !p.bwd) || (p.n_captures && (!p.captures || !p.capture_lens)))
+        return fail(e, ZKE_E_ARG, "zke_verify_email_with_regex: null pointer in a part");
+      uint32_t id = 0;
+      // the same pair gets the same id: a hash lookup, not a parse; pairs registered here are the evictable ones
+      if (int r = dfa_register_impl(e, p.fwd, p.fwd_len, p.bwd, p.bwd_len, &id, true)) return r;
+      pinned.ids.push_back(id);
+      (side ? bids : hids).push_back(id);
+      for (uint32_t c = 0; c < p.n_captures; c++) {
+        if (p.capture_lens[c] && !p.captures[c]) return fail(e, ZKE_E_ARG, "zke_verify_email_with_regex: null capture");
+        blob.insert(blob.end(), p.captures[c], p.captures[c] + p.capture_lens[c]);
+        str_off.push_back((uint32_t)blob.size());
+      }
+      cap_off.push_back((uint32_t)str_off.size() - 1);
+    }
+  }
+  if (blob.empty()) blob.push_back(0);          // (captures that are all empty strings still want a blob pointer)
+  const zke_email_ref one{raw, raw_len, from_domain, domain_len, key, key_len, key_type, external_input_null};
+  const zke_regex_lists lists{n_header_parts, hids.data(), n_body_parts, bids.data(), cap_off.data(), str_off.data(), blob.data()};
+  return zke_verify_emails_with_regex(e, &one, 1, &lists, out);
+}
+
+// ---- signature scan and key selection (include/zkemail_amd.h; kernel: sigscan.hip.h)
+int zke_scan_signatures_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t max_sigs, zke_sig_scan* out, uint64_t* ticket) {
+  static const char who[] = "zke_scan_signatures";
+  if (!e) return ZKE_E_ARG;
+  if (!out || !ticket || (n && !emails)) return arg_error(who, "null pointer");
+  if (max_sigs < 1 || max_sigs > ZKE_SCAN_MAX_SIGS) return arg_error(who, "max_sigs must be 1 .. ZKE_SCAN_MAX_SIGS");
+  if ((uint64_t)n * max_sigs >= (1ull << 21)) return arg_error(who, "n * max_sigs must stay below 2^21 (32-bit selector offsets): split the batch");
+  out->scan_status_need = (size_t)n * 4; out->sig_off_need = (size_t)n + 1; out->sigs_need = 0; out->sel_blob_need = 0; out->n_sigs = 0;
+  if (out->scan_status_cap < out->scan_status_need || out->sig_off_cap < out->sig_off_need) {
+    g_err = std::string(who) + ": a zke_sig_scan buffer is smaller than its *_need";
+    return ZKE_E_NOMEM;
+  }
+  if ((n && !out->scan_status) || !out->sig_off || (out->sigs_cap && !out->sigs) || (out->sel_blob_cap && !out->sel_blob))
+    return arg_error(who, "null buffer in zke_sig_scan");
+  out->sig_off[0] = 0;
+  std::vector<zke_email_ref> refs(emails, emails + n);              // the key fields are ignored: the image has no key section
+  for (zke_email_ref& m : refs) { m.key = nullptr; m.key_len = 0; m.key_type = ZKE_KEY_RSA; m.external_input_null = 0; }
+  HostBatch d;
+  if (int r = host_batch(d, who, reinterpret_cast<const zke_result*>(out), refs.data(), n, nullptr)) return r;
+  const ScanReq q{max_sigs, out};
+  d.scan = &q;
+  return submit_host_batch(e, d, nullptr, ticket);
+}
+
+int zke_scan_signatures(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t max_sigs, zke_sig_scan* out) {
+  uint64_t ticket = 0;
+  if (int r = zke_scan_signatures_async(e, emails, n, max_sigs, out, &ticket)) return r;
+  return n ? zke_batch_wait(e, ticket) : 0;
+}
+
+int zke_select_keys_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off, const zke_key_ref* keys,
+                          zke_result* out, uint32_t* chosen, uint64_t* ticket) {
+  static const char who[] = "zke_select_keys";
+  if (!e) return ZKE_E_ARG;
+  if (!ticket || (n && (!emails || !cand_off || !out || !chosen))) return arg_error(who, "null pointer");
+  if (n && !rising(cand_off, n)) return arg_error(who, "cand_off is not non-decreasing");
+  const uint32_t base = n ? cand_off[0] : 0, M = n ? cand_off[n] - base : 0;
+  if (M >> 31) return arg_error(who, "2^31 candidates or more");
+  if (M && !keys) return arg_error(who, "null pointer");
+  // ONE batch of the (e-mail, candidate key) pairs: the raw e-mail and the domain by reference, once per candidate
+  std::vector<zke_email_ref> refs(M);
+  for (uint32_t i = 0; i < n; i++)
+    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; k++) {
+      zke_email_ref& m = refs[k - base];
+      m = emails[i];
+      m.key = keys[k].key; m.key_len = keys[k].key_len; m.key_type = keys[k].key_type;
+    }
+  HostBatch d;
+  if (int r = host_batch(d, who, out, refs.data(), M, nullptr)) return r;
+  if (!M) {            // no candidate anywhere: nothing to run
+    const std::vector<uint32_t> off((size_t)n + 1, 0u);
+    if (n) fold_selection(nullptr, off, out, chosen);
+    return submit_host_batch(e, d, out, ticket);
+  }
+  const SelectReq q{cand_off, n, out, chosen};
+  d.sel = &q;
+  return submit_host_batch(e, d, out, ticket);
+}
+
+int zke_select_keys(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off, const zke_key_ref* keys,
+                    zke_result* out, uint32_t* chosen) {
+  uint64_t ticket = 0;
+  if (int r = zke_select_keys_async(e, emails, n, cand_off, keys, out, chosen, &ticket)) return r;
+  return n ? zke_batch_wait(e, ticket) : 0;
+}
+
+// ---- key records (include/zkemail_amd.h; kernels: keyrec.hip.h)
+namespace {
+// The checks both entries share, before anything is staged; fills the needs.  A record longer than ZKE_KEYREC_MAX_BYTES is not
+// read: one byte more than the limit is staged, which is all the kernel needs to say so.
+int keyrec_args(const char* who, const zke_keyrec_ref* recs, uint32_t m, uint32_t mode, zke_keyrec_out* out) {
+  if (!out || (m && !recs)) return arg_error(who, "null pointer");
+  if (mode != ZKE_KEYREC_ARCHIVE && mode != ZKE_KEYREC_DNS) return arg_error(who, "mode must be ZKE_KEYREC_ARCHIVE or ZKE_KEYREC_DNS");
+  if (m >= (1u << 19)) return arg_error(who, "2^19 records or more (32-bit key offsets): split the batch");
+  for (uint32_t i = 0; i < m; i++)
+    if (recs[i].len && !recs[i].txt) return arg_error(who, "null buffer with a length");
+  out->infos_need = m; out->keys_need = 0;
+  if (out->infos_cap < m) { g_err = std::string(who) + ": zke_keyrec_out.infos is smaller than infos_need"; return ZKE_E_NOMEM; }
+  if ((m && !out->infos) || (out->keys_cap && !out->keys)) return arg_error(who, "null buffer in zke_keyrec_out");
+  return 0;
+}
+inline size_t keyrec_staged(size_t len) { return std::min<size_t>(len, (size_t)ZKE_KEYREC_MAX_BYTES + 1); }
+}  // namespace
+
+int zke_decode_key_records_async(zke_engine* e, const zke_keyrec_ref* recs, uint32_t m, uint32_t mode, zke_keyrec_out* out, uint64_t* ticket) {
+  static const char who[] = "zke_decode_key_records";
+  if (!e) return ZKE_E_ARG;
+  if (!ticket) return arg_error(who, "null pointer");
+  if (int r = keyrec_args(who, recs, m, mode, out)) return r;
+  std::vector<zke_email_ref> refs(m);                 // the records travel as the image's raw section: no domains, no keys
+  for (uint32_t i = 0; i < m; i++) { refs[i] = zke_email_ref{}; refs[i].raw = recs[i].txt; refs[i].raw_len = keyrec_staged(recs[i].len); }
+  HostBatch d;
+  if (int r = host_batch(d, who, reinterpret_cast<const zke_result*>(out), refs.data(), m, nullptr)) return r;
+  const KeyrecReq q{mode, out};
+  d.keyrec = &q;
+  return submit_host_batch(e, d, nullptr, ticket);
+}
+
+int zke_decode_key_records(zke_engine* e, const zke_keyrec_ref* recs, uint32_t m, uint32_t mode, zke_keyrec_out* out) {
+  uint64_t ticket = 0;
+  if (int r = zke_decode_key_records_async(e, recs, m, mode, out, &ticket)) return r;
+  return m ? zke_batch_wait(e, ticket) : 0;
+}
+
+int zke_select_keys_from_records_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off,
+                                       const zke_keyrec_ref* recs, uint32_t mode, zke_result* out, uint32_t* chosen,
+                                       zke_keyrec_out* keys_out, uint64_t* ticket) {
+  static const char who[] = "zke_select_keys_from_records";
+  if (!e) return ZKE_E_ARG;
+  if (!ticket || !keys_out || (n && (!emails || !cand_off || !out || !chosen))) return arg_error(who, "null pointer");
+  if (n && !rising(cand_off, n)) return arg_error(who, "cand_off is not non-decreasing");
+  const uint32_t base = n ? cand_off[0] : 0, M = n ? cand_off[n] - base : 0;
+  if (int r = keyrec_args(who, recs ? recs + base : nullptr, M, mode, keys_out)) return r;
+  // ONE batch of the (e-mail, candidate) pairs, as zke_select_keys; the key section of its image holds the candidates' records
+  std::vector<zke_email_ref> refs(M);
+  for (uint32_t i = 0; i < n; i++)
+    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; k++) {
+      zke_email_ref& m = refs[k - base];
+      m = emails[i];
+      m.key = recs[k].txt; m.key_len = keyrec_staged(recs[k].len); m.key_type = ZKE_KEY_RSA;
+    }
+  HostBatch d;
+  if (int r = host_batch(d, who, out, refs.data(), M, nullptr)) return r;
+  if (!M) {            // no candidate anywhere: nothing to run
+    const std::vector<uint32_t> off((size_t)n + 1, 0u);
+    if (n) fold_selection(nullptr, off, out, chosen);
+    return submit_host_batch(e, d, out, ticket);
+  }
+  const SelectReq q{cand_off, n, out, chosen};
+  const KeyrecReq kq{mode, keys_out};
+  d.sel = &q; d.keyrec = &kq;
+  return submit_host_batch(e, d, out, ticket);
+}
+
+int zke_select_keys_from_records(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off,
+                                 const zke_keyrec_ref* recs, uint32_t mode, zke_result* out, uint32_t* chosen, zke_keyrec_out* keys_out) {
+  uint64_t ticket = 0;
+  if (int r = zke_select_keys_from_records_async(e, emails, n, cand_off, recs, mode, out, chosen, keys_out, &ticket)) return r;
+  return n ? zke_batch_wait(e, ticket) : 0;
+}
+
+namespace {
+// the sizes an extraction over n e-mails needs, written back; ZKE_E_NOMEM when a buffer of known size is too small
+int check_capture_out(zke_capture_out* o, uint32_t n, uint32_t P, uint32_t G, const char* who) {
+  if (!o) return arg_error(who, "null zke_capture_out");
+  const size_t NP = (size_t)n * P, NG = (size_t)n * G;
+  o->spans_need = NG * 2; o->flags_need = NG; o->cap_off_need = NP + 1; o->cap_str_off_need = NG + 1;
+  o->cap_blob_need = 0; o->n_strings = 0;
+  // string offsets are 32-bit, as the verify entry's tables are: what n * G spans of ZKE_CAP_MAX_SPAN bytes could not address is refused
+  if ((uint64_t)NG * ZKE_CAP_MAX_SPAN > 0xFFFFFFFFull) return arg_error(who, "n x groups beyond what 32-bit string offsets address (n * G * ZKE_CAP_MAX_SPAN must stay below 4 GiB): split the batch");
+  if (o->spans_cap < o->spans_need || o->flags_cap < o->flags_need || o->cap_off_cap < o->cap_off_need || o->cap_str_off_cap < o->cap_str_off_need) {
+    g_err = std::string(who) + ": a zke_capture_out buffer is smaller than its *_need";
+    return ZKE_E_NOMEM;
+  }
+  if (!o->spans || !o->flags || !o->cap_off || !o->cap_str_off || (o->cap_blob_cap && !o->cap_blob)) return arg_error(who, "null buffer in zke_capture_out");
+  return 0;
+}
+}  // namespace
+
+int zke_extract_captures_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
+                               uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
+                               zke_capture_out* caps, uint64_t* ticket) {
+  static const char who[] = "zke_extract_captures";
+  if (!e) return ZKE_E_ARG;
+  if (!ticket || !caps || (n_header_parts && !header_parts) || (n_body_parts && !body_parts)) return arg_error(who, "null pointer");
+  const uint32_t P = n_header_parts + n_body_parts;
+  if (P == 0 || P > ZKE_CAP_MAX_PARTS || n_header_parts > ZKE_CAP_MAX_PARTS) return arg_error(who, "1 .. ZKE_CAP_MAX_PARTS parts");
+  CaptureReq q;
+  q.P = P; q.n_header_parts = n_header_parts; q.out = caps;
+  q.dfa_ids.resize(P);
+  for (uint32_t p = 0; p < P; p++) {
+    const zke_capture_part& cp = p < n_header_parts ? header_parts[p] : body_parts[p - n_header_parts];
+    q.dfa_ids[p] = cp.dfa_id;
+    if (int r = capture_part_shape(q, p, cp.prog_id, cp.groups, cp.n_groups, who)) return r;
+  }
+  if (int r = check_capture_out(caps, n, P, q.G, who)) return r;
+  zke_regex_lists lists{n_header_parts, q.dfa_ids.data(), n_body_parts, q.dfa_ids.data() + n_header_parts, nullptr, nullptr, nullptr};
+  HostBatch d;
+  if (int r = host_batch(d, who, out, emails, n, &lists)) return r;
+  d.cap = &q;
+  return submit_host_batch(e, d, out, ticket);
+}
+
+int zke_extract_captures(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
+                         uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
+                         zke_capture_out* caps) {
+  uint64_t ticket = 0;
+  if (int r = zke_extract_captures_async(e, emails, n, header_parts, n_header_parts, body_parts, n_body_parts, out, caps, &ticket)) return r;
+  return n ? zke_batch_wait(e, ticket) : 0;
+}
+
+}  // extern "C"
