@@ -1,0 +1,80 @@
+#!/usr/bin/env python
+"""queue_trace.py DIR [STEP_MS]: how a rocprofv3 --kernel-trace run of bench.py used the hardware queues.
+
+Reads DIR/**/*_kernel_trace.csv.  Per queue: launches, busy time (sum of kernel durations), the span from its first start to its
+last end, and how much consecutive kernels of that queue overlap (a hardware queue runs its packets one after the other: the
+overlap must be ~0).  Then the steady-state figures the throughput model of DESIGN.md §5 rests on: batches (one verdict kernel
+each) per queue, busy time per batch, and span / batches over all queues = the step the chain would give.
+"""
+import csv
+import glob
+import os
+import sys
+from collections import defaultdict
+
+
+def short(name: str) -> str:
+    name = name.split("(")[0]
+    for pre in ("void ", "zke::"):
+        name = name.replace(pre, "")
+    return name[:40]
+
+
+def main():
+    d = sys.argv[1]
+    files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        raise SystemExit(f"no *kernel_trace.csv under {d}")
+    rows = []
+    for f in files:
+        with open(f, newline="") as fh:
+            for r in csv.DictReader(fh):
+                rows.append((r["Queue_Id"], int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"])))
+    by_q = defaultdict(list)
+    for q, s, e, n in rows:
+        by_q[q].append((s, e, n))
+    # steady state: the last 60 % of the batches of the trace (warm-up, priming and the alone pass come first)
+    verdict_ends = sorted(e for _, _, e, n in rows if n.startswith("ed_verdict"))
+    if len(verdict_ends) < 20:
+        raise SystemExit("fewer than 20 verdict kernels in the trace")
+    t_lo, t_hi = verdict_ends[int(len(verdict_ends) * 0.4)], verdict_ends[-1]
+    print(f"{len(rows)} kernels on {len(by_q)} queues; steady window {1e-6 * (t_hi - t_lo):.3f} ms")
+    tot_batches = 0
+    print("queue  kernels  batches  busy_us/batch  span_us/batch  overlap_us(max)  overlapping_pairs  kernels_us(mean in window)")
+    for q in sorted(by_q):
+        ks = sorted(k for k in by_q[q] if t_lo <= k[0] and k[1] <= t_hi)
+        if not ks:
+            print(f"{q:>5}  (idle in the window)")
+            continue
+        busy = sum(e - s for s, e, _ in ks)
+        span = ks[-1][1] - ks[0][0]
+        nb = sum(1 for k in ks if k[2].startswith("ed_verdict"))
+        ov = [ks[i][1] - ks[i + 1][0] for i in range(len(ks) - 1) if ks[i][1] > ks[i + 1][0]]
+        per = defaultdict(list)
+        for s, e, n in ks:
+            per[n].append(e - s)
+        means = ", ".join(f"{n} {1e-3 * sum(v) / len(v):.1f}" for n, v in sorted(per.items(), key=lambda kv: -sum(kv[1])))
+        tot_batches += nb
+        if nb:
+            print(f"{q:>5}  {len(ks):7d}  {nb:7d}  {1e-3 * busy / nb:13.1f}  {1e-3 * span / nb:13.1f}  {1e-3 * max(ov, default=0):15.2f}  {len(ov):17d}  {means}")
+        else:
+            print(f"{q:>5}  {len(ks):7d}  {nb:7d}  (no batches)  {means}")
+    step_us = 1e-3 * (t_hi - t_lo) / max(1, tot_batches)
+    print(f"batches in window {tot_batches}; step from the trace {step_us:.1f} us")
+    # how many kernels of DIFFERENT queues run at the same time, averaged over the window
+    ev = []
+    for q, s, e, n in rows:
+        if t_lo <= s and e <= t_hi:
+            ev += [(s, 1), (e, -1)]
+    ev.sort()
+    cur, last, acc = 0, t_lo, 0
+    for t, dlt in ev:
+        acc += cur * (t - last)
+        cur, last = cur + dlt, t
+    print(f"kernels running at once, time average {acc / (t_hi - t_lo):.2f}")
+    if len(sys.argv) > 2:
+        print(f"bench step {float(sys.argv[2]) * 1e3:.1f} us")
+
+
+if __name__ == "__main__":
+    main()

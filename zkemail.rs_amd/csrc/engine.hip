@@ -159,6 +159,11 @@ struct zke_engine {
                                     // Low since the modexp runs beside SHA-256 (fused.hip.h): its longer chain no longer sits behind the
                                     // hashes of a small batch; a handful of e-mails is still answered sooner by one signature per wave
   uint32_t rsa_oct_min = 128;       // ... eight lanes (moduli above 2048 bits)
+  uint32_t hw_queues = 4;           // GPU_MAX_HW_QUEUES as read once, at creation (unset: HIP's default of 4).  Streams beyond HIP's queue pool
+                                    // share a queue, and a queue runs its kernels one after the other: min(slots that exist, hw_queues)
+                                    // batches of this engine can be on the chip at once (rsa_route_mask)
+  int rsa_oct9 = -1;                // moduli <= 2048 bits on eight lanes of nine limbs instead of four of eighteen (rsa_quad.hip.h):
+                                    // -1 by the in-flight bound (rsa_route_mask), 0 never, 1 always (ZKE_RSA_OCT9 in the environment)
 #ifdef ZKE_DEV_KNOBS
   uint32_t debug_skip_rsa = 0, debug_skip_ed = 0, debug_parse_stop = 0, debug_skip_launch = 0;
 #else
@@ -244,17 +249,27 @@ int drain_engine(zke_engine* e, bool copy_streams) {
 // bit 1: eight lanes (2049..4096 bits; any_big = the caller's hint that the batch's keys average more than an RSA-2048 key).
 // The front end routes signatures by this mask and the hash / modexp launch gets the matching workgroups: the same value
 // must go to both.  zke_options.rsa_lane_groups: 0 = by batch size, 1 never, 2 always.
+// Bit 2 instead of bit 0: moduli <= 2048 bits take eight lanes of nine limbs.  That routine's chain per product is a third shorter
+// (2 520 instead of 3 684 instructions, profiles/oct9_static.txt) and it issues 1.4 times the instructions per signature, so it is
+// the choice when the engine cannot fill the chip's issue slots: with at most RSA_OCT9_MAX_IN_FLIGHT batches on the chip a batch's
+// time is its dependency chain (DESIGN.md §5 has the sweep over the queue count).  The bound is min(slots, hardware queues) with the
+// slots that exist NOW — zke_engine_reserve only appends, and an engine created with one slot and grown to 22 counts 22 — so an
+// engine with more than four slots on more than four queues keeps four lanes.  Only the choice by batch size is made this way:
+// rsa_lane_groups = 2 asks for the routines by name and keeps four lanes unless the environment says otherwise.
+constexpr uint32_t RSA_OCT9_MAX_IN_FLIGHT = 4;
 uint32_t rsa_route_mask(const zke_engine* e, uint32_t n, bool any_big) {
   if (!e->key_cache.p || e->opt.rsa_lane_groups == 1) return 0;
   const bool always = e->opt.rsa_lane_groups == 2;
+  const uint32_t in_flight_max = std::min<uint32_t>((uint32_t)e->slots.size(), e->hw_queues);
+  const bool oct9 = e->rsa_oct9 >= 0 ? e->rsa_oct9 == 1 : !always && in_flight_max <= RSA_OCT9_MAX_IN_FLIGHT;
   uint32_t m = 0;
-  if (always || n >= e->rsa_quad_min) m |= 1u;
+  if (always || n >= e->rsa_quad_min) m |= oct9 ? 4u : 1u;
   if (any_big && (always || n >= e->rsa_oct_min)) m |= 2u;
   return m;
 }
 
 int launch_stage(zke_engine* e, const StageArgs& A, hipStream_t s) {
-  const uint32_t grid = A.g_sha + A.g_wave + A.g_quad + A.g_oct;
+  const uint32_t grid = A.g_sha + A.g_wave + A.g_quad + A.g_oct + A.g_oct9;
   if (!grid) return 0;
   hipLaunchKernelGGL(hash_modexp_kernel<SHA_TILE>, dim3(grid), dim3(128), sha256_pair_lds_bytes<SHA_TILE>(), s, A);
   HIPCHK(e, hipGetLastError());
@@ -293,6 +308,7 @@ int launch_hash_modexp(zke_engine* e, const ShaJob* sha, uint32_t n_sha, const R
   }
   A.g_quad = (route_mask & 1u) ? (n + 31) / 32 : 0;
   A.g_oct = (route_mask & 2u) ? (n + 15) / 16 : 0;
+  A.g_oct9 = (route_mask & 4u) ? (n + 15) / 16 : 0;
   A.debug_skip_rsa = e->debug_skip_rsa;
   const uint32_t groups = (n_sha + 63) / 64;
   if (sha_takes_pairs(e, groups)) {
@@ -462,6 +478,16 @@ int zke_engine_create(const zke_options* opt, zke_engine** out) {
     }
   }
   if (o.host_threads > 1) e->pool = new CopyPool(o.host_threads - 1);     // the caller's thread is one of them
+  {
+    // What HIP's queue pool is sized by was read (or is about to be read) by the runtime from the same variable; zke_process_init
+    // above has set it unless the host had.  Unset or unreadable: HIP's default of 4.
+    const char* q = getenv("GPU_MAX_HW_QUEUES");
+    const int hwq = q ? atoi(q) : 0;
+    e->hw_queues = hwq > 0 ? (uint32_t)hwq : 4u;
+    // ZKE_RSA_OCT9 = 0 / 1 forces the RSA role for moduli <= 2048 bits.  Unlike the knobs below it is read by the shipped library,
+    // not only under ZKE_DEV_KNOBS: the tests of the role and A/B runs of one build need it there (INTEGRATION.md §5 lists it).
+    if (const char* r9 = getenv("ZKE_RSA_OCT9")) e->rsa_oct9 = atoi(r9) != 0 ? 1 : 0;
+  }
 #ifdef ZKE_DEV_KNOBS
   if (const char* rm = getenv("ZKE_RSA_QUAD_MIN")) e->rsa_quad_min = (uint32_t)atoi(rm);
   if (const char* ro = getenv("ZKE_RSA_OCT_MIN")) e->rsa_oct_min = (uint32_t)atoi(ro);

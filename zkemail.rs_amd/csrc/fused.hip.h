@@ -24,11 +24,13 @@ struct StageArgs {
   const uint32_t* wave_count;              // the front end's list of jobs for the one-signature-per-wave routine (the keys
   const uint32_t* wave_list;               // not cached yet, other exponents ...); nullptr: no list, job = 2 b + wave
   uint32_t g_sha, g_wave, g_quad, g_oct;   // workgroups per role, in this order; blockDim = 128 (two waves)
+  uint32_t g_oct9;                         // ... then the eight-lane role for moduli <= 2048 bits (a launch has it or g_quad, never both)
   const uint32_t* order; uint32_t n_pad;   // length buckets of the body / header-preimage hashes (BatchDev::order), or nullptr
   uint32_t debug_skip_rsa;
 };
 
-constexpr uint32_t QUAD_LDS_DWORDS = 16 * (4 * QL + 4), OCT_LDS_DWORDS = 8 * (8 * QL + 4);      // per wave
+template <int G, int L> constexpr uint32_t group_lds_dwords() { return (64 / G) * (G * L + 4); }      // per wave: rsa_group_wave's Llimb
+constexpr uint32_t QUAD_LDS_DWORDS = group_lds_dwords<4, QL>(), OCT_LDS_DWORDS = group_lds_dwords<8, QL>(), OCT9_LDS_DWORDS = group_lds_dwords<8, QL9>();
 
 // Waves per SIMD of the hash / modexp launch.  The kernel needs 153 registers (the SHA-256 pair routine's), which would let
 // three waves share a SIMD; ZKE_STAGE_WAVES is both the least the compiler must allow AND the most the hardware may place
@@ -39,7 +41,8 @@ constexpr uint32_t QUAD_LDS_DWORDS = 16 * (4 * QL + 4), OCT_LDS_DWORDS = 8 * (8 
 #endif
 template <int T>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(ZKE_STAGE_WAVES, ZKE_STAGE_WAVES))) void hash_modexp_kernel(StageArgs A) {
-  static_assert(sha256_pair_lds_bytes<T>() >= 2 * 4 * QUAD_LDS_DWORDS && sha256_pair_lds_bytes<T>() >= 2 * 4 * OCT_LDS_DWORDS,
+  static_assert(sha256_pair_lds_bytes<T>() >= 2 * 4 * QUAD_LDS_DWORDS && sha256_pair_lds_bytes<T>() >= 2 * 4 * OCT_LDS_DWORDS &&
+                sha256_pair_lds_bytes<T>() >= 2 * 4 * OCT9_LDS_DWORDS,
                 "the RSA roles borrow the launch's LDS");
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   uint32_t b = blockIdx.x;
@@ -73,7 +76,12 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(ZKE_STAGE_W
     return;
   }
   b -= A.g_quad;
-  if (!A.debug_skip_rsa) rsa_group_wave<8>(A.rsa, A.n, (2 * b + wave) * 8, lds + wave * OCT_LDS_DWORDS, nullptr, 0, nullptr, A.em_out, A.cache, A.meta);
+  if (b < A.g_oct) {
+    if (!A.debug_skip_rsa) rsa_group_wave<8>(A.rsa, A.n, (2 * b + wave) * 8, lds + wave * OCT_LDS_DWORDS, nullptr, 0, nullptr, A.em_out, A.cache, A.meta);
+    return;
+  }
+  b -= A.g_oct;
+  if (!A.debug_skip_rsa) rsa_group_wave<8, QL9>(A.rsa, A.n, (2 * b + wave) * 8, lds + wave * OCT9_LDS_DWORDS, nullptr, 0, nullptr, A.em_out, A.cache, A.meta);
 }
 
 }  // namespace zke

@@ -945,12 +945,13 @@ __device__ __forceinline__ uint32_t decode_rsa_key(const Str& k, RsaJob* J, uint
 }
 
 // Which RSA routine takes this key's signatures: RSA_F_QUAD / RSA_F_OCT when the lane-group kernel for its size is part of
-// the batch's launch (mask bit 0 / 1) and the key's Montgomery constants are in the cache — the modulus [np, np + nl) of
+// the batch's launch (mask bit 0 / 1; bit 2: the launch has the eight-lane role for moduli <= 2048 bits, RSA_F_OCT9, in place of
+// the four-lane one) and the key's Montgomery constants are in the cache — the modulus [np, np + nl) of
 // the DER key compared limb by limb with the entry, so a hit is exact; 0 = the one-signature-per-wave routine (which
 // fills the cache for the next batch).
 __device__ __forceinline__ uint32_t rsa_route(const Str& k, uint32_t np, uint32_t nl, uint32_t bits, const KeyCacheEntry* cache, uint32_t mask) {
   // (the bits above RSA_F_* say why a key was not routed: zke_debug_out.rsa_route shows them to the tests)
-  if (bits < 512 || !(mask & (bits <= 2048 ? 1u : 2u))) return 0x100;
+  if (bits < 512 || !(mask & (bits <= 2048 ? 5u : 2u))) return 0x100;
   const uint32_t lane = (uint32_t)lane_id();
   auto limb = [&](uint32_t L) -> uint32_t {       // little-endian 32-bit limb L of the big-endian modulus
     uint32_t v = 0;
@@ -968,7 +969,7 @@ __device__ __forceinline__ uint32_t rsa_route(const Str& k, uint32_t np, uint32_
   if (st != 2u) return 0x200;                                       // not cached (yet)
   if (eb != bits) return 0x400;                                     // the slot belongs to another key
   const bool same = m0 == l0 && m1 == l1;
-  return __ballot(!same) == 0 ? (bits <= 2048 ? (uint32_t)RSA_F_QUAD : (uint32_t)RSA_F_OCT) : 0x400u;
+  return __ballot(!same) == 0 ? (bits > 2048 ? (uint32_t)RSA_F_OCT : (mask & 4u) ? (uint32_t)RSA_F_OCT9 : (uint32_t)RSA_F_QUAD) : 0x400u;
 }
 
 // base64 STANDARD decode of tagbuf[off, off+n) into J->sig (right-aligned).  false = not canonical base64.
@@ -1474,10 +1475,10 @@ __device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i
     M->state = ST_CAND;
     // an Ed25519 candidate leaves the RSA job inactive; ed25519_email_kernel verifies it
     const uint32_t jf = (cand_flags & ZKE_F_ED25519) ? 0u : (RSA_F_ACTIVE | ((cand_flags & ZKE_F_SHA1) ? (uint32_t)RSA_F_SHA1 : 0u) |
-                                                                  (A.route_mask ? M->rsa_route & (RSA_F_QUAD | RSA_F_OCT) : 0u));
+                                                                  (A.route_mask ? M->rsa_route & RSA_F_GROUPS : 0u));
     J->flags = jf;
     M->em_ok = 0;
-    if ((jf & RSA_F_ACTIVE) && !(jf & (RSA_F_QUAD | RSA_F_OCT)) && A.wave_list) A.wave_list[atomicAdd(A.wave_count, 1u)] = i;
+    if ((jf & RSA_F_ACTIVE) && !(jf & RSA_F_GROUPS) && A.wave_list) A.wave_list[atomicAdd(A.wave_count, 1u)] = i;
   }
   // ---- body canonicalisation of the candidate (cfdkim hash::compute_body_hash), same wave, no launch boundary
   canon_body_wave(B, i, 0, cand_flags, body_off, raw.len - body_off, cand_len_tag, L.stage, false, bucket, cand_hdr_len);   // parsing is over: the staged head is dead

@@ -40,6 +40,8 @@ enum : uint32_t {
   RSA_F_SHA1 = 2,               // EMSA block carries the SHA-1 DigestInfo and a 20-byte hash (a=rsa-sha1)
   RSA_F_QUAD = 4,               // set by rsa_verify_kernel: rsa_group_kernel<4> (four lanes per signature) takes this job
   RSA_F_OCT = 8,                // ... rsa_group_kernel<8> (eight lanes per signature: moduli of 2049..4096 bits)
+  RSA_F_OCT9 = 16,              // ... rsa_group_kernel<8, 9> (eight lanes of nine limbs: moduli <= 2048 bits, in place of RSA_F_QUAD)
+  RSA_F_GROUPS = RSA_F_QUAD | RSA_F_OCT | RSA_F_OCT9,
 };
 
 // The limb layout of the lane-group routine (rsa_quad.hip.h), here because the cache entry holds a constant in it.

@@ -69,7 +69,7 @@ __device__ __forceinline__ bool rsa_wave(const RsaJob* __restrict__ jobs, uint32
   const int lane = threadIdx.x & 63;
   const RsaJob* J = jobs + job;
   const uint32_t flags = J->flags, k = J->k, bits = J->bits;
-  if (flags & (RSA_F_QUAD | RSA_F_OCT)) return false;
+  if (flags & RSA_F_GROUPS) return false;
 
   Big<NL> nn, s;
 #pragma unroll

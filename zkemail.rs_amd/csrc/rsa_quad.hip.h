@@ -40,7 +40,15 @@ namespace zke {
 // QL = 18 limbs per lane, QBITS = 29 bits per limb, QMASK: rsa.hip.h (KeyCacheEntry holds R^2 mod n in this layout)
 static_assert(2 * QL < (1 << (64 - 2 * QBITS)), "2 QL products of <= 2^(2 QBITS) and their carries (< one product more) must fit a 64-bit column");
 static_assert(4 * QL * QBITS >= 2048 + 2 && 8 * QL * QBITS >= 4096 + 2, "R > 4n for four lanes (<= 2048 bits) and eight (<= 4096)");
-struct QBig { uint32_t v[QL]; };             // lane p of the group: limbs QL p .. QL p + QL - 1
+// The routines below take the limbs per lane as a parameter L: <4, QL> and <8, QL> are the two above, <8, QL9> is the same 72 limbs
+// as <4, QL> on eight lanes — same radix R = 2^2088, same cached constant (KeyCacheEntry::rrq, limb t in lane t / L), so a key
+// cached for one is cached for the other.  A step then has 2 * 9 multiplies instead of 36: a block of nine steps is 315 VALU
+// instructions and a product eight of them, against four blocks of 921 (profiles/oct9_static.txt) — the launch's RSA chain alone
+// measures 82 us instead of 130 — for 1.4 times the instructions per signature: the routine for an engine that cannot keep the
+// chip's issue slots busy anyway.  A column lives through 2 L = 18 products: more room in its 64 bits, not less.
+constexpr int QL9 = QL / 2;
+static_assert(8 * QL9 == 4 * QL, "eight lanes of QL9 limbs hold the number four lanes of QL limbs hold: one radix, one cached constant");
+template <int L> struct QBigL { uint32_t v[L]; };             // lane p of the group: limbs L p .. L p + L - 1
 
 // Lane groups of G = 4 (one DPP quad: 72 limbs, moduli <= 2048 bits) or G = 8 (half a DPP row: 144 limbs, <= 4096 bits).
 // (bound_ctrl on the full-mask moves: lanes without a source read 0 and the destination needs no initial value)
@@ -54,6 +62,18 @@ template <int G> __device__ __forceinline__ uint32_t g_rotdown(uint32_t x, int p
   const uint32_t a = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x101 /*row_shl:1*/, 0xf, 0xf, true);
   const uint32_t b = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x117 /*row_shr:7*/, 0xf, 0xf, true);
   return p == 7 ? b : a;
+}
+// Eight lanes, where a rotation costs two moves and a select: what the top lane would receive is never used (the multiplier copy:
+// a digit block that wraps round reaches lane 0 after G rotations, and G - 1 are consumed) or is zero by construction (the
+// hand-over: lane 0's finished columns are multiples of 2^QBITS), so ONE move does — row_shl:1; lanes 7 and 15 read the next
+// group's lane 0 or nothing, and the hand-over masks them with a per-lane mask that is zero there.
+__device__ __forceinline__ uint32_t g8_shiftdown(uint32_t x) {                        // lane p <- lane p+1 for p < 7; lane 7: unspecified
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x101 /*row_shl:1*/, 0xf, 0xf, true);
+}
+// ... and a broadcast whose mask rides on the first of its two moves (the quad_perm one has a full mask and no old value)
+__device__ __forceinline__ uint32_t g8_bcast0_masked(uint32_t x, uint32_t qm) {
+  const uint32_t q = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x00 /*quad_perm:[0,0,0,0]*/, 0xf, 0xf, true) & qm;
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)q, (int)q, 0x114 /*row_shr:4*/, 0xf, 0xA /*lanes 4-7, 12-15*/, false);
 }
 template <int G> __device__ __forceinline__ uint32_t g_fromprev(uint32_t x) {      // lane p <- lane p-1 (lane 0: callers mask it)
   if (G == 4) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x90 /*quad_perm:[0,0,1,2]*/, 0xf, 0xf, true);
@@ -78,43 +98,47 @@ __device__ __forceinline__ uint32_t qmask_vgpr() {
 //   With the mask in a VGPR both `and`s fold into their DPP moves for four lanes (v_and_b32_dpp): 792 VALU per block instead of 828.
 // (The four blocks written out, each reading its digit from lane blk of b with one quad_perm move and no rotating copy B, are 786
 // per block and as fast alone, but 25 KB of code: in flight they give back the gain — profiles/rsa_trim_bench_ab.txt.)
-template <int G>
-__device__ __forceinline__ void qmont_columns(uint64_t (&W)[2 * QL], const QBig& a, const QBig& b, const QBig& n, uint32_t ninv, int p) {
+template <int G, int L>
+__device__ __forceinline__ void qmont_columns(uint64_t (&W)[2 * L], const QBigL<L>& a, const QBigL<L>& b, const QBigL<L>& n, uint32_t ninv, int p) {
 #pragma unroll
-  for (int j = 0; j < 2 * QL; j++) W[j] = 0;
+  for (int j = 0; j < 2 * L; j++) W[j] = 0;
   const uint32_t qm = qmask_vgpr();
-  QBig B = b;
+  constexpr bool LEAN = G == 8 && L == QL9;          // the one-move rotations and the masked broadcast above; <8, QL> keeps its code
+  uint32_t qm_recv = p == G - 1 ? 0u : QMASK;        // LEAN: the top lane receives nothing
+  asm("" : "+v"(qm_recv));
+  QBigL<L> B = b;
 #pragma unroll 1
   for (int blk = 0; blk < G; blk++) {
     // QL steps: multiplier digits QL blk + r, held by lane 0 of the group after blk rotations of B
 #pragma unroll
-    for (int r = 0; r < QL; r++) {
+    for (int r = 0; r < L; r++) {
       const uint32_t bd = g_bcast0<G>(B.v[r]);
 #pragma unroll
-      for (int k = 0; k < QL; k++)           // column r + QL - 1 is touched here for the first time in this block (r > 0)
-        W[k + r] = (uint64_t)a.v[k] * bd + ((k == QL - 1 && r > 0) ? 0ull : W[k + r]);
-      const uint32_t m = g_bcast0<G>((uint32_t)W[r] * ninv) & qm;           // lane 0's column r is the lowest live limb
+      for (int k = 0; k < L; k++)           // column r + QL - 1 is touched here for the first time in this block (r > 0)
+        W[k + r] = (uint64_t)a.v[k] * bd + ((k == L - 1 && r > 0) ? 0ull : W[k + r]);
+      const uint32_t m = LEAN ? g8_bcast0_masked((uint32_t)W[r] * ninv, qm)
+                              : g_bcast0<G>((uint32_t)W[r] * ninv) & qm;    // lane 0's column r is the lowest live limb
 #pragma unroll
-      for (int k = 0; k < QL; k++) W[k + r] = (uint64_t)n.v[k] * m + W[k + r];
+      for (int k = 0; k < L; k++) W[k + r] = (uint64_t)n.v[k] * m + W[k + r];
       W[r + 1] += W[r] >> QBITS;           // lane 0: the column is now a multiple of 2^QBITS; other lanes: a partial carry (< 2^35)
     }
     // the window moves up QL limbs: finished low columns go one lane down (lane 0's are zero mod 2^QBITS and reach the top lane)
 #pragma unroll
-    for (int j = 0; j < QL; j++) {
-      const uint32_t recv = g_rotdown<G>((uint32_t)W[j], p) & qm;
-      W[j] = W[QL + j] + recv;
+    for (int j = 0; j < L; j++) {
+      const uint32_t recv = LEAN ? g8_shiftdown((uint32_t)W[j]) & qm_recv : g_rotdown<G>((uint32_t)W[j], p) & qm;
+      W[j] = W[L + j] + recv;
     }
 #pragma unroll
-    for (int r = 0; r < QL; r++) B.v[r] = g_rotdown<G>(B.v[r], p);
+    for (int r = 0; r < L; r++) B.v[r] = LEAN ? g8_shiftdown(B.v[r]) : g_rotdown<G>(B.v[r], p);
   }
 }
 
 // columns -> limbs.  CROSS cross-lane passes: 1 leaves limbs <= 2^QBITS (good enough as an operand), G - 1 is exact.
-template <int G, int CROSS>
-__device__ __forceinline__ void qnorm(QBig& out, const uint64_t (&W)[2 * QL], int p) {
+template <int G, int L, int CROSS>
+__device__ __forceinline__ void qnorm(QBigL<L>& out, const uint64_t (&W)[2 * L], int p) {
   uint64_t c = 0;
 #pragma unroll
-  for (int j = 0; j < QL; j++) {
+  for (int j = 0; j < L; j++) {
     const uint64_t t = W[j] + c;
     out.v[j] = (uint32_t)t & QMASK;
     c = t >> QBITS;                                             // t < 2^64: c < 2^35
@@ -128,7 +152,7 @@ __device__ __forceinline__ void qnorm(QBig& out, const uint64_t (&W)[2 * QL], in
     out.v[0] = (uint32_t)t0 & QMASK;
     uint32_t c32 = (uint32_t)(t0 >> QBITS);                    // t0 < 2^29 + 2^35: c32 < 2^7 (first pass), then 0 or 1
 #pragma unroll
-    for (int j = 1; j < QL; j++) {
+    for (int j = 1; j < L; j++) {
       const uint32_t t = out.v[j] + c32;
       out.v[j] = t & QMASK;
       c32 = t >> QBITS;
@@ -153,13 +177,14 @@ __device__ __forceinline__ uint32_t qlimb_of(const uint8_t* field, uint32_t t) {
 // One wave: NG = 64 / G signatures.  job0 = the wave's first job.  Llimb: NG x (G * QL + 4) dwords of LDS private to the wave.
 //   meta != nullptr: em_ok / em_tail of each signature go to EmailMeta for verdict_kernel (the batch pipeline);
 //   hash_base != nullptr: the digest is at hand, ok_out[job] = full verification.
-template <int G>
+template <int G, int L = QL>
 __device__ __forceinline__ void rsa_group_wave(const RsaJob* __restrict__ jobs, uint32_t n, uint32_t job0, uint32_t* Llimb_raw,
                                                const uint8_t* __restrict__ hash_base, size_t hash_stride,
                                                uint32_t* __restrict__ ok_out, uint8_t* __restrict__ em_out,
                                                const KeyCacheEntry* cache, EmailMeta* meta) {
-  constexpr int NG = 64 / G, LIMBS = G * QL;
-  constexpr uint32_t MY_FLAG = G == 4 ? RSA_F_QUAD : RSA_F_OCT;
+  constexpr int NG = 64 / G, LIMBS = G * L;
+  constexpr uint32_t MY_FLAG = G == 4 ? RSA_F_QUAD : L == QL ? RSA_F_OCT : RSA_F_OCT9;
+  constexpr uint32_t EM_BYTES = LIMBS == 4 * QL ? 256u : 512u;          // the EM field the limbs cover: RSA-2048 / RSA-4096
   uint32_t (*Llimb)[LIMBS + 4] = reinterpret_cast<uint32_t (*)[LIMBS + 4]>(Llimb_raw);
 #ifndef ZKE_QUAD_PRIO
 #define ZKE_QUAD_PRIO 3
@@ -178,18 +203,18 @@ __device__ __forceinline__ void rsa_group_wave(const RsaJob* __restrict__ jobs, 
   // (the signature and the cached constant are operands of one product each: they are read where they are used — s twice — and
   // hold no registers through the seventeen products between: 36 loads per lane, once per signature)
   const KeyCacheEntry* E = cache;
-  QBig nn, acc;
+  QBigL<L> nn, acc;
 #pragma unroll
-  for (int j = 0; j < QL; j++) { nn.v[j] = 0; acc.v[j] = 0; }
+  for (int j = 0; j < L; j++) { nn.v[j] = 0; acc.v[j] = 0; }
   uint32_t ninv = 0, kbytes = 0;
   if (act) {
     // the front end found this modulus in the cache (all limbs compared) before it set MY_FLAG; entries are immutable
     const uint32_t n0 = __builtin_bswap32(*(const uint32_t*)(J->mod + 508)), n1 = __builtin_bswap32(*(const uint32_t*)(J->mod + 504));
     E = cache + key_cache_slot(n0, n1);
 #pragma unroll
-    for (int j = 0; j < QL; j++) {
-      nn.v[j] = qlimb_of(J->mod, QL * p + j);
-      acc.v[j] = qlimb_of(J->sig, QL * p + j);
+    for (int j = 0; j < L; j++) {
+      nn.v[j] = qlimb_of(J->mod, L * p + j);
+      acc.v[j] = qlimb_of(J->sig, L * p + j);
     }
     ninv = ld_agent(&E->ninv) & QMASK;
     kbytes = J->k;
@@ -201,51 +226,51 @@ __device__ __forceinline__ void rsa_group_wave(const RsaJob* __restrict__ jobs, 
     // s >= n: per lane the sign of the highest differing limb; the highest lane of the group that differs decides.
     int c = 0;
 #pragma unroll
-    for (int j = QL - 1; j >= 0; j--) c = c != 0 ? c : (int)(acc.v[j] > nn.v[j]) - (int)(acc.v[j] < nn.v[j]);
+    for (int j = L - 1; j >= 0; j--) c = c != 0 ? c : (int)(acc.v[j] > nn.v[j]) - (int)(acc.v[j] < nn.v[j]);
     const uint64_t gmask0 = (G == 4 ? 0xFull : 0xFFull);
     const uint64_t gtg = (__ballot(c > 0) >> (G * grp)) & gmask0, ltg = (__ballot(c < 0) >> (G * grp)) & gmask0;
     const bool reject = act && (J->sig_len != kbytes || gtg >= ltg);
     if (reject) {
       take = false;
 #pragma unroll
-      for (int j = 0; j < QL; j++) acc.v[j] = 0;
+      for (int j = 0; j < L; j++) acc.v[j] = 0;
     }
   }
 
   // s^65537 in 18 products: s R (into the Montgomery domain), sixteen squarings -> s^65536 R, and the last product takes
   // the PLAIN s: (s^65536 R) s / R = s^65537 — out of the domain without a nineteenth product by one.  That value is
   // < n + n^2 / R (a < 2n, s < n, R > 2^40 n): one conditional subtraction makes it exact.
-  uint64_t W[2 * QL];
+  uint64_t W[2 * L];
 #pragma unroll 1
   for (int step = 0; step < 17; step++) {
-    QBig b = acc;
+    QBigL<L> b = acc;
     if (step == 0) {
 #pragma unroll
-      for (int j = 0; j < QL; j++) b.v[j] = act ? ld_agent(&E->rrq[QL * p + j]) : 0u;
+      for (int j = 0; j < L; j++) b.v[j] = act ? ld_agent(&E->rrq[L * p + j]) : 0u;
     }
-    qmont_columns<G>(W, acc, b, nn, ninv, p);
-    qnorm<G, 1>(acc, W, p);
+    qmont_columns<G, L>(W, acc, b, nn, ninv, p);
+    qnorm<G, L, 1>(acc, W, p);
   }
   {
-    QBig s;
+    QBigL<L> s;
 #pragma unroll
-    for (int j = 0; j < QL; j++) s.v[j] = take ? qlimb_of(J->sig, QL * p + j) : 0u;
-    qmont_columns<G>(W, acc, s, nn, ninv, p);
+    for (int j = 0; j < L; j++) s.v[j] = take ? qlimb_of(J->sig, L * p + j) : 0u;
+    qmont_columns<G, L>(W, acc, s, nn, ninv, p);
   }
-  qnorm<G, G - 1>(acc, W, p);                 // exact limbs
+  qnorm<G, L, G - 1>(acc, W, p);                 // exact limbs
   {
     // acc >= n?  Per lane the sign of the highest differing limb; the highest differing lane of the group decides, and the
     // lanes below a lane decide the borrow it starts with.
     int c = 0;
 #pragma unroll
-    for (int j = QL - 1; j >= 0; j--) c = c != 0 ? c : (int)(acc.v[j] > nn.v[j]) - (int)(acc.v[j] < nn.v[j]);
+    for (int j = L - 1; j >= 0; j--) c = c != 0 ? c : (int)(acc.v[j] > nn.v[j]) - (int)(acc.v[j] < nn.v[j]);
     const uint32_t gm = (G == 4 ? 0xFu : 0xFFu);
     const uint32_t gtg = (uint32_t)(__ballot(c > 0) >> (G * grp)) & gm, ltg = (uint32_t)(__ballot(c < 0) >> (G * grp)) & gm;
     if (gtg >= ltg) {                         // EM + n -> EM (never for a signature that verifies: EM < n / 2^15 there)
       const uint32_t low = (1u << p) - 1u;
       uint32_t borrow = (ltg & low) > (gtg & low) ? 1u : 0u;
 #pragma unroll
-      for (int j = 0; j < QL; j++) {
+      for (int j = 0; j < L; j++) {
         const uint32_t t = acc.v[j] - nn.v[j] - borrow;
         acc.v[j] = t & QMASK;
         borrow = t >> 31;
@@ -256,7 +281,7 @@ __device__ __forceinline__ void rsa_group_wave(const RsaJob* __restrict__ jobs, 
   // EMSA-PKCS1-v1_5 (rsa 0.9.6 pkcs1v15_sign_unpad), limb compares and a byte walk through LDS: the structure in front of the digest is
   // checked here; the digest bytes are compared now (hash_base) or handed to verdict_kernel (meta)
 #pragma unroll
-  for (int j = 0; j < QL; j++) Llimb[grp][QL * p + j] = acc.v[j];
+  for (int j = 0; j < L; j++) Llimb[grp][L * p + j] = acc.v[j];
   if (p < 4) Llimb[grp][LIMBS + p] = 0;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -272,22 +297,22 @@ __device__ __forceinline__ void rsa_group_wave(const RsaJob* __restrict__ jobs, 
     // limbs: the digest, DigestInfo, the 00 separator and the limb that straddles that edge at the bottom, and the limbs
     // around 01 and the top 00.  emsa_byte stays the judge of every byte walked, the single statement of the padding.
     // (k < tLen + 11 makes the ranges meaningless: that verdict is refused below whatever they give, and the walk stays
-    // inside the 64 G bytes.)  tests/test_rsa_group_trim_model.py has the classifier for every k.
+    // inside the EM_BYTES the limbs cover.)  tests/test_rsa_group_trim_model.py has the classifier for every k.
     const uint32_t tlen = sha1 ? 35u : 51u;
     const uint32_t ff_lo = (8 * (tlen + 1) + QBITS - 1) / QBITS, ff_hi = (8 * (kbytes - 2)) / QBITS;
     const uint32_t z_lo = (8 * kbytes + QBITS - 1) / QBITS;
 #pragma unroll
-    for (int j = 0; j < QL; j++) {
-      const uint32_t t = QL * (uint32_t)p + j;
+    for (int j = 0; j < L; j++) {
+      const uint32_t t = L * (uint32_t)p + j;
       if (t >= ff_lo && t < ff_hi) bad = bad || acc.v[j] != QMASK;
       else if (t >= z_lo) bad = bad || acc.v[j] != 0;
     }
     const uint32_t walk_lo = (QBITS * ff_lo + 7) / 8, walk_hi = (QBITS * ff_hi) / 8;
-    const uint32_t walk_top = (QBITS * z_lo + 7) / 8, walk_end = walk_top < 64u * G ? walk_top : 64u * G;
+    const uint32_t walk_top = (QBITS * z_lo + 7) / 8, walk_end = walk_top < EM_BYTES ? walk_top : EM_BYTES;
     // the bottom stretch and the top one; parity / debug, where every byte is written out, keeps the full walk instead
 #pragma unroll 1
     for (int part = 0; part < (em_out ? 1 : 2); part++) {
-      const uint32_t from = part == 1 ? walk_hi : 0u, to = em_out ? 64u * G : part == 0 ? walk_lo : walk_end;
+      const uint32_t from = part == 1 ? walk_hi : 0u, to = em_out ? EM_BYTES : part == 0 ? walk_lo : walk_end;
       for (uint32_t i = from + (uint32_t)p; i < to; i += G) {        // little-endian byte index, the group's lanes side by side
         const uint32_t t = (8 * i) / QBITS, sh = 8 * i - QBITS * t;   // t + 1 <= LIMBS - 1; the + 4 words stay as zeroed padding
         const uint64_t two = (uint64_t)Llimb[grp][t] | ((uint64_t)Llimb[grp][t + 1] << QBITS);
@@ -301,9 +326,9 @@ __device__ __forceinline__ void rsa_group_wave(const RsaJob* __restrict__ jobs, 
         if (em_out) em_out[(size_t)job * 512 + 511 - i] = (uint8_t)got;
       }
     }
-    if (em_out && G == 4) {
+    if (em_out && EM_BYTES == 256) {
 #pragma unroll
-      for (int z = 0; z < 16; z++) *(uint32_t*)(em_out + (size_t)job * 512 + 64 * p + 4 * z) = 0;     // upper half of the slot
+      for (int z = 0; z < 64 / G; z++) *(uint32_t*)(em_out + (size_t)job * 512 + (256 / G) * p + 4 * z) = 0;     // upper half of the slot
     }
   }
   const uint64_t badm = __ballot(bad), tbadm = __ballot(tail_bad);
@@ -315,14 +340,14 @@ __device__ __forceinline__ void rsa_group_wave(const RsaJob* __restrict__ jobs, 
   }
 }
 
-template <int G>
+template <int G, int L = QL>
 __global__ __launch_bounds__(64) void rsa_group_kernel(const RsaJob* __restrict__ jobs, uint32_t n,
                                                        const uint8_t* __restrict__ hash_base, size_t hash_stride,
                                                        uint32_t* __restrict__ ok_out, uint8_t* __restrict__ em_out,
                                                        const KeyCacheEntry* cache, EmailMeta* meta) {
-  constexpr int NG = 64 / G, LIMBS = G * QL;
+  constexpr int NG = 64 / G, LIMBS = G * L;
   __shared__ uint32_t Llimb[NG * (LIMBS + 4)];
-  rsa_group_wave<G>(jobs, n, blockIdx.x * NG, Llimb, hash_base, hash_stride, ok_out, em_out, cache, meta);
+  rsa_group_wave<G, L>(jobs, n, blockIdx.x * NG, Llimb, hash_base, hash_stride, ok_out, em_out, cache, meta);
 }
 
 // (not launched by the engine, which runs the routine inside hash_modexp_kernel: instantiated only for the compiler's resource
@@ -330,6 +355,7 @@ __global__ __launch_bounds__(64) void rsa_group_kernel(const RsaJob* __restrict_
 #ifdef ZKE_LIST_GROUP_KERNELS
 template __global__ void rsa_group_kernel<4>(const RsaJob*, uint32_t, const uint8_t*, size_t, uint32_t*, uint8_t*, const KeyCacheEntry*, EmailMeta*);
 template __global__ void rsa_group_kernel<8>(const RsaJob*, uint32_t, const uint8_t*, size_t, uint32_t*, uint8_t*, const KeyCacheEntry*, EmailMeta*);
+template __global__ void rsa_group_kernel<8, QL9>(const RsaJob*, uint32_t, const uint8_t*, size_t, uint32_t*, uint8_t*, const KeyCacheEntry*, EmailMeta*);
 #endif
 
 }  // namespace zke
