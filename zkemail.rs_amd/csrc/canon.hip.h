@@ -303,15 +303,51 @@ __device__ __forceinline__ void canon_body_wave(const BatchDev& B, uint32_t i, u
 // ---- verdict of one signature round, by the wave that ran the e-mail's RSA job -----------------------
 struct FinArgs { BatchDev b; uint32_t round, max_rounds; uint32_t* pending; uint32_t debug_skip_rsa; };   // debug_skip_rsa: ablation experiments only
 
-// The verdict of e-mail i, by ONE LANE (64 e-mails per wave at once: the loads of an e-mail's state are a dependent
-// chain of a microsecond or so, which a wave walking its e-mails one after the other would pay 64 times over).
+// Everything the verdict of e-mail i is decided from, fetched by its lane in ONE go: the e-mail's EmailMeta as 16-byte loads, the
+// record's two hashes, the external-input flag.  Every address is known when the lane starts, so none of these loads has to
+// wait for another (read field by field where each is needed, behind short-circuit conditions, they were some thirty round trips
+// to L2 one behind the other: most of the verdict launch's time).  Indexed by constants only: the words stay in registers.
+constexpr uint32_t META_WORDS = sizeof(EmailMeta) / 4;
+static_assert(sizeof(EmailMeta) % 16 == 0 && offsetof(EmailMeta, bh) % 4 == 0, "EmailMeta is read as 16-byte words (hipMalloc aligns the array)");
+static_assert(offsetof(zke_result, header_hash) == offsetof(zke_result, body_hash) + 32, "the two hashes are read as one run of 16 words");
+struct VerdictIn {
+  uint32_t m[META_WORDS];     // EmailMeta, word for word (ZKE_MW)
+  uint32_t hash[16];          // zke_result::body_hash, then header_hash, as stored
+  uint32_t ext_null;
+};
+#define ZKE_MW(field) (offsetof(EmailMeta, field) / 4)
+// M, R: the e-mail's EmailMeta and record; ext: its external-input flag, or nullptr
+__device__ __forceinline__ void verdict_load(const EmailMeta* M, const zke_result* R, const uint8_t* ext, VerdictIn& V) {
+  const uint4* mp = reinterpret_cast<const uint4*>(M);
+  const uint32_t* hp = reinterpret_cast<const uint32_t*>(R->body_hash);
+#pragma unroll
+  for (uint32_t k = 0; k < META_WORDS / 4; k++) {
+    const uint4 q = mp[k];
+    V.m[4 * k] = q.x; V.m[4 * k + 1] = q.y; V.m[4 * k + 2] = q.z; V.m[4 * k + 3] = q.w;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < 16; k++) V.hash[k] = hp[k];
+  V.ext_null = ext ? (uint32_t)*ext : 0u;
+}
+// rsa 0.9.6 pkcs1v15 verify, last step: EM's trailing digest (little-endian limbs, left in EmailMeta by the RSA role together with
+// em_ok = EM has the EMSA shape) against the header hash as stored.  All eight limbs are compared, no way out in between.
+__device__ __forceinline__ bool verdict_rsa_ok(const VerdictIn& V) {
+  const uint32_t flags = V.m[ZKE_MW(flags)];
+  const uint32_t* hw = V.hash + 8;
+  bool ok8 = true, ok5 = true;
+#pragma unroll
+  for (uint32_t l = 0; l < 8; l++) ok8 = ok8 & (V.m[ZKE_MW(em_tail) + l] == __builtin_bswap32(hw[7 - l]));
+#pragma unroll
+  for (uint32_t l = 0; l < 5; l++) ok5 = ok5 & (V.m[ZKE_MW(em_tail) + l] == __builtin_bswap32(hw[4 - l]));
+  return (V.m[ZKE_MW(state)] == ST_CAND) & !(flags & ZKE_F_ED25519) & (V.m[ZKE_MW(em_ok)] != 0) & ((flags & ZKE_F_SHA1) ? ok5 : ok8);
+}
+
+// The verdict of the e-mail of M and R, by ONE LANE (16 e-mails per wave at once), decided from what verdict_load fetched.
 // rsa_ok: the RSA outcome (EM's shape and digest both fit); ed_ok / ed_key_bad: the Ed25519 stage's.
-// Returns true when the e-mail now waits for another signature round (ST_PENDING).
-__device__ __forceinline__ bool verdict_lane(const FinArgs& A, uint32_t i, bool rsa_ok, bool ed_ok, bool ed_key_bad) {
-  const BatchDev& B = A.b;
-  EmailMeta* M = B.meta + i;
-  zke_result* R = B.results + i;
-  const uint32_t state = M->state;
+// `round`: the signature round this is (A.round is the launch's first).  Returns true when the e-mail now waits for another one (ST_PENDING).
+__device__ __forceinline__ bool verdict_lane(const FinArgs& A, uint32_t round, EmailMeta* M, zke_result* R, const VerdictIn& V, bool rsa_ok, bool ed_ok,
+                                             bool ed_key_bad) {
+  const uint32_t state = V.m[ZKE_MW(state)], flags = V.m[ZKE_MW(flags)];
   uint32_t status, detail;
   if (ed_key_bad) {
     // DkimPublicKey::try_from_bytes (email.rs:28-29) fails before any signature is looked at: nothing of the
@@ -322,56 +358,58 @@ __device__ __forceinline__ bool verdict_lane(const FinArgs& A, uint32_t i, bool 
 #pragma unroll
     for (int k = 0; k < 8; k++) { ((uint32_t*)R->body_hash)[k] = 0; ((uint32_t*)R->header_hash)[k] = 0; }
   } else if (state == ST_FINAL) {
-    status = M->status; detail = M->detail;
+    status = V.m[ZKE_MW(status)]; detail = V.m[ZKE_MW(detail)];
   } else {
     // cfdkim verify_email_header: bh compare (as base64 strings), b= decode, RSA verify
     uint32_t err = 0;
     {
-      // base64 of the body hash (32 bytes -> 44 chars, SHA-1: 20 -> 28), three bytes / four characters at a time, against bh=
-      const bool sha1 = (M->flags & ZKE_F_SHA1) != 0;
+      // base64 of the body hash (32 bytes -> 44 chars, SHA-1: 20 -> 28), three bytes / four characters at a time, against bh=:
+      // both as the words they were loaded as, all eleven groups (the last four only count for SHA-256)
+      const bool sha1 = (flags & ZKE_F_SHA1) != 0;
       const uint32_t hl = sha1 ? 20u : 32u, nch = sha1 ? 28u : 44u;
-      const uint8_t* h = R->body_hash;
-      bool bad = M->bh_len != nch;
+      bool bad = V.m[ZKE_MW(bh_len)] != nch;
       auto b64c = [](uint32_t six) -> uint32_t {
         return six < 26 ? 'A' + six : (six < 52 ? 'a' + (six - 26) : (six < 62 ? '0' + (six - 52) : (six == 62 ? '+' : '/')));
       };
-      for (uint32_t g = 0; g < nch / 4; g++) {
-        const uint32_t b0 = h[3 * g], b1 = (3 * g + 1 < hl) ? h[3 * g + 1] : 0u, b2 = (3 * g + 2 < hl) ? h[3 * g + 2] : 0u;
+      auto hbyte = [&](uint32_t j) -> uint32_t { return (V.hash[j >> 2] >> (8 * (j & 3))) & 0xFFu; };      // j: a constant, once unrolled
+#pragma unroll
+      for (uint32_t g = 0; g < 11; g++) {
+        const uint32_t b0 = hbyte(3 * g), b1 = (3 * g + 1 < hl) ? hbyte(3 * g + 1) : 0u, b2 = (3 * g + 2 < hl) ? hbyte(3 * g + 2) : 0u;
         const uint32_t v = (b0 << 16) | (b1 << 8) | b2;
         uint32_t c3 = b64c(v & 63);
         if (4 * g + 3 == nch - 1) c3 = '=';                  // 32 and 20 are 2 mod 3: one pad character, the last
         const uint32_t want = b64c(v >> 18) | (b64c((v >> 12) & 63) << 8) | (b64c((v >> 6) & 63) << 16) | (c3 << 24);
-        const uint32_t have = (uint32_t)M->bh[4 * g] | ((uint32_t)M->bh[4 * g + 1] << 8) | ((uint32_t)M->bh[4 * g + 2] << 16) | ((uint32_t)M->bh[4 * g + 3] << 24);
-        bad = bad || want != have;
+        const uint32_t have = V.m[ZKE_MW(bh) + g];           // bh[4 g .. 4 g + 3], little-endian as stored
+        bad = bad | ((4 * g < nch) & (want != have));
       }
       if (bad) err = ZKE_D_BODY_HASH_MISMATCH;
     }
     bool unsupported_here = false;
-    if (!err && !M->sig_b64_ok) err = ZKE_D_SIG_B64;
-    if (!err && M->even_modulus) { err = ZKE_D_U_EVEN_MODULUS; unsupported_here = true; }
-    const bool sig_ok = (M->flags & ZKE_F_ED25519) ? ed_ok : rsa_ok;
+    if (!err && !V.m[ZKE_MW(sig_b64_ok)]) err = ZKE_D_SIG_B64;
+    if (!err && V.m[ZKE_MW(even_modulus)]) { err = ZKE_D_U_EVEN_MODULUS; unsupported_here = true; }
+    const bool sig_ok = (flags & ZKE_F_ED25519) ? ed_ok : rsa_ok;
     if (!err && !sig_ok) err = ZKE_D_SIG_MISMATCH;
     if (!err) {
       status = ZKE_OK; detail = 0;
-      R->sig_index = M->cand_sig_index;
-    } else if (M->cand_total > A.round + 1) {
-      if (A.round + 1 < A.max_rounds) {
+      R->sig_index = V.m[ZKE_MW(cand_sig_index)];
+    } else if (V.m[ZKE_MW(cand_total)] > round + 1) {
+      if (round + 1 < A.max_rounds) {
         if (unsupported_here) M->unsupported = err;
         M->state = ST_PENDING; M->cand_err = err; R->status = ZKE_DKIM_NOT_PASS; R->detail = err;
         atomicAdd(A.pending, 1u);          // statistics only: the next round runs in this launch (verdict.hip.h)
         return true;
       }
       status = ZKE_UNSUPPORTED; detail = ZKE_D_U_TOO_MANY_SIGS;
-      R->sig_index = M->last_touched_sig;
+      R->sig_index = V.m[ZKE_MW(last_touched_sig)];
     } else {
-      R->sig_index = M->last_touched_sig;
-      const uint32_t uns = unsupported_here ? err : M->unsupported;
+      R->sig_index = V.m[ZKE_MW(last_touched_sig)];
+      const uint32_t uns = unsupported_here ? err : V.m[ZKE_MW(unsupported)];
       if (uns) { status = ZKE_UNSUPPORTED; detail = uns; }
-      else { status = ZKE_DKIM_NOT_PASS; detail = M->post_err ? M->post_err : err; }
+      else { status = ZKE_DKIM_NOT_PASS; detail = V.m[ZKE_MW(post_err)] ? V.m[ZKE_MW(post_err)] : err; }
     }
     M->state = ST_FINAL; M->status = status; M->detail = detail;
   }
-  if (status == ZKE_OK && B.ext_null && B.ext_null[i]) status = ZKE_EXTERNAL_INPUT_NULL;   // circuits.rs:24
+  if (status == ZKE_OK && V.ext_null) status = ZKE_EXTERNAL_INPUT_NULL;   // circuits.rs:24
   R->status = status; R->detail = detail;
   if (status != ZKE_OK && status != ZKE_EXTERNAL_INPUT_NULL) {
 #pragma unroll
@@ -379,5 +417,4 @@ __device__ __forceinline__ bool verdict_lane(const FinArgs& A, uint32_t i, bool 
   }
   return false;
 }
-
 }  // namespace zke

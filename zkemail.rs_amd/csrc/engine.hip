@@ -472,7 +472,9 @@ int zke_engine_create(const zke_options* opt, zke_engine** out) {
   e->stream = e->slots[0]->stream;
   if (!o.disable_key_cache) {
     const size_t kc_bytes = (size_t)KEY_CACHE_SLOTS * sizeof(KeyCacheEntry);
-    if (e->key_cache.ensure(kc_bytes) || hipMemset(e->key_cache.p, 0, kc_bytes) != hipSuccess) {
+    // (cleared on slot 0's stream and waited for: a hipMemset on device memory is not waited for, nor ordered in front of the slots' streams)
+    if (e->key_cache.ensure(kc_bytes) || hipMemsetAsync(e->key_cache.p, 0, kc_bytes, e->stream) != hipSuccess ||
+        hipStreamSynchronize(e->stream) != hipSuccess) {
       zke_engine_destroy(e);
       return fail(nullptr, ZKE_E_NOMEM, "key cache allocation");
     }

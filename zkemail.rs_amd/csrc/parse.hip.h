@@ -1485,7 +1485,8 @@ __device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i
 }
 
 #ifndef ZKE_PARSE_PRIO
-#define ZKE_PARSE_PRIO 0
+#define ZKE_PARSE_PRIO 3         // the front end's waves at the priority of the SHA-256 and RSA waves they share a SIMD with (ZKE_SHA_PRIO, ZKE_QUAD_PRIO):
+                                 // those issue a three-operand instruction every 4.3 cycles, which leaves a wave at priority 0 next to nothing
 #endif
 #ifndef ZKE_PARSE_WAVES
 #define ZKE_PARSE_WAVES 5        // waves per SIMD the front end is compiled for: 96 registers, no spills (at 6 — 80 registers — it spills 300 B per

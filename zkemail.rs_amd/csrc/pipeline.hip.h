@@ -12,28 +12,31 @@ struct StageTimer {
 };
 
 // Length-bucket counters start a batch at zero (the verdict launch of the slot's previous batch clears them): a fresh
-// allocation is cleared here.
-int ensure_zeroed(DevBuf& b, size_t need) {
+// allocation is cleared here — on `s`, the stream the batch that reads them is launched on.  Not with hipMemset: on device memory
+// that is a fill on the null stream which the call does not wait for, and the slots' streams are non-blocking ones that the null
+// stream does not order either, so the first kernel of the batch could meet the counters as the allocator left them.
+int ensure_zeroed(DevBuf& b, size_t need, hipStream_t s) {
   const void* old = b.p;
   if (int r = b.ensure(need)) return r;
-  if (b.p != old && hipMemset(b.p, 0, b.cap) != hipSuccess) return ZKE_E_DEVICE;
+  if (b.p != old && hipMemsetAsync(b.p, 0, b.cap, s) != hipSuccess) return ZKE_E_DEVICE;
   return 0;
 }
 
 // Workspace of one slot for batches of up to n e-mails / raw_total raw bytes (P regex parts; with_regex: the buffers of
 // the canonicalize_signed_email pass too).  Grows only: in steady state — or after zke_engine_reserve — this allocates nothing.
-int ensure_workspace(zke_engine* e, Slot& w, uint32_t n, uint64_t raw_total, bool with_regex, uint32_t P, bool want_em) {
+// s: the stream the slot's next batch runs on; counters allocated here are cleared on it (ensure_zeroed).
+int ensure_workspace(zke_engine* e, Slot& w, uint32_t n, uint64_t raw_total, bool with_regex, uint32_t P, bool want_em, hipStream_t s) {
   const uint32_t n_pad = (n + 63) & ~63u;
   int r = 0;
   const size_t scratch_bytes = 2 * (size_t)raw_total + (size_t)(n + 1) * SCR_PER_EMAIL + 256;
   if ((r = w.meta.ensure((size_t)n * sizeof(EmailMeta))) || (r = w.rsa_jobs.ensure((size_t)n * sizeof(RsaJob))) ||
       (r = w.sha_jobs.ensure((size_t)4 * n_pad * sizeof(ShaJob))) || (r = w.rsa_ok.ensure((size_t)n * 4)) ||
-      (r = ensure_zeroed(w.sha_order, (size_t)2 * (SHA_ORDER_KIND_WORDS + n_pad) * 4)) ||
+      (r = ensure_zeroed(w.sha_order, (size_t)2 * (SHA_ORDER_KIND_WORDS + n_pad) * 4, s)) ||
       (r = w.scratch_off.ensure((size_t)(n + 1) * 16)) || (r = w.scratch.ensure(scratch_bytes)))
     return fail(e, r, "workspace allocation");
   if (!w.pending.p) {       // counters: [0] e-mails pending another signature round, [2] length of the wave-routine job list (rsa_ok)
     if ((r = w.pending.ensure(64))) return fail(e, r, "workspace allocation");
-    HIPCHK(e, hipMemset(w.pending.p, 0, 64));
+    HIPCHK(e, hipMemsetAsync(w.pending.p, 0, 64, s));
   }
   if (want_em && (r = w.em_dbg.ensure((size_t)n * 512))) return fail(e, r, "workspace allocation");
   if (with_regex) {
@@ -138,7 +141,7 @@ int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t ra
   const uint32_t n_pad = (n + 63) & ~63u;
   const uint32_t P = in->with_regex ? in->n_header_parts + in->n_body_parts : 0;
   int r = 0;
-  if ((r = ensure_workspace(e, w, n, raw_total, in->with_regex != 0, P, want_em))) return r;
+  if ((r = ensure_workspace(e, w, n, raw_total, in->with_regex != 0, P, want_em, s))) return r;
   uint64_t* scratch_off = w.scratch_off.as<uint64_t>();
   uint64_t* clean_off = scratch_off + (n + 1);
 
@@ -364,7 +367,7 @@ int zke_engine_reserve(zke_engine* e, uint32_t max_n, uint64_t max_raw_total, ui
   }
   if (max_n)
     for (Slot* w : e->slots)
-      if (int r = ensure_workspace(e, *w, max_n, max_raw_total, max_regex_parts != 0, max_regex_parts, false)) return r;
+      if (int r = ensure_workspace(e, *w, max_n, max_raw_total, max_regex_parts != 0, max_regex_parts, false, w->stream)) return r;
   if (max_n && max_regex_parts)          // the capture workspace: four groups of 32 bytes per part is what a larger extraction regrows from
     for (Slot* w : e->slots)
       if (int r = ensure_capture_buffers(e, w->cb, max_n, max_regex_parts, 4 * max_regex_parts, (size_t)max_n * max_regex_parts * 128, true)) return r;
@@ -375,7 +378,8 @@ int zke_engine_reserve(zke_engine* e, uint32_t max_n, uint64_t max_raw_total, ui
   // Then one empty e-mail through the whole pipeline of every slot: kernel code, kernel arguments and the slot's workspace
   // pages have all been touched once before the first real batch arrives.
   if (int r = e->misc.ensure(1024)) return fail(e, r, "workspace allocation");
-  HIPCHK(e, hipMemset(e->misc.p, 0, 1024));
+  HIPCHK(e, hipMemsetAsync(e->misc.p, 0, 1024, e->stream));      // every slot's warm-up batch below reads these zeros: they are there
+  HIPCHK(e, hipStreamSynchronize(e->stream));                    // before the first of them is launched (see ensure_zeroed)
   zke_batch wb{};
   wb.n = 1;
   uint8_t* z = e->misc.as<uint8_t>();            // 1 KB of zeros: CSR offsets {0, 0}, empty blobs, key type "rsa"

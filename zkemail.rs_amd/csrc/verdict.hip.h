@@ -88,6 +88,18 @@ __device__ __noinline__ void next_round(const EdVerdictArgs& A, uint32_t round, 
   }
 }
 
+// The verdict of one e-mail (M, R, ext: verdict_load) in signature round `round`, by one lane (the 16 verdict lanes of a wave at once): every load first
+// (verdict_load), every decision from registers.  `mine`: the Ed25519 stage's result for this e-mail (3: it had no work in this
+// round).  Called once per round, so what a later round's front end, hashes and RSA role have rewritten is read again.  A real
+// call, as next_round is: inlined, its seventy words in flight compete with what the Ed25519 stage keeps in registers across the
+// kernel's loop, and the compiler spills each load behind a wait of its own — one round trip after the other again.
+__device__ __noinline__ bool verdict_round(const EdVerdictArgs& A, uint32_t round, EmailMeta* M, zke_result* R, const uint8_t* ext, uint32_t mine) {
+  VerdictIn V;
+  verdict_load(M, R, ext, V);
+  const bool ed_bad = (mine == 0) || (mine == 3 && V.m[ZKE_MW(ed_key_bad)] != 0);      // decided in round 0
+  return verdict_lane(A.fin, round, M, R, V, verdict_rsa_ok(V), mine == 2, ed_bad);
+}
+
 #ifndef ZKE_VERDICT_WAVES
 #define ZKE_VERDICT_WAVES 2      // waves per SIMD the verdict launch is compiled for: at 1 it takes 364 registers (256 + 108 AGPRs), which
                                  // keeps the waves of other launches off its SIMD — RSA batches 26.8 M e-mails/s instead of 27.8 M,
@@ -113,7 +125,7 @@ __global__ __launch_bounds__(64, ZKE_VERDICT_WAVES) void ed_verdict_kernel(EdVer
   if (blockIdx.x == 0 && B.order)              // the hash stage has consumed the length buckets: counters back to zero for the slot's next batch
     for (uint32_t k = 0; k < 2; k++)
       for (uint32_t c = (uint32_t)lane; c < SHA_CLASSES; c += 64) B.order[sha_order_cnt(k) + c] = 0;
-  FinArgs fin = A.fin;
+  uint32_t round = A.fin.round;
   uint64_t active = 0;                                  // verdict lanes (= e-mails base + lane) this wave still works on
   for (uint32_t j = 0; j < VERDICT_EMAILS_PER_WAVE; j++) if (base + j < B.n) active |= 1ull << j;
   for (;;) {
@@ -123,21 +135,25 @@ __global__ __launch_bounds__(64, ZKE_VERDICT_WAVES) void ed_verdict_kernel(EdVer
     uint32_t ed_res = 3;                                // 3 = no Ed25519 work for this e-mail in this round
     {
       const uint32_t j = (uint32_t)lane >> 2, i = base + j;
+      // the four words a quad decides its work by, requested together (behind one another's conditions they were four round trips)
+      uint32_t q_type = 0, q_key_ok = 0, q_state = 0, q_flags = 0;
+      const bool qact = (active >> j) & 1;
+      if (qact) {
+        const EmailMeta* M = B.meta + i;
+        q_type = B.key_type[i]; q_key_ok = M->key_ok; q_state = M->state; q_flags = M->flags;
+      }
       bool work = false, have_sig = false;
       // (quads without work run along on bytes that are always there: the start of the result records)
       const uint8_t* key = reinterpret_cast<const uint8_t*>(B.results);
       const uint8_t* msg = key;
       const uint8_t* sig = key;
-      if ((active >> j) & 1) {
-        const EmailMeta* M = B.meta + i;
-        if (!A.skip_ed && B.key_type[i] == ZKE_KEY_ED25519 && M->key_ok == 2) {
-          const bool cand = M->state == ST_CAND && (M->flags & ZKE_F_ED25519);
-          if (fin.round == 0 || cand) {               // the key itself is checked in round 0
-            const RsaJob* J = B.rsa + i;
-            work = true;
-            have_sig = cand && J->sig_len == 64;      // a b= of any other length cannot be an Ed25519 signature
-            key = B.key + B.key_off[i]; msg = B.results[i].header_hash; sig = J->sig + (512 - 64);
-          }
+      if (qact && !A.skip_ed && q_type == ZKE_KEY_ED25519 && q_key_ok == 2) {
+        const bool cand = q_state == ST_CAND && (q_flags & ZKE_F_ED25519);
+        if (round == 0 || cand) {                     // the key itself is checked in round 0
+          const RsaJob* J = B.rsa + i;
+          work = true;
+          have_sig = cand && J->sig_len == 64;        // a b= of any other length cannot be an Ed25519 signature
+          key = B.key + B.key_off[i]; msg = B.results[i].header_hash; sig = J->sig + (512 - 64);
         }
       }
       if (__ballot(work)) {
@@ -157,23 +173,13 @@ __global__ __launch_bounds__(64, ZKE_VERDICT_WAVES) void ed_verdict_kernel(EdVer
     bool again = false;
     if (lane < (int)VERDICT_EMAILS_PER_WAVE && ((active >> lane) & 1)) {
       const uint32_t i = base + (uint32_t)lane;
-      const EmailMeta* M = B.meta + i;
-      const bool ed_bad = (mine == 0) || (mine == 3 && M->ed_key_bad != 0);      // decided in round 0
-      bool rsa_ok = false;
-      if (M->state == ST_CAND && !(M->flags & ZKE_F_ED25519) && M->em_ok) {
-        // rsa 0.9.6 pkcs1v15 verify, last step: EM's trailing digest (little-endian limbs) against the header hash as stored
-        const uint32_t* hw = (const uint32_t*)B.results[i].header_hash;
-        const uint32_t hl4 = (M->flags & ZKE_F_SHA1) ? 5u : 8u;
-        rsa_ok = true;
-        for (uint32_t l = 0; l < hl4; l++) rsa_ok = rsa_ok && M->em_tail[l] == __builtin_bswap32(hw[hl4 - 1 - l]);
-      }
-      again = verdict_lane(fin, i, rsa_ok, mine == 2, ed_bad);
+      again = verdict_round(A, round, B.meta + i, B.results + i, B.ext_null ? B.ext_null + i : nullptr, mine);
     }
     active = __ballot(again);
     if (!active) return;
     // ---- the next signature round of the e-mails still undecided (verdict_lane has checked that one is allowed)
-    fin.round++;
-    next_round(A, fin.round, active, base);
+    round++;
+    next_round(A, round, active, base);
     wave_publish();
   }
 }
