@@ -615,6 +615,10 @@ int zke_engine_join(zke_engine* e, void* stream);
  * reports all zeros. */
 int zke_get_timings(zke_engine* e, zke_timings* t);
 int zke_get_slot_timings(zke_engine* e, uint32_t slot, zke_timings* t);
+/* Which two-wave SHA-256 routine the engine's hash launches take as it stands now: 1 the ring (two K+W buffers), 0 the pair
+ * (one).  Chosen like the eight-lane RSA role — min(slots that exist, GPU_MAX_HW_QUEUES as read at creation) <= 4 takes the
+ * ring — or forced by ZKE_SHA_RING = 0 / 1 in the environment at zke_engine_create.  Negative: an error code. */
+int zke_engine_sha_ring(zke_engine* e);
 /* Enable per-launch HIP-event timing (adds event records between the launches). */
 int zke_set_timing(zke_engine* e, int enabled);
 

@@ -71,6 +71,7 @@ CPP_EXAMPLE = os.path.join(ROOT, "tests", "cpp", "mirror_test")
 CPP_SIGSCAN = os.path.join(ROOT, "tests", "cpp", "sigscan_test")
 CPP_KEYREC = os.path.join(ROOT, "tests", "cpp", "keyrec_test")
 ED_PROBE = os.path.join(ROOT, "tests", "cpp", "ed_probe")
+SHA_PROBE = os.path.join(ROOT, "tests", "cpp", "sha_probe")
 
 
 def _build_cpp(exe: str, force: bool) -> str:
@@ -96,6 +97,8 @@ def build_cpp_example(force: bool = False) -> str:
     build_cpp_keyrec(force)
     if os.path.exists(ED_PROBE + ".hip"):       # test infrastructure that lives in tests/: a tree whose tests/ does not carry the probe
         build_ed_probe(force)                   # has nothing that runs it, and the three programs below do not depend on it
+    if os.path.exists(SHA_PROBE + ".hip"):
+        build_sha_probe(force)
     return _build_cpp(CPP_EXAMPLE, force)
 
 
@@ -126,6 +129,26 @@ def build_ed_probe(force: bool = False) -> str:
         sys.stderr.write(r.stdout + r.stderr)
         raise RuntimeError("hipcc failed building tests/cpp/ed_probe")
     return ED_PROBE
+
+
+def build_sha_probe(force: bool = False, stamps: bool = True) -> str:
+    """tests/cpp/sha_probe: the two-role SHA-256 routines of csrc/sha256.hip.h alone on 1 024 messages of 4 KB, timed
+    (tools/sha_timeline.py).  Stand-alone like the Ed25519 probe.  `stamps`: compiled with ZKE_SHA_PROBE, the routines record where
+    their waves ran and when they met each barrier; without, tests/cpp/sha_probe_plain runs the code the library runs."""
+    src = SHA_PROBE + ".hip"
+    if not os.path.exists(src):
+        raise RuntimeError("tests/cpp/sha_probe.hip is missing")
+    exe = SHA_PROBE if stamps else SHA_PROBE + "_plain"
+    deps = [src] + [d for d in _deps(CSRC) if d.endswith(".h")]
+    if not force and not _newer(exe, deps):
+        return exe
+    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
+           "-Wall", "-Wno-unused-function", "-o", exe, src] + (["-DZKE_SHA_PROBE"] if stamps else [])
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout + r.stderr)
+        raise RuntimeError("hipcc failed building tests/cpp/sha_probe")
+    return exe
 
 
 if __name__ == "__main__":

@@ -164,6 +164,9 @@ struct zke_engine {
                                     // batches of this engine can be on the chip at once (rsa_route_mask)
   int rsa_oct9 = -1;                // moduli <= 2048 bits on eight lanes of nine limbs instead of four of eighteen (rsa_quad.hip.h):
                                     // -1 by the in-flight bound (rsa_route_mask), 0 never, 1 always (ZKE_RSA_OCT9 in the environment)
+  int sha_ring = -1;                // the two-wave SHA-256 groups run sha256_ring_group (two K+W buffers, 45 KB of LDS per group) instead of
+                                    // sha256_pair_group (one, 28 KB): -1 by the same in-flight bound (sha_takes_ring), 0 never, 1 always
+                                    // (ZKE_SHA_RING in the environment)
 #ifdef ZKE_DEV_KNOBS
   uint32_t debug_skip_rsa = 0, debug_skip_ed = 0, debug_parse_stop = 0, debug_skip_launch = 0;
 #else
@@ -189,13 +192,23 @@ bool sha_takes_pairs(const zke_engine* e, uint32_t groups) {
   return e->opt.sha_mapping ? e->opt.sha_mapping == 2 : groups <= SHA_PAIR_MAX_GROUPS;
 }
 
+// Which two-wave routine.  The ring takes the K+W hand-over off the rounds wave's chain (sha256.hip.h) for 17 KB more LDS per group: the
+// choice where a batch's time is its dependency chain, i.e. with at most SHA_RING_MAX_IN_FLIGHT batches on the chip — min(slots that
+// exist now, hardware queues), as for the eight-lane RSA role (rsa_route_mask).  With more the chip is issue- and LDS-bound: the pair.
+constexpr uint32_t SHA_RING_MAX_IN_FLIGHT = 4;
+bool sha_takes_ring(const zke_engine* e) {
+  if (e->sha_ring >= 0) return e->sha_ring == 1;
+  return std::min<uint32_t>((uint32_t)e->slots.size(), e->hw_queues) <= SHA_RING_MAX_IN_FLIGHT;
+}
+
 int launch_sha(zke_engine* e, const ShaJob* jobs, uint32_t n, hipStream_t s) {
   if (n == 0) return 0;
   // Few messages: the launch is as long as one wave's chain of compressions, so split the chain over two waves
   // (sha256_pair_kernel).  Many messages: the chip is full and the one-wave kernel does less LDS work per byte.
   const uint32_t groups = (n + 63) / 64;
   if (sha_takes_pairs(e, groups)) {
-    hipLaunchKernelGGL(sha256_pair_kernel<SHA_TILE>, dim3(groups), dim3(128), sha256_pair_lds_bytes<SHA_TILE>(), s, jobs, n);
+    if (sha_takes_ring(e)) hipLaunchKernelGGL(sha256_ring_kernel<SHA_TILE>, dim3(groups), dim3(128), sha256_ring_lds_bytes<SHA_TILE>(), s, jobs, n);
+    else hipLaunchKernelGGL(sha256_pair_kernel<SHA_TILE>, dim3(groups), dim3(128), sha256_pair_lds_bytes<SHA_TILE>(), s, jobs, n);
   } else {
     hipLaunchKernelGGL(sha256_batch_kernel<SHA_TILE>, dim3((n + 255) / 256), dim3(256), sha256_lds_bytes<SHA_TILE>(), s, jobs, n);
   }
@@ -271,7 +284,8 @@ uint32_t rsa_route_mask(const zke_engine* e, uint32_t n, bool any_big) {
 int launch_stage(zke_engine* e, const StageArgs& A, hipStream_t s) {
   const uint32_t grid = A.g_sha + A.g_wave + A.g_quad + A.g_oct + A.g_oct9;
   if (!grid) return 0;
-  hipLaunchKernelGGL(hash_modexp_kernel<SHA_TILE>, dim3(grid), dim3(128), sha256_pair_lds_bytes<SHA_TILE>(), s, A);
+  if (A.g_sha && sha_takes_ring(e)) hipLaunchKernelGGL(hash_modexp_ring_kernel<SHA_TILE>, dim3(grid), dim3(128), sha256_ring_lds_bytes<SHA_TILE>(), s, A);
+  else hipLaunchKernelGGL(hash_modexp_kernel<SHA_TILE>, dim3(grid), dim3(128), sha256_pair_lds_bytes<SHA_TILE>(), s, A);
   HIPCHK(e, hipGetLastError());
   return 0;
 }
@@ -330,6 +344,10 @@ int set_kernel_attrs(zke_engine* e) {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_pair_lds_bytes<SHA_TILE>()));
   HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&hash_modexp_kernel<SHA_TILE>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_pair_lds_bytes<SHA_TILE>()));
+  HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&sha256_ring_kernel<SHA_TILE>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_ring_lds_bytes<SHA_TILE>()));
+  HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&hash_modexp_ring_kernel<SHA_TILE>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_ring_lds_bytes<SHA_TILE>()));
   return 0;
 }
 
@@ -489,6 +507,7 @@ int zke_engine_create(const zke_options* opt, zke_engine** out) {
     // ZKE_RSA_OCT9 = 0 / 1 forces the RSA role for moduli <= 2048 bits.  Unlike the knobs below it is read by the shipped library,
     // not only under ZKE_DEV_KNOBS: the tests of the role and A/B runs of one build need it there (INTEGRATION.md §5 lists it).
     if (const char* r9 = getenv("ZKE_RSA_OCT9")) e->rsa_oct9 = atoi(r9) != 0 ? 1 : 0;
+    if (const char* sr = getenv("ZKE_SHA_RING")) e->sha_ring = atoi(sr) != 0 ? 1 : 0;      // likewise: which two-wave SHA-256 routine
   }
 #ifdef ZKE_DEV_KNOBS
   if (const char* rm = getenv("ZKE_RSA_QUAD_MIN")) e->rsa_quad_min = (uint32_t)atoi(rm);
@@ -522,6 +541,12 @@ void zke_engine_destroy(zke_engine* e) {
     e->pool = nullptr;
   }
   delete e;
+}
+
+int zke_engine_sha_ring(zke_engine* e) {
+  if (!e) return ZKE_E_ARG;
+  std::shared_lock<std::shared_mutex> sh(e->big);
+  return sha_takes_ring(e) ? 1 : 0;
 }
 
 const char* zke_last_error(const zke_engine* e) { (void)e; return g_err.c_str(); }

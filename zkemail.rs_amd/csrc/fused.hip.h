@@ -39,19 +39,24 @@ constexpr uint32_t QUAD_LDS_DWORDS = group_lds_dwords<4, QL>(), OCT_LDS_DWORDS =
 #ifndef ZKE_STAGE_WAVES
 #define ZKE_STAGE_WAVES 2
 #endif
-template <int T>
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(ZKE_STAGE_WAVES, ZKE_STAGE_WAVES))) void hash_modexp_kernel(StageArgs A) {
+// RING: the SHA-256 groups run sha256_ring_group (two K+W buffers: the launch then carries sha256_ring_lds_bytes of LDS, and the
+// RSA roles, whose workgroups are two waves as well, borrow the front of it as before).
+template <int T, bool RING>
+__device__ __forceinline__ void hash_modexp_body(const StageArgs& A, uint8_t* lds_raw) {
   static_assert(sha256_pair_lds_bytes<T>() >= 2 * 4 * QUAD_LDS_DWORDS && sha256_pair_lds_bytes<T>() >= 2 * 4 * OCT_LDS_DWORDS &&
                 sha256_pair_lds_bytes<T>() >= 2 * 4 * OCT9_LDS_DWORDS,
                 "the RSA roles borrow the launch's LDS");
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   uint32_t b = blockIdx.x;
   if (b < A.g_sha) {
-    if (!A.order) { sha256_pair_group<T>(A.sha, A.n_sha, b, lds_raw); return; }
+    if (!A.order) {
+      if (RING) sha256_ring_group<T>(A.sha, A.n_sha, b, lds_raw); else sha256_pair_group<T>(A.sha, A.n_sha, b, lds_raw);
+      return;
+    }
     // kind-major job list: groups [k gpk, (k + 1) gpk) hash kind k; bodies and header preimages by length class
     const uint32_t gpk = A.n_pad / 64, kind = b / gpk, gk = b - kind * gpk;
     const ShaOrder so{kind < 2 ? A.order + sha_order_cnt(kind) : nullptr, kind < 2 ? A.order + sha_order_key(kind, A.n_pad) : nullptr, A.n};
-    sha256_pair_group<T>(A.sha + (size_t)kind * A.n_pad, A.n_pad, gk, lds_raw, &so);
+    if (RING) sha256_ring_group<T>(A.sha + (size_t)kind * A.n_pad, A.n_pad, gk, lds_raw, &so);
+    else sha256_pair_group<T>(A.sha + (size_t)kind * A.n_pad, A.n_pad, gk, lds_raw, &so);
     return;
   }
   b -= A.g_sha;
@@ -82,6 +87,17 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(ZKE_STAGE_W
   }
   b -= A.g_oct;
   if (!A.debug_skip_rsa) rsa_group_wave<8, QL9>(A.rsa, A.n, (2 * b + wave) * 8, lds + wave * OCT9_LDS_DWORDS, nullptr, 0, nullptr, A.em_out, A.cache, A.meta);
+}
+
+template <int T>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(ZKE_STAGE_WAVES, ZKE_STAGE_WAVES))) void hash_modexp_kernel(StageArgs A) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  hash_modexp_body<T, false>(A, lds_raw);
+}
+template <int T>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(ZKE_STAGE_WAVES, ZKE_STAGE_WAVES))) void hash_modexp_ring_kernel(StageArgs A) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  hash_modexp_body<T, true>(A, lds_raw);
 }
 
 }  // namespace zke

@@ -348,6 +348,28 @@ __device__ __forceinline__ uint32_t sha_pick_job(const ShaOrder& O, uint32_t g, 
   return pick[SHA_CLASSES + lane];
 }
 
+// Dev knob (tests/cpp/sha_probe.hip, tools/sha_timeline.py): with ZKE_SHA_PROBE defined every wave of a two-role routine leaves
+// its HW_ID register (SIMD, CU, ...) and XCC id, and the waves of group 0 a clock stamp at each marked point of blocks 8..15, in
+// plain device arrays (ordinary vector stores).  The stamp's asm takes a chaining register in and out, so that the arithmetic in
+// front of it and behind it stays there.  Without the define the product kernels carry none of it.
+#ifdef ZKE_SHA_PROBE
+constexpr uint32_t SHA_PROBE_GROUPS = 1024, SHA_PROBE_BLK0 = 8, SHA_PROBE_BLKS = 8, SHA_PROBE_SLOTS = 8;
+__device__ uint32_t zke_sha_probe_hwid[SHA_PROBE_GROUPS][2][2];                              // [group][role]{HW_ID, XCC_ID}
+__device__ unsigned long long zke_sha_probe_stamp[2][SHA_PROBE_BLKS][SHA_PROBE_SLOTS];       // [role][block - 8][point]
+#define ZKE_SHA_WHERE() do { \
+    if ((threadIdx.x & 63) == 0 && group < SHA_PROBE_GROUPS) { \
+      zke_sha_probe_hwid[group][role][0] = __builtin_amdgcn_s_getreg(4 | (31 << 11)); \
+      zke_sha_probe_hwid[group][role][1] = __builtin_amdgcn_s_getreg(20 | (31 << 11)); } } while (0)
+#define ZKE_SHA_STAMP(kb, slot) do { \
+    unsigned long long t_; \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_), "+v"(st[0]) : : "memory"); \
+    if (group == 0 && (threadIdx.x & 63) == 0 && (kb) >= SHA_PROBE_BLK0 && (kb) < SHA_PROBE_BLK0 + SHA_PROBE_BLKS) \
+      zke_sha_probe_stamp[role][(kb) - SHA_PROBE_BLK0][slot] = t_; } while (0)
+#else
+#define ZKE_SHA_WHERE() ((void)0)
+#define ZKE_SHA_STAMP(kb, slot) ((void)0)
+#endif
+
 // The two waves of workgroup-local threads 0..127 hash messages [64 group, 64 group + 64); lds_raw: sha256_pair_lds_bytes<T>()
 // of 16-byte aligned LDS.  A device routine so that other work can share the launch (fused.hip.h); both waves of the
 // workgroup must call it (it uses __syncthreads()).
@@ -530,14 +552,18 @@ __device__ __forceinline__ void sha256_pair_group(const ShaJob* __restrict__ job
     // LDS instead of 45 KB and finds room on a CU that front-end waves of other batches have nearly filled): the
     // rounds wave pulls the block's 64 words into registers, barrier, then the feeder overwrites the buffer with the
     // next block's while the rounds run from registers, barrier.
+    ZKE_SHA_WHERE();
     for (uint32_t kb = 0; kb < max_nblk; kb++) {
       uint4 kq[16];
+      ZKE_SHA_STAMP(kb, 0);
       if (role == 1) {
         const uint4* src = (const uint4*)(kw + lane * SHA_KW_ROW);
 #pragma unroll
         for (int q = 0; q < 16; q++) kq[q] = src[q];
       }
+      ZKE_SHA_STAMP(kb, 1);
       __syncthreads();                                // the buffer has been read
+      ZKE_SHA_STAMP(kb, 2);
       if (role == 0) {
         const uint32_t nb = kb + 1;
         if (nb < max_nblk) {
@@ -561,7 +587,9 @@ __device__ __forceinline__ void sha256_pair_group(const ShaJob* __restrict__ job
         }
         if (kb < my_nblk) { st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h; }
       }
+      ZKE_SHA_STAMP(kb, 3);
       __syncthreads();                                // the next block's words are in the buffer
+      ZKE_SHA_STAMP(kb, 4);
     }
     if (role == 0) return;
   }
@@ -576,6 +604,228 @@ template <int T>
 __global__ __launch_bounds__(128) void sha256_pair_kernel(const ShaJob* __restrict__ jobs, uint32_t n) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   sha256_pair_group<T>(jobs, n, blockIdx.x, lds_raw);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The ring: the same two roles, TWO K+W buffers and ONE barrier per block.  In the pair loop the rounds wave pulls the
+// block's 64 words into registers in front of round 0 (16 ds_read_b128, a full lgkmcnt(0) drain, a barrier), and the feeder
+// may not touch the buffer before that: the hand-over sits on the chain, and in the first block of every tile the feeder's commit
+// + fetch + schedule is longer than the rounds, which then wait for it (profiles/sha_ring_timeline.txt: blocks of 4 700 and 5 840
+// ticks for 3 970 ticks of rounds).
+// Here the feeder writes block k + 1 into buffer (k + 1) & 1 while the rounds wave reads block k out of buffer k & 1 with no
+// barrier between its reads and its rounds: the 16 reads go out together and round 4 q waits for quad q alone, so only the first
+// quad's latency is in front of round 0.  45 KB of LDS per group instead of 28 KB, so it is the choice where few batches are on
+// the chip (engine.hip).  Groups with a SHA-1 job go to sha256_pair_group (its one-wave path); so does nothing else.
+
+template <int T>
+constexpr size_t sha256_ring_lds_bytes() { return sha256_pair_lds_bytes<T>() + 64 * SHA_KW_ROW * 4; }   // slab, descriptors, K+W x 2, job pick
+
+template <int T>
+__device__ __forceinline__ void sha256_ring_group(const ShaJob* __restrict__ jobs, uint32_t n, uint32_t group, uint8_t* lds_raw,
+                                                  const ShaOrder* order = nullptr) {
+  static_assert(T % 64 == 0 && T >= 64 && T <= 1024, "tile must be whole SHA blocks");
+  constexpr int ROW = T + 16;
+  constexpr int LPR = T / 16;
+  constexpr int RPI = 64 / LPR;
+  constexpr int KW_BUF = 64 * SHA_KW_ROW;          // dwords per buffer
+  __builtin_amdgcn_s_setprio(ZKE_SHA_PRIO);
+  const int lane = threadIdx.x & 63;
+  const int role = threadIdx.x >> 6;               // 0 feeder, 1 rounds
+  uint8_t* slab = lds_raw;
+  uint8_t* desc = slab + 64 * ROW;
+  uint32_t* kw = (uint32_t*)(desc + 64 * 16);      // [2 buffers][64 lanes][SHA_KW_ROW]
+  uint32_t* pick = kw + 2 * KW_BUF;                // 1 KB: sha_pick_job
+
+  uint32_t m = group * 64 + lane;
+  if (order && order->cnt) {                       // as sha256_pair_group
+    bool skip = false;
+    uint32_t mine = 0;
+    if (role == 0) {
+      mine = sha_pick_job(*order, group, m, pick, skip);
+      if (lane == 0) pick[SHA_CLASSES - 1] = skip ? 1u : 0u;
+      pick[SHA_CLASSES + lane] = mine;
+    }
+    __syncthreads();
+    if (pick[SHA_CLASSES - 1]) return;
+    m = pick[SHA_CLASSES + lane];
+    __syncthreads();
+  }
+  uint64_t my_src = 0, my_dst = 0;
+  uint32_t my_len = 0, my_nblk = 0, my_algo = 0;
+  if (m < n) {
+    ShaJob j = jobs[m];
+    my_src = j.src; my_dst = j.dst; my_len = j.len; my_algo = j.pad;
+    my_nblk = my_dst ? (my_len + 9 + 63) >> 6 : 0;
+  }
+  if (__ballot(my_algo != 0) != 0) {               // the same in both waves (same jobs): the pair routine's one-wave path.  It works the
+    sha256_pair_group<T>(jobs, n, group, lds_raw, order);      // picks out again (rsa-sha1 is rare) in its own, smaller layout of this LDS
+    return;
+  }
+  uint32_t max_nblk = my_nblk;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) max_nblk = max(max_nblk, (uint32_t)__shfl_xor((int)max_nblk, o));
+  max_nblk = __builtin_amdgcn_readfirstlane(max_nblk);
+
+  uint32_t st[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+  uint8_t* my_row = slab + lane * ROW;
+
+  if (role == 0) {
+    *(uint64_t*)(desc + lane * 16) = my_src;
+    *(uint32_t*)(desc + lane * 16 + 8) = my_len;
+    *(uint32_t*)(desc + lane * 16 + 12) = my_nblk;
+  }
+  // fetch / commit: tile staging and padding exactly as in sha256_pair_group
+  uint4 stage[LPR];
+  uint32_t live = 0;
+  auto fetch = [&](uint32_t blk0) {
+    const uint32_t tile_off = blk0 * 64;
+    live = 0;
+    uint4 dsc[LPR];
+#pragma unroll
+    for (int g = 0; g < LPR; g++) dsc[g] = *(const uint4*)(desc + (g * RPI + lane / LPR) * 16);
+#pragma unroll
+    for (int g = 0; g < LPR; g++) {
+      const int chunk = lane % LPR;
+      const uint64_t rsrc = ((uint64_t)dsc[g].y << 32) | dsc[g].x;
+      const uint32_t rlen = dsc[g].z;
+      const uint32_t rnblk = dsc[g].w;
+      const uint32_t off = tile_off + chunk * 16;
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (blk0 < rnblk) {
+        live |= 1u << g;
+        if (off + 16 <= rlen) {
+          { const u32x4_raw t4 = *(gptr_u4)(rsrc + off); v = make_uint4(t4.x, t4.y, t4.z, t4.w); }
+        } else if (off < rlen) {
+          gptr_u8 p = (gptr_u8)(rsrc + off);
+          uint32_t rem = rlen - off, t[4] = {0, 0, 0, 0};
+          for (uint32_t b = 0; b < rem; b++) t[b >> 2] |= (uint32_t)p[b] << (8 * (b & 3));
+          v = make_uint4(t[0], t[1], t[2], t[3]);
+        }
+      }
+      stage[g] = v;
+    }
+  };
+  auto commit = [&](uint32_t blk0) {
+    const uint32_t tile_off = blk0 * 64;
+#pragma unroll
+    for (int g = 0; g < LPR; g++) {
+      const int row = g * RPI + lane / LPR;
+      const int chunk = lane % LPR;
+      if (live & (1u << g)) *(uint4*)(slab + row * ROW + chunk * 16) = stage[g];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (blk0 < my_nblk) {
+      if (my_len >= tile_off && my_len < tile_off + T) my_row[my_len - tile_off] = 0x80;
+      const uint32_t last = my_nblk - 1;
+      if (last >= blk0 && last < blk0 + T / 64) {
+        const uint64_t bits = (uint64_t)my_len * 8;
+        uint32_t* tail = (uint32_t*)(my_row + (last - blk0) * 64 + 56);
+        tail[0] = __builtin_bswap32((uint32_t)(bits >> 32));
+        tail[1] = __builtin_bswap32((uint32_t)bits);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  };
+  // feeder: K+W of block kb into buffer kb & 1
+  auto sched = [&](uint32_t kb) {
+    uint32_t w[16];
+    const uint4* src = (const uint4*)(my_row + (kb % (T / 64)) * 64);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      uint4 v = src[q];
+      w[4 * q + 0] = __builtin_bswap32(v.x); w[4 * q + 1] = __builtin_bswap32(v.y);
+      w[4 * q + 2] = __builtin_bswap32(v.z); w[4 * q + 3] = __builtin_bswap32(v.w);
+    }
+    uint4* dst = (uint4*)(kw + (kb & 1) * KW_BUF + lane * SHA_KW_ROW);
+    uint32_t o4[4];
+#pragma unroll
+    for (int i = 0; i < 64; i++) {
+      uint32_t wi;
+      if (i < 16) {
+        wi = w[i];
+      } else {
+        const uint32_t w15 = w[(i - 15) & 15], w2 = w[(i - 2) & 15];
+        const uint32_t s0 = xor3(rotr32(w15, 7), rotr32(w15, 18), w15 >> 3);
+        const uint32_t s1 = xor3(rotr32(w2, 17), rotr32(w2, 19), w2 >> 10);
+        wi = w[i & 15] + s0 + w[(i - 7) & 15] + s1;
+        w[i & 15] = wi;
+      }
+      o4[i & 3] = wi + SHA_K[i];
+      if ((i & 3) == 3) dst[i >> 2] = make_uint4(o4[0], o4[1], o4[2], o4[3]);
+    }
+  };
+  // The block barrier: an s_barrier between LDS-only fences.  (__syncthreads() would also wait for the feeder's global
+  // fetches of the next tile, which only commit() needs.)
+  auto block_barrier = [&]() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+  };
+  if (role == 0 && max_nblk) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    fetch(0); commit(0);
+    if (T / 64 < max_nblk) fetch(T / 64);
+    sched(0);
+    if (T / 64 == 1 && 1 < max_nblk) commit(1);
+  }
+  ZKE_SHA_WHERE();
+  block_barrier();                                  // barrier -1: block 0's words are in buffer 0
+  // Both waves run exactly max_nblk steps and one barrier per step.  In step kb the rounds wave reads buffer kb & 1 and the
+  // feeder writes buffer (kb + 1) & 1.  That buffer was last read in step kb - 1, and every one of those reads had returned
+  // (the rounds that use them were done) before the rounds wave arrived at barrier kb - 1, the one in front of this step: a
+  // buffer is written only while no read of it is outstanding.  Barrier kb in turn puts the feeder's stores of step kb (its
+  // release fence waits for them) in front of the reads of step kb + 1.
+  for (uint32_t kb = 0; kb < max_nblk; kb++) {
+    ZKE_SHA_STAMP(kb, 0);
+    if (role == 0) {
+      // The feeder's tile work is spread over the tile's steps, so that no step of it is longer than the rounds (in the pair
+      // loop the first block of a tile carries commit + fetch + schedule, 5 100 cycles against the rounds' 3 900, and the
+      // rounds wave waits for it at every second barrier): the next tile's loads go out in front of the tile's first
+      // schedule, when the stage registers have just been emptied, and land in the slab behind its last schedule, when
+      // the slab's bytes have all been read — the loads still have a whole tile's steps to arrive.
+      const uint32_t nb = kb + 1;
+      if (nb < max_nblk) {
+        if (nb % (T / 64) == 0 && nb + T / 64 < max_nblk) fetch(nb + T / 64);
+        sched(nb);
+        if (nb % (T / 64) == T / 64 - 1 && nb + 1 < max_nblk) commit(nb + 1);
+      }
+    } else {
+      const uint4* src = (const uint4*)(kw + (kb & 1) * KW_BUF + lane * SHA_KW_ROW);
+      uint4 kq[16];                                 // all 16 reads go out here; each round group waits for its own quad only (lgkmcnt(N))
+#pragma unroll
+      for (int q = 0; q < 16; q++) kq[q] = src[q];
+      uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
+#pragma unroll
+      for (int i = 0; i < 64; i++) {
+        const uint32_t S1 = xor3(rotr32(e, 6), rotr32(e, 11), rotr32(e, 25));
+        const uint4 k4 = kq[i >> 2];
+        const uint32_t kwi = (i & 3) == 0 ? k4.x : (i & 3) == 1 ? k4.y : (i & 3) == 2 ? k4.z : k4.w;
+        const uint32_t t1 = (h + S1 + ch3(e, f, g)) + kwi;
+        const uint32_t S0 = xor3(rotr32(a, 2), rotr32(a, 13), rotr32(a, 22));
+        const uint32_t mj = maj3(a, b, c);
+        h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + S0 + mj;
+      }
+      if (kb < my_nblk) { st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h; }
+    }
+    ZKE_SHA_STAMP(kb, 1);
+    block_barrier();                                // barrier kb
+    ZKE_SHA_STAMP(kb, 2);
+  }
+  if (role == 0) return;
+  if (m < n && my_dst) {
+    gptr_out32 out = (gptr_out32)my_dst;
+#pragma unroll
+    for (int i = 0; i < 8; i++) out[i] = __builtin_bswap32(st[i]);
+  }
+}
+
+template <int T>
+__global__ __launch_bounds__(128) void sha256_ring_kernel(const ShaJob* __restrict__ jobs, uint32_t n) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  sha256_ring_group<T>(jobs, n, blockIdx.x, lds_raw);
 }
 
 }  // namespace zke

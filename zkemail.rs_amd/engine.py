@@ -156,6 +156,9 @@ def load_library(path: Optional[str] = None):
     lib.zke_select_keys_from_records.restype = C.c_int
     lib.zke_select_keys_from_records_async.argtypes = [vp, erp, C.c_uint32, vp, krp, C.c_uint32, vp, vp, kop, C.POINTER(C.c_uint64)]
     lib.zke_select_keys_from_records_async.restype = C.c_int
+    if hasattr(lib, "zke_engine_sha_ring"):         # (a ZKE_LIB build of an older tree, for an A/B run, has no such entry)
+        lib.zke_engine_sha_ring.argtypes = [vp]
+        lib.zke_engine_sha_ring.restype = C.c_int
     lib.zke_version.argtypes = []
     lib.zke_version.restype = C.c_char_p
     lib.zke_device_available.argtypes = []
@@ -178,6 +181,7 @@ EXPORTED_SYMBOLS = [
     "zke_extract_captures_async", "zke_capture_batch",
     "zke_scan_signatures", "zke_scan_signatures_async", "zke_select_keys", "zke_select_keys_async",
     "zke_decode_key_records", "zke_decode_key_records_async", "zke_select_keys_from_records", "zke_select_keys_from_records_async",
+    "zke_engine_sha_ring",
 ]
 
 
@@ -591,6 +595,12 @@ class Engine:
 
     def sync(self):
         self._check(self.lib.zke_engine_sync(self.h), "zke_engine_sync")
+
+    def sha_ring(self) -> bool:
+        """Whether the two-wave SHA-256 groups take the ring routine as the engine stands now (zke_engine_sha_ring)."""
+        r = self.lib.zke_engine_sha_ring(self.h)
+        self._check(min(r, 0), "zke_engine_sha_ring")
+        return r == 1
 
     def join(self, stream: int = 0):
         """Work enqueued on `stream` (a hipStream_t handle; 0 = the null stream) from now on runs behind every batch
