@@ -313,7 +313,8 @@ def _two_sigs(first_broken: bool = False) -> Case:
 
 def fold_offset_emails():
     """Header values whose folding CRLF, WSP runs and end fall on every offset modulo 64 (the device scans header
-    values 64 bytes per step), for both header canonicalisations; signed by the Python signer.
+    values 64 bytes per step), for both header canonicalisations; signed by the Python signer.  This sweeps the
+    canonicaliser's VALUE SCAN; the header split in front of it is swept by tests/hdr_split_cases.py.
     -> (emails, intermediates)"""
     k0 = K()
     emails, inter = [], []

@@ -1331,7 +1331,9 @@ __device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i
     // again (only short, hand-made b= values do) the excised header is written out once to region B of the scratch
     // slot — free until the body is canonicalised — and read back from there.
     const uint32_t bl = b_re - b_rs;
-    Str sv = v;
+    uint8_t* const tmp = regA + (((size_t)raw.len + PRE_SLACK + 15) & ~(size_t)15);    // region B: raw.len + 16 bytes
+    uint32_t tn = 0;
+    bool copied = false;
     if (bl) {
       const uint32_t fl = bl < 8 ? bl : 8;
       auto next_occurrence = [&](uint32_t from, uint32_t skip_at) -> uint32_t {      // first match at >= from, != skip_at
@@ -1350,11 +1352,8 @@ __device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i
       };
       // STRICTNESS SITE b_removes_own_span_only (oracle: build_preimage, same name).  Default: String::replace — every occurrence
       // of the raw b= value goes.  ZKE_STRICT_B_OWN_SPAN: only the tag's own span is emptied.
-      if ((A.strict & ZKE_STRICT_B_OWN_SPAN) || next_occurrence(0, b_rs) == NONE) {
-        sv.len = v.len - bl; sv.cut = b_rs; sv.skip = bl;
-      } else {
-        uint8_t* tmp = regA + (((size_t)raw.len + PRE_SLACK + 15) & ~(size_t)15);    // region B: raw.len + 16 bytes
-        uint32_t pos = 0, tn = 0;
+      if (!(A.strict & ZKE_STRICT_B_OWN_SPAN) && next_occurrence(0, b_rs) != NONE) {
+        uint32_t pos = 0;
         while (pos < v.len) {
           const uint32_t q = next_occurrence(pos, NONE);
           const uint32_t end = (q == NONE) ? v.len : q;
@@ -1366,9 +1365,16 @@ __device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i
         // the wave reads these bytes back with ordinary loads: make them visible past this CU's L1
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        sv = mkstr(tmp, tn);
+        copied = true;
       }
     }
+    // The view is put together here, behind the branches, not inside them.  With `sv` assigned in both arms of the test above the
+    // compiled code set the view's base to `tmp` on the "no second occurrence" path as well; bytes inside the staged head still
+    // came from LDS, so only a signature header BEYOND the staged head was read from the (empty) region B and failed to verify
+    // (tests/test_gpu_hdr_split.py, the S-hbm routes).  Check the join in the assembly when this is reshaped again.
+    Str sv = v;
+    if (copied) sv = mkstr(tmp, tn);
+    else if (bl) { sv.len = v.len - bl; sv.cut = b_rs; sv.skip = bl; }
     ZKE_DEV_STOP(6);
     // ---- header-hash preimage (cfdkim hash::compute_headers_hash)
     Out out{regA, 0, capA, false};
