@@ -881,6 +881,114 @@ impl Engine {
     }
 }
 
+/// One part of a capture extraction (`zke_capture_part`): the registered DFA pair that finds the match, the registered capture
+/// program of the same pattern, the groups wanted (`RegexPattern.capture_indices`).
+#[derive(Clone, Debug)]
+pub struct CapturePart {
+    pub dfa_id: u32,
+    pub prog_id: u32,
+    pub groups: Vec<u32>,
+}
+
+/// What `extract_captures_mapped` delivers: the records, the tables of `zke_capture_out` and the origins of `zke_capture_origin`.
+/// `spans` / `origin_spans`: `{start, end}` per (e-mail, requested group) in the part's haystack and in the haystack BEFORE the QP
+/// filter (the canonical body as it was signed); `origin_flags`: `ZKE_ORGF_SPLIT` / `ZKE_ORGF_PADDING`.
+#[derive(Clone)]
+pub struct MappedCaptures {
+    pub records: Vec<sys::zke_result>,
+    pub spans: Vec<u32>,
+    pub flags: Vec<u8>,
+    pub cap_off: Vec<u32>,
+    pub cap_str_off: Vec<u32>,
+    pub cap_blob: Vec<u8>,
+    pub origin_spans: Vec<u32>,
+    pub origin_flags: Vec<u8>,
+}
+
+impl Engine {
+    /// `remove_quoted_printable_soft_breaks` (`core/src/email.rs:61-86`) over a slice of bodies (`zke_qp_clean_batch`), both return
+    /// values per body: the body without its soft breaks, zero-padded to its length, and `index_map` with `usize::MAX` over the padding.
+    pub fn remove_quoted_printable_soft_breaks_batch(&self, bodies: &[&[u8]]) -> Result<Vec<(Vec<u8>, Vec<usize>)>, EngineError> {
+        let mut off: Vec<u64> = vec![0];
+        let mut blob: Vec<u8> = Vec::new();
+        for b in bodies {
+            blob.extend_from_slice(b);
+            off.push(blob.len() as u64);
+        }
+        let mut cleaned = vec![0u8; blob.len()];
+        let mut map = vec![0u32; blob.len()];
+        let mut kept = vec![0u32; bodies.len()];
+        // SAFETY: the three outputs hold off[n] bytes / entries and n entries; every pointer is alive until the synchronous call returns.
+        let rc = unsafe {
+            sys::zke_qp_clean_batch(self.raw, blob.as_ptr(), off.as_ptr(), bodies.len() as u32, cleaned.as_mut_ptr(), map.as_mut_ptr(), kept.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(self.last_error(rc));
+        }
+        Ok((0..bodies.len())
+            .map(|i| {
+                let (a, b) = (off[i] as usize, off[i + 1] as usize);
+                (cleaned[a..b].to_vec(), map[a..b].iter().map(|&x| if x == sys::ZKE_QP_NO_INDEX { usize::MAX } else { x as usize }).collect())
+            })
+            .collect())
+    }
+
+    /// `zke_extract_captures_mapped` over a slice of e-mails that share one part list: verify_email, canonicalise, QP clean, exactly
+    /// one match per part, the requested groups — and where each of them lies in the body as it was signed.
+    pub fn extract_captures_mapped(&self, emails: &[Email], header_parts: &[CapturePart], body_parts: &[CapturePart]) -> Result<MappedCaptures, EngineError> {
+        let n = emails.len();
+        let refs: Vec<sys::zke_email_ref> = emails.iter().map(email_ref).collect();
+        let part = |p: &CapturePart| sys::zke_capture_part { dfa_id: p.dfa_id, prog_id: p.prog_id, n_groups: p.groups.len() as u32, groups: p.groups.as_ptr() };
+        let hp: Vec<sys::zke_capture_part> = header_parts.iter().map(part).collect();
+        let bp: Vec<sys::zke_capture_part> = body_parts.iter().map(part).collect();
+        let g: usize = header_parts.iter().chain(body_parts).map(|p| p.groups.len()).sum();
+        let (np, ng) = (n * (hp.len() + bp.len()), n * g);
+        let mut m = MappedCaptures {
+            records: vec![zeroed_result(); n],
+            spans: vec![0; ng * 2],
+            flags: vec![0; ng],
+            cap_off: vec![0; np + 1],
+            cap_str_off: vec![0; ng + 1],
+            cap_blob: vec![0; ng * 32 + 1],
+            origin_spans: vec![0; ng * 2],
+            origin_flags: vec![0; ng],
+        };
+        for attempt in 0..2 {
+            let mut caps: sys::zke_capture_out = unsafe { std::mem::zeroed() };
+            caps.spans = m.spans.as_mut_ptr();
+            caps.spans_cap = ng * 2;
+            caps.flags = m.flags.as_mut_ptr();
+            caps.flags_cap = ng;
+            caps.cap_off = m.cap_off.as_mut_ptr();
+            caps.cap_off_cap = np + 1;
+            caps.cap_str_off = m.cap_str_off.as_mut_ptr();
+            caps.cap_str_off_cap = ng + 1;
+            caps.cap_blob = m.cap_blob.as_mut_ptr();
+            caps.cap_blob_cap = m.cap_blob.len();
+            let mut org: sys::zke_capture_origin = unsafe { std::mem::zeroed() };
+            org.spans = m.origin_spans.as_mut_ptr();
+            org.spans_cap = ng * 2;
+            org.flags = m.origin_flags.as_mut_ptr();
+            org.flags_cap = ng;
+            // SAFETY: every pointer refers into the arguments or `m`, alive and unmoved until the synchronous call returns.
+            let rc = unsafe {
+                sys::zke_extract_captures_mapped(self.raw, refs.as_ptr(), n as u32, hp.as_ptr(), hp.len() as u32, bp.as_ptr(), bp.len() as u32, m.records.as_mut_ptr(), &mut caps, &mut org)
+            };
+            if rc == sys::ZKE_E_NOMEM && attempt == 0 && caps.cap_blob_need > m.cap_blob.len() {
+                m.cap_blob = vec![0; caps.cap_blob_need];      // the strings need a larger blob: once more with the size the engine reports
+                continue;
+            }
+            if rc != 0 {
+                return Err(self.last_error(rc));
+            }
+            m.cap_str_off.truncate(caps.n_strings + 1);
+            m.cap_blob.truncate(caps.cap_blob_need);
+            break;
+        }
+        Ok(m)
+    }
+}
+
 impl Drop for Engine {
     fn drop(&mut self) {
         // SAFETY: the handle came from zke_engine_create and is destroyed once.

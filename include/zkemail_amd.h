@@ -469,6 +469,44 @@ int zke_extract_captures_async(zke_engine* e, const zke_email_ref* emails, uint3
 int zke_capture_batch(zke_engine* e, uint32_t dfa_id, uint32_t prog_id, const uint32_t* groups, uint32_t n_groups,
                       const uint8_t* hay_blob, const uint64_t* hay_off, uint32_t n, uint32_t* matches, zke_capture_out* caps);
 
+/* ---- the index map of remove_quoted_printable_soft_breaks (core/src/email.rs:61-86): the function returns (cleaned, index_map),
+ * verify_email_with_regex discards the map (circuits.rs:37), a proving flow cannot — an extraction reports its spans in the
+ * QP-cleaned body, a circuit or a zkVM guest is given the body as it was signed (the canonical body, whose hash is bh=).
+ * Building block: the reference function over n plain host bodies body_blob[body_off[i] .. body_off[i+1]), both return values.
+ * cleaned (body_off[n] - body_off[0] bytes) and index_map (as many entries) are laid out by the same offsets, rebased to
+ * body_off[0]: cleaned is the reference's first value, zero-padded to the body's length; index_map[j] is the position within its
+ * body of cleaned byte j, ZKE_QP_NO_INDEX (the reference's usize::MAX in this ABI's 32-bit positions) from clean_len[i] on;
+ * clean_len[i] is the number of bytes kept.  Any of the three outputs may be NULL, not all of them (ZKE_E_ARG).  Offsets must
+ * be non-decreasing and a body shorter than 2^32 - 1 bytes (ZKE_E_ARG).  Synchronous; runs in one slot, in buffers that only grow. */
+#define ZKE_QP_NO_INDEX 4294967295u
+int zke_qp_clean_batch(zke_engine* e, const uint8_t* body_blob, const uint64_t* body_off, uint32_t n,
+                       uint8_t* cleaned, uint32_t* index_map, uint32_t* clean_len);
+
+/* zke_extract_captures that also says where each span lies BEFORE the QP filter.  Records, caps, statuses and the one fold are
+ * those of zke_extract_captures on the same input; `org` is filled in addition (sizes known up front, the zke_capture_out
+ * convention: too small fails at once with ZKE_E_NOMEM and the *_need fields set).  With im = the index map of the e-mail's regex
+ * haystack (its canonical body, n bytes: after l= unless ZKE_STRICT_CANON_IGNORES_L) and {s, e} the entry of caps.spans:
+ *   header part, or an e-mail without strings ({0xFFFFFFFF, 0xFFFFFFFF})    origin = {s, e}, flags 0 (a header is never cleaned)
+ *   body part    start = s < n ? im[s] : ZKE_QP_NO_INDEX
+ *                end   = e == s ? start : (im[e-1] == ZKE_QP_NO_INDEX ? ZKE_QP_NO_INDEX : im[e-1] + 1)
+ *                ZKE_ORGF_PADDING iff either member is ZKE_QP_NO_INDEX; else ZKE_ORGF_SPLIT iff end - start != e - s
+ * With no flag set, canonical_body[start:end] equals the capture's bytes. */
+#define ZKE_ORGF_SPLIT   1u  /* a soft break was removed inside the span: end-start of the origin != end-start of the span */
+#define ZKE_ORGF_PADDING 2u  /* the span reaches into the zero padding: a member of the origin is ZKE_QP_NO_INDEX */
+typedef struct zke_capture_origin {
+  uint32_t* spans; size_t spans_cap;   /* n*G*2: {start, end} in the haystack BEFORE the QP filter */
+  uint8_t*  flags; size_t flags_cap;   /* n*G   ZKE_ORGF_* */
+  size_t spans_need, flags_need;       /* written by the call */
+} zke_capture_origin;
+int zke_extract_captures_mapped(zke_engine* e, const zke_email_ref* emails, uint32_t n,
+                                const zke_capture_part* header_parts, uint32_t n_header_parts,
+                                const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out, zke_capture_out* caps,
+                                zke_capture_origin* org);
+int zke_extract_captures_mapped_async(zke_engine* e, const zke_email_ref* emails, uint32_t n,
+                                      const zke_capture_part* header_parts, uint32_t n_header_parts,
+                                      const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out, zke_capture_out* caps,
+                                      zke_capture_origin* org, uint64_t* ticket);
+
 /* ---- DKIM-Signature scan and key selection: the compute on both sides of the caller's DNS fetch in the reference's
  * generate_email_inputs (helpers/src/generator.rs:11-53).  The fetch itself, like all IO, stays with the caller:
  *     zke_scan_signatures   raw e-mails + from_domain -> per e-mail every DKIM-Signature header with its validate_header verdict,

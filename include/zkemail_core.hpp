@@ -123,6 +123,26 @@ struct KeyInfo {
 // selector._domainkey.domain (its character-strings joined) or the archive's value —, or nullopt when the fetch fails.
 using FetchRecord = std::function<std::optional<std::string>(const std::string& domain, const std::string& selector)>;
 
+// One part of an extraction (zke_capture_part): the registered DFA pair that finds the match, the registered capture program of the
+// same pattern, the groups wanted (RegexPattern.capture_indices).
+struct CapturePart {
+  uint32_t dfa_id, prog_id;
+  std::vector<uint32_t> groups;
+};
+// What an extraction delivers (zke_capture_out): spans {start, end} and flags per (e-mail, requested group), and the capture tables
+// in the form the verify entries take.
+struct CaptureTables {
+  std::vector<uint32_t> spans;
+  std::vector<uint8_t> flags;
+  std::vector<uint32_t> cap_off, cap_str_off;
+  std::vector<uint8_t> cap_blob;
+};
+// Where the spans lie before the QP filter (zke_capture_origin): {start, end} in the canonical body as it was signed, ZKE_ORGF_* each.
+struct CaptureOrigins {
+  std::vector<uint32_t> spans;
+  std::vector<uint8_t> flags;
+};
+
 class Engine {
  public:
   explicit Engine(int device = -1) {
@@ -218,6 +238,19 @@ class Engine {
     if (int r = zke_verify_emails_with_regex(e_, refs.data(), (uint32_t)refs.size(), &lists, out.data()))
       throw EngineError("zke_verify_emails_with_regex failed: " + std::to_string(r) + " " + zke_last_error(e_));
     return out;
+  }
+
+  // zke_extract_captures over a vector of e-mails that share one part list: verify_email + canonicalise + QP clean + exactly one
+  // match per part + the requested groups.  One record per e-mail; `caps` as zke_capture_out describes it.
+  std::vector<zke_result> extract_captures(const std::vector<Email>& emails, const std::vector<CapturePart>& header_parts,
+                                           const std::vector<CapturePart>& body_parts, CaptureTables& caps) {
+    return extract(emails, header_parts, body_parts, caps, nullptr);
+  }
+  // ... and (zke_extract_captures_mapped) where every span lies in its haystack BEFORE the QP filter: what a circuit that is given
+  // the signed body needs to place a capture there, or to learn that a soft break cuts it in two (ZKE_ORGF_SPLIT).
+  std::vector<zke_result> extract_captures(const std::vector<Email>& emails, const std::vector<CapturePart>& header_parts,
+                                           const std::vector<CapturePart>& body_parts, CaptureTables& caps, CaptureOrigins& origins) {
+    return extract(emails, header_parts, body_parts, caps, &origins);
   }
 
   // helpers/src/generator.rs:17-30 for a batch (zke_scan_signatures): every DKIM-Signature header of every e-mail with
@@ -417,6 +450,44 @@ class Engine {
       return v;
     }
   };
+  std::vector<zke_result> extract(const std::vector<Email>& emails, const std::vector<CapturePart>& header_parts,
+                                  const std::vector<CapturePart>& body_parts, CaptureTables& caps, CaptureOrigins* origins) {
+    const uint32_t n = (uint32_t)emails.size();
+    std::vector<zke_email_ref> refs(n);
+    for (uint32_t i = 0; i < n; i++) {
+      const Email& em = emails[i];
+      uint32_t ext = 0;
+      for (const auto& x : em.external_inputs) if (!x.value) ext = 1;
+      refs[i] = zke_email_ref{em.raw_email.data(), em.raw_email.size(), em.from_domain.data(), em.from_domain.size(),
+                              em.public_key.key.data(), em.public_key.key.size(), key_type_code(em.public_key.key_type), ext};
+    }
+    std::vector<zke_capture_part> hp, bp;
+    size_t G = 0;
+    for (const auto& p : header_parts) { hp.push_back(zke_capture_part{p.dfa_id, p.prog_id, (uint32_t)p.groups.size(), p.groups.data()}); G += p.groups.size(); }
+    for (const auto& p : body_parts) { bp.push_back(zke_capture_part{p.dfa_id, p.prog_id, (uint32_t)p.groups.size(), p.groups.data()}); G += p.groups.size(); }
+    const size_t NP = (size_t)n * (hp.size() + bp.size()), NG = (size_t)n * G;
+    caps.spans.assign(NG * 2 + 1, 0); caps.flags.assign(NG + 1, 0); caps.cap_off.assign(NP + 1, 0); caps.cap_str_off.assign(NG + 1, 0);
+    caps.cap_blob.assign(NG * 32 + 1, 0);
+    zke_capture_origin org{};
+    if (origins) {
+      origins->spans.assign(NG * 2 + 1, 0); origins->flags.assign(NG + 1, 0);
+      org = zke_capture_origin{origins->spans.data(), NG * 2, origins->flags.data(), NG, 0, 0};
+    }
+    std::vector<zke_result> out(n);
+    zke_capture_out o{};
+    for (int attempt = 0; attempt < 2; attempt++) {
+      o = zke_capture_out{caps.spans.data(), NG * 2, caps.flags.data(), NG, caps.cap_off.data(), NP + 1, caps.cap_str_off.data(), NG + 1,
+                          caps.cap_blob.data(), caps.cap_blob.size(), 0, 0, 0, 0, 0, 0};
+      const int r = origins ? zke_extract_captures_mapped(e_, refs.data(), n, hp.data(), (uint32_t)hp.size(), bp.data(), (uint32_t)bp.size(), out.data(), &o, &org)
+                            : zke_extract_captures(e_, refs.data(), n, hp.data(), (uint32_t)hp.size(), bp.data(), (uint32_t)bp.size(), out.data(), &o);
+      if (r == ZKE_E_NOMEM && attempt == 0 && o.cap_blob_need > caps.cap_blob.size()) { caps.cap_blob.resize(o.cap_blob_need); continue; }
+      if (r) throw EngineError("zke_extract_captures failed: " + std::to_string(r) + " " + zke_last_error(e_));
+      break;
+    }
+    caps.spans.resize(NG * 2); caps.flags.resize(NG); caps.cap_str_off.resize(o.n_strings + 1); caps.cap_blob.resize(o.cap_blob_need);
+    if (origins) { origins->spans.resize(NG * 2); origins->flags.resize(NG); }
+    return out;
+  }
   static uint32_t key_type_code(const std::string& t) {
     return t == "rsa" ? ZKE_KEY_RSA : (t == "ed25519" ? ZKE_KEY_ED25519 : ZKE_KEY_OTHER);
   }
@@ -474,6 +545,20 @@ inline Engine& default_engine() {
   return e;
 }
 inline EmailVerifierOutput verify_email(const Email& email) { return default_engine().verify_email(email); }
+// core/src/email.rs:61-86 remove_quoted_printable_soft_breaks, both return values (zke_qp_clean_batch on a batch of one): the body
+// without its "=\r\n" soft breaks, zero-padded to its length, and index_map — the position in `body` of every cleaned byte,
+// usize::MAX over the padding.
+inline std::pair<std::vector<uint8_t>, std::vector<size_t>> remove_quoted_printable_soft_breaks(Engine& engine, const std::vector<uint8_t>& body) {
+  const uint64_t off[2] = {0, body.size()};
+  std::vector<uint8_t> cleaned(body.size());
+  std::vector<uint32_t> map32(body.size());
+  uint32_t kept = 0;
+  if (int r = zke_qp_clean_batch(engine.raw(), body.data(), off, 1, cleaned.data(), map32.data(), &kept))
+    throw EngineError("zke_qp_clean_batch failed: " + std::to_string(r) + " " + zke_last_error(engine.raw()));
+  std::vector<size_t> index_map(body.size());
+  for (size_t j = 0; j < body.size(); j++) index_map[j] = map32[j] == ZKE_QP_NO_INDEX ? SIZE_MAX : (size_t)map32[j];
+  return {std::move(cleaned), std::move(index_map)};
+}
 inline EmailWithRegexVerifierOutput verify_email_with_regex(const EmailWithRegex& in) {
   return default_engine().verify_email_with_regex(in);
 }

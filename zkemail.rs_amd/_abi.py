@@ -171,6 +171,18 @@ class zke_capture_out(C.Structure):
     ]
 
 
+QP_NO_INDEX = 0xFFFFFFFF
+ORGF_SPLIT, ORGF_PADDING = 1, 2
+
+
+class zke_capture_origin(C.Structure):
+    """Where the spans of a mapped extraction lie before the QP filter (zke_extract_captures_mapped); capacities in entries."""
+    _fields_ = [
+        ("spans", C.c_void_p), ("spans_cap", C.c_size_t), ("flags", C.c_void_p), ("flags_cap", C.c_size_t),
+        ("spans_need", C.c_size_t), ("flags_need", C.c_size_t),
+    ]
+
+
 SCAN_MAX_SIGS = 64
 SIG_ALGO_RSA_SHA256, SIG_ALGO_RSA_SHA1, SIG_ALGO_ED25519_SHA256, SIG_ALGO_OTHER = 0, 1, 2, 3
 SEL_NONE, SEL_AFTER_UNSUPPORTED = 0xFFFFFFFF, 0x80000000

@@ -70,6 +70,7 @@ def build_oracle(force: bool = False) -> str:
 CPP_EXAMPLE = os.path.join(ROOT, "tests", "cpp", "mirror_test")
 CPP_SIGSCAN = os.path.join(ROOT, "tests", "cpp", "sigscan_test")
 CPP_KEYREC = os.path.join(ROOT, "tests", "cpp", "keyrec_test")
+CPP_QPMAP = os.path.join(ROOT, "tests", "cpp", "qpmap_test")
 ED_PROBE = os.path.join(ROOT, "tests", "cpp", "ed_probe")
 SHA_PROBE = os.path.join(ROOT, "tests", "cpp", "sha_probe")
 
@@ -91,10 +92,12 @@ def _build_cpp(exe: str, force: bool) -> str:
 
 def build_cpp_example(force: bool = False) -> str:
     """The C++ host mirror (include/zkemail_core.hpp) compiled against the built library: the verify program, whose path is
-    returned, the generator program (build_cpp_sigscan) and the key-record program (build_cpp_keyrec); and the Ed25519 probe
-    (build_ed_probe), which needs no library."""
+    returned, the generator program (build_cpp_sigscan), the key-record program (build_cpp_keyrec) and the index-map program
+    (build_cpp_qpmap); and the Ed25519 probe (build_ed_probe), which needs no library."""
     build_cpp_sigscan(force)
     build_cpp_keyrec(force)
+    if os.path.exists(CPP_QPMAP + ".cpp"):
+        build_cpp_qpmap(force)
     if os.path.exists(ED_PROBE + ".hip"):       # test infrastructure that lives in tests/: a tree whose tests/ does not carry the probe
         build_ed_probe(force)                   # has nothing that runs it, and the three programs below do not depend on it
     if os.path.exists(SHA_PROBE + ".hip"):
@@ -110,6 +113,11 @@ def build_cpp_sigscan(force: bool = False) -> str:
 def build_cpp_keyrec(force: bool = False) -> str:
     """tests/cpp/keyrec_test: decode_key_records / generate_email_inputs_from_records of the C++ mirror."""
     return _build_cpp(CPP_KEYREC, force)
+
+
+def build_cpp_qpmap(force: bool = False) -> str:
+    """tests/cpp/qpmap_test: remove_quoted_printable_soft_breaks and the extract_captures overload with origins of the C++ mirror."""
+    return _build_cpp(CPP_QPMAP, force)
 
 
 def build_ed_probe(force: bool = False) -> str:

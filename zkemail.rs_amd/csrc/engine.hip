@@ -26,6 +26,7 @@
 #include "parse.hip.h"
 #include "regex.hip.h"
 #include "capture.hip.h"
+#include "qpmap.hip.h"
 #include "sigscan.hip.h"
 #include "keyrec.hip.h"
 #include "rsa_kernel.hip.h"
@@ -111,8 +112,14 @@ struct Slot {
   // pinned twin, the packed key section the front end reads, and where the pending batch's infos and keys go
   KeyrecBufs kb;
   zke_keyrec_out* keyrec_out = nullptr;
-  DevBuf* all[21] = {&meta, &rsa_jobs, &sha_jobs, &sha_order, &rsa_ok, &em_dbg, &scratch_off, &scratch, &clean, &meta2, &scratch2, &parts,
-                     &pending, &d_image, &d_results, &cb.cap, &cb.work, &sb.out, &sb.ovf, &kb.out, &kb.pack};
+  // mapped extraction (zke_extract_captures_mapped): the origins of the pending batch's spans, in a buffer of their own with its pinned
+  // twin, and where they go; zke_qp_clean_batch: the bodies, cleaned bytes, index maps and kept lengths of the call
+  OriginBufs ob;
+  zke_capture_origin* org_out = nullptr;
+  QpBufs qb;
+  DevBuf* all[27] = {&meta, &rsa_jobs, &sha_jobs, &sha_order, &rsa_ok, &em_dbg, &scratch_off, &scratch, &clean, &meta2, &scratch2, &parts,
+                     &pending, &d_image, &d_results, &cb.cap, &cb.work, &sb.out, &sb.ovf, &kb.out, &kb.pack,
+                     &ob.org, &qb.in, &qb.off, &qb.clean, &qb.map, &qb.len};
   // hipGraph replay of a batch's kernel sequence (zke_options.replay_graphs).  The graph holds this slot's
   // workspace pointers, so it is valid only while none of them has been reallocated: `generation` counts reallocations.
   hipGraphExec_t graph_exec = nullptr;
@@ -234,7 +241,7 @@ void free_slot(Slot* w) {
   if (!w) return;
   if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
   for (auto* b : w->all) b->release();
-  w->h_image.release(); w->h_results.release(); w->cb.h_cap.release(); w->sb.h_out.release(); w->kb.h_out.release();
+  w->h_image.release(); w->h_results.release(); w->cb.h_cap.release(); w->sb.h_out.release(); w->kb.h_out.release(); w->ob.h_org.release();
   for (auto& ev : w->ev) if (ev) (void)hipEventDestroy(ev);
   if (w->done) (void)hipEventDestroy(w->done);
   if (w->host_done) (void)hipEventDestroy(w->host_done);

@@ -71,6 +71,21 @@ int deliver_captures(zke_engine* e, CapBufs& b, zke_capture_out* o, hipStream_t 
   return 0;
 }
 
+// A mapped extraction's origins into the caller's zke_capture_origin: from the slot's pinned twin where capture_origin_kernel ran,
+// else (no body part asks for a group) the spans themselves, which the capture buffer's pinned twin holds, and no flag.
+void deliver_origins(const CapBufs& b, const OriginBufs& ob, zke_capture_origin* o) {
+  const OriginLayout& L = ob.L;
+  if (!L.NG) return;
+  if (ob.launched) {
+    const uint8_t* hp = ob.h_org.as<uint8_t>();
+    memcpy(o->spans, hp, L.NG * 8);
+    memcpy(o->flags, hp + L.flags, L.NG);
+  } else {
+    memcpy(o->spans, b.h_cap.as<uint8_t>() + b.L.spans, L.NG * 8);
+    memset(o->flags, 0, L.NG);
+  }
+}
+
 // A scan from the slot's pinned twin into the caller's zke_sig_scan: statuses, the CSR over the record slots in use (the
 // compaction: one memcpy per e-mail), the selector bytes.  ZKE_E_NOMEM when sigs or sel_blob is too small (*_need says how much).
 int deliver_scan(zke_engine* e, const ScanBufs& b, zke_sig_scan* o) {
@@ -147,6 +162,8 @@ int retire_host(zke_engine* e, Slot& w, int* cap_rc = nullptr) {
   w.scan_out = nullptr;
   zke_keyrec_out* pending_keyrec = w.keyrec_out;
   w.keyrec_out = nullptr;
+  zke_capture_origin* pending_org = w.org_out;
+  w.org_out = nullptr;
   HIPCHK(e, hipEventSynchronize(w.host_done));
   if (w.host_out && w.host_n) memcpy(w.host_out, w.h_results.p, (size_t)w.host_n * sizeof(zke_result));
   w.host_out = nullptr;
@@ -172,6 +189,7 @@ int retire_host(zke_engine* e, Slot& w, int* cap_rc = nullptr) {
     if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
     else if (r) return r;
   }
+  if (pending_org) deliver_origins(w.cb, w.ob, pending_org);
   return 0;
 }
 
@@ -259,6 +277,12 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   if (d.cap) {
     if (int r = ensure_capture_buffers(e, w.cb, n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap, d.cap->needs_work)) return r;
     w.cb.L = cap_layout(n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap);
+  }
+  if (d.cap && d.cap->org) {
+    w.ob.L = origin_layout(n, d.cap->G);
+    w.ob.launched = d.cap->origin_launch();
+    if (w.ob.launched)
+      if (int r = w.ob.org.ensure(w.ob.L.total) ? ZKE_E_NOMEM : w.ob.h_org.ensure(w.ob.L.total)) return fail(e, r, "capture-origin buffer allocation");
   }
   if (d.scan) {      // (a selector is at most ZKE_MAX_TAGBUF bytes: a larger blob than that per record slot is never used)
     const size_t blob = std::min<size_t>(d.scan->out->sel_blob_cap, (size_t)n * d.scan->max_sigs * ZKE_MAX_TAGBUF);
@@ -388,12 +412,14 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   if (d.keyrec) HIPCHK(e, hipMemcpyAsync(w.kb.h_out.p, w.kb.out.p, w.kb.L.total, hipMemcpyDeviceToHost, s));
   }
   if (d.cap) HIPCHK(e, hipMemcpyAsync(w.cb.h_cap.p, w.cb.cap.p, w.cb.L.fixed_end, hipMemcpyDeviceToHost, s));
+  if (d.cap && d.cap->org && w.ob.launched) HIPCHK(e, hipMemcpyAsync(w.ob.h_org.p, w.ob.org.p, w.ob.L.total, hipMemcpyDeviceToHost, s));
   tm.mark(MK_D2H);
   HIPCHK(e, hipEventRecord(w.host_done, s));
   w.host_gen++;
   w.host_out = (d.scan || d.sel || d.keyrec) ? nullptr : out; w.host_n = n;
   w.keyrec_out = d.keyrec ? d.keyrec->out : nullptr;
   w.cap_out = d.cap ? d.cap->out : nullptr;
+  w.org_out = d.cap ? d.cap->org : nullptr;
   w.scan_out = d.scan ? d.scan->out : nullptr;
   w.sel_off.clear();
   if (d.sel) {
@@ -756,14 +782,25 @@ int check_capture_out(zke_capture_out* o, uint32_t n, uint32_t P, uint32_t G, co
   if (!o->spans || !o->flags || !o->cap_off || !o->cap_str_off || (o->cap_blob_cap && !o->cap_blob)) return arg_error(who, "null buffer in zke_capture_out");
   return 0;
 }
-}  // namespace
+// the same for the origins of a mapped extraction: both sizes are known up front
+int check_capture_origin(zke_capture_origin* o, uint32_t n, uint32_t G, const char* who) {
+  if (!o) return arg_error(who, "null zke_capture_origin");
+  const size_t NG = (size_t)n * G;
+  o->spans_need = NG * 2; o->flags_need = NG;
+  if (o->spans_cap < o->spans_need || o->flags_cap < o->flags_need) {
+    g_err = std::string(who) + ": a zke_capture_origin buffer is smaller than its *_need";
+    return ZKE_E_NOMEM;
+  }
+  if (NG && (!o->spans || !o->flags)) return arg_error(who, "null buffer in zke_capture_origin");
+  return 0;
+}
 
-int zke_extract_captures_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
-                               uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
-                               zke_capture_out* caps, uint64_t* ticket) {
-  static const char who[] = "zke_extract_captures";
+// zke_extract_captures_async and its mapped form (`mapped`: org is wanted, and checked behind caps)
+int extract_captures_submit(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
+                            uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
+                            zke_capture_out* caps, bool mapped, zke_capture_origin* org, uint64_t* ticket, const char* who) {
   if (!e) return ZKE_E_ARG;
-  if (!ticket || !caps || (n_header_parts && !header_parts) || (n_body_parts && !body_parts)) return arg_error(who, "null pointer");
+  if (!ticket || !caps || (mapped && !org) || (n_header_parts && !header_parts) || (n_body_parts && !body_parts)) return arg_error(who, "null pointer");
   const uint32_t P = n_header_parts + n_body_parts;
   if (P == 0 || P > ZKE_CAP_MAX_PARTS || n_header_parts > ZKE_CAP_MAX_PARTS) return arg_error(who, "1 .. ZKE_CAP_MAX_PARTS parts");
   CaptureReq q;
@@ -775,11 +812,80 @@ int zke_extract_captures_async(zke_engine* e, const zke_email_ref* emails, uint3
     if (int r = capture_part_shape(q, p, cp.prog_id, cp.groups, cp.n_groups, who)) return r;
   }
   if (int r = check_capture_out(caps, n, P, q.G, who)) return r;
+  if (mapped) { if (int r = check_capture_origin(org, n, q.G, who)) return r; q.org = org; }
   zke_regex_lists lists{n_header_parts, q.dfa_ids.data(), n_body_parts, q.dfa_ids.data() + n_header_parts, nullptr, nullptr, nullptr};
   HostBatch d;
   if (int r = host_batch(d, who, out, emails, n, &lists)) return r;
   d.cap = &q;
   return submit_host_batch(e, d, out, ticket);
+}
+}  // namespace
+
+int zke_extract_captures_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
+                               uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
+                               zke_capture_out* caps, uint64_t* ticket) {
+  return extract_captures_submit(e, emails, n, header_parts, n_header_parts, body_parts, n_body_parts, out, caps, false, nullptr, ticket,
+                                 "zke_extract_captures");
+}
+
+int zke_extract_captures_mapped_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
+                                      uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
+                                      zke_capture_out* caps, zke_capture_origin* org, uint64_t* ticket) {
+  return extract_captures_submit(e, emails, n, header_parts, n_header_parts, body_parts, n_body_parts, out, caps, true, org, ticket,
+                                 "zke_extract_captures_mapped");
+}
+
+int zke_extract_captures_mapped(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
+                                uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
+                                zke_capture_out* caps, zke_capture_origin* org) {
+  uint64_t ticket = 0;
+  if (int r = zke_extract_captures_mapped_async(e, emails, n, header_parts, n_header_parts, body_parts, n_body_parts, out, caps, org, &ticket)) return r;
+  return n ? zke_batch_wait(e, ticket) : 0;
+}
+
+// ---- remove_quoted_printable_soft_breaks with its index map over plain bodies (include/zkemail_amd.h; kernel: qpmap.hip.h).  One
+// slot, its stream and its QpBufs (grow only); the caller's buffers are read and written by the copies themselves.
+int zke_qp_clean_batch(zke_engine* e, const uint8_t* body_blob, const uint64_t* body_off, uint32_t n,
+                       uint8_t* cleaned, uint32_t* index_map, uint32_t* clean_len) {
+  static const char who[] = "zke_qp_clean_batch";
+  if (!e) return ZKE_E_ARG;
+  if (!cleaned && !index_map && !clean_len) return arg_error(who, "all three outputs are null");
+  if (n == 0) return 0;
+  if (!body_off) return arg_error(who, "null pointer");
+  if (!rising(body_off, n)) return arg_error(who, "offset array is not non-decreasing");
+  for (uint32_t i = 0; i < n; i++) if (body_off[i + 1] - body_off[i] >= 0xFFFFFFFFull) return arg_error(who, "body of 2^32 - 1 bytes or more");
+  const uint64_t base0 = body_off[0], total = body_off[n] - base0;
+  if (total && !body_blob) return arg_error(who, "null pointer");
+  std::shared_lock<std::shared_mutex> sh(e->big);
+  HIPCHK(e, hipSetDevice(e->device));
+  uint32_t slot;
+  Slot& w = next_slot(e, slot);
+  std::lock_guard<std::mutex> g(w.mu);
+  QpBufs& b = w.qb;
+  int r = 0;
+  if ((r = b.in.ensure((size_t)total + 16)) || (r = b.off.ensure((size_t)(n + 1) * 8)) || (cleaned && (r = b.clean.ensure((size_t)total + 16))) ||
+      (index_map && (r = b.map.ensure(((size_t)total + 4) * 4))) || (clean_len && (r = b.len.ensure((size_t)n * 4))))
+    return fail(e, r, "zke_qp_clean_batch: allocation");
+  hipStream_t s = w.stream;
+  SlotUse use(e, w, s);
+  if ((r = use.acquire())) return r;
+  auto enqueue = [&]() -> int {
+    if (total) HIPCHK(e, hipMemcpyAsync(b.in.p, body_blob + base0, (size_t)total, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(b.off.p, body_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));      // (as given: the kernel subtracts off[0])
+    const QpIndexArgs qa{n, b.in.as<uint8_t>(), b.off.as<uint64_t>(), cleaned ? b.clean.as<uint8_t>() : nullptr,
+                         index_map ? b.map.as<uint32_t>() : nullptr, clean_len ? b.len.as<uint32_t>() : nullptr};
+    hipLaunchKernelGGL(qp_index_kernel, dim3(std::min<uint32_t>(n, 1u << 16)), dim3(64), 0, s, qa);
+    HIPCHK(e, hipGetLastError());
+    if (cleaned && total) HIPCHK(e, hipMemcpyAsync(cleaned, b.clean.p, (size_t)total, hipMemcpyDeviceToHost, s));
+    if (index_map && total) HIPCHK(e, hipMemcpyAsync(index_map, b.map.p, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+    if (clean_len) HIPCHK(e, hipMemcpyAsync(clean_len, b.len.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    return use.release();
+  };
+  r = enqueue();
+  const hipError_t hs = hipStreamSynchronize(s);      // also behind a failed enqueue: no copy outlives the caller's buffers
+  if (r) return r;
+  if (hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "zke_qp_clean_batch: sync", hs);
+  return 0;
 }
 
 int zke_extract_captures(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,

@@ -277,4 +277,25 @@ struct KeyrecBufs {
   void release() { out.release(); pack.release(); h_out.release(); }
 };
 
+// The origins of one mapped extraction (a slot's; zke_extract_captures_mapped): {spans n*G*2 | flags n*G} in a device buffer of its own
+// with a pinned twin — a plain extraction never sees it.  `launched`: capture_origin_kernel ran for the pending batch (it does not
+// when no body part asks for a group: the origins are then the spans themselves).
+struct OriginLayout { size_t flags, total; size_t NG; };
+inline OriginLayout origin_layout(uint32_t n, uint32_t G) {
+  OriginLayout L{};
+  L.NG = (size_t)n * G;
+  L.flags = align_up(L.NG * 8, 64);
+  L.total = align_up(L.flags + L.NG, 64);
+  return L;
+}
+struct OriginBufs {
+  DevBuf org;
+  PinnedBuf h_org;
+  OriginLayout L{};
+  bool launched = false;
+};
+
+// The buffers of zke_qp_clean_batch (a slot's): the bodies and their offsets, cleaned bytes, index map, kept lengths.
+struct QpBufs { DevBuf in, off, clean, map, len; };
+
 }  // namespace

@@ -62,6 +62,8 @@ struct CaptureReq {
   std::vector<uint32_t> dfa_ids;         // [P] header parts, then body parts
   uint32_t prog_ids[CAP_MAX_PARTS]{};    // resolved against the registry by capture_resolve, under the engine's `big` lock
   zke_capture_out* out = nullptr;
+  zke_capture_origin* org = nullptr;     // zke_extract_captures_mapped: the spans' origins before the QP filter are wanted too
+  bool origin_launch() const { return org && G > gbase[n_header_parts]; }      // some body part asks for a group
 };
 constexpr uint32_t CAP_WORK_WAVES = 256;      // waves of a capture launch whose rows live in the slot's workspace (one slice each)
 
@@ -126,6 +128,19 @@ int launch_capture(zke_engine* e, CapBufs& b, const CaptureReq& q, uint32_t n, b
   ga.tmp = reinterpret_cast<uint32_t*>(cb + L.tmp);
   for (uint32_t p = 0; p <= q.P; p++) ga.gbase[p] = q.gbase[p];
   hipLaunchKernelGGL(capture_gather_kernel, dim3(1), dim3(1024), 0, s, ga);
+  HIPCHK(e, hipGetLastError());
+  return 0;
+}
+
+// A mapped extraction's third launch, behind the two above: the origins of the body parts' spans (qpmap.hip.h), one wave per e-mail.
+int launch_capture_origin(zke_engine* e, const CapBufs& b, OriginBufs& ob, const CaptureReq& q, uint32_t n, const DfaArgs& base,
+                          const zke_result* results, hipStream_t s) {
+  uint8_t* op = ob.org.as<uint8_t>();
+  CapOriginArgs oa{};
+  oa.n = n; oa.G = q.G; oa.gb0 = q.gbase[q.n_header_parts]; oa.d = base; oa.results = results;
+  oa.spans = reinterpret_cast<const uint32_t*>(b.cap.as<uint8_t>() + b.L.spans);
+  oa.org_spans = reinterpret_cast<uint32_t*>(op); oa.org_flags = op + ob.L.flags;
+  hipLaunchKernelGGL(capture_origin_kernel, dim3(n), dim3(64), 0, s, oa);
   HIPCHK(e, hipGetLastError());
   return 0;
 }
@@ -274,6 +289,8 @@ int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t ra
     // capture extraction (zke_extract_captures): two more launches behind the regex verdict, in the slot's capture buffer
     if (cap)
       if ((r = launch_capture(e, w.cb, *cap, n, false, base, nullptr, nullptr, w.parts.as<PartRes>(), out_dev, s))) return r;
+    if (cap && cap->origin_launch())
+      if ((r = launch_capture_origin(e, w.cb, w.ob, *cap, n, base, out_dev, s))) return r;
     tm.mark(MK_DFA);
     HIPCHK(e, hipGetLastError());
   }

@@ -138,7 +138,16 @@ def load_library(path: Optional[str] = None):
     lib.zke_extract_captures_async.restype = C.c_int
     lib.zke_capture_batch.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, vp, cop]
     lib.zke_capture_batch.restype = C.c_int
-    erp = C.POINTER(A.zke_email_ref)
+    if hasattr(lib, "zke_qp_clean_batch"):          # (as zke_engine_sha_ring below: an older tree's library has none of the three)
+        orp = C.POINTER(A.zke_capture_origin)
+        lib.zke_qp_clean_batch.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp]
+        lib.zke_qp_clean_batch.restype = C.c_int
+        lib.zke_extract_captures_mapped.argtypes = [vp, C.POINTER(A.zke_email_ref), C.c_uint32, cpp, C.c_uint32, cpp, C.c_uint32, vp, cop, orp]
+        lib.zke_extract_captures_mapped.restype = C.c_int
+        lib.zke_extract_captures_mapped_async.argtypes = [vp, C.POINTER(A.zke_email_ref), C.c_uint32, cpp, C.c_uint32, cpp, C.c_uint32, vp, cop, orp,
+                                                          C.POINTER(C.c_uint64)]
+        lib.zke_extract_captures_mapped_async.restype = C.c_int
+    erp =C.POINTER(A.zke_email_ref)
     lib.zke_scan_signatures.argtypes = [vp, erp, C.c_uint32, C.c_uint32, C.POINTER(A.zke_sig_scan)]
     lib.zke_scan_signatures.restype = C.c_int
     lib.zke_scan_signatures_async.argtypes = [vp, erp, C.c_uint32, C.c_uint32, C.POINTER(A.zke_sig_scan), C.POINTER(C.c_uint64)]
@@ -182,6 +191,7 @@ EXPORTED_SYMBOLS = [
     "zke_scan_signatures", "zke_scan_signatures_async", "zke_select_keys", "zke_select_keys_async",
     "zke_decode_key_records", "zke_decode_key_records_async", "zke_select_keys_from_records", "zke_select_keys_from_records_async",
     "zke_engine_sha_ring",
+    "zke_qp_clean_batch", "zke_extract_captures_mapped", "zke_extract_captures_mapped_async",
 ]
 
 
@@ -404,11 +414,34 @@ class Engine:
         strings = [[raw[cap_str_off[k]:cap_str_off[k + 1]] for k in range(cap_off[i], cap_off[i + 1])] for i in range(n)]
         return matches[:n], spans, flags, strings
 
-    def extract_captures(self, emails: Sequence[Email], regex_config, *, unicode: bool = True):
+    def qp_clean_batch(self, bodies: Sequence[bytes]):
+        """zke_qp_clean_batch: remove_quoted_printable_soft_breaks (core/src/email.rs:61-86) over a batch of bodies, both return
+        values.  Returns (cleaned: the bodies without their soft breaks, zero-padded to their lengths; index_maps: per body a
+        uint32 array, entry j = the position in the body of cleaned byte j, QP_NO_INDEX over the padding; clean_len: uint32[n],
+        the bytes kept)."""
+        n = len(bodies)
+        blob, off = A._csr(list(bodies))
+        total = int(off[n]) if n else 0
+        cleaned = np.zeros(max(total, 1), np.uint8)
+        imap = np.zeros(max(total, 1), np.uint32)
+        clen = np.zeros(max(n, 1), np.uint32)
+        self._check(self.lib.zke_qp_clean_batch(self.h, blob.ctypes.data, off.ctypes.data, n, cleaned.ctypes.data, imap.ctypes.data,
+                                                clen.ctypes.data), "zke_qp_clean_batch")
+        raw = cleaned.tobytes()
+        return ([raw[int(off[i]):int(off[i + 1])] for i in range(n)], [imap[int(off[i]):int(off[i + 1])].copy() for i in range(n)], clen[:n])
+
+    def remove_quoted_printable_soft_breaks(self, body: bytes):
+        """The reference's function on one body (a batch of one): (cleaned, index_map) with usize::MAX = 2**64 - 1 over the padding."""
+        cleaned, maps, _ = self.qp_clean_batch([bytes(body)])
+        return cleaned[0], [2 ** 64 - 1 if int(x) == A.QP_NO_INDEX else int(x) for x in maps[0]]
+
+    def extract_captures(self, emails: Sequence[Email], regex_config, *, unicode: bool = True, origins: bool = False):
         """helpers/src/generator.rs:55-87 without the key fetch: verify_email + canonicalise + QP clean + exactly one match per
         pattern + the groups named by capture_indices, one batch on the GPU.  `regex_config`: a regex_compile.RegexConfig (or
         its JSON dict).  Returns (records, regex_infos): regex_infos[i] is the RegexInfo of e-mail i — what
-        compile_regex_parts returns for it — or None where the record is not OK (the reference returns Err / panics there)."""
+        compile_regex_parts returns for it — or None where the record is not OK (the reference returns Err / panics there).
+        origins=True (zke_extract_captures_mapped): a third value (origin_spans [n, G, 2], origin_flags [n, G]) — where each
+        requested group lies in its haystack BEFORE the QP filter (the canonical body as it was signed), ORGF_* per group."""
         from . import regex_compile as rc
         if isinstance(regex_config, dict):
             regex_config = rc.RegexConfig.from_json(regex_config)
@@ -422,10 +455,15 @@ class Engine:
         n, P, G = refs.n, len(comp), sum(len(g) for g in groups)
         out = np.zeros(max(n, 1), dtype=A.RESULT_DTYPE)
         body = C.cast(C.byref(arr, len(hp) * C.sizeof(A.zke_capture_part)), C.POINTER(A.zke_capture_part))
-        rcode, spans, flags, cap_off, cap_str_off, cblob = self._run_captures(
-            n, P, G, lambda o: self.lib.zke_extract_captures(self.h, refs.arr, n, arr, len(hp), body, len(bp), out.ctypes.data, C.byref(o)),
-            32 * n * G)
-        self._check(rcode, "zke_extract_captures")
+        call = lambda o: self.lib.zke_extract_captures(self.h, refs.arr, n, arr, len(hp), body, len(bp), out.ctypes.data, C.byref(o))
+        if origins:
+            ospans, oflags = np.zeros(max(n * G * 2, 1), np.uint32), np.zeros(max(n * G, 1), np.uint8)
+            org = A.zke_capture_origin()
+            org.spans, org.spans_cap, org.flags, org.flags_cap = ospans.ctypes.data, n * G * 2, oflags.ctypes.data, n * G
+            call = lambda o: self.lib.zke_extract_captures_mapped(self.h, refs.arr, n, arr, len(hp), body, len(bp), out.ctypes.data,
+                                                                  C.byref(o), C.byref(org))
+        rcode, spans, flags, cap_off, cap_str_off, cblob = self._run_captures(n, P, G, call, 32 * n * G)
+        self._check(rcode, "zke_extract_captures_mapped" if origins else "zke_extract_captures")
         raw = cblob.tobytes()
         infos: List[Optional[A.RegexInfo]] = []
         for i in range(n):
@@ -443,6 +481,8 @@ class Engine:
                 parts.append(CompiledRegex(comp[p][0], strs))
             infos.append(A.RegexInfo(parts[:len(hp)] if regex_config.header_parts is not None else None,
                                      parts[len(hp):] if regex_config.body_parts is not None else None))
+        if origins:
+            return out[:n], infos, (ospans[:n * G * 2].reshape(n, G, 2), oflags[:n * G].reshape(n, G))
         return out[:n], infos
 
     # ---- DKIM-Signature scan and key selection (helpers/src/generator.rs:11-53 around the caller's DNS fetch)
