@@ -13,16 +13,39 @@
 // per tile), park it in the wave's private LDS slab, and every lane
 // then pulls its own message's 64-byte blocks back with ds_read_b128.  Row stride T+16
 // bytes keeps both the ds_write_b128 and the ds_read_b128 phases conflict-free
-// (lane stride = 4 banks mod 64).  No __syncthreads: a wave's LDS operations execute in
-// order, and no other wave touches its slab.
+// (lane stride = 4 banks mod 64).  No __syncthreads in the staging: a wave's LDS operations
+// execute in order, and no other wave touches its slab.
 //
 // Roofline: integer-VALU bound (about 1.4k VALU per 64-byte block per lane), not HBM
-// bound; DESIGN.md §3 has the arithmetic.  Two kernels: sha256_batch_kernel (one wave per 64 messages, for
-// launches that fill the chip) and sha256_pair_kernel (two waves per 64 messages — message schedule and rounds
-// — for launches whose duration is one wave's chain of compressions; it is the one BASELINE-sized batches use).
+// bound; DESIGN.md §3 has the arithmetic.
+//
+// Three routines, each its own control flow over the shared pieces below:
+//   sha256_batch_kernel  one wave per 64 messages, for launches that fill the chip;
+//   sha256_pair_group    two waves per 64 messages — message schedule and rounds —, ONE K+W buffer and two barriers per
+//                        block, 28 KB of LDS: for launches whose duration is one wave's chain of compressions, where
+//                        many batches share the chip.  Its one-wave path takes the groups that hold a SHA-1 job;
+//   sha256_ring_group    the same two roles, TWO K+W buffers and one LDS-only barrier per block, 45 KB: where few batches
+//                        are on the chip (engine.hip chooses).
+// The group routines are device functions, so that other work can share their launch (fused.hip.h); sha256_pair_kernel
+// and sha256_ring_kernel run them alone.
+// Shared, one definition each: the round constants SHA_K; sha_init_state / sha_store_digest (sha_lane of verdict.hip.h
+// uses them too); sha_load_block; ShaLaneJob (a lane's job, the wave's longest message, its SHA-1 ballot); ShaTile
+// (descriptor rows, fetch / commit: tile staging and padding); sha_one_wave_tiles (the one-wave tile loop);
+// sha_group_pick (the length-bucket protocol of a two-wave group); sha_kw_schedule and sha_rounds_kw (the two halves of
+// a split compression).  The pair and the ring block loops are NOT shared: they differ in their barrier structure, and
+// that difference is what a reader has to see.  The ring also keeps its 64 rounds written out, for a measured reason
+// (the comment there).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+// A message is a serial chain of compressions, so a hash launch's duration is set by its longest message, not by
+// the chip: with several batches in flight its few waves share SIMDs with thousands of front-end / RSA waves and
+// the chain stretches ~2x.  Raising the wave priority keeps the chain near its unloaded latency; the other
+// kernels have parallel slack to absorb it.
+#ifndef ZKE_SHA_PRIO
+#define ZKE_SHA_PRIO 3
+#endif
 
 namespace zke {
 
@@ -61,24 +84,26 @@ struct ShaOrder {                 // one kind's part of the slot's order buffer 
   uint32_t n;                     // e-mails
 };
 
+// ---- one compression and its pieces ----------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t rotr32(uint32_t x, int n) { return __builtin_amdgcn_alignbit(x, x, n); }
 // gfx950 v_bitop3_b32: any 3-input boolean function in one VALU op (truth table in the immediate)
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
 __device__ __forceinline__ uint32_t ch3(uint32_t e, uint32_t f, uint32_t g) { return __builtin_amdgcn_bitop3_b32(e, f, g, 0xCA); }   // e ? f : g
 __device__ __forceinline__ uint32_t maj3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8); }
 
+// The round constants: compile-time literals after full unrolling (no loads), in sha256_compress and in sha_kw_schedule.
+constexpr uint32_t SHA_K[64] = {
+    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
+    0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
+    0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
+    0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
+    0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
+    0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
+    0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
+    0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+
 // One compression.  w[16] holds the big-endian message words and is consumed.
-// The round constants are compile-time literals after full unrolling (no loads).
 __device__ __forceinline__ void sha256_compress(uint32_t (&st)[8], uint32_t (&w)[16]) {
-  constexpr uint32_t K[64] = {
-      0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
-      0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
-      0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
-      0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
-      0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
-      0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
-      0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
-      0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
   uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
 #pragma unroll
   for (int i = 0; i < 64; i++) {
@@ -93,7 +118,7 @@ __device__ __forceinline__ void sha256_compress(uint32_t (&st)[8], uint32_t (&w)
       w[i & 15] = wi;
     }
     uint32_t S1 = xor3(rotr32(e, 6), rotr32(e, 11), rotr32(e, 25));
-    uint32_t t1 = (h + S1 + ch3(e, f, g)) + (K[i] + wi);
+    uint32_t t1 = (h + S1 + ch3(e, f, g)) + (SHA_K[i] + wi);
     uint32_t S0 = xor3(rotr32(a, 2), rotr32(a, 13), rotr32(a, 22));
     uint32_t mj = maj3(a, b, c);
     h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + S0 + mj;
@@ -126,6 +151,33 @@ __device__ __forceinline__ void sha1_compress(uint32_t (&st)[8], uint32_t (&w)[1
   st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e;
 }
 
+// The initial chaining state.  sha1: ShaJob::pad != 0 (SHA-1: five words, the other three idle at zero).
+__device__ __forceinline__ void sha_init_state(uint32_t (&st)[8], bool sha1) {
+  st[0] = 0x6a09e667; st[1] = 0xbb67ae85; st[2] = 0x3c6ef372; st[3] = 0xa54ff53a;
+  st[4] = 0x510e527f; st[5] = 0x9b05688c; st[6] = 0x1f83d9ab; st[7] = 0x5be0cd19;
+  if (sha1) { st[0] = 0x67452301; st[1] = 0xEFCDAB89; st[2] = 0x98BADCFE; st[3] = 0x10325476; st[4] = 0xC3D2E1F0; st[5] = st[6] = st[7] = 0; }
+}
+
+// The digest into its 32-byte slot, big-endian; a SHA-1 digest is 20 bytes and the slot's rest zero.  Out: the caller's
+// pointer type, so that the stores stay in its address space (gptr_out32: global_store; sha_lane's plain pointer: as it was).
+template <class Out>
+__device__ __forceinline__ void sha_store_digest(Out out, const uint32_t (&st)[8], bool sha1) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) out[i] = (sha1 && i >= 5) ? 0u : __builtin_bswap32(st[i]);
+}
+
+// A 64-byte block (16-byte aligned; the routines read their LDS rows: four ds_read_b128) as the 16 big-endian words.
+__device__ __forceinline__ void sha_load_block(uint32_t (&w)[16], const uint8_t* block) {
+  const uint4* src = (const uint4*)block;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    uint4 v = src[q];
+    w[4 * q + 0] = __builtin_bswap32(v.x); w[4 * q + 1] = __builtin_bswap32(v.y);
+    w[4 * q + 2] = __builtin_bswap32(v.z); w[4 * q + 3] = __builtin_bswap32(v.w);
+  }
+}
+
+// ---- a lane's job, the tile staging ----------------------------------------------------------------------------------
 typedef uint4 __attribute__((aligned(1))) uint4_unaligned;
 // Message bytes are in HBM, but their addresses arrive as integers (ShaJob::src), so the compiler would emit FLAT
 // loads: those count on lgkmcnt as well as vmcnt, and every wait for an LDS read behind one (the next row's
@@ -134,57 +186,58 @@ typedef uint4 __attribute__((aligned(1))) uint4_unaligned;
 typedef uint32_t u32x4_raw __attribute__((ext_vector_type(4)));          // a plain vector: the host pass cannot bind HIP's uint4 class across address spaces
 typedef const u32x4_raw __attribute__((aligned(1), address_space(1)))* gptr_u4;
 typedef const uint8_t __attribute__((address_space(1)))* gptr_u8;
-typedef uint32_t __attribute__((address_space(1)))* gptr_out32;
+typedef uint32_t __attribute__((address_space(1)))* gptr_out32;         // digests are 4-byte aligned (result records / engine buffers)
 
-// Launch: blockDim = 256 (4 independent waves), grid = ceil(n / 256).
-// LDS (sha256_lds_bytes): 4 waves * (64 rows * (T + 16) bytes + 64 descriptors * 16 bytes) — 40 960 B per block at the
-// engine's T = SHA_TILE = 128 (engine.hip); 73 728 B at T = 256.
-template <int T>
-__global__ __launch_bounds__(256) void sha256_batch_kernel(const ShaJob* __restrict__ jobs, uint32_t n) {
-  static_assert(T % 64 == 0 && T >= 64 && T <= 1024, "tile must be whole SHA blocks");
-  constexpr int ROW = T + 16;            // bytes
-  constexpr int LPR = T / 16;            // lanes that cover one row's tile
-  constexpr int RPI = 64 / LPR;          // rows per load instruction
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-  // A message is a serial chain of compressions, so this kernel's duration is set by its longest message, not by
-  // the chip: with several batches in flight its few waves share SIMDs with thousands of front-end / RSA waves and
-  // the chain stretches ~2x.  Raising the wave priority keeps the chain near its unloaded latency; the other
-  // kernels have parallel slack to absorb it.
-#ifndef ZKE_SHA_PRIO
-#define ZKE_SHA_PRIO 3
-#endif
-  __builtin_amdgcn_s_setprio(ZKE_SHA_PRIO);
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  uint8_t* slab = lds_raw + (size_t)wave * (64 * ROW + 64 * 16);
-  uint8_t* desc = slab + 64 * ROW;       // 64 x {src(8), len(4), pad(4)}
-
-  const uint32_t m = (blockIdx.x * 4 + wave) * 64 + lane;
-  uint64_t my_src = 0, my_dst = 0;
-  uint32_t my_len = 0, my_nblk = 0, my_algo = 0;
-  if (m < n) {
-    ShaJob j = jobs[m];
-    my_src = j.src; my_dst = j.dst; my_len = j.len; my_algo = j.pad;
-    my_nblk = my_dst ? (my_len + 9 + 63) >> 6 : 0;      // dst == 0 marks an inactive job
+// Job m of `jobs` as the lane that hashes it holds it (m >= n, or dst == 0 for an inactive job: nothing to do, nblk 0).
+struct ShaLaneJob {
+  uint64_t src = 0, dst = 0;
+  uint32_t len = 0, nblk = 0, algo = 0;
+  __device__ __forceinline__ ShaLaneJob(const ShaJob* __restrict__ jobs, uint32_t m, uint32_t n) {
+    if (m < n) {
+      ShaJob j = jobs[m];
+      src = j.src; dst = j.dst; len = j.len; algo = j.pad;
+      nblk = dst ? (len + 9 + 63) >> 6 : 0;
+    }
   }
-  *(uint64_t*)(desc + lane * 16) = my_src;
-  *(uint32_t*)(desc + lane * 16 + 8) = my_len;
-  *(uint32_t*)(desc + lane * 16 + 12) = my_nblk;
-  uint32_t max_nblk = my_nblk;
+  // wave-uniform: the blocks of the wave's longest message
+  __device__ __forceinline__ uint32_t wave_max_nblk() const {
+    uint32_t max_nblk = nblk;
 #pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) max_nblk = max(max_nblk, (uint32_t)__shfl_xor((int)max_nblk, o));
-  max_nblk = __builtin_amdgcn_readfirstlane(max_nblk);
+    for (int o = 32; o >= 1; o >>= 1) max_nblk = max(max_nblk, (uint32_t)__shfl_xor((int)max_nblk, o));
+    return __builtin_amdgcn_readfirstlane(max_nblk);
+  }
+  // wave-uniform: SHA-256-only waves skip the SHA-1 code
+  __device__ __forceinline__ bool wave_any_sha1() const { return __ballot(algo != 0) != 0; }
+};
 
-  uint32_t st[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
-  const bool any_sha1 = __ballot(my_algo != 0) != 0;        // wave-uniform: SHA-256-only waves skip the SHA-1 code
-  if (my_algo) { st[0] = 0x67452301; st[1] = 0xEFCDAB89; st[2] = 0x98BADCFE; st[3] = 0x10325476; st[4] = 0xC3D2E1F0; st[5] = st[6] = st[7] = 0; }
-  uint8_t* my_row = slab + lane * ROW;
-
-  // Software pipeline: the global loads of tile t+1 are issued into registers BEFORE tile t is compressed and
-  // land in LDS after it, so a wave's HBM latency hides under its own ~LPR/4 x 1.4k VALU of compression.
+// The tile staging of one wave's 64 messages.  LDS at `slab`: 64 rows of T + 16 bytes, then 64 descriptors of 16 bytes.
+// Software pipeline: the global loads of a tile are issued into registers (fetch) BEFORE the tile in front of it is
+// compressed and land in LDS after it (commit), so a wave's HBM latency hides under ~LPR/4 x 1.4k VALU of compression.
+template <int T>
+struct ShaTile {
+  static_assert(T % 64 == 0 && T >= 64 && T <= 1024, "tile must be whole SHA blocks");
+  static constexpr int ROW = T + 16;            // bytes
+  static constexpr int LPR = T / 16;            // lanes that cover one row's tile
+  static constexpr int RPI = 64 / LPR;          // rows per load instruction
+  static constexpr size_t BYTES = 64 * ROW + 64 * 16;
+  uint8_t* slab;
+  uint8_t* desc;                                // 64 x {src(8), len(4), nblk(4)}
+  uint8_t* my_row;                              // the lane's own message
+  int lane;
+  uint32_t my_len, my_nblk;
   uint4 stage[LPR];
-  uint32_t live = 0;                       // bit g: stage[g] holds a row chunk that must be written to LDS
-  auto fetch = [&](uint32_t blk0) {
+  uint32_t live = 0;                            // bit g: stage[g] holds a row chunk that must be written to LDS
+
+  __device__ __forceinline__ ShaTile(uint8_t* slab_, int lane_, const ShaLaneJob& J)
+      : slab(slab_), desc(slab_ + 64 * ROW), my_row(slab_ + lane_ * ROW), lane(lane_), my_len(J.len), my_nblk(J.nblk) {}
+
+  // the lane's descriptor row (by the wave that fetches)
+  __device__ __forceinline__ void describe(const ShaLaneJob& J) {
+    *(uint64_t*)(desc + lane * 16) = J.src;
+    *(uint32_t*)(desc + lane * 16 + 8) = J.len;
+    *(uint32_t*)(desc + lane * 16 + 12) = J.nblk;
+  }
+  __device__ __forceinline__ void fetch(uint32_t blk0) {
     const uint32_t tile_off = blk0 * 64;
     live = 0;
     uint4 dsc[LPR];                              // every row descriptor first (one ds_read_b128 each), then the loads
@@ -211,8 +264,8 @@ __global__ __launch_bounds__(256) void sha256_batch_kernel(const ShaJob* __restr
       }
       stage[g] = v;
     }
-  };
-  auto commit = [&](uint32_t blk0) {           // registers -> LDS slab, then the padding of this tile
+  }
+  __device__ __forceinline__ void commit(uint32_t blk0) {           // registers -> LDS slab, then the padding of this tile
     const uint32_t tile_off = blk0 * 64;
 #pragma unroll
     for (int g = 0; g < LPR; g++) {
@@ -235,36 +288,53 @@ __global__ __launch_bounds__(256) void sha256_batch_kernel(const ShaJob* __restr
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-  };
+  }
+};
 
-  if (max_nblk) { fetch(0); commit(0); }
+// The one-wave routine: every lane compresses its own message, a tile at a time; the next tile's loads are in flight
+// during the compression.  sha1: this lane's message is a SHA-1 job.
+template <int T>
+__device__ __forceinline__ void sha_one_wave_tiles(ShaTile<T>& tile, uint32_t (&st)[8], uint32_t max_nblk, bool sha1) {
+  if (max_nblk) { tile.fetch(0); tile.commit(0); }
   for (uint32_t blk0 = 0; blk0 < max_nblk; blk0 += T / 64) {
     const uint32_t next = blk0 + T / 64;
     const bool more = next < max_nblk;
-    if (more) fetch(next);                     // in flight during the compression below
+    if (more) tile.fetch(next);                // in flight during the compression below
     // ---- compress: one message per lane
 #pragma unroll 1
     for (int b = 0; b < T / 64; b++) {
-      if (blk0 + b < my_nblk) {
+      if (blk0 + b < tile.my_nblk) {
         uint32_t w[16];
-        const uint4* src = (const uint4*)(my_row + b * 64);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          uint4 v = src[q];
-          w[4 * q + 0] = __builtin_bswap32(v.x); w[4 * q + 1] = __builtin_bswap32(v.y);
-          w[4 * q + 2] = __builtin_bswap32(v.z); w[4 * q + 3] = __builtin_bswap32(v.w);
-        }
-        if (any_sha1 && my_algo) sha1_compress(st, w); else sha256_compress(st, w);
+        sha_load_block(w, tile.my_row + b * 64);
+        if (sha1) sha1_compress(st, w); else sha256_compress(st, w);
       }
     }
     __builtin_amdgcn_wave_barrier();
-    if (more) commit(next);
+    if (more) tile.commit(next);
   }
-  if (m < n && my_dst) {
-    gptr_out32 out = (gptr_out32)my_dst;      // digests are 4-byte aligned (result records / engine buffers)
-#pragma unroll
-    for (int i = 0; i < 8; i++) out[i] = (my_algo && i >= 5) ? 0u : __builtin_bswap32(st[i]);
-  }
+}
+
+// Launch: blockDim = 256 (4 independent waves), grid = ceil(n / 256).
+// LDS (sha256_lds_bytes): 4 waves * (64 rows * (T + 16) bytes + 64 descriptors * 16 bytes) — 40 960 B per block at the
+// engine's T = SHA_TILE = 128 (engine.hip); 73 728 B at T = 256.
+template <int T>
+__global__ __launch_bounds__(256) void sha256_batch_kernel(const ShaJob* __restrict__ jobs, uint32_t n) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  __builtin_amdgcn_s_setprio(ZKE_SHA_PRIO);
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+
+  const uint32_t m = (blockIdx.x * 4 + wave) * 64 + lane;
+  const ShaLaneJob J(jobs, m, n);
+  ShaTile<T> tile(lds_raw + (size_t)wave * ShaTile<T>::BYTES, lane, J);
+  tile.describe(J);
+  const uint32_t max_nblk = J.wave_max_nblk();
+
+  uint32_t st[8];
+  const bool any_sha1 = J.wave_any_sha1();
+  sha_init_state(st, J.algo != 0);
+  sha_one_wave_tiles<T>(tile, st, max_nblk, any_sha1 && J.algo);
+  if (m < n && J.dst) sha_store_digest((gptr_out32)J.dst, st, J.algo != 0);
 }
 
 template <int T>
@@ -281,16 +351,6 @@ constexpr size_t sha256_lds_bytes() { return 4 * (64 * (T + 16) + 64 * 16); }
 // instructions on the critical path.  Groups that contain a SHA-1 job fall back to the one-wave routine.
 // LDS per group: slab 64 x (T+16) + descriptors 1 KB + 64 lanes x 68 words of K+W (row stride 68 words = 4 banks
 // mod 64: conflict-free 16-byte writes and reads, a quarter of the LDS instructions of word accesses).
-constexpr uint32_t SHA_K[64] = {
-    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
-    0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
-    0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
-    0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
-    0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
-    0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
-    0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
-    0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
-
 constexpr int SHA_KW_ROW = 68;        // dwords per lane and buffer
 
 template <int T>
@@ -348,6 +408,67 @@ __device__ __forceinline__ uint32_t sha_pick_job(const ShaOrder& O, uint32_t g, 
   return pick[SHA_CLASSES + lane];
 }
 
+// Length buckets in a two-wave group: the feeder (role 0) works the picks out, the rounds wave reads them.  Every thread of
+// the group calls this (it uses __syncthreads()).  `order` nullptr or without counters: direct mapping, m stays.  Otherwise m
+// becomes the lane's job under the buckets; true: the group has nothing to do and leaves as a whole.
+__device__ __forceinline__ bool sha_group_pick(const ShaOrder* order, uint32_t group, uint32_t& m, uint32_t* pick, int role) {
+  if (!(order && order->cnt)) return false;
+  const int lane = threadIdx.x & 63;
+  bool skip = false;
+  uint32_t mine = 0;
+  if (role == 0) {
+    mine = sha_pick_job(*order, group, m, pick, skip);
+    if (lane == 0) pick[SHA_CLASSES - 1] = skip ? 1u : 0u;          // (class 191 = 2^25 blocks and more: never populated)
+    pick[SHA_CLASSES + lane] = mine;
+  }
+  __syncthreads();
+  if (pick[SHA_CLASSES - 1]) return true;
+  m = pick[SHA_CLASSES + lane];
+  __syncthreads();                               // the pick area is dead from here (nobody writes it again)
+  return false;
+}
+
+// Feeder: K[t] + W[t], t = 0..63, of the 64-byte block at `block` into kw_row (the lane's SHA_KW_ROW dwords of a K+W
+// buffer: 16 ds_write_b128).
+__device__ __forceinline__ void sha_kw_schedule(const uint8_t* block, uint32_t* kw_row) {
+  uint32_t w[16];
+  sha_load_block(w, block);
+  uint4* dst = (uint4*)kw_row;
+  uint32_t o4[4];
+#pragma unroll
+  for (int i = 0; i < 64; i++) {
+    uint32_t wi;
+    if (i < 16) {
+      wi = w[i];
+    } else {
+      const uint32_t w15 = w[(i - 15) & 15], w2 = w[(i - 2) & 15];
+      const uint32_t s0 = xor3(rotr32(w15, 7), rotr32(w15, 18), w15 >> 3);
+      const uint32_t s1 = xor3(rotr32(w2, 17), rotr32(w2, 19), w2 >> 10);
+      wi = w[i & 15] + s0 + w[(i - 7) & 15] + s1;
+      w[i & 15] = wi;
+    }
+    o4[i & 3] = wi + SHA_K[i];
+    if ((i & 3) == 3) dst[i >> 2] = make_uint4(o4[0], o4[1], o4[2], o4[3]);
+  }
+}
+
+// Rounds wave: the 64 rounds of one block out of its K+W words in registers.  live: the lane's message has this block
+// (the wave runs as many blocks as its longest message).
+__device__ __forceinline__ void sha_rounds_kw(uint32_t (&st)[8], const uint4 (&kq)[16], bool live) {
+  uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
+#pragma unroll
+  for (int i = 0; i < 64; i++) {
+    const uint32_t S1 = xor3(rotr32(e, 6), rotr32(e, 11), rotr32(e, 25));
+    const uint4 k4 = kq[i >> 2];
+    const uint32_t kwi = (i & 3) == 0 ? k4.x : (i & 3) == 1 ? k4.y : (i & 3) == 2 ? k4.z : k4.w;
+    const uint32_t t1 = (h + S1 + ch3(e, f, g)) + kwi;
+    const uint32_t S0 = xor3(rotr32(a, 2), rotr32(a, 13), rotr32(a, 22));
+    const uint32_t mj = maj3(a, b, c);
+    h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + S0 + mj;
+  }
+  if (live) { st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h; }
+}
+
 // Dev knob (tests/cpp/sha_probe.hip, tools/sha_timeline.py): with ZKE_SHA_PROBE defined every wave of a two-role routine leaves
 // its HW_ID register (SIMD, CU, ...) and XCC id, and the waves of group 0 a clock stamp at each marked point of blocks 8..15, in
 // plain device arrays (ordinary vector stores).  The stamp's asm takes a chaining register in and out, so that the arithmetic in
@@ -377,174 +498,38 @@ __device__ unsigned long long zke_sha_probe_stamp[2][SHA_PROBE_BLKS][SHA_PROBE_S
 template <int T>
 __device__ __forceinline__ void sha256_pair_group(const ShaJob* __restrict__ jobs, uint32_t n, uint32_t group, uint8_t* lds_raw,
                                                   const ShaOrder* order = nullptr) {
-  static_assert(T % 64 == 0 && T >= 64 && T <= 1024, "tile must be whole SHA blocks");
-  constexpr int ROW = T + 16;
-  constexpr int LPR = T / 16;
-  constexpr int RPI = 64 / LPR;
-#ifndef ZKE_SHA_PRIO
-#define ZKE_SHA_PRIO 3
-#endif
   __builtin_amdgcn_s_setprio(ZKE_SHA_PRIO);
   const int lane = threadIdx.x & 63;
   const int role = threadIdx.x >> 6;               // 0 feeder, 1 rounds
-  uint8_t* slab = lds_raw;
-  uint8_t* desc = slab + 64 * ROW;
-  uint32_t* kw = (uint32_t*)(desc + 64 * 16);      // [64 lanes][SHA_KW_ROW]: a lane's 64 words are contiguous (b128 accesses)
+  uint32_t* kw = (uint32_t*)(lds_raw + ShaTile<T>::BYTES);      // [64 lanes][SHA_KW_ROW]: a lane's 64 words are contiguous (b128 accesses)
   uint32_t* pick = kw + 64 * SHA_KW_ROW;           // 1 KB: sha_pick_job
 
   uint32_t m = group * 64 + lane;                  // both waves look at the same 64 jobs
-  if (order && order->cnt) {
-    // length buckets: the feeder works the picks out, the rounds wave reads them (one barrier; every thread of the group
-    // arrives here, and a group with nothing to do leaves as a whole)
-    bool skip = false;
-    uint32_t mine = 0;
-    if (role == 0) {
-      mine = sha_pick_job(*order, group, m, pick, skip);
-      if (lane == 0) pick[SHA_CLASSES - 1] = skip ? 1u : 0u;          // (class 191 = 2^25 blocks and more: never populated)
-      pick[SHA_CLASSES + lane] = mine;
-    }
-    __syncthreads();
-    if (pick[SHA_CLASSES - 1]) return;
-    m = pick[SHA_CLASSES + lane];
-    __syncthreads();                               // the pick area is dead from here (nobody writes it again)
-  }
-  uint64_t my_src = 0, my_dst = 0;
-  uint32_t my_len = 0, my_nblk = 0, my_algo = 0;
-  if (m < n) {
-    ShaJob j = jobs[m];
-    my_src = j.src; my_dst = j.dst; my_len = j.len; my_algo = j.pad;
-    my_nblk = my_dst ? (my_len + 9 + 63) >> 6 : 0;
-  }
-  uint32_t max_nblk = my_nblk;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) max_nblk = max(max_nblk, (uint32_t)__shfl_xor((int)max_nblk, o));
-  max_nblk = __builtin_amdgcn_readfirstlane(max_nblk);
-  const bool any_sha1 = __ballot(my_algo != 0) != 0;          // the same in both waves: they read the same jobs
+  if (sha_group_pick(order, group, m, pick, role)) return;
+  const ShaLaneJob J(jobs, m, n);
+  const uint32_t max_nblk = J.wave_max_nblk();
+  const bool any_sha1 = J.wave_any_sha1();         // the same in both waves: they read the same jobs
 
-  uint32_t st[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
-  uint8_t* my_row = slab + lane * ROW;
-
-  if (role == 0) {
-    *(uint64_t*)(desc + lane * 16) = my_src;
-    *(uint32_t*)(desc + lane * 16 + 8) = my_len;
-    *(uint32_t*)(desc + lane * 16 + 12) = my_nblk;
-  }
-  uint4 stage[LPR];
-  uint32_t live = 0;
-  auto fetch = [&](uint32_t blk0) {
-    const uint32_t tile_off = blk0 * 64;
-    live = 0;
-    uint4 dsc[LPR];                              // every row descriptor first (one ds_read_b128 each), then the loads
-#pragma unroll
-    for (int g = 0; g < LPR; g++) dsc[g] = *(const uint4*)(desc + (g * RPI + lane / LPR) * 16);
-#pragma unroll
-    for (int g = 0; g < LPR; g++) {
-      const int chunk = lane % LPR;
-      const uint64_t rsrc = ((uint64_t)dsc[g].y << 32) | dsc[g].x;
-      const uint32_t rlen = dsc[g].z;
-      const uint32_t rnblk = dsc[g].w;
-      const uint32_t off = tile_off + chunk * 16;
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (blk0 < rnblk) {
-        live |= 1u << g;
-        if (off + 16 <= rlen) {
-          { const u32x4_raw t4 = *(gptr_u4)(rsrc + off); v = make_uint4(t4.x, t4.y, t4.z, t4.w); }
-        } else if (off < rlen) {
-          gptr_u8 p = (gptr_u8)(rsrc + off);
-          uint32_t rem = rlen - off, t[4] = {0, 0, 0, 0};
-          for (uint32_t b = 0; b < rem; b++) t[b >> 2] |= (uint32_t)p[b] << (8 * (b & 3));
-          v = make_uint4(t[0], t[1], t[2], t[3]);
-        }
-      }
-      stage[g] = v;
-    }
-  };
-  auto commit = [&](uint32_t blk0) {
-    const uint32_t tile_off = blk0 * 64;
-#pragma unroll
-    for (int g = 0; g < LPR; g++) {
-      const int row = g * RPI + lane / LPR;
-      const int chunk = lane % LPR;
-      if (live & (1u << g)) *(uint4*)(slab + row * ROW + chunk * 16) = stage[g];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (blk0 < my_nblk) {
-      if (my_len >= tile_off && my_len < tile_off + T) my_row[my_len - tile_off] = 0x80;
-      const uint32_t last = my_nblk - 1;
-      if (last >= blk0 && last < blk0 + T / 64) {
-        const uint64_t bits = (uint64_t)my_len * 8;
-        uint32_t* tail = (uint32_t*)(my_row + (last - blk0) * 64 + 56);
-        tail[0] = __builtin_bswap32((uint32_t)(bits >> 32));
-        tail[1] = __builtin_bswap32((uint32_t)bits);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  };
+  uint32_t st[8];
+  sha_init_state(st, false);
+  ShaTile<T> tile(lds_raw, lane, J);
+  if (role == 0) tile.describe(J);
 
   if (any_sha1) {
     // one-wave routine (as sha256_batch_kernel) by the feeder; the other wave has nothing to do.  No barrier below.
     if (role != 0) return;
-    if (my_algo) { st[0] = 0x67452301; st[1] = 0xEFCDAB89; st[2] = 0x98BADCFE; st[3] = 0x10325476; st[4] = 0xC3D2E1F0; st[5] = st[6] = st[7] = 0; }
+    sha_init_state(st, J.algo != 0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (max_nblk) { fetch(0); commit(0); }
-    for (uint32_t blk0 = 0; blk0 < max_nblk; blk0 += T / 64) {
-      const uint32_t next = blk0 + T / 64;
-      const bool more = next < max_nblk;
-      if (more) fetch(next);
-#pragma unroll 1
-      for (int b = 0; b < T / 64; b++) {
-        if (blk0 + b < my_nblk) {
-          uint32_t w[16];
-          const uint4* src = (const uint4*)(my_row + b * 64);
-#pragma unroll
-          for (int q = 0; q < 4; q++) {
-            uint4 v = src[q];
-            w[4 * q + 0] = __builtin_bswap32(v.x); w[4 * q + 1] = __builtin_bswap32(v.y);
-            w[4 * q + 2] = __builtin_bswap32(v.z); w[4 * q + 3] = __builtin_bswap32(v.w);
-          }
-          if (my_algo) sha1_compress(st, w); else sha256_compress(st, w);
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (more) commit(next);
-    }
+    sha_one_wave_tiles<T>(tile, st, max_nblk, J.algo != 0);
   } else {
-    // feeder: K+W of block kb into kw[kb & 1]
-    auto sched = [&](uint32_t kb) {
-      uint32_t w[16];
-      const uint4* src = (const uint4*)(my_row + (kb % (T / 64)) * 64);
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        uint4 v = src[q];
-        w[4 * q + 0] = __builtin_bswap32(v.x); w[4 * q + 1] = __builtin_bswap32(v.y);
-        w[4 * q + 2] = __builtin_bswap32(v.z); w[4 * q + 3] = __builtin_bswap32(v.w);
-      }
-      uint4* dst = (uint4*)(kw + lane * SHA_KW_ROW);
-      uint32_t o4[4];
-#pragma unroll
-      for (int i = 0; i < 64; i++) {
-        uint32_t wi;
-        if (i < 16) {
-          wi = w[i];
-        } else {
-          const uint32_t w15 = w[(i - 15) & 15], w2 = w[(i - 2) & 15];
-          const uint32_t s0 = xor3(rotr32(w15, 7), rotr32(w15, 18), w15 >> 3);
-          const uint32_t s1 = xor3(rotr32(w2, 17), rotr32(w2, 19), w2 >> 10);
-          wi = w[i & 15] + s0 + w[(i - 7) & 15] + s1;
-          w[i & 15] = wi;
-        }
-        o4[i & 3] = wi + SHA_K[i];
-        if ((i & 3) == 3) dst[i >> 2] = make_uint4(o4[0], o4[1], o4[2], o4[3]);
-      }
-    };
+    // feeder: K+W of block kb into the one buffer
+    auto sched = [&](uint32_t kb) { sha_kw_schedule(tile.my_row + (kb % (T / 64)) * 64, kw + lane * SHA_KW_ROW); };
     if (role == 0 && max_nblk) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      fetch(0); commit(0);
-      if (T / 64 < max_nblk) fetch(T / 64);
+      tile.fetch(0); tile.commit(0);
+      if (T / 64 < max_nblk) tile.fetch(T / 64);
       sched(0);
     }
     __syncthreads();
@@ -568,24 +553,13 @@ __device__ __forceinline__ void sha256_pair_group(const ShaJob* __restrict__ job
         const uint32_t nb = kb + 1;
         if (nb < max_nblk) {
           if (nb % (T / 64) == 0) {                  // first block of the next tile: its bytes were fetched a tile ago
-            commit(nb);
-            if (nb + T / 64 < max_nblk) fetch(nb + T / 64);
+            tile.commit(nb);
+            if (nb + T / 64 < max_nblk) tile.fetch(nb + T / 64);
           }
           sched(nb);
         }
       } else {
-        uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
-#pragma unroll
-        for (int i = 0; i < 64; i++) {
-          const uint32_t S1 = xor3(rotr32(e, 6), rotr32(e, 11), rotr32(e, 25));
-          const uint4 k4 = kq[i >> 2];
-          const uint32_t kwi = (i & 3) == 0 ? k4.x : (i & 3) == 1 ? k4.y : (i & 3) == 2 ? k4.z : k4.w;
-          const uint32_t t1 = (h + S1 + ch3(e, f, g)) + kwi;
-          const uint32_t S0 = xor3(rotr32(a, 2), rotr32(a, 13), rotr32(a, 22));
-          const uint32_t mj = maj3(a, b, c);
-          h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + S0 + mj;
-        }
-        if (kb < my_nblk) { st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h; }
+        sha_rounds_kw(st, kq, kb < J.nblk);
       }
       ZKE_SHA_STAMP(kb, 3);
       __syncthreads();                                // the next block's words are in the buffer
@@ -593,11 +567,7 @@ __device__ __forceinline__ void sha256_pair_group(const ShaJob* __restrict__ job
     }
     if (role == 0) return;
   }
-  if (m < n && my_dst) {
-    gptr_out32 out = (gptr_out32)my_dst;
-#pragma unroll
-    for (int i = 0; i < 8; i++) out[i] = (my_algo && i >= 5) ? 0u : __builtin_bswap32(st[i]);
-  }
+  if (m < n && J.dst) sha_store_digest((gptr_out32)J.dst, st, J.algo != 0);
 }
 
 template <int T>
@@ -623,139 +593,28 @@ constexpr size_t sha256_ring_lds_bytes() { return sha256_pair_lds_bytes<T>() + 6
 template <int T>
 __device__ __forceinline__ void sha256_ring_group(const ShaJob* __restrict__ jobs, uint32_t n, uint32_t group, uint8_t* lds_raw,
                                                   const ShaOrder* order = nullptr) {
-  static_assert(T % 64 == 0 && T >= 64 && T <= 1024, "tile must be whole SHA blocks");
-  constexpr int ROW = T + 16;
-  constexpr int LPR = T / 16;
-  constexpr int RPI = 64 / LPR;
   constexpr int KW_BUF = 64 * SHA_KW_ROW;          // dwords per buffer
   __builtin_amdgcn_s_setprio(ZKE_SHA_PRIO);
   const int lane = threadIdx.x & 63;
   const int role = threadIdx.x >> 6;               // 0 feeder, 1 rounds
-  uint8_t* slab = lds_raw;
-  uint8_t* desc = slab + 64 * ROW;
-  uint32_t* kw = (uint32_t*)(desc + 64 * 16);      // [2 buffers][64 lanes][SHA_KW_ROW]
+  uint32_t* kw = (uint32_t*)(lds_raw + ShaTile<T>::BYTES);      // [2 buffers][64 lanes][SHA_KW_ROW]
   uint32_t* pick = kw + 2 * KW_BUF;                // 1 KB: sha_pick_job
 
   uint32_t m = group * 64 + lane;
-  if (order && order->cnt) {                       // as sha256_pair_group
-    bool skip = false;
-    uint32_t mine = 0;
-    if (role == 0) {
-      mine = sha_pick_job(*order, group, m, pick, skip);
-      if (lane == 0) pick[SHA_CLASSES - 1] = skip ? 1u : 0u;
-      pick[SHA_CLASSES + lane] = mine;
-    }
-    __syncthreads();
-    if (pick[SHA_CLASSES - 1]) return;
-    m = pick[SHA_CLASSES + lane];
-    __syncthreads();
-  }
-  uint64_t my_src = 0, my_dst = 0;
-  uint32_t my_len = 0, my_nblk = 0, my_algo = 0;
-  if (m < n) {
-    ShaJob j = jobs[m];
-    my_src = j.src; my_dst = j.dst; my_len = j.len; my_algo = j.pad;
-    my_nblk = my_dst ? (my_len + 9 + 63) >> 6 : 0;
-  }
-  if (__ballot(my_algo != 0) != 0) {               // the same in both waves (same jobs): the pair routine's one-wave path.  It works the
+  if (sha_group_pick(order, group, m, pick, role)) return;
+  const ShaLaneJob J(jobs, m, n);
+  if (J.wave_any_sha1()) {                         // the same in both waves (same jobs): the pair routine's one-wave path.  It works the
     sha256_pair_group<T>(jobs, n, group, lds_raw, order);      // picks out again (rsa-sha1 is rare) in its own, smaller layout of this LDS
     return;
   }
-  uint32_t max_nblk = my_nblk;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) max_nblk = max(max_nblk, (uint32_t)__shfl_xor((int)max_nblk, o));
-  max_nblk = __builtin_amdgcn_readfirstlane(max_nblk);
+  const uint32_t max_nblk = J.wave_max_nblk();
 
-  uint32_t st[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
-  uint8_t* my_row = slab + lane * ROW;
-
-  if (role == 0) {
-    *(uint64_t*)(desc + lane * 16) = my_src;
-    *(uint32_t*)(desc + lane * 16 + 8) = my_len;
-    *(uint32_t*)(desc + lane * 16 + 12) = my_nblk;
-  }
-  // fetch / commit: tile staging and padding exactly as in sha256_pair_group
-  uint4 stage[LPR];
-  uint32_t live = 0;
-  auto fetch = [&](uint32_t blk0) {
-    const uint32_t tile_off = blk0 * 64;
-    live = 0;
-    uint4 dsc[LPR];
-#pragma unroll
-    for (int g = 0; g < LPR; g++) dsc[g] = *(const uint4*)(desc + (g * RPI + lane / LPR) * 16);
-#pragma unroll
-    for (int g = 0; g < LPR; g++) {
-      const int chunk = lane % LPR;
-      const uint64_t rsrc = ((uint64_t)dsc[g].y << 32) | dsc[g].x;
-      const uint32_t rlen = dsc[g].z;
-      const uint32_t rnblk = dsc[g].w;
-      const uint32_t off = tile_off + chunk * 16;
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (blk0 < rnblk) {
-        live |= 1u << g;
-        if (off + 16 <= rlen) {
-          { const u32x4_raw t4 = *(gptr_u4)(rsrc + off); v = make_uint4(t4.x, t4.y, t4.z, t4.w); }
-        } else if (off < rlen) {
-          gptr_u8 p = (gptr_u8)(rsrc + off);
-          uint32_t rem = rlen - off, t[4] = {0, 0, 0, 0};
-          for (uint32_t b = 0; b < rem; b++) t[b >> 2] |= (uint32_t)p[b] << (8 * (b & 3));
-          v = make_uint4(t[0], t[1], t[2], t[3]);
-        }
-      }
-      stage[g] = v;
-    }
-  };
-  auto commit = [&](uint32_t blk0) {
-    const uint32_t tile_off = blk0 * 64;
-#pragma unroll
-    for (int g = 0; g < LPR; g++) {
-      const int row = g * RPI + lane / LPR;
-      const int chunk = lane % LPR;
-      if (live & (1u << g)) *(uint4*)(slab + row * ROW + chunk * 16) = stage[g];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (blk0 < my_nblk) {
-      if (my_len >= tile_off && my_len < tile_off + T) my_row[my_len - tile_off] = 0x80;
-      const uint32_t last = my_nblk - 1;
-      if (last >= blk0 && last < blk0 + T / 64) {
-        const uint64_t bits = (uint64_t)my_len * 8;
-        uint32_t* tail = (uint32_t*)(my_row + (last - blk0) * 64 + 56);
-        tail[0] = __builtin_bswap32((uint32_t)(bits >> 32));
-        tail[1] = __builtin_bswap32((uint32_t)bits);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  };
+  uint32_t st[8];
+  sha_init_state(st, false);
+  ShaTile<T> tile(lds_raw, lane, J);
+  if (role == 0) tile.describe(J);
   // feeder: K+W of block kb into buffer kb & 1
-  auto sched = [&](uint32_t kb) {
-    uint32_t w[16];
-    const uint4* src = (const uint4*)(my_row + (kb % (T / 64)) * 64);
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      uint4 v = src[q];
-      w[4 * q + 0] = __builtin_bswap32(v.x); w[4 * q + 1] = __builtin_bswap32(v.y);
-      w[4 * q + 2] = __builtin_bswap32(v.z); w[4 * q + 3] = __builtin_bswap32(v.w);
-    }
-    uint4* dst = (uint4*)(kw + (kb & 1) * KW_BUF + lane * SHA_KW_ROW);
-    uint32_t o4[4];
-#pragma unroll
-    for (int i = 0; i < 64; i++) {
-      uint32_t wi;
-      if (i < 16) {
-        wi = w[i];
-      } else {
-        const uint32_t w15 = w[(i - 15) & 15], w2 = w[(i - 2) & 15];
-        const uint32_t s0 = xor3(rotr32(w15, 7), rotr32(w15, 18), w15 >> 3);
-        const uint32_t s1 = xor3(rotr32(w2, 17), rotr32(w2, 19), w2 >> 10);
-        wi = w[i & 15] + s0 + w[(i - 7) & 15] + s1;
-        w[i & 15] = wi;
-      }
-      o4[i & 3] = wi + SHA_K[i];
-      if ((i & 3) == 3) dst[i >> 2] = make_uint4(o4[0], o4[1], o4[2], o4[3]);
-    }
-  };
+  auto sched = [&](uint32_t kb) { sha_kw_schedule(tile.my_row + (kb % (T / 64)) * 64, kw + (kb & 1) * KW_BUF + lane * SHA_KW_ROW); };
   // The block barrier: an s_barrier between LDS-only fences.  (__syncthreads() would also wait for the feeder's global
   // fetches of the next tile, which only commit() needs.)
   auto block_barrier = [&]() {
@@ -766,10 +625,10 @@ __device__ __forceinline__ void sha256_ring_group(const ShaJob* __restrict__ job
   if (role == 0 && max_nblk) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    fetch(0); commit(0);
-    if (T / 64 < max_nblk) fetch(T / 64);
+    tile.fetch(0); tile.commit(0);
+    if (T / 64 < max_nblk) tile.fetch(T / 64);
     sched(0);
-    if (T / 64 == 1 && 1 < max_nblk) commit(1);
+    if (T / 64 == 1 && 1 < max_nblk) tile.commit(1);
   }
   ZKE_SHA_WHERE();
   block_barrier();                                  // barrier -1: block 0's words are in buffer 0
@@ -788,15 +647,16 @@ __device__ __forceinline__ void sha256_ring_group(const ShaJob* __restrict__ job
       // the slab's bytes have all been read — the loads still have a whole tile's steps to arrive.
       const uint32_t nb = kb + 1;
       if (nb < max_nblk) {
-        if (nb % (T / 64) == 0 && nb + T / 64 < max_nblk) fetch(nb + T / 64);
+        if (nb % (T / 64) == 0 && nb + T / 64 < max_nblk) tile.fetch(nb + T / 64);
         sched(nb);
-        if (nb % (T / 64) == T / 64 - 1 && nb + 1 < max_nblk) commit(nb + 1);
+        if (nb % (T / 64) == T / 64 - 1 && nb + 1 < max_nblk) tile.commit(nb + 1);
       }
     } else {
       const uint4* src = (const uint4*)(kw + (kb & 1) * KW_BUF + lane * SHA_KW_ROW);
       uint4 kq[16];                                 // all 16 reads go out here; each round group waits for its own quad only (lgkmcnt(N))
 #pragma unroll
       for (int q = 0; q < 16; q++) kq[q] = src[q];
+      // sha_rounds_kw written out: through the call all 16 reads stand in front of round 0, which waits for 13 of them: headline - 1.9 % (profiles/sha_shared_bench_ab.txt)
       uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
 #pragma unroll
       for (int i = 0; i < 64; i++) {
@@ -808,18 +668,14 @@ __device__ __forceinline__ void sha256_ring_group(const ShaJob* __restrict__ job
         const uint32_t mj = maj3(a, b, c);
         h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + S0 + mj;
       }
-      if (kb < my_nblk) { st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h; }
+      if (kb < J.nblk) { st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h; }
     }
     ZKE_SHA_STAMP(kb, 1);
     block_barrier();                                // barrier kb
     ZKE_SHA_STAMP(kb, 2);
   }
   if (role == 0) return;
-  if (m < n && my_dst) {
-    gptr_out32 out = (gptr_out32)my_dst;
-#pragma unroll
-    for (int i = 0; i < 8; i++) out[i] = __builtin_bswap32(st[i]);
-  }
+  if (m < n && J.dst) sha_store_digest((gptr_out32)J.dst, st, false);      // no SHA-1 job in a ring group
 }
 
 template <int T>

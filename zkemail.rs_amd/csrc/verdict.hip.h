@@ -30,8 +30,8 @@ __device__ __forceinline__ void sha_lane(const ShaJob& j) {
   if (!j.dst) return;
   const uint8_t* src = (const uint8_t*)j.src;
   const uint32_t len = j.len, nblk = (len + 9 + 63) >> 6;
-  uint32_t st[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
-  if (j.pad) { st[0] = 0x67452301; st[1] = 0xEFCDAB89; st[2] = 0x98BADCFE; st[3] = 0x10325476; st[4] = 0xC3D2E1F0; st[5] = st[6] = st[7] = 0; }
+  uint32_t st[8];
+  sha_init_state(st, j.pad != 0);
   typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
   for (uint32_t b = 0; b < nblk; b++) {
     uint32_t w[16];
@@ -54,9 +54,7 @@ __device__ __forceinline__ void sha_lane(const ShaJob& j) {
     if (b == nblk - 1) { const uint64_t bits = (uint64_t)len * 8; w[14] = (uint32_t)(bits >> 32); w[15] = (uint32_t)bits; }
     if (j.pad) sha1_compress(st, w); else sha256_compress(st, w);
   }
-  uint32_t* out = (uint32_t*)j.dst;
-#pragma unroll
-  for (int k = 0; k < 8; k++) out[k] = (j.pad && k >= 5) ? 0u : __builtin_bswap32(st[k]);
+  sha_store_digest((uint32_t*)j.dst, st, j.pad != 0);
 }
 
 // what one lane stored, the other lanes of this wave read back: past this CU's L1 (rare paths only: an agent-scope
