@@ -1,4 +1,4 @@
-"""Seeded populations that walk the header split of csrc/parse.hip.h (split_headers_lines, scan_headers, find_body) through
+"""Seeded populations that walk the header split of csrc/hdrsplit.hip.h (split_headers_lines, scan_headers, find_body) through
 its geometry: every lane of a 64-byte chunk, the chunk and line-group edges, the 64-entry span table, the LINE_CAP and
 ZKE_MAX_HEADERS limits and the staged edge at byte 3 568.  No engine and no oracle in here: tests/test_hdr_split_model.py
 certifies on the CPU what each population reaches, tests/test_gpu_hdr_split.py runs them on the device.

@@ -1,4 +1,4 @@
-"""The mailparse header split of csrc/parse.hip.h, stated twice on the CPU — test infrastructure.
+"""The mailparse header split of csrc/hdrsplit.hip.h, stated twice on the CPU — test infrastructure.
 
 `serial`       scan_headers (the serial walk: the fallback of round 0, the only path of later signature rounds and of the
                MIME sub-part walk) as plain Python over bytes.

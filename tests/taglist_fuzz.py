@@ -1,6 +1,6 @@
 """DKIM-Signature tag lists in every spelling RFC 6376 §3.2 allows — and a few it does not — signed by the Python signer's
 primitives (tests/synth.py: canonicalisation, hashlib, Python integers), for the tag-list parsers (cfdkim parser::tag_list
-behind core/src/email.rs:31-33; oracle parse_tag_list, device taglist_lanes / taglist_serial in csrc/parse.hip.h).
+behind core/src/email.rs:31-33; oracle parse_tag_list, device taglist_lanes / taglist_serial in csrc/taglist.hip.h).
 
 A message is laid out tag by tag: random order (b= anywhere), FWS of random shape and length in the four places the
 grammar has it ([FWS] name [FWS] "=" [FWS] value [FWS]), values folded inside, unknown tags (names of one, two and many

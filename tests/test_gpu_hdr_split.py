@@ -1,4 +1,4 @@
-"""-m gpu: the header split of csrc/parse.hip.h (split_headers_lines, scan_headers behind it and in later signature rounds,
+"""-m gpu: the header split of csrc/hdrsplit.hip.h (split_headers_lines, scan_headers behind it and in later signature rounds,
 find_body) on the populations of tests/hdr_split_cases.py, one batch per population and entry.  The verify entry is compared
 with the oracle record for record and with tests/hdr_split_model.py (header count, body offset, which error); the scan entry
 with tests/sigscan_model.py, and the header index and value span of every header named DKIM-Signature with the model's span

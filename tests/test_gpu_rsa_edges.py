@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 
 KEY_NAMES = ("rsa1024_00", "rsa1025_00", "rsa2047_00", "rsa2047e3_00", "rsa2048_03", "rsa2049_00", "rsa3071_00",
              "rsa4095_00", "rsa4096_03")
-ROUTE_NOT_CACHED, ROUTE_SLOT_TAKEN, ROUTE_NOT_TAKEN = 0x200, 0x400, 0x800       # parse.hip.h rsa_route / the e != 65537 case
+ROUTE_NOT_CACHED, ROUTE_SLOT_TAKEN, ROUTE_NOT_TAKEN = 0x200, 0x400, 0x800       # keydec.hip.h rsa_route / the e != 65537 case
 
 
 def key_cache_slot(n):

@@ -1,4 +1,4 @@
-"""CPU (-m "not gpu"): the two header splits of csrc/parse.hip.h as tests/hdr_split_model.py states them, against each
+"""CPU (-m "not gpu"): the two header splits of csrc/hdrsplit.hip.h as tests/hdr_split_model.py states them, against each
 other, against the oracle's zko_parse_headers and against mime_model.parse_headers (string operations, independent of the
 oracle's C), on every population of tests/hdr_split_cases.py and on 5 000 seeded structured blocks — and the census of what
 each population makes the line-parallel split do.  tests/test_gpu_hdr_split.py runs exactly these populations, so a GPU

@@ -1,5 +1,5 @@
 """The strictness flags of zke_options (include/zkemail_amd.h): each switches ONE named site in the oracle
-(oracle/zke_oracle.c, "STRICTNESS SITE <flag>") and the same site in the device front end (csrc/parse.hip.h, csrc/canon.hip.h).
+(oracle/zke_oracle.c, "STRICTNESS SITE <flag>") and the same site in the device front end (csrc/taglist.hip.h, csrc/parse.hip.h, csrc/canon.hip.h).
 
 CPU tier: the oracle in both positions of every flag against outcomes derived in Python (tests/strict_cases.py).
 GPU tier (-m gpu): an engine created with the flag against the oracle run with the flag — whole records and the

@@ -1,4 +1,4 @@
-"""CPU (-m "not gpu"): a Python statement of taglist_lanes (csrc/parse.hip.h) — the DKIM-Signature tag list parsed one LANE
+"""CPU (-m "not gpu"): a Python statement of taglist_lanes (csrc/taglist.hip.h) — the DKIM-Signature tag list parsed one LANE
 per tag-spec — step for step as the device does it (the ';' by rank, the first byte no tag value can hold, per-lane walks of
 head and tail with the 40-step budget, the compaction of the values by piece lookup, last-tag-wins), against a plain serial
 statement of cfdkim's parser::tag_list (the grammar the oracle's parse_tag_list restates: [FWS] name [FWS] "=" [FWS] value

@@ -9,11 +9,11 @@
 //
 // Phases, all on the record's copy in LDS (the record is read from HBM once, 16 bytes per lane):
 //   1. find the tags — ZKE_KEYREC_ARCHIVE: dkim.rs:74-85, split at ';', ASCII trim, "k=" / "p=" prefixes, last wins;
-//      ZKE_KEYREC_DNS: RFC 6376 3.6.1 in the tag-list grammar of the signature parser (parse.hip.h, parse_tag_spec), FWS
+//      ZKE_KEYREC_DNS: RFC 6376 3.6.1 in the tag-list grammar of the signature parser (taglist.hip.h, parse_tag_spec), FWS
 //      removed from the k= and p= values in place;
 //   2. base64 STANDARD, strict (padding required, trailing bits zero): each lane takes four characters, 192 bytes per step;
 //   3. k=rsa: SubjectPublicKeyInfo first, then PKCS#1, then the range RsaPublicKey::new applies — with der_len / der_uint of
-//      parse.hip.h, the one copy decode_rsa_key uses too; k=ed25519: 32 bytes.
+//      keydec.hip.h, the one copy decode_rsa_key uses too; k=ed25519: 32 bytes.
 //
 // "Re-encoding" (dkim.rs:100 to_pkcs1_der).  DER admits exactly one encoding per value and the der crate rejects every other
 // one, so the PKCS#1 bytes a validated key re-encodes to ARE the bytes it was decoded from: for a SubjectPublicKeyInfo the
@@ -25,7 +25,8 @@
 // them out (zke_decode_key_records); for zke_select_keys_from_records keyrec_pack_kernel / keyrec_gather_kernel turn them into the
 // packed CSR key_blob[key_off[i] .. key_off[i+1]) + key_type[i] the front end reads, in HBM.
 #pragma once
-#include "parse.hip.h"
+#include "bytes.hip.h"
+#include "keydec.hip.h"
 
 namespace zke {
 
@@ -89,26 +90,12 @@ __device__ __forceinline__ bool kr_eq(const uint8_t* s, uint32_t a, uint32_t b, 
 // str::trim's ASCII share: U+0009..U+000D and space
 __device__ __forceinline__ bool is_trim_ws(uint32_t c) { return (c >= 9 && c <= 13) || c == ' '; }
 
-// PKCS#1 RSAPublicKey at k[p0, p0 + len): the structure decode_rsa_key reads and the range RsaPublicKey::new applies
-// (rsa 0.9.6: <= 4096 bits, 2 <= e <= 2^33 - 1).  0, ZKE_D_KEYREC_DER or ZKE_D_KEYREC_RANGE
+// PKCS#1 RSAPublicKey at k[p0, p0 + len): pkcs1_walk (keydec.hip.h), the walk decode_rsa_key takes, under the key records' codes.
+// 0, ZKE_D_KEYREC_DER or ZKE_D_KEYREC_RANGE
 __device__ __forceinline__ uint32_t kr_pkcs1(const Str& k, Win& w, uint32_t p0, uint32_t len) {
-  if (len < 2 || at(k, w, p0) != 0x30) return ZKE_D_KEYREC_DER;
-  uint32_t sl, c = der_len(k, w, p0 + 1, len - 1, sl);
-  if (!c || (uint64_t)1 + c + sl != len) return ZKE_D_KEYREC_DER;
-  uint32_t p = p0 + 1 + c, avail = sl, np, nl, ep, el;
-  uint32_t used = der_uint(k, w, p, avail, np, nl);
-  if (!used) return ZKE_D_KEYREC_DER;
-  p += used; avail -= used;
-  used = der_uint(k, w, p, avail, ep, el);
-  if (!used || used != avail) return ZKE_D_KEYREC_DER;
-  const uint32_t n0 = at(k, w, np);
-  uint32_t bits = 0;
-  if (!(nl == 1 && n0 == 0)) bits = nl * 8 - (uint32_t)(__builtin_clz(n0) - 24);
-  if (bits > 4096 || el > 8) return ZKE_D_KEYREC_RANGE;
-  uint64_t e = 0;
-  for (uint32_t i = 0; i < el; i++) e = (e << 8) | at(k, w, ep + i);
-  if (e < 2 || e > ((1ull << 33) - 1)) return ZKE_D_KEYREC_RANGE;
-  return 0;
+  Pkcs1 pk;
+  const uint32_t r = pkcs1_walk(k, w, p0, len, pk);
+  return r == PKCS1_OK ? 0u : r == PKCS1_DER ? (uint32_t)ZKE_D_KEYREC_DER : (uint32_t)ZKE_D_KEYREC_RANGE;
 }
 
 // SubjectPublicKeyInfo at k[0, len) (rsa 0.9.6 from_public_key_der: spki 0.7 + verify_algorithm_id): the outer SEQUENCE fills the
@@ -147,14 +134,7 @@ __device__ __forceinline__ void keyrec_record(const KeyrecArgs& A, const uint32_
   if (r1 - r0 > ZKE_KEYREC_MAX_BYTES) { finish(ZKE_D_KEYREC_TOO_LONG, 0, 0); return; }
   const uint32_t n = (uint32_t)(r1 - r0);
   uint8_t* s = L.rec;
-  {
-    const uint8_t* src = A.rec + r0;
-    const uint32_t full = n & ~15u;
-    for (uint32_t o = lane * 16; o < full; o += 64 * 16) *(uint4*)(s + o) = *(const uint4_unaligned*)(src + o);
-    for (uint32_t o = full + lane; o < n; o += 64) s[o] = src[o];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  }
+  stage_lds(s, A.rec + r0, n);
 
   // ---- phase 1: the k= and p= values, s[kt_s, kt_e) and s[pk_s, pk_e)
   uint32_t kt_s = 0, kt_e = 0, pk_s = 0, pk_e = 0;
@@ -188,7 +168,7 @@ __device__ __forceinline__ void keyrec_record(const KeyrecArgs& A, const uint32_
     if (kr_find(s, 0, n, [](uint32_t c) { return c >= 0x80; }) < n) { finish(ZKE_D_KEYREC_SYNTAX, 0, 0); return; }
     bool have_p = false;
     for (uint32_t pos = 0, idx = 0;; idx++) {
-      // tag-spec = [FWS] tag-name [FWS] "=" [FWS] tag-value [FWS]   (parse.hip.h, parse_tag_spec)
+      // tag-spec = [FWS] tag-name [FWS] "=" [FWS] tag-value [FWS]   (taglist.hip.h, parse_tag_spec)
       uint32_t p = kr_find(s, pos, n, [](uint32_t c) { return !is_fws(c); });
       bool ok = p < n && is_alpha(kr_at(s, p));
       uint32_t ns = p, ne = p, rs = 0, re = 0, rend = 0;
@@ -233,24 +213,18 @@ __device__ __forceinline__ void keyrec_record(const KeyrecArgs& A, const uint32_
   const uint32_t nc = pk_e - pk_s;
   if (nc % 4) { finish(ZKE_D_KEYREC_B64, key_type, 0); return; }
   const uint8_t* t = s + pk_s;
-  const uint32_t pad = kr_at(t, nc - 1) == '=' ? (kr_at(t, nc - 2) == '=' ? 2u : 1u) : 0u;
+  const uint32_t pad = b64_pad(t, nc);
   const uint32_t total = 3 * (nc / 4) - pad;                                          // <= 3069 < KEYREC_DER_MAX
   {
     bool bad = false;
     for (uint32_t q0 = 0; q0 < nc / 4; q0 += 64) {
       const uint32_t q = q0 + lane;
       if (q < nc / 4) {
-        const bool last = q + 1 == nc / 4;
-        const uint32_t a = b64v(t[4 * q]), b = b64v(t[4 * q + 1]);
-        uint32_t c = b64v(t[4 * q + 2]), d = b64v(t[4 * q + 3]);
-        uint32_t nb = 3;
-        if (last && pad == 2) { c = 0; d = 0; nb = 1; if (b & 15) bad = true; }
-        else if (last && pad == 1) { d = 0; nb = 2; if (c < 64 && (c & 3)) bad = true; }
-        if (a > 63 || b > 63 || c > 63 || d > 63) bad = true;
-        const uint32_t v = (a << 18) | (b << 12) | (c << 6) | d;
-        L.der[3 * q] = (uint8_t)(v >> 16);
-        if (nb > 1) L.der[3 * q + 1] = (uint8_t)(v >> 8);
-        if (nb > 2) L.der[3 * q + 2] = (uint8_t)v;
+        const B64Quad d = b64_quad(t, nc / 4, pad, q);
+        bad = bad || d.bad;
+        L.der[3 * q] = (uint8_t)(d.v >> 16);
+        if (d.nb > 1) L.der[3 * q + 1] = (uint8_t)(d.v >> 8);
+        if (d.nb > 2) L.der[3 * q + 2] = (uint8_t)d.v;
       }
     }
     if (__ballot(bad)) { finish(ZKE_D_KEYREC_B64, key_type, 0); return; }

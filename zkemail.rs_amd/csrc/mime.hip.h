@@ -54,7 +54,7 @@ __device__ __forceinline__ uint32_t mime_content_type(const Str& v, uint32_t& bs
     const uint64_t semi = __ballot(c == ';');
     const uint32_t t0 = semi ? (uint32_t)__builtin_ctzll(semi) : (n <= 64 ? n : 65u);
     if (t0 <= 63) {                                                       // (a token that fills the chunk goes the long way)
-      const uint32_t nx = lane_shl1(c);                                   // lane 63 is outside the token
+      const uint32_t nx = lane_up(c);                                   // lane 63 is outside the token
       const bool in = l < t0;
       const uint64_t und = __ballot(in && (c >= 0x80 || (c == '=' && nx == '?')));
       const uint64_t nws = __ballot(in && !rust_ws(c));

@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lanes.hip.h"
+
 namespace zke {
 
 struct RsaJob {                 // written by the parse kernel (or the host for the unit entry point)
@@ -74,15 +76,7 @@ static_assert(KEY_CACHE_SLOTS == (1u << 12), "key_cache_slot yields 12 bits");
 __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// ---- cross-lane helpers -------------------------------------------------------------
-// value of lane+1 (lane 63 gets 0): v_mov_b32_dpp wave_shl:1 bound_ctrl:0
-__device__ __forceinline__ uint32_t lane_up(uint32_t x) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x130 /*wave_shl:1*/, 0xf, 0xf, false);
-}
-// value of lane-1 (lane 0 gets 0): wave_shr:1
-__device__ __forceinline__ uint32_t lane_down(uint32_t x) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x138 /*wave_shr:1*/, 0xf, 0xf, false);
-}
+// ---- cross-lane helpers (lane_up / lane_down: lanes.hip.h) --------------------------
 __device__ __forceinline__ uint64_t ballot64(bool p) { return __ballot(p); }
 
 // A big number in "lane-major" layout: limb index = q*64 + lane for q in [0,NL).

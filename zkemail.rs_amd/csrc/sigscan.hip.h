@@ -1,6 +1,7 @@
 // sigscan.hip.h — the DKIM-Signature scan: the first step of the reference's input generation
 // (helpers/src/generator.rs:17-30), one e-mail per wavefront like the front end and built from the front end's own helpers
-// (parse.hip.h: the header split, the MIME subpart walk, validate_sig, the ASCII-folded d= / from_domain comparison).
+// (hdrsplit.hip.h: the header split, the MIME subpart walk, the DKIM-Signature fields; taglist.hip.h: validate_sig, the
+// ASCII-folded d= / from_domain comparison, a=).
 //
 // Per e-mail: parse_mail, then EVERY header field named DKIM-Signature in file order gets one record — its validate_header
 // verdict, whether d= names from_domain, a= classified, the FWS-stripped s= value, the span of the header's value.  No key is
@@ -13,7 +14,8 @@
 // (sel_off, sel_len) and nothing else).  A selector that does not fit is not written, the counter still advances: the host
 // reads the size a second call needs from it.
 #pragma once
-#include "parse.hip.h"
+#include "hdrsplit.hip.h"
+#include "parse.hip.h"       // ZKE_PARSE_WAVES: the scan is compiled for the front end's occupancy
 
 namespace zke {
 
@@ -39,19 +41,7 @@ __device__ __forceinline__ void sigscan_email(const SigScanArgs& A, const uint32
   };
   if (r1 - r0 >= (1ull << 31)) { finish(ZKE_UNSUPPORTED, ZKE_D_U_EMAIL_TOO_LARGE, 0, 0); return; }
   Str raw = mkstr(A.raw + r0, (uint32_t)(r1 - r0));
-  {
-    // the head of the e-mail in LDS, as the front end stages it (parse_email, stage_head)
-    const uint32_t want = raw.len < PARSE_STAGE_BYTES ? raw.len : PARSE_STAGE_BYTES;
-    const uint32_t full = want & ~15u;
-    for (uint32_t base = 0; base < full; base += 64 * 16) {
-      const uint32_t o = base + lane * 16;
-      if (o < full) *(uint4*)(L.stage + o) = *(const uint4_unaligned*)(raw.base + o);
-    }
-    { const uint32_t o = full + lane; if (o < want) L.stage[o] = raw.base[o]; }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    raw.lds = L.stage; raw.lds_len = want;
-  }
+  stage_head(raw, L);
   const Str dom = mkstr(A.dom + A.dom_off[i], (uint32_t)(A.dom_off[i + 1] - A.dom_off[i]));
 
   // ---- mailparse::parse_mail: the header list, then the MIME subparts
@@ -59,40 +49,18 @@ __device__ __forceinline__ void sigscan_email(const SigScanArgs& A, const uint32
   uint32_t* hdr_ovf = A.hdr_ovf + (size_t)i * (HDR_OVF_BYTES / 4);
   if (!split_headers_lines(L, hdr_ovf, raw, nh, perr, hdr_end)) nh = split_headers(L, hdr_ovf, raw, perr, hdr_end);
   if (nh == NONE) { finish(perr == ZKE_D_U_TOO_MANY_HEADERS ? ZKE_UNSUPPORTED : ZKE_PARSE_FAIL, perr, 0, 0); return; }
-  uint32_t hks_lane = 0, hnl_lane = NONE;
-  if (lane < nh && lane < HDR_LDS_ENTRIES) { hks_lane = L.hdr[4 * lane]; hnl_lane = L.hdr[4 * lane + 1] - hks_lane; }
+  const HdrNames hn = hdr_names(L, nh);
   {
-    bool has_ct = false;
-    uint32_t cvs = 0, cve = 0;
-    for (uint64_t m = __ballot(hnl_lane == 12u); m; m &= m - 1) {
-      const uint32_t x = (uint32_t)__builtin_ctzll(m);
-      if (span_ieq(raw, __builtin_amdgcn_readlane(hks_lane, x), 12, LIT("content-type"))) { const HdrSpan hs = hdr_get(L, hdr_ovf, x); has_ct = true; cvs = hs.vs; cve = hs.ve; break; }
-    }
-    for (uint32_t x = HDR_LDS_ENTRIES; !has_ct && x < nh; x++) {
-      const HdrSpan hs = hdr_get(L, hdr_ovf, x);
-      if (span_ieq(raw, hs.ks, hs.ke - hs.ks, LIT("content-type"))) { has_ct = true; cvs = hs.vs; cve = hs.ve; }
-    }
-    if (has_ct) {
-      uint32_t ixb = hdr_end;
-      if (ixb < raw.len) ixb += (uni(ldb(raw, ixb)) == '\r') ? 2u : 1u;
-      uint32_t md = 0;
-      const uint32_t mr = mime_walk((uint32_t*)L.tagbuf, raw, ixb, true, cvs, cve, md);
-      if (mr) { finish(mr, md, 0, 0); return; }
-    }
+    uint32_t md = 0;
+    const uint32_t mr = mime_subparts(L, hdr_ovf, raw, hn, nh, hdr_end, md);
+    if (mr) { finish(mr, md, 0, 0); return; }
   }
-  {
-    // U+212A KELVIN SIGN in from_domain: its to_lowercase() is ASCII, the ASCII fold below would not be exact (parse_email)
-    bool kelvin = false;
-    for (uint32_t base = 0; base + 2 < dom.len; base += 64) {
-      const uint32_t o = base + lane;
-      kelvin = kelvin || (o + 2 < dom.len && ldb(dom, o) == 0xE2 && ldb(dom, o + 1) == 0x84 && ldb(dom, o + 2) == 0xAA);
-    }
-    if (__ballot(kelvin)) { finish(ZKE_UNSUPPORTED, ZKE_D_U_DOMAIN_FOLD, 0, 0); return; }
-  }
+  if (domain_has_kelvin(dom)) { finish(ZKE_UNSUPPORTED, ZKE_D_U_DOMAIN_FOLD, 0, 0); return; }      // the d= comparison below folds ASCII alone
 
-  // ---- every DKIM-Signature header, file order
+  // ---- every DKIM-Signature header, file order.  (The walk is written out here; through next_sig_header, as parse_email takes it,
+  // sigscan_kernel alone measured 2 % longer: profiles/frontend_shared_bench_ab.txt.)
   uint32_t sig_ix = 0, n_cand = 0;
-  const uint64_t sig_len_mask = __ballot(hnl_lane == 14u);
+  const uint64_t sig_len_mask = __ballot(hn.nl == 14u);
   for (uint32_t hx = 0; hx < nh; hx++) {
     if (hx < 64 && !((sig_len_mask >> hx) & 1)) continue;
     const HdrSpan hs = hdr_get(L, hdr_ovf, hx);
@@ -103,21 +71,8 @@ __device__ __forceinline__ void sigscan_email(const SigScanArgs& A, const uint32
     uint32_t code = validate_sig<true>(L, v, present, A.strict, A.now);
     uint32_t algo = 0, sel_off = 0, sel_len = 0;
     if (code == 0) {
-      // signing_domain.to_lowercase() == from_domain.to_lowercase()
-      bool same = tagf(L, TG_D, 3) == dom.len;
-      if (same) {
-        bool bad = false;
-        const uint32_t dofs = tagf(L, TG_D, 2);
-        for (uint32_t o = 0; o < dom.len; o += 64) {
-          const uint32_t l = o + lane;
-          if (l < dom.len) bad |= lower(L.tagbuf[dofs + l]) != lower(ldb(dom, l));
-        }
-        same = __ballot(bad) == 0;
-      }
-      if (same) n_cand++; else code = ZKE_D_NEUTRAL;
-      const TagVal a = tagval(L, TG_A);
-      algo = a == LIT("rsa-sha256") ? ZKE_SIG_ALGO_RSA_SHA256 : a == LIT("rsa-sha1") ? ZKE_SIG_ALGO_RSA_SHA1
-           : a == LIT("ed25519-sha256") ? ZKE_SIG_ALGO_ED25519_SHA256 : ZKE_SIG_ALGO_OTHER;
+      if (sig_names_domain(L, dom)) n_cand++; else code = ZKE_D_NEUTRAL;
+      algo = sig_algo(L);
       if (this_ix < A.max_sigs) {
         sel_len = tagf(L, TG_S, 3);                       // <= ZKE_MAX_TAGBUF
         if (sel_len) {
