@@ -657,6 +657,11 @@ int zke_get_slot_timings(zke_engine* e, uint32_t slot, zke_timings* t);
  * (one).  Chosen like the eight-lane RSA role — min(slots that exist, GPU_MAX_HW_QUEUES as read at creation) <= 4 takes the
  * ring — or forced by ZKE_SHA_RING = 0 / 1 in the environment at zke_engine_create.  Negative: an error code. */
 int zke_engine_sha_ring(zke_engine* e);
+/* The lane mapping of the ring's rounds wave as the engine stands now: 1 two lanes per message (the twin: groups of 32 messages, for
+ * bodies and header preimages in the hash / modexp launch and for zke_sha256_batch), 0 one lane per message.  1 only where
+ * zke_engine_sha_ring answers 1; ZKE_SHA_TWIN = 0 / 1 in the environment at zke_engine_create turns it off / asks for it wherever the
+ * ring is taken.  Negative: an error code. */
+int zke_engine_sha_twin(zke_engine* e);
 /* Enable per-launch HIP-event timing (adds event records between the launches). */
 int zke_set_timing(zke_engine* e, int enabled);
 

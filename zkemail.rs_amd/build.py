@@ -159,6 +159,26 @@ def build_sha_probe(force: bool = False, stamps: bool = True) -> str:
     return exe
 
 
+SHA_TWIN_PROBE = os.path.join(ROOT, "tests", "cpp", "sha_twin_probe")
+
+
+def build_sha_twin_probe(force: bool = False, stamps: bool = True) -> str:
+    """tests/cpp/sha_twin_probe: sha256_ring_kernel against sha256_twin_kernel on the messages of sha_probe
+    (tools/sha_twin_timeline.py).  Built on request only, with the flags of build_sha_probe."""
+    src = SHA_TWIN_PROBE + ".hip"
+    exe = SHA_TWIN_PROBE if stamps else SHA_TWIN_PROBE + "_plain"
+    deps = [src] + [d for d in _deps(CSRC) if d.endswith(".h")]
+    if not force and not _newer(exe, deps):
+        return exe
+    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
+           "-Wall", "-Wno-unused-function", "-o", exe, src] + (["-DZKE_SHA_PROBE"] if stamps else [])
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout + r.stderr)
+        raise RuntimeError("hipcc failed building tests/cpp/sha_twin_probe")
+    return exe
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
     print(build_oracle(force))

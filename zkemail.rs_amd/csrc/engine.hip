@@ -174,6 +174,12 @@ struct zke_engine {
   int sha_ring = -1;                // the two-wave SHA-256 groups run sha256_ring_group (two K+W buffers, 45 KB of LDS per group) instead of
                                     // sha256_pair_group (one, 28 KB): -1 by the same in-flight bound (sha_takes_ring), 0 never, 1 always
                                     // (ZKE_SHA_RING in the environment)
+  int sha_twin = -1;                // where the ring is taken, bodies and header preimages run sha256_twin_group (two lanes per message in the
+                                    // rounds wave, 32 messages per group): -1 the default (SHA_TWIN_DEFAULT), 0 never, 1 wherever the ring is
+                                    // taken (ZKE_SHA_TWIN in the environment)
+  uint32_t sha_twin_kinds = 3;      // which kinds of the hash / modexp launch the twin takes (bit 0 bodies, bit 1 header preimages; domains and
+                                    // keys are one block each and keep 64-wide ring groups: 32 more workgroups per batch would keep the RSA
+                                    // roles waiting for room).  ZKE_SHA_TWIN_KINDS in the environment, for A/B runs
 #ifdef ZKE_DEV_KNOBS
   uint32_t debug_skip_rsa = 0, debug_skip_ed = 0, debug_parse_stop = 0, debug_skip_launch = 0;
 #else
@@ -208,13 +214,21 @@ bool sha_takes_ring(const zke_engine* e) {
   return std::min<uint32_t>((uint32_t)e->slots.size(), e->hw_queues) <= SHA_RING_MAX_IN_FLIGHT;
 }
 
+// The twin is a refinement of the ring: the same roles, buffers and LDS, a shorter rounds chain (sha256.hip.h).
+constexpr bool SHA_TWIN_DEFAULT = true;
+bool sha_takes_twin(const zke_engine* e) {
+  return sha_takes_ring(e) && (e->sha_twin >= 0 ? e->sha_twin == 1 : SHA_TWIN_DEFAULT);
+}
+
 int launch_sha(zke_engine* e, const ShaJob* jobs, uint32_t n, hipStream_t s) {
   if (n == 0) return 0;
   // Few messages: the launch is as long as one wave's chain of compressions, so split the chain over two waves
   // (sha256_pair_kernel).  Many messages: the chip is full and the one-wave kernel does less LDS work per byte.
   const uint32_t groups = (n + 63) / 64;
   if (sha_takes_pairs(e, groups)) {
-    if (sha_takes_ring(e)) hipLaunchKernelGGL(sha256_ring_kernel<SHA_TILE>, dim3(groups), dim3(128), sha256_ring_lds_bytes<SHA_TILE>(), s, jobs, n);
+    if (sha_takes_twin(e))
+      hipLaunchKernelGGL(sha256_twin_kernel<SHA_TILE>, dim3((n + SHA_TWIN_WIDTH - 1) / SHA_TWIN_WIDTH), dim3(128), sha256_ring_lds_bytes<SHA_TILE>(), s, jobs, n);
+    else if (sha_takes_ring(e)) hipLaunchKernelGGL(sha256_ring_kernel<SHA_TILE>, dim3(groups), dim3(128), sha256_ring_lds_bytes<SHA_TILE>(), s, jobs, n);
     else hipLaunchKernelGGL(sha256_pair_kernel<SHA_TILE>, dim3(groups), dim3(128), sha256_pair_lds_bytes<SHA_TILE>(), s, jobs, n);
   } else {
     hipLaunchKernelGGL(sha256_batch_kernel<SHA_TILE>, dim3((n + 255) / 256), dim3(256), sha256_lds_bytes<SHA_TILE>(), s, jobs, n);
@@ -291,7 +305,8 @@ uint32_t rsa_route_mask(const zke_engine* e, uint32_t n, bool any_big) {
 int launch_stage(zke_engine* e, const StageArgs& A, hipStream_t s) {
   const uint32_t grid = A.g_sha + A.g_wave + A.g_quad + A.g_oct + A.g_oct9;
   if (!grid) return 0;
-  if (A.g_sha && sha_takes_ring(e)) hipLaunchKernelGGL(hash_modexp_ring_kernel<SHA_TILE>, dim3(grid), dim3(128), sha256_ring_lds_bytes<SHA_TILE>(), s, A);
+  if (A.g_sha && A.twin_kinds) hipLaunchKernelGGL(hash_modexp_twin_kernel<SHA_TILE>, dim3(grid), dim3(128), sha256_ring_lds_bytes<SHA_TILE>(), s, A);
+  else if (A.g_sha && sha_takes_ring(e)) hipLaunchKernelGGL(hash_modexp_ring_kernel<SHA_TILE>, dim3(grid), dim3(128), sha256_ring_lds_bytes<SHA_TILE>(), s, A);
   else hipLaunchKernelGGL(hash_modexp_kernel<SHA_TILE>, dim3(grid), dim3(128), sha256_pair_lds_bytes<SHA_TILE>(), s, A);
   HIPCHK(e, hipGetLastError());
   return 0;
@@ -333,7 +348,10 @@ int launch_hash_modexp(zke_engine* e, const ShaJob* sha, uint32_t n_sha, const R
   A.debug_skip_rsa = e->debug_skip_rsa;
   const uint32_t groups = (n_sha + 63) / 64;
   if (sha_takes_pairs(e, groups)) {
-    A.g_sha = groups;
+    // Launches without a kind layout keep 64-wide groups.  Launches with the RSA-4096 role (route bit 1) take the twin like the
+    // others: keeping them on the ring was tried and measured slower (profiles/sha_twin_bench_ab.txt, section 4).
+    if (order && sha_takes_twin(e)) A.twin_kinds = e->sha_twin_kinds;
+    A.g_sha = A.twin_kinds ? sha_stage_groups(A.n_pad, A.twin_kinds) : groups;
     return launch_stage(e, A, s);
   }
   if (int r = launch_sha(e, sha, n_sha, s)) return r;      // (beyond 512 groups: arrival order; the chip is full either way)
@@ -354,6 +372,10 @@ int set_kernel_attrs(zke_engine* e) {
   HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&sha256_ring_kernel<SHA_TILE>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_ring_lds_bytes<SHA_TILE>()));
   HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&hash_modexp_ring_kernel<SHA_TILE>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_ring_lds_bytes<SHA_TILE>()));
+  HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&sha256_twin_kernel<SHA_TILE>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_ring_lds_bytes<SHA_TILE>()));
+  HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&hash_modexp_twin_kernel<SHA_TILE>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_ring_lds_bytes<SHA_TILE>()));
   return 0;
 }
@@ -515,6 +537,8 @@ int zke_engine_create(const zke_options* opt, zke_engine** out) {
     // not only under ZKE_DEV_KNOBS: the tests of the role and A/B runs of one build need it there (INTEGRATION.md §5 lists it).
     if (const char* r9 = getenv("ZKE_RSA_OCT9")) e->rsa_oct9 = atoi(r9) != 0 ? 1 : 0;
     if (const char* sr = getenv("ZKE_SHA_RING")) e->sha_ring = atoi(sr) != 0 ? 1 : 0;      // likewise: which two-wave SHA-256 routine
+    if (const char* st = getenv("ZKE_SHA_TWIN")) e->sha_twin = atoi(st) != 0 ? 1 : 0;      // ... and whether the ring's rounds wave takes two lanes per message
+    if (const char* tk = getenv("ZKE_SHA_TWIN_KINDS")) e->sha_twin_kinds = (uint32_t)atoi(tk) & 3u;
   }
 #ifdef ZKE_DEV_KNOBS
   if (const char* rm = getenv("ZKE_RSA_QUAD_MIN")) e->rsa_quad_min = (uint32_t)atoi(rm);
@@ -554,6 +578,12 @@ int zke_engine_sha_ring(zke_engine* e) {
   if (!e) return ZKE_E_ARG;
   std::shared_lock<std::shared_mutex> sh(e->big);
   return sha_takes_ring(e) ? 1 : 0;
+}
+
+int zke_engine_sha_twin(zke_engine* e) {
+  if (!e) return ZKE_E_ARG;
+  std::shared_lock<std::shared_mutex> sh(e->big);
+  return sha_takes_twin(e) ? 1 : 0;
 }
 
 const char* zke_last_error(const zke_engine* e) { (void)e; return g_err.c_str(); }

@@ -26,8 +26,32 @@ struct StageArgs {
   uint32_t g_sha, g_wave, g_quad, g_oct;   // workgroups per role, in this order; blockDim = 128 (two waves)
   uint32_t g_oct9;                         // ... then the eight-lane role for moduli <= 2048 bits (a launch has it or g_quad, never both)
   const uint32_t* order; uint32_t n_pad;   // length buckets of the body / header-preimage hashes (BatchDev::order), or nullptr
+  uint32_t twin_kinds;                     // bit k: kind k is hashed by sha256_twin_group in groups of 32 (launches with `order` only)
   uint32_t debug_skip_rsa;
 };
+
+// The SHA-256 groups of a launch with a kind layout (kind-major job list, n_pad jobs per kind, n_pad a multiple of 64): kind k takes
+// n_pad / width(k) consecutive workgroups, width 32 for the kinds of twin_kinds and 64 otherwise.  The host sizes g_sha by
+// sha_stage_groups and the kernel finds its kind by sha_stage_kind: the one place that knows the layout.
+constexpr uint32_t SHA_KINDS = 4;          // bodies, header preimages, domains, keys
+__host__ __device__ inline uint32_t sha_kind_groups(uint32_t n_pad, uint32_t twin_kinds, uint32_t kind) {
+  return n_pad / ((twin_kinds >> kind & 1u) ? SHA_TWIN_WIDTH : 64u);
+}
+__host__ __device__ inline uint32_t sha_stage_groups(uint32_t n_pad, uint32_t twin_kinds) {
+  uint32_t g = 0;
+  for (uint32_t k = 0; k < SHA_KINDS; k++) g += sha_kind_groups(n_pad, twin_kinds, k);
+  return g;
+}
+// workgroup b < g_sha -> its kind; b becomes the group within the kind
+__host__ __device__ inline uint32_t sha_stage_kind(uint32_t n_pad, uint32_t twin_kinds, uint32_t& b) {
+  uint32_t kind = 0;
+  for (; kind + 1 < SHA_KINDS; kind++) {
+    const uint32_t g = sha_kind_groups(n_pad, twin_kinds, kind);
+    if (b < g) break;
+    b -= g;
+  }
+  return kind;
+}
 
 template <int G, int L> constexpr uint32_t group_lds_dwords() { return (64 / G) * (G * L + 4); }      // per wave: rsa_group_wave's Llimb
 constexpr uint32_t QUAD_LDS_DWORDS = group_lds_dwords<4, QL>(), OCT_LDS_DWORDS = group_lds_dwords<8, QL>(), OCT9_LDS_DWORDS = group_lds_dwords<8, QL9>();
@@ -40,8 +64,9 @@ constexpr uint32_t QUAD_LDS_DWORDS = group_lds_dwords<4, QL>(), OCT_LDS_DWORDS =
 #define ZKE_STAGE_WAVES 2
 #endif
 // RING: the SHA-256 groups run sha256_ring_group (two K+W buffers: the launch then carries sha256_ring_lds_bytes of LDS, and the
-// RSA roles, whose workgroups are two waves as well, borrow the front of it as before).
-template <int T, bool RING>
+// RSA roles, whose workgroups are two waves as well, borrow the front of it as before).  TWIN (with RING): the kinds of
+// A.twin_kinds run sha256_twin_group — the ring's LDS, 32 messages per group —, the other kinds the ring.
+template <int T, bool RING, bool TWIN = false>
 __device__ __forceinline__ void hash_modexp_body(const StageArgs& A, uint8_t* lds_raw) {
   static_assert(sha256_pair_lds_bytes<T>() >= 2 * 4 * QUAD_LDS_DWORDS && sha256_pair_lds_bytes<T>() >= 2 * 4 * OCT_LDS_DWORDS &&
                 sha256_pair_lds_bytes<T>() >= 2 * 4 * OCT9_LDS_DWORDS,
@@ -53,9 +78,12 @@ __device__ __forceinline__ void hash_modexp_body(const StageArgs& A, uint8_t* ld
       return;
     }
     // kind-major job list: groups [k gpk, (k + 1) gpk) hash kind k; bodies and header preimages by length class
-    const uint32_t gpk = A.n_pad / 64, kind = b / gpk, gk = b - kind * gpk;
+    const uint32_t twin_kinds = TWIN ? A.twin_kinds : 0u;
+    uint32_t gk = b;
+    const uint32_t kind = sha_stage_kind(A.n_pad, twin_kinds, gk);
     const ShaOrder so{kind < 2 ? A.order + sha_order_cnt(kind) : nullptr, kind < 2 ? A.order + sha_order_key(kind, A.n_pad) : nullptr, A.n};
-    if (RING) sha256_ring_group<T>(A.sha + (size_t)kind * A.n_pad, A.n_pad, gk, lds_raw, &so);
+    if (TWIN && (twin_kinds >> kind & 1u)) sha256_twin_group<T>(A.sha + (size_t)kind * A.n_pad, A.n_pad, gk, lds_raw, &so);
+    else if (RING) sha256_ring_group<T>(A.sha + (size_t)kind * A.n_pad, A.n_pad, gk, lds_raw, &so);
     else sha256_pair_group<T>(A.sha + (size_t)kind * A.n_pad, A.n_pad, gk, lds_raw, &so);
     return;
   }
@@ -98,6 +126,11 @@ template <int T>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(ZKE_STAGE_WAVES, ZKE_STAGE_WAVES))) void hash_modexp_ring_kernel(StageArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   hash_modexp_body<T, true>(A, lds_raw);
+}
+template <int T>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(ZKE_STAGE_WAVES, ZKE_STAGE_WAVES))) void hash_modexp_twin_kernel(StageArgs A) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  hash_modexp_body<T, true, true>(A, lds_raw);
 }
 
 }  // namespace zke

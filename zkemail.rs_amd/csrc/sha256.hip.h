@@ -19,22 +19,25 @@
 // Roofline: integer-VALU bound (about 1.4k VALU per 64-byte block per lane), not HBM
 // bound; DESIGN.md §3 has the arithmetic.
 //
-// Three routines, each its own control flow over the shared pieces below:
+// Four routines, each its own control flow over the shared pieces below:
 //   sha256_batch_kernel  one wave per 64 messages, for launches that fill the chip;
 //   sha256_pair_group    two waves per 64 messages — message schedule and rounds —, ONE K+W buffer and two barriers per
 //                        block, 28 KB of LDS: for launches whose duration is one wave's chain of compressions, where
 //                        many batches share the chip.  Its one-wave path takes the groups that hold a SHA-1 job;
 //   sha256_ring_group    the same two roles, TWO K+W buffers and one LDS-only barrier per block, 45 KB: where few batches
-//                        are on the chip (engine.hip chooses).
-// The group routines are device functions, so that other work can share their launch (fused.hip.h); sha256_pair_kernel
-// and sha256_ring_kernel run them alone.
+//                        are on the chip (engine.hip chooses);
+//   sha256_twin_group    the ring with 32 messages per group and TWO LANES PER MESSAGE in the rounds wave (e..h in one, a..d in
+//                        its partner, exchanged by DPP): 10 instead of 14 instructions per round on the chain, two blocks per
+//                        feeder pass, one barrier per pass.  The ring's LDS; taken with the ring, for messages of many blocks.
+// The group routines are device functions, so that other work can share their launch (fused.hip.h); sha256_pair_kernel,
+// sha256_ring_kernel and sha256_twin_kernel run them alone.
 // Shared, one definition each: the round constants SHA_K; sha_init_state / sha_store_digest (sha_lane of verdict.hip.h
 // uses them too); sha_load_block; ShaLaneJob (a lane's job, the wave's longest message, its SHA-1 ballot); ShaTile
 // (descriptor rows, fetch / commit: tile staging and padding); sha_one_wave_tiles (the one-wave tile loop);
 // sha_group_pick (the length-bucket protocol of a two-wave group); sha_kw_schedule and sha_rounds_kw (the two halves of
-// a split compression).  The pair and the ring block loops are NOT shared: they differ in their barrier structure, and
-// that difference is what a reader has to see.  The ring also keeps its 64 rounds written out, for a measured reason
-// (the comment there).
+// a split compression).  The pair, the ring and the twin block loops are NOT shared: they differ in their barrier structure,
+// and that difference is what a reader has to see.  The ring and the twin also keep their 64 rounds written out, for a
+// measured reason (the comment in the ring).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -356,11 +359,11 @@ constexpr int SHA_KW_ROW = 68;        // dwords per lane and buffer
 template <int T>
 constexpr size_t sha256_pair_lds_bytes() { return 64 * (T + 16) + 64 * 16 + 64 * SHA_KW_ROW * 4 + 1024; }      // slab, descriptors, K+W, job pick
 
-// The job of each of a group's 64 lanes under length buckets (see ShaOrder): lane l of group g takes the message at global
-// position 64 g + l of the longest-first order.  `pick`: 1 KB of LDS (192 class bases + 64 picks), written and read by the
+// The job of each of a group's `width` positions (64, or 32 for sha256_twin_group) under length buckets (see ShaOrder): lane
+// l < width of group g takes the message at global position width g + l of the longest-first order.  `pick`: 1 KB of LDS (192 class bases + 64 picks), written and read by the
 // calling wave only.  Returns the lane's job index within the kind (SHA_KEY_NONE: no message), or `direct` when the batch is
 // uniform enough for the direct mapping.  *skip = the whole group has nothing to do.
-__device__ __forceinline__ uint32_t sha_pick_job(const ShaOrder& O, uint32_t g, uint32_t direct, uint32_t* pick, bool& skip) {
+__device__ __forceinline__ uint32_t sha_pick_job(const ShaOrder& O, uint32_t g, uint32_t direct, uint32_t* pick, bool& skip, uint32_t width = 64) {
   const uint32_t lane = threadIdx.x & 63;
   skip = false;
   // class bases, longest class first: base[c] = messages in classes above c
@@ -382,7 +385,7 @@ __device__ __forceinline__ uint32_t sha_pick_job(const ShaOrder& O, uint32_t g, 
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) { const uint32_t t = (uint32_t)__shfl_down((int)above, o); if (lane + o < 64) above += t; }
   const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)above);
-  if (64 * g >= total) { skip = true; return SHA_KEY_NONE; }
+  if (width * g >= total) { skip = true; return SHA_KEY_NONE; }
   uint32_t b = above - tot3;                               // messages in the classes above this lane's
   pick[3 * lane + 2] = b; b += c3[2];
   pick[3 * lane + 1] = b; b += c3[1];
@@ -390,7 +393,7 @@ __device__ __forceinline__ uint32_t sha_pick_job(const ShaOrder& O, uint32_t g, 
   pick[SHA_CLASSES + lane] = SHA_KEY_NONE;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  const uint32_t lo = 64 * g;
+  const uint32_t lo = width * g;
   for (uint32_t t0 = 0; t0 < O.n; t0 += 256) {             // four keys per lane and step: the loads of a step are in flight together
     uint32_t k4[4];
 #pragma unroll
@@ -399,7 +402,7 @@ __device__ __forceinline__ uint32_t sha_pick_job(const ShaOrder& O, uint32_t g, 
     for (int q = 0; q < 4; q++) {
       if (k4[q] != SHA_KEY_NONE) {
         const uint32_t gp = pick[k4[q] >> 24] + (k4[q] & 0xFFFFFFu) - lo;
-        if (gp < 64) pick[SHA_CLASSES + gp] = t0 + 64 * q + lane;
+        if (gp < width) pick[SHA_CLASSES + gp] = t0 + 64 * q + lane;
       }
     }
   }
@@ -410,20 +413,23 @@ __device__ __forceinline__ uint32_t sha_pick_job(const ShaOrder& O, uint32_t g, 
 
 // Length buckets in a two-wave group: the feeder (role 0) works the picks out, the rounds wave reads them.  Every thread of
 // the group calls this (it uses __syncthreads()).  `order` nullptr or without counters: direct mapping, m stays.  Otherwise m
-// becomes the lane's job under the buckets; true: the group has nothing to do and leaves as a whole.
-__device__ __forceinline__ bool sha_group_pick(const ShaOrder* order, uint32_t group, uint32_t& m, uint32_t* pick, int role) {
+// becomes the lane's job under the buckets; true: the group has nothing to do and leaves as a whole.  A group of `width` < 64
+// messages: `pos` is the thread's position in the group (its message is that of feeder lane pos; sha256_twin_group).
+__device__ __forceinline__ bool sha_group_pick(const ShaOrder* order, uint32_t group, uint32_t& m, uint32_t* pick, int role,
+                                               uint32_t width = 64, int pos = -1) {
   if (!(order && order->cnt)) return false;
   const int lane = threadIdx.x & 63;
+  if (pos < 0) pos = lane;
   bool skip = false;
   uint32_t mine = 0;
   if (role == 0) {
-    mine = sha_pick_job(*order, group, m, pick, skip);
+    mine = sha_pick_job(*order, group, m, pick, skip, width);
     if (lane == 0) pick[SHA_CLASSES - 1] = skip ? 1u : 0u;          // (class 191 = 2^25 blocks and more: never populated)
     pick[SHA_CLASSES + lane] = mine;
   }
   __syncthreads();
   if (pick[SHA_CLASSES - 1]) return true;
-  m = pick[SHA_CLASSES + lane];
+  m = pick[SHA_CLASSES + pos];
   __syncthreads();                               // the pick area is dead from here (nobody writes it again)
   return false;
 }
@@ -682,6 +688,190 @@ template <int T>
 __global__ __launch_bounds__(128) void sha256_ring_kernel(const ShaJob* __restrict__ jobs, uint32_t n) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   sha256_ring_group<T>(jobs, n, blockIdx.x, lds_raw);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The twin: the ring with a group of 32 messages and TWO LANES PER MESSAGE in the rounds wave.  What bounds a ring block is the
+// rounds wave's own instruction count (14 VALU per round, one issue every ~4.8 cycles for a lone wave), and its lanes are free: so
+// the two halves of a round go to two lanes.  The Σ functions are one instruction sequence with different rotation amounts
+// (v_alignbit_b32 takes its amount from a VGPR), and Maj(a, b, c) = Ch(a ^ c, b, c), so lane A of a pair holds e, f, g, h, lane B
+// holds a, b, c, d, in the same four registers R0..R3, and one round is
+//   r1, r2, r3 = alignbit(R0, R0, sh0 | sh1 | sh2)   3   sh* per lane (SHA_TWIN_SH): A 6, 11, 25   B 2, 13, 22
+//   S = bitop3(r1, r2, r3, 0x96)                     1   A: Σ1(e)              B: Σ0(a)
+//   D = bitop3(R0, R2, maskb, 0x78)                  1   A: e                  B: a ^ c       (x ^ (z & m); maskb 0 on A, ~0 on B)
+//   F = bitop3(D, R1, R2, 0xCA)                      1   A: Ch(e, f, g)        B: Maj(a, b, c)
+//   U = add3(S, F, KW)                               1   A: Σ1 + Ch + K + W    B: Σ0 + Maj    (B lanes read zeros for K + W)
+//   R3 = R3 + U      A lanes only                    1   A: t1                 B: d
+//   U  = 0 | R3      A lanes only                    1   A: t1                 B: Σ0 + Maj
+//   N  = R3[partner] + U                             1   A: d + t1 = e'        B: t1 + Σ0 + Maj = a'
+//   R3 <- R2 <- R1 <- R0 <- N
+// 10 VALU instead of 14, and the Davies-Meyer add is 4 instead of 8.  The last three are DPP instructions (sha_twin_exchange).
+// Pairs: lane l and lane l ^ 7 (row_half_mirror: 7 - l within each eight); A lanes are those with (l & 4) == 0 (bank_mask 0x5 of an
+// identity quad_perm), so message p of the group sits in lanes 8 (p / 4) + p % 4 (A) and 8 (p / 4) + 7 - p % 4 (B).
+// The feeder wave's 64 lanes then serve two blocks of the 32 messages at once: lane l < 32 schedules block 2 j of message l, lane
+// l + 32 block 2 j + 1 — with T = 128 exactly the two blocks of a slab row —, so one feeder pass (schedule, commit, fetch) serves
+// two steps of the rounds wave, and there is one barrier per pass.  K+W row 32 h + p of buffer j & 1 is block 2 j + h of message p.
+// Slab rows 32..63 hold no message (their descriptors say nblk 0); the first 256 bytes of row 32 are the zeros the B lanes read.
+// LDS and workgroup shape are the ring's.  Groups with a SHA-1 job take the one-wave path, here, 32 wide.
+constexpr uint32_t SHA_TWIN_WIDTH = 32;                       // messages per group
+constexpr uint32_t SHA_TWIN_SH[2][3] = {{6, 11, 25}, {2, 13, 22}};      // [A | B]: Σ1, Σ0
+constexpr uint32_t SHA_TWIN_MASKB[2] = {0u, 0xFFFFFFFFu};
+
+// the lane's half of its pair, and its message's position in the group
+__device__ __forceinline__ bool sha_twin_is_b(int lane) { return (lane & 4) != 0; }
+__device__ __forceinline__ int sha_twin_pos(int lane) { return (lane >> 3) * 4 + (sha_twin_is_b(lane) ? 7 - (lane & 7) : (lane & 3)); }
+
+// The three DPP steps of a round.  The masked add takes the old R3 as its DPP operand and the fresh U as its plain one; the masked
+// OR takes R3 as its plain operand (the DPP one is a register of zeros): neither reads through DPP what the instruction in front
+// wrote.  The last add reads R3 through DPP two instructions behind its write: one wait state (the rule of rsa.hip.h's dpp
+// helpers; the compiler does not look inside an asm).  Callers keep a VALU write of r3 two wait states away from this asm.
+__device__ __forceinline__ uint32_t sha_twin_exchange(uint32_t& r3, uint32_t u, uint32_t zero) {
+  uint32_t n;
+  asm("v_add_u32_dpp %1, %1, %2 quad_perm:[0,1,2,3] row_mask:0xf bank_mask:0x5\n\t"
+      "v_or_b32_dpp %2, %3, %1 quad_perm:[0,1,2,3] row_mask:0xf bank_mask:0x5\n\t"
+      "s_nop 0\n\t"
+      "v_add_u32_dpp %0, %1, %2 row_half_mirror row_mask:0xf bank_mask:0xf"
+      : "=&v"(n), "+v"(r3), "+v"(u)
+      : "v"(zero));
+  return n;
+}
+
+template <int T>
+__device__ __forceinline__ void sha256_twin_group(const ShaJob* __restrict__ jobs, uint32_t n, uint32_t group, uint8_t* lds_raw,
+                                                  const ShaOrder* order = nullptr) {
+  static_assert(T == 128, "a slab row is the two blocks of a feeder pass");
+  constexpr int KW_BUF = 64 * SHA_KW_ROW;          // dwords per buffer
+  constexpr int ROW = ShaTile<T>::ROW;
+  __builtin_amdgcn_s_setprio(ZKE_SHA_PRIO);
+  const int lane = threadIdx.x & 63;
+  const int role = threadIdx.x >> 6;               // 0 feeder, 1 rounds
+  uint32_t* kw = (uint32_t*)(lds_raw + ShaTile<T>::BYTES);      // [2 buffers][2 block parities][32 messages][SHA_KW_ROW]
+  uint32_t* pick = kw + 2 * KW_BUF;                // 1 KB: sha_pick_job
+  uint8_t* zeros = lds_raw + 32 * ROW;             // 256 bytes in the slab's unused rows
+
+  const bool is_b = sha_twin_is_b(lane);
+  const int pos = role == 0 ? (lane & 31) : sha_twin_pos(lane);      // the message: two feeder lanes and a rounds pair each
+  const int half = lane >> 5;                      // feeder: which block of the pass
+  uint32_t m = group * SHA_TWIN_WIDTH + pos;
+  if (sha_group_pick(order, group, m, pick, role, SHA_TWIN_WIDTH, pos)) return;
+  const ShaLaneJob J(jobs, m, n);
+  const ShaLaneJob none(jobs, n, n);
+  const uint32_t max_nblk = J.wave_max_nblk();     // the same in both waves: each sees the 32 jobs twice
+
+  if (J.wave_any_sha1()) {
+    // one-wave routine by the feeder's lower lanes, a message each; no barrier below
+    if (role != 0) return;
+    const ShaLaneJob J1 = half ? none : J;
+    uint32_t st[8];
+    sha_init_state(st, J1.algo != 0);
+    ShaTile<T> tile(lds_raw, lane, J1);
+    tile.describe(J1);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    sha_one_wave_tiles<T>(tile, st, max_nblk, J1.algo != 0);
+    if (!half && m < n && J1.dst) sha_store_digest((gptr_out32)J1.dst, st, J1.algo != 0);
+    return;
+  }
+
+  const uint32_t passes = (max_nblk + 1) / 2;
+  // The block barrier: an s_barrier between LDS-only fences, as in the ring.
+  auto block_barrier = [&]() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+  };
+  // In pass j the rounds wave reads buffer j & 1 (steps 2 j and 2 j + 1) and the feeder writes buffer (j + 1) & 1; barrier j - 1
+  // stands behind the last read of that buffer and barrier j in front of the first read of what the feeder wrote: the ring's
+  // argument with a pass for a step.  Both waves run `passes` barriers behind barrier -1.
+  if (role == 0) {
+    // ---- feeder.  Rows 32..63 are described as empty, and the upper lanes patch no padding: the lower lane of a row does.
+    ShaTile<T> tile(lds_raw, lane, J);
+    tile.my_row = lds_raw + pos * ROW;
+    if (half) tile.my_nblk = 0;
+    tile.describe(half ? none : J);
+    // K+W of block 2 j + half of message pos into row `lane` of buffer j & 1 (an odd max_nblk: the upper lanes idle in the last pass)
+    auto sched = [&](uint32_t j) {
+      if (2 * j + half < max_nblk) sha_kw_schedule(tile.my_row + half * 64, kw + (j & 1) * KW_BUF + lane * SHA_KW_ROW);
+    };
+    // a tile's loads go out behind the commit of the tile in front of it and land a whole pass later
+    auto next_tile = [&](uint32_t j) {
+      if (j < passes) { tile.commit(2 * j); if (j + 1 < passes) tile.fetch(2 * (j + 1)); }
+    };
+    if (passes) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      tile.fetch(0);
+      next_tile(0);
+      sched(0);
+      next_tile(1);
+    }
+    ZKE_SHA_WHERE();
+    block_barrier();                                // barrier -1: blocks 0 and 1 are in buffer 0
+    uint32_t st[1] = {0};                           // (the probe's stamps thread a register through)
+    for (uint32_t j = 0; j < passes; j++) {
+      ZKE_SHA_STAMP(2 * j, 0);
+      if (j + 1 < passes) { sched(j + 1); next_tile(j + 2); }
+      ZKE_SHA_STAMP(2 * j, 1);
+      block_barrier();                              // barrier j
+      ZKE_SHA_STAMP(2 * j, 2);
+    }
+    (void)st;
+    return;
+  }
+
+  // ---- rounds: st = the lane's half of the chaining state, e..h on A lanes and a..d on B lanes
+  uint32_t st[4];
+  {
+    uint32_t iv[8];
+    sha_init_state(iv, false);
+#pragma unroll
+    for (int i = 0; i < 4; i++) st[i] = is_b ? iv[i] : iv[4 + i];
+  }
+  const uint32_t sh0 = is_b ? SHA_TWIN_SH[1][0] : SHA_TWIN_SH[0][0], sh1 = is_b ? SHA_TWIN_SH[1][1] : SHA_TWIN_SH[0][1];
+  const uint32_t sh2 = is_b ? SHA_TWIN_SH[1][2] : SHA_TWIN_SH[0][2], maskb = is_b ? SHA_TWIN_MASKB[1] : SHA_TWIN_MASKB[0];
+  uint32_t zero = 0;
+  asm volatile("" : "+v"(zero));                    // a register of its own, not a literal in the asm
+  if (lane < 16) ((uint4*)zeros)[lane] = make_uint4(0, 0, 0, 0);
+  ZKE_SHA_WHERE();
+  block_barrier();                                  // barrier -1 (the zeros are this wave's own: in order behind its store)
+  for (uint32_t kb = 0; kb < max_nblk; kb++) {
+    ZKE_SHA_STAMP(kb, 0);
+    const uint4* src = is_b ? (const uint4*)zeros
+                            : (const uint4*)(kw + ((kb >> 1) & 1) * KW_BUF + ((kb & 1) * 32 + pos) * SHA_KW_ROW);
+    uint4 kq[16];                                   // all 16 reads go out here; each round group waits for its own quad only
+#pragma unroll
+    for (int q = 0; q < 16; q++) kq[q] = src[q];
+    uint32_t r0 = st[0], r1 = st[1], r2 = st[2], r3 = st[3];
+    asm volatile("s_nop 1" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));      // whatever wrote them is two wait states away from the first DPP read
+    // the rounds written out, as in the ring and for its reason
+#pragma unroll
+    for (int i = 0; i < 64; i++) {
+      const uint32_t s = xor3(__builtin_amdgcn_alignbit(r0, r0, sh0), __builtin_amdgcn_alignbit(r0, r0, sh1), __builtin_amdgcn_alignbit(r0, r0, sh2));
+      const uint32_t d = __builtin_amdgcn_bitop3_b32(r0, r2, maskb, 0x78);
+      const uint32_t f = ch3(d, r1, r2);
+      const uint4 k4 = kq[i >> 2];
+      const uint32_t kwi = (i & 3) == 0 ? k4.x : (i & 3) == 1 ? k4.y : (i & 3) == 2 ? k4.z : k4.w;
+      const uint32_t u = s + f + kwi;
+      const uint32_t nw = sha_twin_exchange(r3, u, zero);
+      r3 = r2; r2 = r1; r1 = r0; r0 = nw;
+    }
+    if (kb < J.nblk) { st[0] += r0; st[1] += r1; st[2] += r2; st[3] += r3; }
+    ZKE_SHA_STAMP(kb, 1);
+    if ((kb & 1) || kb + 1 == max_nblk) block_barrier();       // barrier kb / 2: the pass is read
+    ZKE_SHA_STAMP(kb, 2);
+  }
+  if (m < n && J.dst) {                             // a..d by the B lane, e..h by the A lane; no SHA-1 job in a twin group
+    gptr_out32 out = (gptr_out32)J.dst + (is_b ? 0 : 4);
+#pragma unroll
+    for (int i = 0; i < 4; i++) out[i] = __builtin_bswap32(st[i]);
+  }
+}
+
+// grid = ceil(n / 32)
+template <int T>
+__global__ __launch_bounds__(128) void sha256_twin_kernel(const ShaJob* __restrict__ jobs, uint32_t n) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  sha256_twin_group<T>(jobs, n, blockIdx.x, lds_raw);
 }
 
 }  // namespace zke

@@ -168,6 +168,9 @@ def load_library(path: Optional[str] = None):
     if hasattr(lib, "zke_engine_sha_ring"):         # (a ZKE_LIB build of an older tree, for an A/B run, has no such entry)
         lib.zke_engine_sha_ring.argtypes = [vp]
         lib.zke_engine_sha_ring.restype = C.c_int
+    if hasattr(lib, "zke_engine_sha_twin"):         # (likewise)
+        lib.zke_engine_sha_twin.argtypes = [vp]
+        lib.zke_engine_sha_twin.restype = C.c_int
     lib.zke_version.argtypes = []
     lib.zke_version.restype = C.c_char_p
     lib.zke_device_available.argtypes = []
@@ -190,7 +193,7 @@ EXPORTED_SYMBOLS = [
     "zke_extract_captures_async", "zke_capture_batch",
     "zke_scan_signatures", "zke_scan_signatures_async", "zke_select_keys", "zke_select_keys_async",
     "zke_decode_key_records", "zke_decode_key_records_async", "zke_select_keys_from_records", "zke_select_keys_from_records_async",
-    "zke_engine_sha_ring",
+    "zke_engine_sha_ring", "zke_engine_sha_twin",
     "zke_qp_clean_batch", "zke_extract_captures_mapped", "zke_extract_captures_mapped_async",
 ]
 
@@ -640,6 +643,12 @@ class Engine:
         """Whether the two-wave SHA-256 groups take the ring routine as the engine stands now (zke_engine_sha_ring)."""
         r = self.lib.zke_engine_sha_ring(self.h)
         self._check(min(r, 0), "zke_engine_sha_ring")
+        return r == 1
+
+    def sha_twin(self) -> bool:
+        """Whether the ring's rounds wave takes two lanes per message as the engine stands now (zke_engine_sha_twin)."""
+        r = self.lib.zke_engine_sha_twin(self.h)
+        self._check(min(r, 0), "zke_engine_sha_twin")
         return r == 1
 
     def join(self, stream: int = 0):
