@@ -15,7 +15,9 @@
 //!   * per regex pattern: `dfa::regex::Regex::new(pattern)`, both `to_bytes_little_endian()` blobs with the padding stripped
 //!     as `helpers/src/regex.rs:7-14` does — these are the first UNANCHORED, accelerated dense DFAs the engine's parser sees —
 //!     and the `find_iter` spans over the canonical header and over the cleaned body (core/src/regex.rs:36);
-//!   * `VerificationOutput::abi_encode()` of the outputs (core/src/io.rs:28-44).
+//!   * `VerificationOutput::abi_encode()` of the outputs (core/src/io.rs:28-44);
+//!   * for every case of `tests/golden/body_manifest.json`: `extract_email_body(&parse_mail(raw).unwrap())` (core/src/email.rs:7-23),
+//!     its bytes or its panic, into `tests/golden/ref/body/` (compared by `tests/test_reference_body_fixtures.py`).
 //!
 //! Then `python -m pytest tests/test_reference_fixtures.py` (CPU: the oracle; `-m gpu`: the engine) compares field by field and
 //! names the first behaviour that differs — each of them sits behind a strictness flag of `zke_options` or a single named site.
@@ -32,7 +34,7 @@ use cfdkim::{canonicalize_signed_email, verify_email_with_key, DkimPublicKey};
 use mailparse::parse_mail;
 use regex_automata::dfa::regex::Regex as DFARegex;
 use serde_json::{json, Value};
-use zkemail_core::{hash_bytes, remove_quoted_printable_soft_breaks, EmailVerifierOutput, VerificationOutput};
+use zkemail_core::{extract_email_body, hash_bytes, remove_quoted_printable_soft_breaks, EmailVerifierOutput, VerificationOutput};
 
 fn hex(b: &[u8]) -> String {
     b.iter().map(|x| format!("{x:02x}")).collect()
@@ -148,5 +150,29 @@ fn main() {
         let path: &Path = &out_dir.join(format!("{name}.json"));
         fs::write(path, serde_json::to_vec_pretty(&out).unwrap()).expect("write");
         println!("{name}");
+    }
+
+    // ---- extract_email_body (core/src/email.rs:7-23): the e-mails of body_manifest.json, one file each under ref/body/
+    let body_manifest: Value = serde_json::from_slice(&fs::read(golden.join("body_manifest.json")).expect("body_manifest.json")).expect("json");
+    let body_dir = out_dir.join("body");
+    fs::create_dir_all(&body_dir).expect("mkdir ref/body");
+    for case in body_manifest["cases"].as_array().expect("cases") {
+        let name = case["name"].as_str().unwrap();
+        let raw = fs::read(golden.join(case["eml"].as_str().unwrap())).expect("eml");
+        let mut out = json!({ "name": name });
+        // parse_mail(..).unwrap() and get_body_raw().unwrap() both panic: told apart by parsing first
+        match std::panic::catch_unwind(|| parse_mail(&raw).map(|_| ()).map_err(|e| e.to_string())) {
+            Ok(Ok(())) => {
+                out["parse_mail"] = json!("ok");
+                match std::panic::catch_unwind(|| extract_email_body(&parse_mail(&raw).unwrap())) {
+                    Ok(body) => out["body_hex"] = json!(hex(&body)),
+                    Err(_) => out["extract_email_body"] = json!("panic"),
+                }
+            }
+            Ok(Err(e)) => out["parse_mail"] = json!({ "error": e }),
+            Err(_) => out["parse_mail"] = json!("panic"),
+        }
+        fs::write(body_dir.join(format!("{name}.json")), serde_json::to_vec_pretty(&out).unwrap()).expect("write");
+        println!("body/{name}");
     }
 }

@@ -53,6 +53,7 @@ impl Panic {
             sys::ZKE_HEADER_REGEX_FAIL => "core/src/circuits.rs:45 assert!(verified)",
             sys::ZKE_BODY_REGEX_FAIL => "core/src/circuits.rs:54 assert!(verified)",
             sys::ZKE_UNSUPPORTED => "input outside what the engine implements (never a silent mis-verify)",
+            sys::ZKE_BODY_DECODE_FAIL => "core/src/email.rs:17-21 part.get_body_raw().unwrap() in extract_email_body",
             _ => "unknown status",
         }
     }
@@ -905,7 +906,72 @@ pub struct MappedCaptures {
     pub origin_flags: Vec<u8>,
 }
 
+/// One e-mail's `extract_email_body` as an extraction reports it (`zke_body_info`, the decoded body as bytes).
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct BodyInfo {
+    /// `ZKE_OK` | `ZKE_PARSE_FAIL` | `ZKE_BODY_DECODE_FAIL` | `ZKE_UNSUPPORTED`, and the rule or limit it names.
+    pub status: u32,
+    pub detail: u32,
+    /// 0: the message itself; k >= 1: its k-th direct subpart; bit 31: chosen as text/html.
+    pub part: u32,
+    /// `ZKE_CTE_*`.
+    pub encoding: u32,
+    /// `body_bytes` of the chosen part inside the raw e-mail, before decoding.
+    pub src_span: (u32, u32),
+    /// Empty unless `status` is `ZKE_OK`.
+    pub body: Vec<u8>,
+}
+
 impl Engine {
+    /// `extract_email_body(&parse_mail(raw).unwrap())` (`core/src/email.rs:7-23`) over a slice of raw e-mails (`zke_extract_bodies`):
+    /// the text/html subpart (else the first, else the message) with its Content-Transfer-Encoding undone.  `part_keeps_eol`:
+    /// `ZKE_BODYF_PART_KEEPS_EOL`, the line break in front of a boundary line stays part of the body.
+    pub fn extract_email_bodies(&self, raw_emails: &[&[u8]], part_keeps_eol: bool) -> Result<Vec<BodyInfo>, EngineError> {
+        let n = raw_emails.len();
+        let refs: Vec<sys::zke_email_ref> = raw_emails
+            .iter()
+            .map(|r| sys::zke_email_ref {
+                raw: r.as_ptr(),
+                raw_len: r.len(),
+                from_domain: ptr::null(),
+                domain_len: 0,
+                key: ptr::null(),
+                key_len: 0,
+                key_type: 0,
+                external_input_null: 0,
+            })
+            .collect();
+        let total: usize = raw_emails.iter().map(|r| r.len()).sum();
+        // SAFETY: zke_body_info is plain integers; all-zero is a value of it.
+        let mut infos: Vec<sys::zke_body_info> = vec![unsafe { std::mem::zeroed() }; n];
+        let mut bytes = vec![0u8; 2 * total + 1];      // a decoded body is at most twice its source (lone LF becomes CRLF)
+        let mut out = sys::zke_body_out {
+            infos: infos.as_mut_ptr(),
+            infos_cap: n,
+            bytes: bytes.as_mut_ptr(),
+            bytes_cap: bytes.len(),
+            infos_need: 0,
+            bytes_need: 0,
+        };
+        let flags = if part_keeps_eol { sys::ZKE_BODYF_PART_KEEPS_EOL } else { 0 };
+        // SAFETY: every pointer refers into `raw_emails`, `refs`, `infos` or `bytes`, alive until the synchronous call returns.
+        let rc = unsafe { sys::zke_extract_bodies(self.raw, refs.as_ptr(), n as u32, flags, &mut out) };
+        if rc != 0 {
+            return Err(self.last_error(rc));
+        }
+        Ok(infos
+            .iter()
+            .map(|f| BodyInfo {
+                status: f.status,
+                detail: f.detail,
+                part: f.part,
+                encoding: f.encoding,
+                src_span: (f.src_off, f.src_off + f.src_len),
+                body: bytes[f.body_off as usize..f.body_off as usize + f.body_len as usize].to_vec(),
+            })
+            .collect())
+    }
+
     /// `remove_quoted_printable_soft_breaks` (`core/src/email.rs:61-86`) over a slice of bodies (`zke_qp_clean_batch`), both return
     /// values per body: the body without its soft breaks, zero-padded to its length, and `index_map` with `usize::MAX` over the padding.
     pub fn remove_quoted_printable_soft_breaks_batch(&self, bodies: &[&[u8]]) -> Result<Vec<(Vec<u8>, Vec<usize>)>, EngineError> {
@@ -1055,5 +1121,21 @@ pub fn verify_email_with_regex(input: &EmailWithRegex) -> EmailWithRegexVerifier
         Err(e) => panic!("{e}"),
         Ok(Err(p)) => panic!("{p}"),
         Ok(Ok(out)) => out,
+    }
+}
+
+/// `zkemail_core::extract_email_body` (core/src/email.rs:7-23) over the raw e-mail — `extract_email_body(&parse_mail(raw).unwrap())`:
+/// the decoded body of the text/html subpart (else the first subpart, else the message).  Panics where the reference panics
+/// (`email.rs:26` the parse, `email.rs:17-21` get_body_raw) and for an input the engine does not decide.
+pub fn extract_email_body(raw: &[u8]) -> Vec<u8> {
+    match default_engine().extract_email_bodies(&[raw], false) {
+        Err(e) => panic!("{e}"),
+        Ok(mut v) => {
+            let f = v.remove(0);
+            if f.status != sys::ZKE_OK {
+                panic!("{}", Panic { status: f.status, detail: f.detail });
+            }
+            f.body
+        }
     }
 }

@@ -42,7 +42,8 @@ enum {
   ZKE_DFA_DECODE_FAIL     = 7,  /* dense::DFA::from_bytes(..).unwrap()           core/src/regex.rs:32-33 */
   ZKE_HEADER_REGEX_FAIL   = 8,  /* assert!(verified) on header parts             core/src/circuits.rs:45 */
   ZKE_BODY_REGEX_FAIL     = 9,  /* assert!(verified) on body parts               core/src/circuits.rs:54 */
-  ZKE_UNSUPPORTED         = 10  /* input is outside what this engine implements; never a silent mis-verify */
+  ZKE_UNSUPPORTED         = 10, /* input is outside what this engine implements; never a silent mis-verify */
+  ZKE_BODY_DECODE_FAIL    = 11  /* part.get_body_raw().unwrap() in extract_email_body (zke_extract_bodies only)  core/src/email.rs:17-21 */
 };
 
 /* `detail` sub-codes.  For ZKE_DKIM_NOT_PASS they mirror cfdkim's DKIMError of the
@@ -140,7 +141,13 @@ enum {
   ZKE_D_KEYREC_NON_ASCII_EDGE = 108, /* ZKE_KEYREC_ARCHIVE: a ';'-separated part begins or ends, after ASCII trimming, with a byte
                                        >= 0x80: str::trim trims Unicode white space there, the engine trims ASCII only.  "Cannot
                                        answer", never a guess */
-  ZKE_D_KEYREC_TOO_LONG      = 109  /* the record is longer than ZKE_KEYREC_MAX_BYTES */
+  ZKE_D_KEYREC_TOO_LONG      = 109, /* the record is longer than ZKE_KEYREC_MAX_BYTES */
+  /* body extraction (zke_extract_bodies): the rule of strict RFC 4648 base64 a body breaks (ZKE_BODY_DECODE_FAIL), named so that a
+   * more permissive decoder in the real crate shows up as a named difference; and the transfer encoding that is not decided */
+  ZKE_D_BODY_B64_CHAR        = 110, /* after the ASCII white space is dropped: a byte outside the alphabet, or '=' anywhere but in the last two places */
+  ZKE_D_BODY_B64_LENGTH      = 111, /* ... the length is no multiple of 4 (padding is required) */
+  ZKE_D_BODY_B64_TRAILING_BITS = 112, /* ... the bits of the last character that belong to no byte are not zero */
+  ZKE_D_U_BODY_CTE           = 113  /* ZKE_UNSUPPORTED: the chosen part's Content-Transfer-Encoding value holds bytes >= 0x80 or an RFC 2047 encoded word */
 };
 #define ZKE_D_DFA_BWD_OFFSET 10u /* added to ZKE_D_DFA_LABEL .. ZKE_D_DFA_QUITSET when the reverse blob is the one that fails (80..88) */
 
@@ -634,6 +641,59 @@ int zke_select_keys_from_records(zke_engine* e, const zke_email_ref* emails, uin
 int zke_select_keys_from_records_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off,
                                        const zke_keyrec_ref* recs, uint32_t mode, zke_result* out, uint32_t* chosen,
                                        zke_keyrec_out* keys_out, uint64_t* ticket);
+
+/* ---- extract_email_body (core/src/email.rs:7-23, public through `pub use email::*`): the body a reader sees — the text/html part
+ * with its Content-Transfer-Encoding undone — for whole batches, one e-mail per wavefront (body_extract_kernel, csrc/bodyext.hip.h).
+ * Per e-mail, parse_mail(raw).unwrap() then extract_email_body(&parsed).  This is this engine's reading: mailparse 0.15.0,
+ * data-encoding and quoted_printable are not vendored and the rules below are restated from recollection (parity unpinned,
+ * DESIGN.md 4; tests/golden/body_manifest.json lists the e-mails that sit on the unverified behaviours).
+ *  1. The parse verdict is the verify path's: the same header split and MIME walk, ZKE_PARSE_FAIL / ZKE_UNSUPPORTED with the same
+ *     details.  No parse rule is added or changed.
+ *  2. Candidates are the DIRECT subparts the walk finds under the message; nested ones are not.
+ *  3. A subpart's mimetype: its first Content-Type header (eq_ignore_ascii_case), unfolded as get_value does, the first ';'-token,
+ *     trimmed, ASCII-lower-cased; none: text/plain.  (A first token with a byte >= 0x80 or "=?" is the walk's ZKE_D_U_MIME_CTYPE.)
+ *  4. The first subpart whose mimetype is "text/html", else the first subpart, else the message itself.
+ *  5. body_bytes of that part P: from the end of its header block to its end; when P is itself a multipart whose first boundary
+ *     line is found, up to that line (its preamble).  Where the end is a boundary line — P's own end as a subpart, the end of a
+ *     preamble — it is moved back over one LF and then one CR in front of it, never past the start.  ZKE_BODYF_PART_KEEPS_EOL
+ *     leaves that end alone; the flag moves nothing but the end of the span and never changes a verdict.
+ *  6. P's first Content-Transfer-Encoding header, get_value, ASCII-lower-cased, compared WHOLE (no trimming): "base64",
+ *     "quoted-printable", anything else or none: identity.  A value with a byte >= 0x80 or "=?": ZKE_UNSUPPORTED / ZKE_D_U_BODY_CTE.
+ *  7. Identity: the bytes as they are.
+ *  8. Base64: every u8::is_ascii_whitespace byte (HT LF FF CR SP; not VT) is dropped, the rest is strict RFC 4648, standard
+ *     alphabet, padding required, trailing bits zero (as ZKE_KEYREC_ARCHIVE).  A failure is get_body_raw().unwrap()'s panic:
+ *     ZKE_BODY_DECODE_FAIL with ZKE_D_BODY_B64_CHAR, else _LENGTH, else _TRAILING_BITS (the first that applies, in this order).
+ *  9. Quoted-printable (quoted_printable::decode(.., Robust)), never fails: (a) bytes other than HT CR LF and 0x20..0x7E are dropped;
+ *     (b) lines as str::lines() (at LF, one CR in front of it removed, a final empty piece is no line); (c) each line's end is
+ *     trimmed (SP HT CR); (d) '=' as a line's last character is a soft break: no line break follows the line; (e) '=' and ONE
+ *     character at the end of a line are both literal; (f) '=' and two hex digits of either case are that byte; (g) '=' and two
+ *     characters that are not both hex are all three literal, and an '=' among the two starts nothing; (h) a line that ended
+ *     normally owes one CRLF, paid when another line follows and only then.
+ *     "a=\r\nb" -> "ab"; "a \t\r\nb\r\n" -> "a\r\nb"; "=4" -> "=4"; "=zz=41" -> "=zzA"; "==41" -> "==41"; "\r\n\r\n" -> "\r\n".
+ *     (A lone LF becomes CRLF: a decoded body can be LONGER than its source, up to twice.)
+ * Only raw / raw_len of each zke_email_ref are read.  Slots, tickets and zke_batch_wait are zke_decode_key_records': infos (n
+ * entries) too small fails at once with ZKE_E_NOMEM and infos_need set; bytes too small returns ZKE_E_NOMEM (zke_batch_wait for the
+ * asynchronous form) with the infos delivered all the same, body_off as it will be and bytes_need exact.  Checked before anything
+ * is staged: null pointers, unknown flag bits, an e-mail of 2^31 bytes or more (ZKE_E_ARG). */
+#define ZKE_BODYF_PART_KEEPS_EOL 1u
+#define ZKE_CTE_IDENTITY 0u
+#define ZKE_CTE_BASE64   1u
+#define ZKE_CTE_QP       2u
+typedef struct zke_body_info {     /* 40 bytes */
+  uint32_t status, detail;         /* ZKE_OK | ZKE_PARSE_FAIL | ZKE_BODY_DECODE_FAIL | ZKE_UNSUPPORTED */
+  uint32_t part;                   /* 0: the message itself; k >= 1: its k-th direct subpart; bit 31: chosen as text/html */
+  uint32_t encoding;               /* ZKE_CTE_* */
+  uint32_t src_off, src_len;       /* body_bytes of the chosen part inside the raw e-mail (before decoding) */
+  uint32_t body_len, reserved;     /* decoded length; 0 unless status is ZKE_OK */
+  uint64_t body_off;               /* into zke_body_out.bytes */
+} zke_body_info;                   /* part, encoding, src_off, src_len: as far as the e-mail got (0 with a parse verdict) */
+typedef struct zke_body_out {
+  zke_body_info* infos; size_t infos_cap;
+  uint8_t*       bytes; size_t bytes_cap;
+  size_t infos_need, bytes_need;           /* written by the call */
+} zke_body_out;
+int zke_extract_bodies(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t flags, zke_body_out* out);
+int zke_extract_bodies_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t flags, zke_body_out* out, uint64_t* ticket);
 
 /* Device-resident batch: every pointer in `in` and `out_dev` is device memory (the part-id lists stay host arrays);
  * `raw_total`, `domain_total`, `key_total` are the blob sizes (the CSR tails), which the

@@ -97,6 +97,10 @@ struct VerifyPanic : std::runtime_error {
   VerifyPanic(uint32_t s, uint32_t d)
       : std::runtime_error("zkemail_core panic site status=" + std::to_string(s) + " detail=" + std::to_string(d)),
         status(s), detail(d) {}
+  // ... at a site the status alone does not name (extract_email_body: email.rs:26 the parse, :17 / :21 get_body_raw)
+  VerifyPanic(uint32_t s, uint32_t d, const std::string& site)
+      : std::runtime_error("zkemail_core panic site " + site + " status=" + std::to_string(s) + " detail=" + std::to_string(d)),
+        status(s), detail(d) {}
 };
 
 // One DKIM-Signature header as a scan reports it (zke_sig_info, the selector as a string).
@@ -118,6 +122,13 @@ struct KeyInfo {
   uint32_t code, key_type;                 // key_type: ZKE_KEY_* as far as the record got
   std::vector<uint8_t> key;                // PKCS#1 DER or 32 raw bytes
   PublicKey public_key() const { return PublicKey{key, key_type == ZKE_KEY_ED25519 ? "ed25519" : "rsa"}; }
+};
+// One e-mail's extract_email_body as an extraction reports it (zke_body_info, the decoded body as bytes).
+struct BodyInfo {
+  uint32_t status, detail;                 // ZKE_OK | ZKE_PARSE_FAIL | ZKE_BODY_DECODE_FAIL | ZKE_UNSUPPORTED
+  uint32_t part, encoding;                 // 0 the message, k its k-th direct subpart, bit 31: chosen as text/html; ZKE_CTE_*
+  uint32_t src_off, src_len;               // body_bytes of the chosen part in the raw e-mail, before decoding
+  std::vector<uint8_t> body;               // empty unless status is ZKE_OK
 };
 // The resolver of generate_email_inputs_from_records: (from_domain, selector) -> the RAW answer — the TXT record of
 // selector._domainkey.domain (its character-strings joined) or the archive's value —, or nullopt when the fetch fails.
@@ -349,6 +360,31 @@ class Engine {
     return c.result();
   }
 
+  // core/src/email.rs:7-23 for a batch (zke_extract_bodies): parse_mail, the text/html subpart (else the first, else the message),
+  // its Content-Transfer-Encoding undone.  part_keeps_eol: ZKE_BODYF_PART_KEEPS_EOL.
+  std::vector<BodyInfo> extract_email_bodies(const std::vector<std::vector<uint8_t>>& raw_emails, bool part_keeps_eol = false) {
+    const uint32_t n = (uint32_t)raw_emails.size();
+    std::vector<zke_email_ref> refs(n);
+    size_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      refs[i] = zke_email_ref{};
+      refs[i].raw = raw_emails[i].data(); refs[i].raw_len = raw_emails[i].size();
+      total += raw_emails[i].size();
+    }
+    std::vector<zke_body_info> infos(n);
+    std::vector<uint8_t> bytes(2 * total + 1);           // a decoded body is at most twice its source (lone LF becomes CRLF)
+    zke_body_out out{infos.data(), n, bytes.data(), bytes.size(), 0, 0};
+    if (int r = zke_extract_bodies(e_, refs.data(), n, part_keeps_eol ? ZKE_BODYF_PART_KEEPS_EOL : 0u, &out))
+      throw EngineError("zke_extract_bodies failed: " + std::to_string(r) + " " + zke_last_error(e_));
+    std::vector<BodyInfo> res(n);
+    for (uint32_t i = 0; i < n; i++) {
+      const zke_body_info& f = infos[i];
+      res[i] = BodyInfo{f.status, f.detail, f.part, f.encoding, f.src_off, f.src_len,
+                        std::vector<uint8_t>(bytes.begin() + (size_t)f.body_off, bytes.begin() + (size_t)f.body_off + f.body_len)};
+    }
+    return res;
+  }
+
   // zke_select_keys_from_records: select_keys with the resolver's raw answers in place of keys; the records are decoded on the GPU in
   // front of the verify launches.  infos[i][k]: what candidate k of e-mail i decoded to.
   std::vector<zke_result> select_keys_from_records(const std::vector<Email>& emails, const std::vector<std::vector<std::optional<std::string>>>& candidate_records,
@@ -562,6 +598,16 @@ inline std::pair<std::vector<uint8_t>, std::vector<size_t>> remove_quoted_printa
 inline EmailWithRegexVerifierOutput verify_email_with_regex(const EmailWithRegex& in) {
   return default_engine().verify_email_with_regex(in);
 }
+// core/src/email.rs:7 extract_email_body(&parse_mail(raw).unwrap()): the decoded body.  Throws VerifyPanic naming the site where the
+// reference panics — core/src/email.rs:26 (parse_mail), :21 (get_body_raw of the text/html part), :17 (of the first part or the
+// message) — or, for an input the engine does not decide (ZKE_UNSUPPORTED), the site it stopped in front of.
+inline std::vector<uint8_t> extract_email_body(Engine& engine, const std::vector<uint8_t>& raw) {
+  BodyInfo f = engine.extract_email_bodies({raw})[0];
+  if (f.status == ZKE_OK) return std::move(f.body);
+  const bool parse = f.status == ZKE_PARSE_FAIL || (f.status == ZKE_UNSUPPORTED && f.detail != ZKE_D_U_BODY_CTE);
+  throw VerifyPanic(f.status, f.detail, parse ? "core/src/email.rs:26" : (f.part >> 31) ? "core/src/email.rs:21" : "core/src/email.rs:17");
+}
+inline std::vector<uint8_t> extract_email_body(const std::vector<uint8_t>& raw) { return extract_email_body(default_engine(), raw); }
 // helpers/src/generator.rs:11 generate_email_inputs(from_domain, raw_email, external_inputs) with the key fetch as a callback
 inline Email generate_email_inputs(const std::string& from_domain, const std::vector<uint8_t>& raw_email, const FetchKey& fetch_key,
                                    std::optional<std::vector<ExternalInput>> external_inputs = std::nullopt) {

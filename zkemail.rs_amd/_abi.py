@@ -24,18 +24,19 @@ ZKE_DFA_DECODE_FAIL = 7
 ZKE_HEADER_REGEX_FAIL = 8
 ZKE_BODY_REGEX_FAIL = 9
 ZKE_UNSUPPORTED = 10
+ZKE_BODY_DECODE_FAIL = 11
 
 STATUS_NAMES = {
     0: "OK", 1: "PARSE_FAIL", 2: "KEY_DECODE_FAIL", 3: "DKIM_ERROR", 4: "DKIM_NOT_PASS",
     5: "EXTERNAL_INPUT_NULL", 6: "CANON_FAIL", 7: "DFA_DECODE_FAIL", 8: "HEADER_REGEX_FAIL",
-    9: "BODY_REGEX_FAIL", 10: "UNSUPPORTED",
+    9: "BODY_REGEX_FAIL", 10: "UNSUPPORTED", 11: "BODY_DECODE_FAIL",
 }
 # the reference panic site each status stands for
 STATUS_SITE = {
     1: "core/src/email.rs:26", 2: "core/src/email.rs:29", 3: "core/src/email.rs:33",
     4: "core/src/circuits.rs:13", 5: "core/src/circuits.rs:24", 6: "core/src/circuits.rs:35",
     7: "core/src/regex.rs:32-33", 8: "core/src/circuits.rs:45", 9: "core/src/circuits.rs:54",
-    10: "outside this engine's implemented subset",
+    10: "outside this engine's implemented subset", 11: "core/src/email.rs:17-21",
 }
 
 D_NONE = 0
@@ -242,6 +243,30 @@ class zke_keyrec_out(C.Structure):
     """Caller-sized buffers of a decode; capacities in entries, the sizes needed written back."""
     _fields_ = [("infos", C.c_void_p), ("infos_cap", C.c_size_t), ("keys", C.c_void_p), ("keys_cap", C.c_size_t),
                 ("infos_need", C.c_size_t), ("keys_need", C.c_size_t)]
+
+
+# extract_email_body for whole batches (zke_extract_bodies)
+BODYF_PART_KEEPS_EOL = 1
+CTE_IDENTITY, CTE_BASE64, CTE_QP = 0, 1, 2
+D_BODY_B64_CHAR, D_BODY_B64_LENGTH, D_BODY_B64_TRAILING_BITS, D_U_BODY_CTE = 110, 111, 112, 113
+BODY_PART_HTML = 0x80000000          # zke_body_info.part, bit 31: chosen as text/html
+
+
+class zke_body_info(C.Structure):
+    """What one e-mail's extraction gives: verdict, the chosen part, its body_bytes in the raw e-mail, the decoded bytes."""
+    _fields_ = [("status", C.c_uint32), ("detail", C.c_uint32), ("part", C.c_uint32), ("encoding", C.c_uint32), ("src_off", C.c_uint32),
+                ("src_len", C.c_uint32), ("body_len", C.c_uint32), ("reserved", C.c_uint32), ("body_off", C.c_uint64)]
+
+
+BODY_INFO_DTYPE = np.dtype([("status", "<u4"), ("detail", "<u4"), ("part", "<u4"), ("encoding", "<u4"), ("src_off", "<u4"),
+                            ("src_len", "<u4"), ("body_len", "<u4"), ("reserved", "<u4"), ("body_off", "<u8")])
+assert C.sizeof(zke_body_info) == 40 == BODY_INFO_DTYPE.itemsize
+
+
+class zke_body_out(C.Structure):
+    """Caller-sized buffers of an extraction; capacities in entries, the sizes needed written back."""
+    _fields_ = [("infos", C.c_void_p), ("infos_cap", C.c_size_t), ("bytes", C.c_void_p), ("bytes_cap", C.c_size_t),
+                ("infos_need", C.c_size_t), ("bytes_need", C.c_size_t)]
 
 
 STRICT_FLAGS = ("enforce_expiry_x", "canon_takes_verified_signature", "canon_ignores_l", "i_must_be_subdomain",

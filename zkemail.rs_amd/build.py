@@ -71,6 +71,7 @@ CPP_EXAMPLE = os.path.join(ROOT, "tests", "cpp", "mirror_test")
 CPP_SIGSCAN = os.path.join(ROOT, "tests", "cpp", "sigscan_test")
 CPP_KEYREC = os.path.join(ROOT, "tests", "cpp", "keyrec_test")
 CPP_QPMAP = os.path.join(ROOT, "tests", "cpp", "qpmap_test")
+CPP_BODY = os.path.join(ROOT, "tests", "cpp", "body_test")
 ED_PROBE = os.path.join(ROOT, "tests", "cpp", "ed_probe")
 SHA_PROBE = os.path.join(ROOT, "tests", "cpp", "sha_probe")
 
@@ -98,6 +99,8 @@ def build_cpp_example(force: bool = False) -> str:
     build_cpp_keyrec(force)
     if os.path.exists(CPP_QPMAP + ".cpp"):
         build_cpp_qpmap(force)
+    if os.path.exists(CPP_BODY + ".cpp"):
+        build_cpp_body(force)
     if os.path.exists(ED_PROBE + ".hip"):       # test infrastructure that lives in tests/: a tree whose tests/ does not carry the probe
         build_ed_probe(force)                   # has nothing that runs it, and the three programs below do not depend on it
     if os.path.exists(SHA_PROBE + ".hip"):
@@ -118,6 +121,11 @@ def build_cpp_keyrec(force: bool = False) -> str:
 def build_cpp_qpmap(force: bool = False) -> str:
     """tests/cpp/qpmap_test: remove_quoted_printable_soft_breaks and the extract_captures overload with origins of the C++ mirror."""
     return _build_cpp(CPP_QPMAP, force)
+
+
+def build_cpp_body(force: bool = False) -> str:
+    """tests/cpp/body_test: extract_email_bodies / extract_email_body of the C++ mirror."""
+    return _build_cpp(CPP_BODY, force)
 
 
 def build_ed_probe(force: bool = False) -> str:

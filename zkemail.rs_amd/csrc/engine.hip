@@ -29,6 +29,7 @@
 #include "qpmap.hip.h"
 #include "sigscan.hip.h"
 #include "keyrec.hip.h"
+#include "bodyext.hip.h"
 #include "rsa_kernel.hip.h"
 #include "rsa_quad.hip.h"
 #include "fused.hip.h"
@@ -117,9 +118,13 @@ struct Slot {
   OriginBufs ob;
   zke_capture_origin* org_out = nullptr;
   QpBufs qb;
-  DevBuf* all[27] = {&meta, &rsa_jobs, &sha_jobs, &sha_order, &rsa_ok, &em_dbg, &scratch_off, &scratch, &clean, &meta2, &scratch2, &parts,
+  // body extraction (zke_extract_bodies): infos and decoded bytes in one buffer (BodyLayout) with its pinned twin, the header-span
+  // overflow area, and where the pending batch's infos and bytes go
+  BodyBufs bb;
+  zke_body_out* body_out = nullptr;
+  DevBuf* all[29] = {&meta, &rsa_jobs, &sha_jobs, &sha_order, &rsa_ok, &em_dbg, &scratch_off, &scratch, &clean, &meta2, &scratch2, &parts,
                      &pending, &d_image, &d_results, &cb.cap, &cb.work, &sb.out, &sb.ovf, &kb.out, &kb.pack,
-                     &ob.org, &qb.in, &qb.off, &qb.clean, &qb.map, &qb.len};
+                     &ob.org, &qb.in, &qb.off, &qb.clean, &qb.map, &qb.len, &bb.out, &bb.ovf};
   // hipGraph replay of a batch's kernel sequence (zke_options.replay_graphs).  The graph holds this slot's
   // workspace pointers, so it is valid only while none of them has been reallocated: `generation` counts reallocations.
   hipGraphExec_t graph_exec = nullptr;
@@ -255,7 +260,7 @@ void free_slot(Slot* w) {
   if (!w) return;
   if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
   for (auto* b : w->all) b->release();
-  w->h_image.release(); w->h_results.release(); w->cb.h_cap.release(); w->sb.h_out.release(); w->kb.h_out.release(); w->ob.h_org.release();
+  w->h_image.release(); w->h_results.release(); w->cb.h_cap.release(); w->sb.h_out.release(); w->kb.h_out.release(); w->ob.h_org.release(); w->bb.h_out.release();
   for (auto& ev : w->ev) if (ev) (void)hipEventDestroy(ev);
   if (w->done) (void)hipEventDestroy(w->done);
   if (w->host_done) (void)hipEventDestroy(w->host_done);
@@ -405,6 +410,7 @@ const char* zke_status_name(uint32_t status) {
       "assert!(verified) on header parts  core/src/circuits.rs:45",
       "assert!(verified) on body parts  core/src/circuits.rs:54",
       "input outside what this engine implements (ZKE_UNSUPPORTED; detail says which limit)",
+      "part.get_body_raw().unwrap() in extract_email_body  core/src/email.rs:17-21",
   };
   return status < sizeof names / sizeof names[0] ? names[status] : "unknown status";
 }

@@ -217,9 +217,11 @@ __device__ __forceinline__ HdrNames hdr_names(const ParseLds& L, uint32_t nh) {
 
 // Still parse_mail: the MIME subparts of the top-level message (mime.hip.h).  Its first Content-Type header decides — fields
 // 0..63 tested by name length first, all at once, the later ones one by one.  Returns mime_walk's status (0: nothing wrong,
-// or no Content-Type at all) with its `detail`.  The walk's stack is the tag buffer: not in use yet.
+// or no Content-Type at all) with its `detail`.  The walk's stack is the tag buffer: not in use yet.  `part`: mime.hip.h, MimeNoParts
+// (a message without a Content-Type header never reaches the walk: no call at all, it is a leaf).
+template <class Parts = MimeNoParts>
 __device__ __forceinline__ uint32_t mime_subparts(ParseLds& L, const uint32_t* hdr_ovf, const Str& raw, const HdrNames& hn, uint32_t nh,
-                                                  uint32_t hdr_end, uint32_t& detail) {
+                                                  uint32_t hdr_end, uint32_t& detail, Parts part = Parts()) {
   bool has_ct = false;
   uint32_t cvs = 0, cve = 0;
   for (uint64_t m = __ballot(hn.nl == 12u); m; m &= m - 1) {
@@ -233,7 +235,7 @@ __device__ __forceinline__ uint32_t mime_subparts(ParseLds& L, const uint32_t* h
   if (!has_ct) return 0;
   uint32_t ixb = hdr_end;                      // behind the empty line that ended the header list
   if (ixb < raw.len) ixb += (uni(ldb(raw, ixb)) == '\r') ? 2u : 1u;
-  return mime_walk((uint32_t*)L.tagbuf, raw, ixb, true, cvs, cve, detail);
+  return mime_walk((uint32_t*)L.tagbuf, raw, ixb, true, cvs, cve, detail, part);
 }
 
 // The first header field at or after hx that is named DKIM-Signature, its spans in hs; NONE when there is none.  Only a

@@ -28,12 +28,23 @@ struct SelectReq { const uint32_t* cand_off; uint32_t n; zke_result* out; uint32
 // pipeline.  With a SelectReq: the image's key section holds the records, and the decode + pack launches in front of the front end
 // replace it by the decoded keys (zke_select_keys_from_records).
 struct KeyrecReq { uint32_t mode; zke_keyrec_out* out; };
+// ---- body extraction (bodyext.hip.h): the batch's raw section holds the e-mails, body_extract_kernel runs instead of the verify pipeline
+struct BodyReq { uint32_t flags; zke_body_out* out; };
 
 int ensure_keyrec_buffers(zke_engine* e, KeyrecBufs& b, uint32_t m, size_t rec_total, bool pack) {
   const KeyrecLayout L = keyrec_layout(m, rec_total);
   int r = 0;
   if ((r = b.out.ensure(L.total)) || (r = b.h_out.ensure(L.total)) || (pack && (r = b.pack.ensure(L.p_total))))
     return fail(e, r, "key-record buffer allocation");
+  b.L = L;
+  return 0;
+}
+
+int ensure_body_buffers(zke_engine* e, BodyBufs& b, uint32_t n, size_t raw_total) {
+  const BodyLayout L = body_layout(n, raw_total);
+  int r = 0;
+  if ((r = b.out.ensure(L.total)) || (r = b.h_out.ensure(L.total)) || (r = b.ovf.ensure((size_t)n * HDR_OVF_BYTES)))
+    return fail(e, r, "body-extraction buffer allocation");
   b.L = L;
   return 0;
 }
@@ -129,6 +140,24 @@ int deliver_keyrec(zke_engine* e, const KeyrecBufs& b, zke_keyrec_out* o) {
   return 0;
 }
 
+// An extraction from the slot's pinned twin into the caller's zke_body_out (host_stage.hip.h: body_measure, body_compact): the infos
+// with body_off rewritten to the packed offsets, the bodies compacted.  The second places (bodies that outgrew their e-mail) are
+// fetched only when one is in use.  ZKE_E_NOMEM when bytes is too small (bytes_need says how much).
+int deliver_body(zke_engine* e, const BodyBufs& b, zke_body_out* o, hipStream_t s) {
+  const BodyLayout& K = b.L;
+  uint8_t* hp = b.h_out.as<uint8_t>();
+  bool spilled = false;
+  const int r = body_measure(K, hp, o, spilled);
+  if (r == ZKE_E_DEVICE) return fail(e, r, "body extraction: an info points outside its e-mail's place");
+  if (r) return fail(e, r, "body extraction: bytes is smaller than the decoded bodies (zke_body_out.bytes_need)");
+  if (spilled) {
+    HIPCHK(e, hipMemcpyAsync(hp + K.first_copy, b.out.as<uint8_t>() + K.first_copy, K.region, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+  }
+  body_compact(K, hp, o);
+  return 0;
+}
+
 // A key selection's fold: the records of the (e-mail, candidate) pairs are in the pinned buffer; per e-mail the first ZKE_OK.
 void fold_selection(const zke_result* R, const std::vector<uint32_t>& off, zke_result* out, uint32_t* chosen) {
   for (size_t i = 0; i + 1 < off.size(); i++) {
@@ -164,6 +193,8 @@ int retire_host(zke_engine* e, Slot& w, int* cap_rc = nullptr) {
   w.keyrec_out = nullptr;
   zke_capture_origin* pending_org = w.org_out;
   w.org_out = nullptr;
+  zke_body_out* pending_body = w.body_out;
+  w.body_out = nullptr;
   HIPCHK(e, hipEventSynchronize(w.host_done));
   if (w.host_out && w.host_n) memcpy(w.host_out, w.h_results.p, (size_t)w.host_n * sizeof(zke_result));
   w.host_out = nullptr;
@@ -180,6 +211,12 @@ int retire_host(zke_engine* e, Slot& w, int* cap_rc = nullptr) {
   if (pending_keyrec) {
     const std::string keep = g_err;
     const int r = deliver_keyrec(e, w.kb, pending_keyrec);
+    if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
+    else if (r) return r;
+  }
+  if (pending_body) {
+    const std::string keep = g_err;
+    const int r = deliver_body(e, w.bb, pending_body, w.stream);
     if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
     else if (r) return r;
   }
@@ -216,6 +253,7 @@ struct HostBatch {
   const ScanReq* scan = nullptr;        // zke_scan_signatures: sigscan_kernel runs instead of the verify pipeline
   const SelectReq* sel = nullptr;       // zke_select_keys: the batch's entries are (e-mail, candidate key) pairs, folded on delivery
   const KeyrecReq* keyrec = nullptr;    // key records: decoded instead of the verify pipeline, or (with sel) in front of it
+  const BodyReq* body = nullptr;        // zke_extract_bodies: body_extract_kernel runs instead of the verify pipeline
   uint64_t raw_total = 0, dom_total = 0, key_total = 0, raw_base = 0, dom_base = 0, key_base = 0;   // blob bytes; off[0] of packed offsets
   size_t cap_words = 0, cap_strs = 0, cap_bytes = 0;      // entries of cap_off and cap_str_off, bytes of cap_blob (0: no tables)
   ImageLayout L{};
@@ -290,6 +328,8 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   }
   if (d.keyrec)
     if (int r = ensure_keyrec_buffers(e, w.kb, n, (size_t)(d.sel ? d.key_total : d.raw_total), d.sel != nullptr)) return r;
+  if (d.body)
+    if (int r = ensure_body_buffers(e, w.bb, n, (size_t)d.raw_total)) return r;
   uint8_t* hp = w.h_image.as<uint8_t>();
   if (d.refs) {
     // the CSR arrays are written where they will be read from (prefix sums over the lengths), and every e-mail's three buffers
@@ -379,6 +419,15 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
     HIPCHK(e, hipGetLastError());
     tm.mark(MK_FRONT); tm.mark(MK_HASH); tm.mark(MK_VERDICT);      // zke_timings.front_end_us is the scan; the other stages are empty
     HIPCHK(e, hipMemcpyAsync(w.sb.h_out.p, so, S.total, hipMemcpyDeviceToHost, s));
+  } else if (d.body) {
+    // one launch over the e-mails (the image's raw section), infos and first places back as one copy
+    const BodyLayout& K = w.bb.L;
+    uint8_t* bo = w.bb.out.as<uint8_t>();
+    const BodyArgs ba{n, d.body->flags, dv.raw_blob, dv.raw_off, reinterpret_cast<zke_body_info*>(bo), bo + K.bytes, (uint64_t)K.region, w.bb.ovf.as<uint32_t>()};
+    hipLaunchKernelGGL(body_extract_kernel, dim3(n), dim3(64), 0, s, ba);
+    HIPCHK(e, hipGetLastError());
+    tm.mark(MK_FRONT); tm.mark(MK_HASH); tm.mark(MK_VERDICT);      // zke_timings.front_end_us is the extraction; the other stages are empty
+    HIPCHK(e, hipMemcpyAsync(w.bb.h_out.p, bo, K.first_copy, hipMemcpyDeviceToHost, s));
   } else if (d.keyrec && !d.sel) {
     // one launch over the records (the image's raw section), infos and keys back as one copy
     const KeyrecLayout& K = w.kb.L;
@@ -416,8 +465,9 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   tm.mark(MK_D2H);
   HIPCHK(e, hipEventRecord(w.host_done, s));
   w.host_gen++;
-  w.host_out = (d.scan || d.sel || d.keyrec) ? nullptr : out; w.host_n = n;
+  w.host_out = (d.scan || d.sel || d.keyrec || d.body) ? nullptr : out; w.host_n = n;
   w.keyrec_out = d.keyrec ? d.keyrec->out : nullptr;
+  w.body_out = d.body ? d.body->out : nullptr;
   w.cap_out = d.cap ? d.cap->out : nullptr;
   w.org_out = d.cap ? d.cap->org : nullptr;
   w.scan_out = d.scan ? d.scan->out : nullptr;
@@ -763,6 +813,34 @@ int zke_select_keys_from_records(zke_engine* e, const zke_email_ref* emails, uin
                                  const zke_keyrec_ref* recs, uint32_t mode, zke_result* out, uint32_t* chosen, zke_keyrec_out* keys_out) {
   uint64_t ticket = 0;
   if (int r = zke_select_keys_from_records_async(e, emails, n, cand_off, recs, mode, out, chosen, keys_out, &ticket)) return r;
+  return n ? zke_batch_wait(e, ticket) : 0;
+}
+
+// ---- extract_email_body for whole batches (include/zkemail_amd.h; kernel: bodyext.hip.h)
+int zke_extract_bodies_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t flags, zke_body_out* out, uint64_t* ticket) {
+  static const char who[] = "zke_extract_bodies";
+  if (!e) return ZKE_E_ARG;
+  if (!ticket || !out || (n && !emails)) return arg_error(who, "null pointer");
+  if (flags & ~ZKE_BODYF_PART_KEEPS_EOL) return arg_error(who, "unknown flag bits");
+  for (uint32_t i = 0; i < n; i++) {
+    if (emails[i].raw_len && !emails[i].raw) return arg_error(who, "null buffer with a length");
+    if (emails[i].raw_len >= (1ull << 31)) return arg_error(who, "an e-mail of 2^31 bytes or more");
+  }
+  out->infos_need = n; out->bytes_need = 0;
+  if (out->infos_cap < n) { g_err = std::string(who) + ": zke_body_out.infos is smaller than infos_need"; return ZKE_E_NOMEM; }
+  if ((n && !out->infos) || (out->bytes_cap && !out->bytes)) return arg_error(who, "null buffer in zke_body_out");
+  std::vector<zke_email_ref> refs(n);                 // only the raw e-mails travel: no domains, no keys
+  for (uint32_t i = 0; i < n; i++) { refs[i] = zke_email_ref{}; refs[i].raw = emails[i].raw; refs[i].raw_len = emails[i].raw_len; }
+  HostBatch d;
+  if (int r = host_batch(d, who, reinterpret_cast<const zke_result*>(out), refs.data(), n, nullptr)) return r;
+  const BodyReq q{flags, out};
+  d.body = &q;
+  return submit_host_batch(e, d, nullptr, ticket);
+}
+
+int zke_extract_bodies(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t flags, zke_body_out* out) {
+  uint64_t ticket = 0;
+  if (int r = zke_extract_bodies_async(e, emails, n, flags, out, &ticket)) return r;
   return n ? zke_batch_wait(e, ticket) : 0;
 }
 

@@ -277,6 +277,65 @@ struct KeyrecBufs {
   void release() { out.release(); pack.release(); h_out.release(); }
 };
 
+// The buffers of one body extraction (a slot's; zke_extract_bodies): {infos | first places | second places} in one device buffer
+// with a pinned twin.  E-mail i decodes into the first place at its raw offset; only a quoted-printable body that outgrows its e-mail
+// (lone LF line ends become CRLF) goes on in the second place at the same offset (bodyext.hip.h).  ONE copy brings {infos | first
+// places} back; the second places follow in a copy of their own when an info says one is in use (first_copy, then the rest).
+struct BodyLayout { size_t bytes, region, first_copy, total; uint32_t n; };
+inline BodyLayout body_layout(uint32_t n, size_t raw_total) {
+  BodyLayout L{};
+  L.n = n;
+  L.bytes = align_up((size_t)n * sizeof(zke_body_info), 64);
+  L.region = align_up(raw_total, 64);
+  L.first_copy = L.bytes + L.region;
+  L.total = L.first_copy + L.region;
+  return L;
+}
+struct BodyBufs {
+  DevBuf out, ovf;
+  PinnedBuf h_out;
+  BodyLayout L{};
+  void release() { out.release(); ovf.release(); h_out.release(); }
+};
+// The compaction of a finished extraction, host code only, in two steps around the one copy that may lie between them.
+// body_measure: the device's infos (body_off = the e-mail's raw offset, reserved = its raw length: its place) checked against the
+// layout — an info that points outside its place is refused, nothing is read through it — and delivered with body_off rewritten to
+// the packed offsets; bytes_need; `spilled`: some body uses its second place.  0, ZKE_E_DEVICE (an info the kernel cannot have
+// written) or ZKE_E_NOMEM (bytes is too small; the infos are delivered all the same).
+inline int body_measure(const BodyLayout& K, const uint8_t* twin, zke_body_out* o, bool& spilled) {
+  const zke_body_info* src = reinterpret_cast<const zke_body_info*>(twin);
+  spilled = false;
+  for (uint32_t i = 0; i < K.n; i++) {
+    const zke_body_info& f = src[i];
+    const uint64_t len = f.status == ZKE_OK ? f.body_len : 0;
+    if (f.body_off > K.region || f.reserved > K.region - f.body_off || len > 2 * (uint64_t)f.reserved) return ZKE_E_DEVICE;
+  }
+  size_t total = 0;
+  for (uint32_t i = 0; i < K.n; i++) {
+    zke_body_info f = src[i];
+    if (f.status != ZKE_OK) f.body_len = 0;
+    spilled = spilled || f.body_len > f.reserved;
+    f.body_off = total; f.reserved = 0;
+    total += f.body_len;
+    o->infos[i] = f;
+  }
+  o->bytes_need = total;
+  return total > o->bytes_cap ? ZKE_E_NOMEM : 0;
+}
+// body_compact: behind a body_measure that returned 0 (and, when it said `spilled`, the copy of the second places): one memcpy per
+// body, two for a spilled one.
+inline void body_compact(const BodyLayout& K, const uint8_t* twin, zke_body_out* o) {
+  const zke_body_info* src = reinterpret_cast<const zke_body_info*>(twin);
+  for (uint32_t i = 0; i < K.n; i++) {
+    const size_t len = o->infos[i].body_len, cap = src[i].reserved, at = (size_t)src[i].body_off;
+    if (!len) continue;
+    uint8_t* dst = o->bytes + o->infos[i].body_off;
+    const size_t a = std::min(len, cap);
+    memcpy(dst, twin + K.bytes + at, a);
+    if (len > a) memcpy(dst + a, twin + K.first_copy + at, len - a);
+  }
+}
+
 // The origins of one mapped extraction (a slot's; zke_extract_captures_mapped): {spans n*G*2 | flags n*G} in a device buffer of its own
 // with a pinned twin — a plain extraction never sees it.  `launched`: capture_origin_kernel ran for the pending batch (it does not
 // when no body part asks for a group: the origins are then the spans themselves).

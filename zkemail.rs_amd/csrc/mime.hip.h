@@ -120,23 +120,33 @@ __device__ __forceinline__ uint32_t find_boundary_line(const Str& raw, uint32_t 
   return NONE;
 }
 
+// What the walk tells about every part it accepts, in file order: part(level, ps, pe, ixb, ct, cvs, cve, fb) — the part is
+// raw[ps, pe), `level` multiparts deep (0: the message), its body starts at ixb, [cvs, cve) is the value of its first Content-Type
+// header (ct), fb its first boundary line when it is a multipart that opens a frame, else NONE.  The verify launches pass nothing:
+// the calls vanish.  The body extraction (bodyext.hip.h) picks its part from the level-1 calls.
+struct MimeNoParts {
+  __device__ __forceinline__ void operator()(uint32_t, uint32_t, uint32_t, uint32_t, bool, uint32_t, uint32_t, uint32_t) const {}
+};
+
 // The walk.  0, or ZKE_PARSE_FAIL / ZKE_UNSUPPORTED with `detail`.  The top-level part's headers are already split:
 // ix_body = the byte behind its empty line, [ct_vs, ct_ve) = the value of its first Content-Type header (has_ct).
 // stk: 4 words per open multipart (slice end, boundary value span, where the last boundary line's prefix ended), LDS.
+template <class Parts = MimeNoParts>
 __device__ __forceinline__ uint32_t mime_walk(uint32_t* stk, const Str& raw, uint32_t ix_body, bool has_ct, uint32_t ct_vs, uint32_t ct_ve,
-                                              uint32_t& detail) {
+                                              uint32_t& detail, Parts part = Parts()) {
   const int lane = lane_id();
   uint32_t depth = 0;
   // a part whose headers are known: open a frame when it is a multipart whose first boundary line exists
-  auto enter = [&](uint32_t b, uint32_t ixb, bool ct, uint32_t cvs, uint32_t cve) -> uint32_t {
-    if (!ct) return 0;
+  auto enter = [&](uint32_t ps, uint32_t b, uint32_t ixb, bool ct, uint32_t cvs, uint32_t cve) -> uint32_t {
+    if (!ct) { part(depth, ps, b, ixb, ct, cvs, cve, NONE); return 0; }
     uint32_t bs = 0, be = 0;
     const uint32_t m = mime_content_type(substr(raw, cvs, cve), bs, be);
     if (m & 0x80000000u) { detail = m & 0xFFFFu; return ZKE_UNSUPPORTED; }
-    if (m == 0 || !(b > ixb)) return 0;
+    if (m == 0 || !(b > ixb)) { part(depth, ps, b, ixb, ct, cvs, cve, NONE); return 0; }
     if (depth >= MIME_MAX_DEPTH) { detail = ZKE_D_U_MIME_DEPTH; return ZKE_UNSUPPORTED; }
     bs += cvs; be += cvs;
     const uint32_t pos = find_boundary_line(raw, ixb, b, bs, be);
+    part(depth, ps, b, ixb, ct, cvs, cve, pos);
     if (pos == NONE) return 0;
     if (lane == 0) { uint32_t* f = stk + 4 * depth; f[0] = b; f[1] = bs; f[2] = be; f[3] = pos + 2 + (be - bs); }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -144,7 +154,7 @@ __device__ __forceinline__ uint32_t mime_walk(uint32_t* stk, const Str& raw, uin
     depth++;
     return 0;
   };
-  if (const uint32_t r = enter(raw.len, ix_body, has_ct, ct_vs, ct_ve)) return r;
+  if (const uint32_t r = enter(0, raw.len, ix_body, has_ct, ct_vs, ct_ve)) return r;
   Win w; w.wpos = WNONE; w.c = 0;
   while (depth) {
     uint32_t* f = stk + 4 * (depth - 1);
@@ -175,7 +185,7 @@ __device__ __forceinline__ uint32_t mime_walk(uint32_t* stk, const Str& raw, uin
     // hdr_end is where the list stopped: at the empty line (LF or CRLF) or at the end of the slice
     uint32_t ixb = hdr_end;
     if (ixb < sub.len) ixb += (uni(ldb(sub, ixb)) == '\r') ? 2u : 1u;
-    if (const uint32_t r = enter(pe, ps + ixb, ct, ps + cvs, ps + cve)) return r;
+    if (const uint32_t r = enter(ps, pe, ps + ixb, ct, ps + cvs, ps + cve)) return r;
   }
   return 0;
 }

@@ -165,6 +165,11 @@ def load_library(path: Optional[str] = None):
     lib.zke_select_keys_from_records.restype = C.c_int
     lib.zke_select_keys_from_records_async.argtypes = [vp, erp, C.c_uint32, vp, krp, C.c_uint32, vp, vp, kop, C.POINTER(C.c_uint64)]
     lib.zke_select_keys_from_records_async.restype = C.c_int
+    bop = C.POINTER(A.zke_body_out)
+    lib.zke_extract_bodies.argtypes = [vp, erp, C.c_uint32, C.c_uint32, bop]
+    lib.zke_extract_bodies.restype = C.c_int
+    lib.zke_extract_bodies_async.argtypes = [vp, erp, C.c_uint32, C.c_uint32, bop, C.POINTER(C.c_uint64)]
+    lib.zke_extract_bodies_async.restype = C.c_int
     if hasattr(lib, "zke_engine_sha_ring"):         # (a ZKE_LIB build of an older tree, for an A/B run, has no such entry)
         lib.zke_engine_sha_ring.argtypes = [vp]
         lib.zke_engine_sha_ring.restype = C.c_int
@@ -195,6 +200,7 @@ EXPORTED_SYMBOLS = [
     "zke_decode_key_records", "zke_decode_key_records_async", "zke_select_keys_from_records", "zke_select_keys_from_records_async",
     "zke_engine_sha_ring", "zke_engine_sha_twin",
     "zke_qp_clean_batch", "zke_extract_captures_mapped", "zke_extract_captures_mapped_async",
+    "zke_extract_bodies", "zke_extract_bodies_async",
 ]
 
 
@@ -278,6 +284,41 @@ class _KeyrecBuffers:
         if self.off is None:
             return flat
         return [flat[int(self.off[i]):int(self.off[i + 1])] for i in range(len(self.off) - 1)]
+
+
+class BodyInfo(NamedTuple):
+    """One e-mail's extract_email_body as zke_extract_bodies reports it (zke_body_info, the decoded body as bytes)."""
+    status: int                    # ZKE_OK | ZKE_PARSE_FAIL | ZKE_BODY_DECODE_FAIL | ZKE_UNSUPPORTED
+    detail: int
+    part: int                      # 0 the message itself | k its k-th direct subpart; bit 31 (BODY_PART_HTML): chosen as text/html
+    encoding: int                  # CTE_IDENTITY / CTE_BASE64 / CTE_QP
+    src_off: int                   # body_bytes of the chosen part in the raw e-mail, before decoding
+    src_len: int
+    body: bytes                    # b"" unless status is ZKE_OK
+
+
+class _BodyBuffers:
+    """The e-mails of one call as zke_email_ref[n] (raw bytes only) and the caller-sized buffers of its zke_body_out (kept alive
+    until the batch has been waited for)."""
+
+    def __init__(self, raw_emails: Sequence[bytes], body_bytes: Optional[int] = None):
+        self.n = n = len(raw_emails)
+        self._keep = [bytes(r) for r in raw_emails]
+        self.arr = (A.zke_email_ref * max(n, 1))()
+        for j, r in enumerate(self._keep):
+            self.arr[j].raw = C.cast(C.c_char_p(r), C.c_void_p).value if r else None
+            self.arr[j].raw_len = len(r)
+        if body_bytes is None:                   # a decoded body is at most twice its source (lone LF line ends of a QP body become CRLF)
+            body_bytes = 2 * sum(len(r) for r in self._keep)
+        self.infos = np.zeros(max(n, 1), A.BODY_INFO_DTYPE)
+        self.bytes = np.zeros(max(body_bytes, 1), np.uint8)
+        o = self.c = A.zke_body_out()
+        o.infos, o.infos_cap, o.bytes, o.bytes_cap = self.infos.ctypes.data, n, self.bytes.ctypes.data, body_bytes
+
+    def result(self) -> List[BodyInfo]:
+        blob = self.bytes.tobytes()
+        return [BodyInfo(int(f["status"]), int(f["detail"]), int(f["part"]), int(f["encoding"]), int(f["src_off"]), int(f["src_len"]),
+                         blob[int(f["body_off"]):int(f["body_off"]) + int(f["body_len"])]) for f in self.infos[:self.n]]
 
 
 class Engine:
@@ -604,6 +645,23 @@ class Engine:
                                                                 chosen.ctypes.data, C.byref(b.c), C.byref(t)), "zke_select_keys_from_records_async")
         return t.value, out[:refs.n], chosen[:refs.n], b
 
+    # ---- extract_email_body (core/src/email.rs:7-23): the text/html part, transfer-decoded
+    def extract_bodies(self, raw_emails: Sequence[bytes], *, part_keeps_eol: bool = False, body_bytes: Optional[int] = None) -> List[BodyInfo]:
+        """zke_extract_bodies: one BodyInfo per raw e-mail.  `part_keeps_eol`: ZKE_BODYF_PART_KEEPS_EOL, the line break in front of a
+        boundary line stays part of the body.  `body_bytes`: the byte buffer's size (default: twice the e-mails' bytes, which always
+        suffices); too small raises EngineError(ZKE_E_NOMEM)."""
+        b = _BodyBuffers(raw_emails, body_bytes)
+        self._check(self.lib.zke_extract_bodies(self.h, b.arr, b.n, A.BODYF_PART_KEEPS_EOL if part_keeps_eol else 0, C.byref(b.c)), "zke_extract_bodies")
+        return b.result()
+
+    def extract_bodies_async(self, raw_emails: Sequence[bytes], *, part_keeps_eol: bool = False, body_bytes: Optional[int] = None):
+        """zke_extract_bodies_async: (ticket, pending); ``pending.result()`` is valid once ``wait(ticket)`` has returned."""
+        b = _BodyBuffers(raw_emails, body_bytes)
+        t = C.c_uint64()
+        self._check(self.lib.zke_extract_bodies_async(self.h, b.arr, b.n, A.BODYF_PART_KEEPS_EOL if part_keeps_eol else 0, C.byref(b.c), C.byref(t)),
+                    "zke_extract_bodies_async")
+        return t.value, b
+
     # ---- batches
     def verify_batch_async(self, batch: PackedBatch):
         """zke_verify_batch_async: returns (ticket, records); the records are valid once ``wait(ticket)`` has returned.
@@ -841,6 +899,15 @@ def verify_email(email: Email) -> EmailVerifierOutput:
 
 def verify_email_with_regex(inp: EmailWithRegex) -> EmailWithRegexVerifierOutput:
     return default_engine().verify_email_with_regex(inp)
+
+
+def extract_email_body(raw: bytes, *, engine: Optional[Engine] = None) -> bytes:
+    """extract_email_body(&parse_mail(raw).unwrap()) (core/src/email.rs:7-23): the decoded body, or VerifyPanic where the reference
+    panics (email.rs:26 the parse, email.rs:17-21 get_body_raw) or the input is outside what the engine decides."""
+    f = (engine or default_engine()).extract_bodies([raw])[0]
+    if f.status != A.ZKE_OK:
+        raise VerifyPanic(f.status, f.detail)
+    return f.body
 
 
 def generate_email_with_regex_inputs(emails: Sequence[Email], regex_config, *, unicode: bool = True, engine: Optional[Engine] = None):
