@@ -8,6 +8,8 @@
 //   * host_batch (the host entries' batch descriptor): both shapes of one batch agree, malformed ones are refused;
 //   * deliver_scan and fold_selection (what a retired scan / key selection hands its caller): random results in the device layout
 //     into exact-size caller buffers, every capacity from none to plenty;
+//   * deliver_pending (a slot's pending-delivery record paid in one call) against those individual calls, every kind of batch, and
+//     the shortfall rule with each variable-size buffer one byte too small;
 //   * zke_shard_bounds, image_layout, pair_hash on edge sizes.
 // tests/test_host_sanitizers.py builds and runs it.  (The same source with -fsanitize=thread instead: clean as well, run by hand —
 // the second 40 s build is not worth a place in the suite.)
@@ -262,7 +264,7 @@ int main(int argc, char** argv) {
         memcpy(twin.data() + b.L.status, st.data(), st.size() * 4);
         memcpy(twin.data() + b.L.recs, recs.data(), recs.size() * sizeof(zke_sig_info));
         if (std::min(used, b.L.blob_cap)) memcpy(twin.data() + b.L.blob, sel.data(), std::min(used, b.L.blob_cap));
-        b.h_out.p = twin.data(); b.h_out.cap = twin.size();
+        b.t.h.p = twin.data(); b.t.h.cap = twin.size();
         std::vector<uint32_t> status(4 * (size_t)n, 7u), off(n + 1, 7u);
         std::vector<zke_sig_info> sigs(sigs_cap);
         std::vector<uint8_t> blob(blob_cap, 0xCC);
@@ -270,7 +272,7 @@ int main(int argc, char** argv) {
                        blob_cap ? blob.data() : nullptr, blob_cap, 4 * (size_t)n, (size_t)n + 1, 99, 99, 99};
         zke_engine eng;
         const int r = deliver_scan(&eng, b, &o);
-        b.h_out.p = nullptr; b.h_out.cap = 0;
+        b.t.h.p = nullptr; b.t.h.cap = 0;
         const bool sigs_short = sigs_cap < total, blob_short = blob_cap < used;
         bool ok = r == (sigs_short || blob_short ? ZKE_E_NOMEM : 0) && o.sigs_need == total && o.sel_blob_need == used && off == want_off &&
                   status == st && o.n_sigs == (sigs_short ? 0 : total);
@@ -304,6 +306,152 @@ int main(int argc, char** argv) {
     fold_selection(R.data(), off, out.data(), chosen.data());
     if (chosen != want_chosen || (n && memcmp(out.data(), want.data(), n * sizeof(zke_result)))) { fprintf(stderr, "fold_selection differs from its rule\n"); return 1; }
     cases++;
+  }
+  // ---- deliver_pending (what a slot owes for a finished batch) against the individual deliver_* / fold_selection calls, byte for
+  // byte: a default-constructed Slot — no stream, no event, no device — whose pinned twins are exact-size heap vectors, and two
+  // callers with buffers of the same sizes, one served by deliver_pending, the other by the calls it stands for, in its order.
+  // Then every output that can fall short with its variable-size buffer one byte too small: ZKE_E_NOMEM to cap_rc where there is
+  // one, zke_last_error left alone where there is none, 0 returned, the fixed-size outputs and every *_need exact either way.
+  {
+    const uint32_t n = 3, max_sigs = 2, P = 2, G = 3, NP = n * P, NG = n * G;
+    struct Caps { size_t sigs, sel_blob, keys, bytes, cap_blob; };
+    struct Caller {                                                                   // every buffer of exactly its capacity
+      std::vector<zke_result> rec, sel;
+      std::vector<uint32_t> chosen, st, off, spans, cap_off, cap_str_off, ospans;
+      std::vector<zke_sig_info> sigs;
+      std::vector<zke_key_info> kinfos;
+      std::vector<zke_body_info> binfos;
+      std::vector<uint8_t> blob, keys, bytes, flags, cblob, oflags;
+      zke_sig_scan scan; zke_keyrec_out keyrec; zke_body_out body; zke_capture_out caps; zke_capture_origin org;
+      Caller(const Caps& c, uint32_t m)
+          : rec(m), sel(n), chosen(n, 7u), st(4 * n, 7u), off(n + 1, 7u), spans(NG * 2, 7u), cap_off(NP + 1, 7u), cap_str_off(NG + 1, 7u), ospans(NG * 2, 7u),
+            sigs(c.sigs), kinfos(m), binfos(n), blob(c.sel_blob, 0xCC), keys(c.keys, 0xCC), bytes(c.bytes, 0xCC), flags(NG, 0xCC), cblob(c.cap_blob, 0xCC), oflags(NG, 0xCC) {
+        for (auto* v : {&rec, &sel}) memset(v->data(), 0xCC, v->size() * sizeof(zke_result));
+        memset(sigs.data(), 0xCC, sigs.size() * sizeof(zke_sig_info)); memset(kinfos.data(), 0xCC, kinfos.size() * sizeof(zke_key_info));
+        memset(binfos.data(), 0xCC, binfos.size() * sizeof(zke_body_info));
+        scan = zke_sig_scan{st.data(), st.size(), off.data(), off.size(), c.sigs ? sigs.data() : nullptr, c.sigs, c.sel_blob ? blob.data() : nullptr, c.sel_blob, 4 * (size_t)n, (size_t)n + 1, 99, 99, 99};
+        keyrec = zke_keyrec_out{kinfos.data(), m, c.keys ? keys.data() : nullptr, c.keys, m, 99};
+        body = zke_body_out{binfos.data(), n, c.bytes ? bytes.data() : nullptr, c.bytes, n, 99};
+        caps = zke_capture_out{spans.data(), spans.size(), flags.data(), flags.size(), cap_off.data(), cap_off.size(), cap_str_off.data(), cap_str_off.size(),
+                               c.cap_blob ? cblob.data() : nullptr, c.cap_blob, (size_t)NG * 2, NG, (size_t)NP + 1, (size_t)NG + 1, 99, 99};
+        org = zke_capture_origin{ospans.data(), ospans.size(), oflags.data(), oflags.size(), (size_t)NG * 2, NG};
+      }
+      bool same(const Caller& o) const {
+        auto eq = [](const auto& a, const auto& b) { return a.size() == b.size() && (a.empty() || !memcmp(a.data(), b.data(), a.size() * sizeof a[0])); };
+        return eq(rec, o.rec) && eq(sel, o.sel) && eq(chosen, o.chosen) && eq(st, o.st) && eq(off, o.off) && eq(spans, o.spans) && eq(cap_off, o.cap_off) &&
+               eq(cap_str_off, o.cap_str_off) && eq(ospans, o.ospans) && eq(sigs, o.sigs) && eq(kinfos, o.kinfos) && eq(binfos, o.binfos) && eq(blob, o.blob) &&
+               eq(keys, o.keys) && eq(bytes, o.bytes) && eq(flags, o.flags) && eq(cblob, o.cblob) && eq(oflags, o.oflags) &&
+               scan.sigs_need == o.scan.sigs_need && scan.sel_blob_need == o.scan.sel_blob_need && scan.n_sigs == o.scan.n_sigs && keyrec.keys_need == o.keyrec.keys_need &&
+               body.bytes_need == o.body.bytes_need && caps.cap_blob_need == o.caps.cap_blob_need && caps.n_strings == o.caps.n_strings;
+      }
+    };
+    enum : uint32_t { REC = 1, SEL = 2, SCAN = 4, KEYREC = 8, BODY = 16, CAPS = 32 };
+    for (int it = 0; it < 60; it++) {
+      // what the device left behind, in the pinned twins' layouts
+      const std::vector<uint32_t> sel_off{0, 2, 2, 5};                                 // 5 (e-mail, candidate) pairs; their records are also "the records"
+      const uint32_t m = sel_off[n];
+      std::vector<zke_result> R(m);
+      for (auto& x : R) { uint8_t* q = reinterpret_cast<uint8_t*>(&x); for (size_t k = 0; k < sizeof x; k++) q[k] = (uint8_t)rng(); x.status = rng() % 2 ? ZKE_OK : ZKE_DKIM_NOT_PASS; }
+      std::vector<uint32_t> st(4 * n);
+      size_t total_sigs = 0;
+      for (uint32_t i = 0; i < n; i++) { st[4 * i] = 0; st[4 * i + 1] = (uint32_t)rng(); st[4 * i + 2] = 1 + (uint32_t)(rng() % 3); st[4 * i + 3] = 1; total_sigs += std::min(st[4 * i + 2], max_sigs); }
+      const uint32_t sel_used = 1 + (uint32_t)(rng() % 40);
+      std::vector<uint32_t> rec_off(m + 1, 0), key_len(m);
+      size_t total_keys = 0;
+      for (uint32_t i = 0; i < m; i++) { rec_off[i + 1] = rec_off[i] + 8 + (uint32_t)(rng() % 300); key_len[i] = 1 + (uint32_t)(rng() % (rec_off[i + 1] - rec_off[i])); total_keys += key_len[i]; }
+      std::vector<uint32_t> raw_off(n + 1, 0), body_len(n);
+      size_t total_body = 0;
+      for (uint32_t i = 0; i < n; i++) { raw_off[i + 1] = raw_off[i] + 4 + (uint32_t)(rng() % 500); body_len[i] = 1 + (uint32_t)(rng() % (raw_off[i + 1] - raw_off[i])); total_body += body_len[i]; }      // none outgrows its place
+      std::vector<uint8_t> scan_twin, keyrec_twin, body_twin, cap_twin;
+      Slot w;
+      zke_engine eng;
+      auto stage = [&](const Caps& c, size_t cap_bytes) {                              // cap_bytes: the capture strings' bytes (0: an empty blob)
+        auto noise = [&](std::vector<uint8_t>& v, size_t bytes) { v.resize(bytes); for (auto& x : v) x = (uint8_t)rng(); };
+        w.h_results.p = R.data(); w.h_results.cap = R.size() * sizeof(zke_result);
+        w.sb.L = scan_layout(n, max_sigs, std::min<size_t>(c.sel_blob, (size_t)n * max_sigs * ZKE_MAX_TAGBUF));
+        noise(scan_twin, w.sb.L.total);
+        memcpy(scan_twin.data(), &sel_used, 4);
+        memcpy(scan_twin.data() + w.sb.L.status, st.data(), st.size() * 4);
+        w.sb.t.h.p = scan_twin.data(); w.sb.t.h.cap = scan_twin.size();
+        w.kb.L = keyrec_layout(m, rec_off[m]);
+        noise(keyrec_twin, w.kb.L.total);
+        for (uint32_t i = 0; i < m; i++) reinterpret_cast<zke_key_info*>(keyrec_twin.data())[i] = zke_key_info{0, ZKE_KEY_RSA, rec_off[i], key_len[i]};
+        w.kb.t.h.p = keyrec_twin.data(); w.kb.t.h.cap = keyrec_twin.size();
+        w.bb.L = body_layout(n, raw_off[n]);
+        noise(body_twin, w.bb.L.first_copy);                                           // the second places are not there: nothing may read them
+        for (uint32_t i = 0; i < n; i++)
+          reinterpret_cast<zke_body_info*>(body_twin.data())[i] = zke_body_info{ZKE_OK, 0, 1, 0, 0, body_len[i], body_len[i], raw_off[i + 1] - raw_off[i], (uint64_t)raw_off[i]};
+        w.bb.t.h.p = body_twin.data(); w.bb.t.h.cap = body_twin.size();
+        w.cb.L = cap_layout(n, P, G, c.cap_blob);
+        noise(cap_twin, w.cb.L.fixed_end);                                             // the twin ends in front of the blob
+        const uint64_t hdr[2] = {NG, cap_bytes};
+        memcpy(cap_twin.data() + w.cb.L.hdr, hdr, sizeof hdr);
+        w.cb.t.h.p = cap_twin.data(); w.cb.t.h.cap = cap_twin.size();
+        w.ob.L = origin_layout(n, G); w.ob.launched = false;                           // no body part asks for a group: the origins are the spans
+      };
+      auto owed = [&](uint32_t kinds, Caller& c) {
+        PendingDelivery p;
+        if (kinds & REC) { p.records = c.rec.data(); p.n = m; }
+        if (kinds & SEL) { p.sel_off = sel_off; p.sel_out = c.sel.data(); p.sel_chosen = c.chosen.data(); }
+        if (kinds & SCAN) p.scan = &c.scan;
+        if (kinds & KEYREC) p.keyrec = &c.keyrec;
+        if (kinds & BODY) p.body = &c.body;
+        if (kinds & CAPS) { p.caps = &c.caps; p.org = &c.org; }
+        return p;
+      };
+      // the calls deliver_pending stands for, in its order; a shortfall in *rc, anything else returned
+      auto one_by_one = [&](uint32_t kinds, Caller& c, int* rc) {
+        if (kinds & REC) memcpy(c.rec.data(), R.data(), m * sizeof(zke_result));
+        if (kinds & SEL) fold_selection(R.data(), sel_off, c.sel.data(), c.chosen.data());
+        int r = 0;
+        if ((kinds & SCAN) && (r = deliver_scan(&eng, w.sb, &c.scan))) { if (r != ZKE_E_NOMEM) return r; *rc = r; }
+        if ((kinds & KEYREC) && (r = deliver_keyrec(&eng, w.kb, &c.keyrec))) { if (r != ZKE_E_NOMEM) return r; *rc = r; }
+        if ((kinds & BODY) && (r = deliver_body(&eng, w.bb, &c.body, nullptr))) { if (r != ZKE_E_NOMEM) return r; *rc = r; }
+        if ((kinds & CAPS) && (r = deliver_captures(&eng, w.cb, &c.caps, nullptr))) { if (r != ZKE_E_NOMEM) return r; *rc = r; }
+        if (kinds & CAPS) deliver_origins(w.cb, w.ob, &c.org);
+        return 0;
+      };
+      auto needs_exact = [&](uint32_t kinds, const Caller& c, size_t cap_bytes) {
+        return (!(kinds & SCAN) || (c.scan.sigs_need == total_sigs && c.scan.sel_blob_need == sel_used && c.st == st && c.off[n] == total_sigs)) &&
+               (!(kinds & KEYREC) || (c.keyrec.keys_need == total_keys && c.kinfos[m - 1].key_off + c.kinfos[m - 1].key_len == total_keys)) &&
+               (!(kinds & BODY) || (c.body.bytes_need == total_body && c.binfos[n - 1].body_off + c.binfos[n - 1].body_len == total_body)) &&
+               (!(kinds & CAPS) || (c.caps.cap_blob_need == cap_bytes && c.caps.n_strings == NG && !memcmp(c.spans.data(), cap_twin.data() + w.cb.L.spans, NG * 8) &&
+                                    c.ospans == c.spans && c.oflags == std::vector<uint8_t>(NG, 0)));
+      };
+      const Caps exact{total_sigs, sel_used, total_keys, total_body, 0};
+      // records only; a selection; a scan; a lone key-record decode; a selection with key records; a body extraction that did not spill;
+      // captures with an empty blob, origins not launched (an extraction's records come as they are)
+      for (uint32_t kinds : {(uint32_t)REC, (uint32_t)SEL, (uint32_t)SCAN, (uint32_t)KEYREC, SEL | KEYREC, (uint32_t)BODY, REC | CAPS}) {
+        stage(exact, 0);
+        Caller a(exact, m), b(exact, m);
+        int rc_a = 0, rc_b = 0;
+        const int ra = deliver_pending(&eng, w, owed(kinds, a), &rc_a), rb = one_by_one(kinds, b, &rc_b);
+        if (ra || rb || rc_a || rc_b || !a.same(b) || !needs_exact(kinds, a, 0)) { fprintf(stderr, "deliver_pending: kinds %u: %d/%d, cap_rc %d/%d, or the outputs differ\n", kinds, ra, rb, rc_a, rc_b); return 1; }
+        cases++;
+      }
+      // one byte too small: sigs, sel_blob, keys, bytes, cap_blob (one string byte, no capacity: nothing is left to fetch from HBM)
+      struct Short { uint32_t kinds; Caps caps; size_t cap_bytes; };
+      const Short shorts[] = {{SCAN, {total_sigs - 1, sel_used, total_keys, total_body, 0}, 0}, {SCAN, {total_sigs, sel_used - 1u, total_keys, total_body, 0}, 0},
+                              {KEYREC, {total_sigs, sel_used, total_keys - 1, total_body, 0}, 0}, {SEL | KEYREC, {total_sigs, sel_used, total_keys - 1, total_body, 0}, 0},
+                              {BODY, {total_sigs, sel_used, total_keys, total_body - 1, 0}, 0}, {REC | CAPS, exact, 1}};
+      for (const Short& sh : shorts)
+        for (int told = 0; told < 2; told++) {
+          stage(sh.caps, sh.cap_bytes);
+          Caller a(sh.caps, m), b(sh.caps, m);
+          int rc_a = 0, rc_b = 0;
+          g_err = "sentinel";
+          const int ra = deliver_pending(&eng, w, owed(sh.kinds, a), told ? &rc_a : nullptr);
+          const bool err_ok = told ? g_err != "sentinel" : g_err == "sentinel";
+          const int rb = one_by_one(sh.kinds, b, &rc_b);
+          if (ra || rb || rc_b != ZKE_E_NOMEM || rc_a != (told ? ZKE_E_NOMEM : 0) || !err_ok || !a.same(b) || !needs_exact(sh.kinds, a, sh.cap_bytes)) {
+            fprintf(stderr, "deliver_pending: kinds %u one byte short, %s: %d/%d, cap_rc %d/%d, last error '%s', or the outputs differ\n", sh.kinds,
+                    told ? "with cap_rc" : "nobody to tell", ra, rb, rc_a, rc_b, g_err.c_str());
+            return 1;
+          }
+          cases++;
+        }
+      w.h_results = PinnedBuf{}; w.sb.t.h = PinnedBuf{}; w.kb.t.h = PinnedBuf{}; w.bb.t.h = PinnedBuf{}; w.cb.t.h = PinnedBuf{};      // (the vectors own the memory)
+    }
   }
   // ---- small pure functions on edge sizes
   {

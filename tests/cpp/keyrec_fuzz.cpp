@@ -74,7 +74,7 @@ int main() {
     b.L = keyrec_layout(m, rec_off[m]);
     std::vector<uint8_t> twin(b.L.total);                 // stands for the pinned twin: exact size
     for (auto& x : twin) x = (uint8_t)rng();
-    b.h_out.p = twin.data(); b.h_out.cap = twin.size();
+    b.t.h.p = twin.data(); b.t.h.cap = twin.size();
     zke_key_info* dev = reinterpret_cast<zke_key_info*>(twin.data());
     std::vector<std::vector<uint8_t>> want(m);
     size_t total = 0;
@@ -101,7 +101,7 @@ int main() {
       }
       cases++;
     }
-    b.h_out.p = nullptr; b.h_out.cap = 0;
+    b.t.h.p = nullptr; b.t.h.cap = 0;
   }
   printf("keyrec_fuzz ok: %zu cases\n", cases);
   return 0;

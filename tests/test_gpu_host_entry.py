@@ -2,6 +2,7 @@
 asynchronous form through several submission slots, re-entrancy from many host threads on ONE engine (SURVEY §8(b) Threading:
 the reference's functions are re-entrant), slot timings, and the error path's slot hygiene."""
 import ctypes as C
+import os
 import threading
 
 import numpy as np
@@ -9,8 +10,11 @@ import pytest
 
 from zkemail_rs_amd import _abi as A
 
+import body_cases
+import body_model
 import cases
 import synth
+import test_gpu_qp_map as QM
 from test_gpu_verify import assert_records_equal
 
 pytestmark = pytest.mark.gpu
@@ -348,10 +352,11 @@ def test_engine_lifecycle_returns_its_memory(oracle):
 
 
 def test_unwaited_batches_with_short_buffers_are_retired_by_the_next_batch():
-    """One slot; a scan, a key-record decode and an extraction are submitted asynchronously, each with its variable-size buffer too
-    small (sel_blob, keys, cap_blob of capacity 0), and never waited for.  The slot's next batch retires each: that batch is not
-    disturbed (it returns 0, its record is right), the unwaited batch's fixed-size outputs are there with the exact *_need, and
-    the shortfall — which had nobody to be told to — does not come back from a later wait on the old ticket."""
+    """One slot; a scan, a key-record decode, an extraction and a body extraction are submitted asynchronously, each with its
+    variable-size buffer too small (sel_blob, keys, cap_blob, bytes of capacity 0), and never waited for.  The slot's next batch
+    retires each: that batch is not disturbed (it returns 0, its record is right), the unwaited batch's fixed-size outputs are there
+    with the exact *_need, and the shortfall — which had nobody to be told to — does not come back from a later wait on the old
+    ticket.  A mapped extraction's origins arrive the same way, with the batch that retires it."""
     import base64
     import re
     import zkemail_rs_amd as z
@@ -401,5 +406,99 @@ def test_unwaited_batches_with_short_buffers_are_retired_by_the_next_batch():
         assert (int(o.n_strings), int(o.cap_blob_need)) == (1, len(subject[0]))
         assert [int(x) for x in cap_off] == [0, 1] and [int(x) for x in cap_str_off] == [0, len(subject[0])] and int(flags[0]) == 0
         assert int(spans[1]) - int(spans[0]) == len(subject[0])
+        # a body extraction whose byte buffer holds nothing: the info and the exact need, by the model
+        kind, want = body_model.verdict(c.email.raw_email, False)
+        assert kind == "ok" and len(want.data) > 0
+        tb, bb = eng.extract_bodies_async([c.email.raw_email], body_bytes=0)
+        next_batch_retires(tb)
+        assert (int(bb.c.infos_need), int(bb.c.bytes_need)) == (1, len(want.data))
+        assert [int(bb.infos[0][f]) for f in ("status", "detail", "part", "encoding", "src_off", "src_len", "body_len", "reserved", "body_off")] == \
+            [A.ZKE_OK, 0, want.part, want.encoding, want.src_off, want.src_len, len(want.data), 0, 0]
+        # a mapped extraction (a header part and a body part: the origin launch runs) nobody waits for: spans, strings AND origins are
+        # there once the next batch has retired it, and they are what the synchronous entry delivers
+        parts = QM.parts_of(eng, [synth.HEADER_PATTERNS[1], _body_word_pattern(c)])
+        st = QM.run_extract(eng, [c.email], parts, 1, mapped=True, asynchronous=True)
+        next_batch_retires(st["ticket"].value)
+        ref = QM.run_extract(eng, [c.email], parts, 1, mapped=True)
+        assert int(ref["out"][0]["status"]) == A.ZKE_OK and (ref["spans"] != QM.NO).all()
+        assert QM.delivered(st) == QM.delivered(ref)
+        assert st["ospans"].tolist() == ref["ospans"].tolist() and st["oflags"].tolist() == ref["oflags"].tolist() == [0, 0]
     finally:
         eng.close()
+
+
+def _body_word_pattern(c):
+    """A body pattern that matches exactly once in a case's e-mail: the first word of the body's last line, the word behind it as group 1."""
+    import re
+    body = c.email.raw_email.split(b"\r\n\r\n", 1)[1]
+    m = re.search(rb"\r\n([A-Za-z0-9]{4,}) ([A-Za-z0-9]+)[^\r\n]*\r\n$", body)
+    assert m and body.count(m.group(1)) == 1, body[-200:]
+    return (m.group(1).decode() + " ([A-Za-z0-9]+)", [1])
+
+
+def test_every_side_output_in_turn_on_one_slot():
+    """Every kind of pending delivery through ONE slot, one after the other, none waited for: a scan, a lone key-record decode, a body
+    extraction, a selection from records, a mapped extraction, a plain verify — each retired by the submission behind it, the last by
+    its wait.  Every output equals what the synchronous entry returns for the same call on a fresh engine, and waiting on the old
+    tickets afterwards returns 0.  Then the same sequence through two slots, waited for in reverse order.  Three signed e-mails of
+    the case list; behind them two unsigned ones for the body extraction: the golden qp_lone_lf_lines.eml, and the case whose body
+    outgrows its e-mail, so that a second place is in use."""
+    import base64
+    import zkemail_rs_amd as z
+    good = [x for x in cases.build_cases() if x.status == A.ZKE_OK and x.email.public_key.key_type == "rsa"][:3]
+    assert len(good) == 3
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "body_cases", "qp_lone_lf_lines.eml"), "rb") as f:
+        lone_lf = f.read()
+    outgrows = dict(body_cases.all_cases())["qp_lf_lines_outgrow_the_email"]
+    emails = [x.email for x in good] + [A.Email("example.com", raw, good[0].email.public_key) for raw in (lone_lf, outgrows)]
+    raws, doms = [e.raw_email for e in emails], [e.from_domain for e in emails]
+    record = lambda e: b"v=DKIM1; k=rsa; p=" + base64.b64encode(e.public_key.key)
+    records = [record(e) for e in emails[:3]] + [b"v=DKIM1; p=", None]
+    cand = [[b"v=DKIM1; k=rsa; p=AAAA", record(emails[0])], [record(emails[1])], [], [record(emails[0])], [None, record(emails[2])]]
+    patterns = [synth.HEADER_PATTERNS[1], _body_word_pattern(good[0])]
+
+    def submit_all(eng, parts):
+        """The six submissions in turn; returns (tickets, a function that reads every output once they have been delivered)."""
+        t1, scan = eng.scan_signatures_async(raws, doms, 8)
+        t2, keyrec = eng.decode_key_records_async(records)
+        t3, bodies = eng.extract_bodies_async(raws)
+        t4, sel_out, sel_chosen, sel_keys = eng.select_keys_from_records_async(emails, cand)
+        ext = QM.run_extract(eng, emails, parts, 1, mapped=True, asynchronous=True)
+        refs = A.EmailRefs(emails)
+        t6, recs = eng.verify_emails_async(refs)
+
+        def outputs():
+            return dict(scan=scan.result(), keyrec=keyrec.result(), bodies=bodies.result(), sel_out=sel_out, sel_chosen=sel_chosen.tolist(),
+                        sel_keys=sel_keys.result(), ext=QM.delivered(ext), ospans=ext["ospans"].tolist(), oflags=ext["oflags"].tolist(), recs=recs, keep=refs)
+        return [t1, t2, t3, t4, ext["ticket"].value, t6], outputs
+
+    fresh = z.Engine()
+    try:
+        parts = QM.parts_of(fresh, patterns)
+        sel = fresh.select_keys_from_records(emails, cand)
+        ext = QM.run_extract(fresh, emails, parts, 1, mapped=True)
+        want = dict(scan=fresh.scan_signatures(raws, doms, 8), keyrec=fresh.decode_key_records(records), bodies=fresh.extract_bodies(raws),
+                    sel_out=sel[0], sel_chosen=sel[1].tolist(), sel_keys=sel[2], ext=QM.delivered(ext), ospans=ext["ospans"].tolist(),
+                    oflags=ext["oflags"].tolist(), recs=fresh.verify_emails(emails))
+    finally:
+        fresh.close()
+    # the inputs do what they are there for: signatures found, keys decoded, a body in its second place, a selection made, strings captured
+    assert [len(x.sigs) for x in want["scan"]] == [1, 1, 1, 0, 0] and [k.code for k in want["keyrec"][:3]] == [0, 0, 0]
+    assert [want["bodies"][k].body for k in (3, 4)] == [body_model.verdict(raws[k], False)[1].data for k in (3, 4)]
+    assert want["bodies"][3].body.startswith(b"a\r\nb\r\n\r\nc") and len(want["bodies"][4].body) > len(outgrows)
+    assert want["sel_chosen"][:3] == [1, 0, A.SEL_NONE] and [int(x) for x in want["recs"]["status"][:3]] == [A.ZKE_OK] * 3
+    assert int(ext["out"][0]["status"]) == A.ZKE_OK and (ext["spans"][:4] != QM.NO).all()
+
+    for slots, reverse in ((1, False), (2, True)):
+        eng = z.Engine(slots=slots)
+        try:
+            tickets, outputs = submit_all(eng, QM.parts_of(eng, patterns))
+            for t in (reversed(tickets) if reverse else tickets):
+                assert eng.lib.zke_batch_wait(eng.h, t) == 0, (slots, t)
+            got = outputs()
+            for k in ("scan", "keyrec", "bodies", "sel_chosen", "sel_keys", "ext", "ospans", "oflags"):
+                assert got[k] == want[k], (slots, k)
+            assert_records_equal(got["sel_out"], want["sel_out"], None, f"selection, {slots} slot(s)")
+            assert_records_equal(got["recs"], want["recs"], None, f"verify, {slots} slot(s)")
+        finally:
+            eng.close()

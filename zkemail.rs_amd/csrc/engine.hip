@@ -56,6 +56,7 @@ struct DevBuf {
     return 0;
   }
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+  void track(uint64_t* counter) { generation = counter; }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
@@ -83,48 +84,33 @@ struct Slot {
   hipEvent_t ev[MK_N]{};               // timing marks
   uint32_t marks = 0;                  // bit k: ev[k] was recorded for the slot's last timed batch
   zke_timings last{};                  // ... and what they said, once read
-  DevBuf meta, rsa_jobs, sha_jobs, sha_order, rsa_ok, em_dbg, scratch_off, scratch, clean, meta2, scratch2, parts;
-  DevBuf pending;  // device counters: e-mails that need another signature round, the wave-routine job list's length
-  uint32_t* wave_feedback = nullptr;   // pinned host word the verdict launch leaves that length in: the slot's next batch sizes the
+  // Every buffer the slot owns is declared by this list, so the walk over them (each_buffer: release, generation tracking) cannot
+  // miss one.  The workspace of the device pipeline (`pending`: device counters — e-mails that need another signature round, the
+  // wave-routine job list's length); the host entry's packed input image and records, pinned and in HBM; and the buffers of the
+  // side outputs, each a device buffer with its pinned twin, its extra device buffers and its layout (host_stage.hip.h):
+  // cb capture extraction, sb signature scan, kb key records, ob origins of a mapped extraction, bb body extraction; qb: zke_qp_clean_batch.
+#define ZKE_SLOT_BUFFERS(X)                                                                                                           \
+  X(DevBuf, meta) X(DevBuf, rsa_jobs) X(DevBuf, sha_jobs) X(DevBuf, sha_order) X(DevBuf, rsa_ok) X(DevBuf, em_dbg)                    \
+  X(DevBuf, scratch_off) X(DevBuf, scratch) X(DevBuf, clean) X(DevBuf, meta2) X(DevBuf, scratch2) X(DevBuf, parts) X(DevBuf, pending) \
+  X(PinnedBuf, h_image) X(PinnedBuf, h_results) X(DevBuf, d_image) X(DevBuf, d_results)                                               \
+  X(CapBufs, cb) X(ScanBufs, sb) X(KeyrecBufs, kb) X(OriginBufs, ob) X(QpBufs, qb) X(BodyBufs, bb)
+#define X(type, name) type name;
+  ZKE_SLOT_BUFFERS(X)
+#undef X
+  template <class F> void each_buffer(F f) {      // f(DevBuf&) and f(PinnedBuf&), once per buffer
+#define X(type, name) ::each_buffer(name, f);
+    ZKE_SLOT_BUFFERS(X)
+#undef X
+  }
+  uint32_t* wave_feedback = nullptr;   // pinned host word the verdict launch leaves the job list's length in: the slot's next batch sizes the
                                        // one-signature-per-wave role of its hash / modexp launch by it (0xFFFFFFFF: nothing known yet)
-  // host entry: the packed input image (pinned + HBM), the records (HBM + pinned), the batch not yet delivered
-  PinnedBuf h_image, h_results;
-  DevBuf d_image, d_results;
+  // host entry: the batch not yet delivered
   hipEvent_t host_done = nullptr;      // recorded behind the D2H of the records
   hipEvent_t h2d_done = nullptr;       // recorded behind the slot's input image on the engine's copy stream
   std::vector<CopyPool::Piece> gather; // zke_verify_emails: the 3 n pieces of the batch being packed (kept: no allocation per call)
   uint64_t host_gen = 0;               // host batches submitted to this slot
-  uint64_t host_retired = 0;           // ... of which this many have been delivered to their caller's `out`
-  zke_result* host_out = nullptr;      // where the pending batch's records go
-  uint32_t host_n = 0;
-  // capture extraction (zke_extract_captures): spans, flags, codes and the three tables in one buffer (CapLayout), the rows of
-  // programs too large for LDS, the pinned twin of everything but the blob, and where the pending batch's extraction goes
-  CapBufs cb;
-  zke_capture_out* cap_out = nullptr;
-  // signature scan (zke_scan_signatures): statuses, record slots and selector blob in one buffer (ScanLayout) with its pinned
-  // twin, the header-span overflow area, and where the pending batch's scan goes
-  ScanBufs sb;
-  zke_sig_scan* scan_out = nullptr;
-  // key selection (zke_select_keys): the pending batch's records are folded per e-mail on delivery
-  std::vector<uint32_t> sel_off;       // cand_off of the pending selection (n + 1 entries; empty: the pending batch is no selection)
-  zke_result* sel_out = nullptr;
-  uint32_t* sel_chosen = nullptr;
-  // key records (zke_decode_key_records, zke_select_keys_from_records): infos and decoded keys in one buffer (KeyrecLayout) with its
-  // pinned twin, the packed key section the front end reads, and where the pending batch's infos and keys go
-  KeyrecBufs kb;
-  zke_keyrec_out* keyrec_out = nullptr;
-  // mapped extraction (zke_extract_captures_mapped): the origins of the pending batch's spans, in a buffer of their own with its pinned
-  // twin, and where they go; zke_qp_clean_batch: the bodies, cleaned bytes, index maps and kept lengths of the call
-  OriginBufs ob;
-  zke_capture_origin* org_out = nullptr;
-  QpBufs qb;
-  // body extraction (zke_extract_bodies): infos and decoded bytes in one buffer (BodyLayout) with its pinned twin, the header-span
-  // overflow area, and where the pending batch's infos and bytes go
-  BodyBufs bb;
-  zke_body_out* body_out = nullptr;
-  DevBuf* all[29] = {&meta, &rsa_jobs, &sha_jobs, &sha_order, &rsa_ok, &em_dbg, &scratch_off, &scratch, &clean, &meta2, &scratch2, &parts,
-                     &pending, &d_image, &d_results, &cb.cap, &cb.work, &sb.out, &sb.ovf, &kb.out, &kb.pack,
-                     &ob.org, &qb.in, &qb.off, &qb.clean, &qb.map, &qb.len, &bb.out, &bb.ovf};
+  uint64_t host_retired = 0;           // ... of which this many have been delivered to their caller's buffers
+  PendingDelivery owed;                // where the pending batch's outputs go (host_gen > host_retired; else nothing)
   // hipGraph replay of a batch's kernel sequence (zke_options.replay_graphs).  The graph holds this slot's
   // workspace pointers, so it is valid only while none of them has been reallocated: `generation` counts reallocations.
   hipGraphExec_t graph_exec = nullptr;
@@ -253,14 +239,13 @@ Slot* new_slot(zke_engine* e) {
   ok = ok && hipHostMalloc((void**)&w->wave_feedback, 64, hipHostMallocMapped) == hipSuccess;
   if (ok) *w->wave_feedback = 0xFFFFFFFFu;
   if (!ok) { g_err = "slot stream / event creation"; delete w; return nullptr; }
-  for (auto* b : w->all) b->generation = &w->generation;
+  w->each_buffer([w](auto& b) { b.track(&w->generation); });      // a reallocation of any device buffer invalidates the slot's captured graph
   return w;
 }
 void free_slot(Slot* w) {
   if (!w) return;
   if (w->graph_exec) (void)hipGraphExecDestroy(w->graph_exec);
-  for (auto* b : w->all) b->release();
-  w->h_image.release(); w->h_results.release(); w->cb.h_cap.release(); w->sb.h_out.release(); w->kb.h_out.release(); w->ob.h_org.release(); w->bb.h_out.release();
+  w->each_buffer([](auto& b) { b.release(); });
   for (auto& ev : w->ev) if (ev) (void)hipEventDestroy(ev);
   if (w->done) (void)hipEventDestroy(w->done);
   if (w->host_done) (void)hipEventDestroy(w->host_done);
@@ -680,12 +665,9 @@ int zke_sha256_batch(zke_engine* e, const uint8_t* blob, const uint64_t* off, ui
   std::lock_guard<std::mutex> g(e->misc_mu);
   HIPCHK(e, hipSetDevice(e->device));
   const size_t total = (size_t)off[n];
-  DevBuf dblob, doff, ddig;
+  Scoped<DevBuf> dblob, doff, ddig;
   int r = 0;
-  if ((r = dblob.ensure(total + 16)) || (r = doff.ensure((size_t)(n + 1) * 8)) || (r = ddig.ensure((size_t)n * 32))) {
-    dblob.release(); doff.release(); ddig.release();
-    return fail(e, r, "hipMalloc");
-  }
+  if ((r = dblob.ensure(total + 16)) || (r = doff.ensure((size_t)(n + 1) * 8)) || (r = ddig.ensure((size_t)n * 32))) return fail(e, r, "hipMalloc");
   hipError_t he = hipSuccess;
   if (total) he = hipMemcpyAsync(dblob.p, blob, total, hipMemcpyHostToDevice, e->stream);
   if (he == hipSuccess) he = hipMemcpyAsync(doff.p, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, e->stream);
@@ -694,7 +676,6 @@ int zke_sha256_batch(zke_engine* e, const uint8_t* blob, const uint64_t* off, ui
     if (r == 0) he = hipMemcpyAsync(digests, ddig.p, (size_t)n * 32, hipMemcpyDeviceToHost, e->stream);
   }
   hipError_t hs = hipStreamSynchronize(e->stream);
-  dblob.release(); doff.release(); ddig.release();
   if (r) return r;
   if (he != hipSuccess) return fail(e, ZKE_E_DEVICE, "sha256 batch copy", he);
   if (hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "sha256 batch sync", hs);
@@ -727,13 +708,11 @@ int zke_rsa_modexp_batch(zke_engine* e, const uint8_t* sig, const uint8_t* mod, 
     j.flags = RSA_F_ACTIVE;
     ok[i] = (uint8_t)((m[bytes - 1] & 1) && bits >= 2 && memcmp(s, m, bytes) < 0);
   }
-  DevBuf dj, dok, dem, dh;
+  Scoped<DevBuf> dj, dok, dem, dh;
   int r = 0;
   if ((r = dj.ensure(jobs.size() * sizeof(RsaJob))) || (r = dok.ensure((size_t)n * 4)) || (r = dem.ensure((size_t)n * 512)) ||
-      (r = dh.ensure((size_t)n * 32))) {
-    dj.release(); dok.release(); dem.release(); dh.release();
+      (r = dh.ensure((size_t)n * 32)))
     return fail(e, r, "hipMalloc");
-  }
   hipError_t he = hipMemcpyAsync(dj.p, jobs.data(), jobs.size() * sizeof(RsaJob), hipMemcpyHostToDevice, e->stream);
   if (he == hipSuccess) he = hipMemsetAsync(dh.p, 0, (size_t)n * 32, e->stream);
   if (he == hipSuccess) he = hipMemsetAsync(dem.p, 0, (size_t)n * 512, e->stream);
@@ -745,7 +724,6 @@ int zke_rsa_modexp_batch(zke_engine* e, const uint8_t* sig, const uint8_t* mod, 
   std::vector<uint8_t> emh((size_t)n * 512);
   if (he == hipSuccess && r == 0) he = hipMemcpyAsync(emh.data(), dem.p, emh.size(), hipMemcpyDeviceToHost, e->stream);
   hipError_t hs = hipStreamSynchronize(e->stream);
-  dj.release(); dok.release(); dem.release(); dh.release();
   if (r) return r;
   if (he != hipSuccess) return fail(e, ZKE_E_DEVICE, "rsa batch", he);
   if (hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "rsa batch sync", hs);
@@ -762,12 +740,10 @@ int zke_ed25519_verify_batch(zke_engine* e, const uint8_t* keys, const uint8_t* 
   std::shared_lock<std::shared_mutex> sh(e->big);
   std::lock_guard<std::mutex> g(e->misc_mu);
   HIPCHK(e, hipSetDevice(e->device));
-  DevBuf dk, dm, ds, dout;
+  Scoped<DevBuf> dk, dm, ds, dout;
   int r = 0;
-  if ((r = dk.ensure((size_t)n * 32)) || (r = dm.ensure((size_t)n * msg_len)) || (r = ds.ensure((size_t)n * 64)) || (r = dout.ensure((size_t)n * 4))) {
-    dk.release(); dm.release(); ds.release(); dout.release();
+  if ((r = dk.ensure((size_t)n * 32)) || (r = dm.ensure((size_t)n * msg_len)) || (r = ds.ensure((size_t)n * 64)) || (r = dout.ensure((size_t)n * 4)))
     return fail(e, r, "ed25519 batch allocation");
-  }
   hipError_t he = hipMemcpyAsync(dk.p, keys, (size_t)n * 32, hipMemcpyHostToDevice, e->stream);
   if (he == hipSuccess) he = hipMemcpyAsync(dm.p, msgs, (size_t)n * msg_len, hipMemcpyHostToDevice, e->stream);
   if (he == hipSuccess) he = hipMemcpyAsync(ds.p, sigs, (size_t)n * 64, hipMemcpyHostToDevice, e->stream);
@@ -778,76 +754,9 @@ int zke_ed25519_verify_batch(zke_engine* e, const uint8_t* keys, const uint8_t* 
   }
   if (he == hipSuccess) he = hipMemcpyAsync(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream);
   hipError_t hs = hipStreamSynchronize(e->stream);
-  dk.release(); dm.release(); ds.release(); dout.release();
   if (he != hipSuccess) return fail(e, ZKE_E_DEVICE, "ed25519 batch", he);
   if (hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "ed25519 batch sync", hs);
   return 0;
-}
-
-// ---- capture extraction over haystacks of the caller's (registry.hip.h; checks and delivery: host_entry.hip.h)
-int zke_capture_batch(zke_engine* e, uint32_t dfa_id, uint32_t prog_id, const uint32_t* groups, uint32_t n_groups,
-                      const uint8_t* hay_blob, const uint64_t* hay_off, uint32_t n, uint32_t* matches, zke_capture_out* caps) {
-  static const char who[] = "zke_capture_batch";
-  if (!e) return ZKE_E_ARG;
-  if (!caps || (n && (!hay_off || !matches)) || (n && hay_off[n] > hay_off[0] && !hay_blob)) return arg_error(who, "null pointer");
-  if (n && (!rising(hay_off, n) || hay_off[n] - hay_off[0] > (1ull << 32))) return arg_error(who, "offset array is not non-decreasing, or the haystacks exceed 4 GiB");
-  for (uint32_t i = 0; i < n; i++) if (hay_off[i + 1] - hay_off[i] >= (1ull << 31)) return arg_error(who, "haystack of 2 GiB or more");
-  CaptureReq q;
-  q.P = 1; q.n_header_parts = 1; q.out = caps;
-  if (int r = capture_part_shape(q, 0, prog_id, groups, n_groups, who)) return r;
-  if (int r = check_capture_out(caps, n, 1, q.G, who)) return r;
-  if (n == 0) return 0;
-  std::shared_lock<std::shared_mutex> sh(e->big);      // from the registry lookups to the last launch: no table is freed meanwhile
-  std::lock_guard<std::mutex> g(e->misc_mu);
-  HIPCHK(e, hipSetDevice(e->device));
-  capture_resolve(e, q);
-  PartInfo pi{};
-  {
-    std::shared_lock<std::shared_mutex> rl(e->reg_mu);
-    const RegisteredDfa* rd = dfa_id < e->dfas.size() ? e->dfas[dfa_id] : nullptr;
-    if (rd) { pi.detail = rd->detail; pi.dev = rd->valid ? rd->dev.as<RegexDev>() : nullptr; }
-  }
-  // the building blocks run in buffers of their own on slot 0's stream
-  const uint64_t base0 = hay_off[0], total = hay_off[n] - base0;
-  CapBufs tmp;
-  DevBuf dhay, doff, dparts;
-  std::vector<uint8_t> fixed;
-  int r = 0;
-  hipError_t he = hipSuccess;
-  tmp.L = cap_layout(n, 1, q.G, caps->cap_blob_cap);
-  const CapLayout& L = tmp.L;
-  hipStream_t s = e->stream;
-  auto done = [&](int rc) { dhay.release(); doff.release(); dparts.release(); tmp.release(); return rc; };
-  if ((r = dhay.ensure((size_t)total + 64)) || (r = doff.ensure((size_t)(n + 1) * 8)) || (r = dparts.ensure((size_t)n * sizeof(PartRes))) ||
-      (r = ensure_capture_buffers(e, tmp, n, 1, q.G, caps->cap_blob_cap, q.needs_work)))
-    return done(fail(e, r, "zke_capture_batch: allocation"));
-  std::vector<uint64_t> rel(n + 1);
-  for (uint32_t i = 0; i <= n; i++) rel[i] = hay_off[i] - base0;
-  if (total) he = hipMemcpyAsync(dhay.p, hay_blob + base0, (size_t)total, hipMemcpyHostToDevice, s);
-  if (he == hipSuccess) he = hipMemsetAsync(dhay.as<uint8_t>() + total, 0, 64, s);         // the DFA walk loads 16 bytes at a time
-  if (he == hipSuccess) he = hipMemcpyAsync(doff.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s);
-  if (he != hipSuccess) { (void)hipStreamSynchronize(s); return done(fail(e, ZKE_E_DEVICE, "zke_capture_batch: copy", he)); }
-  CapFindArgs fa{};
-  fa.d.re = pi.dev; fa.d.P = 1; fa.d.out = dparts.as<PartRes>(); fa.d.idle = 0xFFFFFFFFu; fa.d.decode_detail = pi.detail;
-  fa.hay_blob = dhay.as<uint8_t>(); fa.hay_off = doff.as<uint64_t>(); fa.n = n;
-  hipLaunchKernelGGL(capture_find_kernel, dim3((n + 255) / 256), dim3(256), 1024, s, fa);
-  r = launch_capture(e, tmp, q, n, true, DfaArgs{}, fa.hay_blob, fa.hay_off, dparts.as<PartRes>(), nullptr, s);
-  std::vector<PartRes> prs(n);
-  if (!r) {
-    he = hipMemcpyAsync(tmp.h_cap.p, tmp.cap.p, L.fixed_end, hipMemcpyDeviceToHost, s);
-    if (he == hipSuccess) he = hipMemcpyAsync(prs.data(), dparts.p, (size_t)n * sizeof(PartRes), hipMemcpyDeviceToHost, s);
-  }
-  const hipError_t hs = hipStreamSynchronize(s);
-  if (r) return done(r);
-  if (he != hipSuccess || hs != hipSuccess) return done(fail(e, ZKE_E_DEVICE, "zke_capture_batch", he != hipSuccess ? he : hs));
-  const uint32_t* codes = reinterpret_cast<const uint32_t*>(tmp.h_cap.as<uint8_t>() + L.codes);
-  for (uint32_t i = 0; i < n; i++) {
-    const PartRes& pr = prs[i];
-    const bool undecodable = pr.code == PART_DECODE_FAIL;
-    matches[4 * i] = undecodable ? pr.count : (pr.code ? pr.code : codes[i]);
-    matches[4 * i + 1] = undecodable ? 0 : pr.count; matches[4 * i + 2] = pr.start; matches[4 * i + 3] = pr.end;
-  }
-  return done(deliver_captures(e, tmp, caps, s));
 }
 
 }  // extern "C"

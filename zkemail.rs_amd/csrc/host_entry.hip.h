@@ -31,40 +31,34 @@ struct KeyrecReq { uint32_t mode; zke_keyrec_out* out; };
 // ---- body extraction (bodyext.hip.h): the batch's raw section holds the e-mails, body_extract_kernel runs instead of the verify pipeline
 struct BodyReq { uint32_t flags; zke_body_out* out; };
 
+// A slot's buffers for one side output of a batch of n: the layout, then the buffers it asks for (ensure_side_buffers).
+// `pack`: zke_select_keys_from_records, the decoded keys are packed for the front end.
 int ensure_keyrec_buffers(zke_engine* e, KeyrecBufs& b, uint32_t m, size_t rec_total, bool pack) {
-  const KeyrecLayout L = keyrec_layout(m, rec_total);
-  int r = 0;
-  if ((r = b.out.ensure(L.total)) || (r = b.h_out.ensure(L.total)) || (pack && (r = b.pack.ensure(L.p_total))))
-    return fail(e, r, "key-record buffer allocation");
-  b.L = L;
-  return 0;
+  b.L = keyrec_layout(m, rec_total);
+  return ensure_side_buffers(e, b.t, b.L.total, b.L.total, pack ? &b.pack : nullptr, b.L.p_total, "key-record buffer allocation");
 }
-
 int ensure_body_buffers(zke_engine* e, BodyBufs& b, uint32_t n, size_t raw_total) {
-  const BodyLayout L = body_layout(n, raw_total);
-  int r = 0;
-  if ((r = b.out.ensure(L.total)) || (r = b.h_out.ensure(L.total)) || (r = b.ovf.ensure((size_t)n * HDR_OVF_BYTES)))
-    return fail(e, r, "body-extraction buffer allocation");
-  b.L = L;
-  return 0;
+  b.L = body_layout(n, raw_total);
+  return ensure_side_buffers(e, b.t, b.L.total, b.L.total, &b.ovf, (size_t)n * HDR_OVF_BYTES, "body-extraction buffer allocation");
 }
-
-// A slot's scan buffers for n e-mails with max_sigs record slots each and blob_cap bytes of selectors.  Grow only: the first scan
-// of a shape allocates, a later one of the same shape does not.
-int ensure_scan_buffers(zke_engine* e, ScanBufs& b, uint32_t n, uint32_t max_sigs, size_t blob_cap) {
-  const ScanLayout L = scan_layout(n, max_sigs, blob_cap);
-  int r = 0;
-  if ((r = b.out.ensure(L.total)) || (r = b.h_out.ensure(L.total)) || (r = b.ovf.ensure((size_t)n * HDR_OVF_BYTES)))
-    return fail(e, r, "signature-scan buffer allocation");
-  b.L = L;
-  return 0;
+// max_sigs record slots per e-mail and the caller's sel_blob_cap bytes of selectors (a selector is at most ZKE_MAX_TAGBUF bytes: a
+// larger blob than that per record slot is never used)
+int ensure_scan_buffers(zke_engine* e, ScanBufs& b, uint32_t n, uint32_t max_sigs, size_t sel_blob_cap) {
+  b.L = scan_layout(n, max_sigs, std::min<size_t>(sel_blob_cap, (size_t)n * max_sigs * ZKE_MAX_TAGBUF));
+  return ensure_side_buffers(e, b.t, b.L.total, b.L.total, &b.ovf, (size_t)n * HDR_OVF_BYTES, "signature-scan buffer allocation");
+}
+// `launched`: capture_origin_kernel runs for this batch; where it does not, nothing is allocated
+int ensure_origin_buffers(zke_engine* e, OriginBufs& b, uint32_t n, const CaptureReq& q) {
+  b.L = origin_layout(n, q.G);
+  b.launched = q.origin_launch();
+  return b.launched ? ensure_side_buffers(e, b.t, b.L.total, b.L.total, nullptr, 0, "capture-origin buffer allocation") : 0;
 }
 
 // An extraction's tables from the slot's pinned twin (and the blob from HBM) into the caller's zke_capture_out.  Returns
 // ZKE_E_NOMEM when the caller's cap_blob is too small for the strings (everything else is delivered; cap_blob_need says how much).
 int deliver_captures(zke_engine* e, CapBufs& b, zke_capture_out* o, hipStream_t s) {
   const CapLayout& L = b.L;
-  const uint8_t* hp = b.h_cap.as<uint8_t>();
+  const uint8_t* hp = b.t.h.as<uint8_t>();
   const uint64_t* hdr = reinterpret_cast<const uint64_t*>(hp + L.hdr);
   const size_t strings = (size_t)hdr[0], bytes = (size_t)hdr[1];
   memcpy(o->spans, hp + L.spans, o->spans_need * 4);
@@ -75,7 +69,7 @@ int deliver_captures(zke_engine* e, CapBufs& b, zke_capture_out* o, hipStream_t 
   o->cap_blob_need = bytes;
   const size_t take = std::min(bytes, L.blob_cap);
   if (take) {
-    HIPCHK(e, hipMemcpyAsync(o->cap_blob, b.cap.as<uint8_t>() + L.blob, take, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(o->cap_blob, b.t.d.as<uint8_t>() + L.blob, take, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
   }
   if (bytes > L.blob_cap) return fail(e, ZKE_E_NOMEM, "capture extraction: cap_blob is smaller than the strings (zke_capture_out.cap_blob_need)");
@@ -88,11 +82,11 @@ void deliver_origins(const CapBufs& b, const OriginBufs& ob, zke_capture_origin*
   const OriginLayout& L = ob.L;
   if (!L.NG) return;
   if (ob.launched) {
-    const uint8_t* hp = ob.h_org.as<uint8_t>();
+    const uint8_t* hp = ob.t.h.as<uint8_t>();
     memcpy(o->spans, hp, L.NG * 8);
     memcpy(o->flags, hp + L.flags, L.NG);
   } else {
-    memcpy(o->spans, b.h_cap.as<uint8_t>() + b.L.spans, L.NG * 8);
+    memcpy(o->spans, b.t.h.as<uint8_t>() + b.L.spans, L.NG * 8);
     memset(o->flags, 0, L.NG);
   }
 }
@@ -101,7 +95,7 @@ void deliver_origins(const CapBufs& b, const OriginBufs& ob, zke_capture_origin*
 // compaction: one memcpy per e-mail), the selector bytes.  ZKE_E_NOMEM when sigs or sel_blob is too small (*_need says how much).
 int deliver_scan(zke_engine* e, const ScanBufs& b, zke_sig_scan* o) {
   const ScanLayout& S = b.L;
-  const uint8_t* hp = b.h_out.as<uint8_t>();
+  const uint8_t* hp = b.t.h.as<uint8_t>();
   const uint32_t* st = reinterpret_cast<const uint32_t*>(hp + S.status);
   const zke_sig_info* recs = reinterpret_cast<const zke_sig_info*>(hp + S.recs);
   const size_t used = *reinterpret_cast<const uint32_t*>(hp);
@@ -123,7 +117,7 @@ int deliver_scan(zke_engine* e, const ScanBufs& b, zke_sig_scan* o) {
 // the key bytes compacted (one memcpy per key).  ZKE_E_NOMEM when keys is too small (keys_need says how much).
 int deliver_keyrec(zke_engine* e, const KeyrecBufs& b, zke_keyrec_out* o) {
   const KeyrecLayout& K = b.L;
-  const uint8_t* hp = b.h_out.as<uint8_t>();
+  const uint8_t* hp = b.t.h.as<uint8_t>();
   const zke_key_info* src = reinterpret_cast<const zke_key_info*>(hp);
   size_t total = 0;
   for (uint32_t i = 0; i < K.m; i++) {
@@ -145,13 +139,13 @@ int deliver_keyrec(zke_engine* e, const KeyrecBufs& b, zke_keyrec_out* o) {
 // fetched only when one is in use.  ZKE_E_NOMEM when bytes is too small (bytes_need says how much).
 int deliver_body(zke_engine* e, const BodyBufs& b, zke_body_out* o, hipStream_t s) {
   const BodyLayout& K = b.L;
-  uint8_t* hp = b.h_out.as<uint8_t>();
+  uint8_t* hp = b.t.h.as<uint8_t>();
   bool spilled = false;
   const int r = body_measure(K, hp, o, spilled);
   if (r == ZKE_E_DEVICE) return fail(e, r, "body extraction: an info points outside its e-mail's place");
   if (r) return fail(e, r, "body extraction: bytes is smaller than the decoded bodies (zke_body_out.bytes_need)");
   if (spilled) {
-    HIPCHK(e, hipMemcpyAsync(hp + K.first_copy, b.out.as<uint8_t>() + K.first_copy, K.region, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(hp + K.first_copy, b.t.d.as<uint8_t>() + K.first_copy, K.region, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
   }
   body_compact(K, hp, o);
@@ -178,59 +172,42 @@ void fold_selection(const zke_result* R, const std::vector<uint32_t>& off, zke_r
   }
 }
 
-// Deliver a host batch that was enqueued in this slot and not waited for yet: wait for its D2H, copy the records from the
-// pinned buffer to the caller's `out`.  Caller holds the slot's lock.
-// `cap_rc` (zke_batch_wait, the synchronous entries): where an extraction's or a scan's shortfall is reported; a slot that retires
-// a batch nobody waited for has nobody to tell.
-int retire_host(zke_engine* e, Slot& w, int* cap_rc = nullptr) {
-  if (w.host_retired == w.host_gen) return 0;
-  w.host_retired = w.host_gen;                       // whatever happens below, the batch is no longer pending
-  zke_capture_out* pending_caps = w.cap_out;
-  w.cap_out = nullptr;
-  zke_sig_scan* pending_scan = w.scan_out;
-  w.scan_out = nullptr;
-  zke_keyrec_out* pending_keyrec = w.keyrec_out;
-  w.keyrec_out = nullptr;
-  zke_capture_origin* pending_org = w.org_out;
-  w.org_out = nullptr;
-  zke_body_out* pending_body = w.body_out;
-  w.body_out = nullptr;
-  HIPCHK(e, hipEventSynchronize(w.host_done));
-  if (w.host_out && w.host_n) memcpy(w.host_out, w.h_results.p, (size_t)w.host_n * sizeof(zke_result));
-  w.host_out = nullptr;
-  if (!w.sel_off.empty()) {
-    fold_selection(w.h_results.as<zke_result>(), w.sel_off, w.sel_out, w.sel_chosen);
-    w.sel_off.clear();
-  }
-  if (pending_scan) {
-    const std::string keep = g_err;
-    const int r = deliver_scan(e, w.sb, pending_scan);
+// Pay what a slot owes for a batch whose last copy has arrived, from the slot's pinned buffers into the caller's.  The order: the
+// records, the selection fold, the scan, the key records, the bodies, the captures, the origins.  Needs no device where nothing is
+// left in HBM (a body that did not spill, no capture strings).
+// The shortfall rule: an output whose variable-size buffer is too small is ZKE_E_NOMEM to whoever waits — `cap_rc` (zke_batch_wait,
+// the synchronous entries) — and nobody's business otherwise: a slot that retires a batch nobody waited for has nobody to tell, and
+// zke_last_error stays what it was.  Everything of fixed size and every *_need is delivered either way; any other error ends the delivery.
+int deliver_pending(zke_engine* e, Slot& w, const PendingDelivery& d, int* cap_rc) {
+  if (d.records && d.n) memcpy(d.records, w.h_results.p, (size_t)d.n * sizeof(zke_result));
+  if (!d.sel_off.empty()) fold_selection(w.h_results.as<zke_result>(), d.sel_off, d.sel_out, d.sel_chosen);
+  const std::string keep = cap_rc ? std::string() : g_err;
+  auto settled = [&](int r) {      // the shortfall rule
     if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
-    else if (r) return r;
-  }
-  if (pending_keyrec) {
-    const std::string keep = g_err;
-    const int r = deliver_keyrec(e, w.kb, pending_keyrec);
-    if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
-    else if (r) return r;
-  }
-  if (pending_body) {
-    const std::string keep = g_err;
-    const int r = deliver_body(e, w.bb, pending_body, w.stream);
-    if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
-    else if (r) return r;
-  }
-  if (pending_caps) {
-    const std::string keep = g_err;
-    const int r = deliver_captures(e, w.cb, pending_caps, w.stream);
-    if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
-    else if (r) return r;
-  }
-  if (pending_org) deliver_origins(w.cb, w.ob, pending_org);
+    return r == ZKE_E_NOMEM ? 0 : r;
+  };
+  int r = 0;
+  if (d.scan && (r = settled(deliver_scan(e, w.sb, d.scan)))) return r;
+  if (d.keyrec && (r = settled(deliver_keyrec(e, w.kb, d.keyrec)))) return r;
+  if (d.body && (r = settled(deliver_body(e, w.bb, d.body, w.stream)))) return r;
+  if (d.caps && (r = settled(deliver_captures(e, w.cb, d.caps, w.stream)))) return r;
+  if (d.org) deliver_origins(w.cb, w.ob, d.org);
   return 0;
 }
 
+// Deliver a host batch that was enqueued in this slot and not waited for yet: wait for its last D2H, pay what is owed for it.
+// Caller holds the slot's lock.
+int retire_host(zke_engine* e, Slot& w, int* cap_rc = nullptr) {
+  if (w.host_retired == w.host_gen) return 0;
+  w.host_retired = w.host_gen;                       // whatever happens below, the batch is no longer pending
+  const PendingDelivery d = std::move(w.owed);
+  w.owed = PendingDelivery{};
+  HIPCHK(e, hipEventSynchronize(w.host_done));
+  return deliver_pending(e, w, d, cap_rc);
+}
+
 int arg_error(const char* who, const char* what) { g_err = std::string(who) + ": " + what; return ZKE_E_ARG; }
+int nomem_error(const char* who, const char* what) { g_err = std::string(who) + ": " + what; return ZKE_E_NOMEM; }      // a buffer of known size is too small
 template <class T> bool rising(const T* off, size_t cnt) { uint64_t bad = 0; for (size_t i = 0; i < cnt; i++) bad |= (uint64_t)(off[i + 1] < off[i]); return !bad; }
 // The part-id lists of a batch (host arrays in every entry) ...
 int check_part_ids(const zke_batch& b, const char* who) {
@@ -306,30 +283,37 @@ int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_e
   return measure_host_batch(d, who);
 }
 
-// One host batch into slot w (caller holds its lock): pack -> one H2D -> the launches -> one D2H -> event.
+// What the slot will owe for the batch d: only a batch that is nothing but a verify hands the records over as they are.
+PendingDelivery pending_delivery(const HostBatch& d, zke_result* out) {
+  PendingDelivery p;
+  if (!(d.scan || d.sel || d.keyrec || d.body)) { p.records = out; p.n = d.b.n; }
+  if (d.sel) {
+    p.sel_off.resize((size_t)d.sel->n + 1);
+    for (uint32_t i = 0; i <= d.sel->n; i++) p.sel_off[i] = d.sel->cand_off[i] - d.sel->cand_off[0];
+    p.sel_out = d.sel->out; p.sel_chosen = d.sel->chosen;
+  }
+  if (d.scan) p.scan = d.scan->out;
+  if (d.keyrec) p.keyrec = d.keyrec->out;
+  if (d.body) p.body = d.body->out;
+  if (d.cap) { p.caps = d.cap->out; p.org = d.cap->org; }
+  return p;
+}
+
+// One host batch into slot w (caller holds its lock): the side outputs' buffers, then pack -> one H2D -> the launches (one stand-alone
+// side launch, or the verify pipeline, behind the key-record prefix if the keys come as records) -> the D2H of every twin -> event, and
+// the slot owes the delivery.
 int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, bool want_em, bool want_clean) {
   const uint32_t n = d.b.n;
   const ImageLayout& L = d.L;
-  if (int r = retire_host(e, w)) return r;           // the pinned buffers are about to be overwritten
-  if (int r = ensure_host_buffers(e, w, L.total, n)) return r;      // (a no-op: submit_host_batch has grown every slot's staging)
-  if (d.cap) {
-    if (int r = ensure_capture_buffers(e, w.cb, n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap, d.cap->needs_work)) return r;
-    w.cb.L = cap_layout(n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap);
-  }
-  if (d.cap && d.cap->org) {
-    w.ob.L = origin_layout(n, d.cap->G);
-    w.ob.launched = d.cap->origin_launch();
-    if (w.ob.launched)
-      if (int r = w.ob.org.ensure(w.ob.L.total) ? ZKE_E_NOMEM : w.ob.h_org.ensure(w.ob.L.total)) return fail(e, r, "capture-origin buffer allocation");
-  }
-  if (d.scan) {      // (a selector is at most ZKE_MAX_TAGBUF bytes: a larger blob than that per record slot is never used)
-    const size_t blob = std::min<size_t>(d.scan->out->sel_blob_cap, (size_t)n * d.scan->max_sigs * ZKE_MAX_TAGBUF);
-    if (int r = ensure_scan_buffers(e, w.sb, n, d.scan->max_sigs, blob)) return r;
-  }
-  if (d.keyrec)
-    if (int r = ensure_keyrec_buffers(e, w.kb, n, (size_t)(d.sel ? d.key_total : d.raw_total), d.sel != nullptr)) return r;
-  if (d.body)
-    if (int r = ensure_body_buffers(e, w.bb, n, (size_t)d.raw_total)) return r;
+  int rc = 0;
+  if ((rc = retire_host(e, w))) return rc;           // the pinned buffers are about to be overwritten
+  if ((rc = ensure_host_buffers(e, w, L.total, n))) return rc;      // (a no-op: submit_host_batch has grown every slot's staging)
+  if (d.cap) w.cb.L = cap_layout(n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap);
+  if (d.cap && (rc = ensure_capture_buffers(e, w.cb, w.cb.L, d.cap->needs_work))) return rc;
+  if (d.cap && d.cap->org && (rc = ensure_origin_buffers(e, w.ob, n, *d.cap))) return rc;
+  if (d.scan && (rc = ensure_scan_buffers(e, w.sb, n, d.scan->max_sigs, d.scan->out->sel_blob_cap))) return rc;
+  if (d.keyrec && (rc = ensure_keyrec_buffers(e, w.kb, n, (size_t)(d.sel ? d.key_total : d.raw_total), d.sel != nullptr))) return rc;
+  if (d.body && (rc = ensure_body_buffers(e, w.bb, n, (size_t)d.raw_total))) return rc;
   uint8_t* hp = w.h_image.as<uint8_t>();
   if (d.refs) {
     // the CSR arrays are written where they will be read from (prefix sums over the lengths), and every e-mail's three buffers
@@ -369,7 +353,7 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   }
   hipStream_t s = w.stream;
   SlotUse use(e, w, s);
-  if (int r = use.acquire()) return r;
+  if ((rc = use.acquire())) return rc;
   StageTimer tm(e, &w, s);
   tm.mark(MK_START);
   if (ZKE_HOST_COPY_STREAM && L.total >= (256u << 10)) {
@@ -401,82 +385,28 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   dv.cap_off = d.cap_words ? reinterpret_cast<const uint32_t*>(dp + L.cap_off) : nullptr;
   dv.cap_str_off = d.cap_words ? reinterpret_cast<const uint32_t*>(dp + L.cap_str_off) : nullptr;
   dv.cap_blob = d.cap_words ? dp + L.cap_blob : nullptr;
-  if (d.scan) {
-    // one launch, no verify workspace: the counter of selector bytes starts at zero, everything comes back as one copy
-    const ScanLayout& S = w.sb.L;
-    uint8_t* so = w.sb.out.as<uint8_t>();
-    HIPCHK(e, hipMemsetAsync(so, 0, 64, s));
-    SigScanArgs sa{};
-    sa.n = n; sa.max_sigs = S.max_sigs;
-    sa.raw = dv.raw_blob; sa.raw_off = dv.raw_off; sa.dom = dv.domain_blob; sa.dom_off = dv.domain_off;
-    sa.strict = e->strict; sa.now = batch_clock(e);
-    sa.status = reinterpret_cast<uint32_t*>(so + S.status);
-    sa.recs = reinterpret_cast<zke_sig_info*>(so + S.recs);
-    sa.sel_blob = so + S.blob; sa.sel_cap = (uint32_t)S.blob_cap;
-    sa.sel_used = reinterpret_cast<uint32_t*>(so);
-    sa.hdr_ovf = w.sb.ovf.as<uint32_t>();
-    hipLaunchKernelGGL(sigscan_kernel, dim3(n), dim3(64), 0, s, sa);
-    HIPCHK(e, hipGetLastError());
-    tm.mark(MK_FRONT); tm.mark(MK_HASH); tm.mark(MK_VERDICT);      // zke_timings.front_end_us is the scan; the other stages are empty
-    HIPCHK(e, hipMemcpyAsync(w.sb.h_out.p, so, S.total, hipMemcpyDeviceToHost, s));
-  } else if (d.body) {
-    // one launch over the e-mails (the image's raw section), infos and first places back as one copy
-    const BodyLayout& K = w.bb.L;
-    uint8_t* bo = w.bb.out.as<uint8_t>();
-    const BodyArgs ba{n, d.body->flags, dv.raw_blob, dv.raw_off, reinterpret_cast<zke_body_info*>(bo), bo + K.bytes, (uint64_t)K.region, w.bb.ovf.as<uint32_t>()};
-    hipLaunchKernelGGL(body_extract_kernel, dim3(n), dim3(64), 0, s, ba);
-    HIPCHK(e, hipGetLastError());
-    tm.mark(MK_FRONT); tm.mark(MK_HASH); tm.mark(MK_VERDICT);      // zke_timings.front_end_us is the extraction; the other stages are empty
-    HIPCHK(e, hipMemcpyAsync(w.bb.h_out.p, bo, K.first_copy, hipMemcpyDeviceToHost, s));
-  } else if (d.keyrec && !d.sel) {
-    // one launch over the records (the image's raw section), infos and keys back as one copy
-    const KeyrecLayout& K = w.kb.L;
-    uint8_t* ko = w.kb.out.as<uint8_t>();
-    const KeyrecArgs ka{n, d.keyrec->mode, dv.raw_blob, dv.raw_off, reinterpret_cast<zke_key_info*>(ko), ko + K.keys};
-    hipLaunchKernelGGL(keyrec_kernel, dim3(n), dim3(64), 0, s, ka);
-    HIPCHK(e, hipGetLastError());
-    tm.mark(MK_FRONT); tm.mark(MK_HASH); tm.mark(MK_VERDICT);      // zke_timings.front_end_us is the decode; the other stages are empty
-    HIPCHK(e, hipMemcpyAsync(w.kb.h_out.p, ko, K.total, hipMemcpyDeviceToHost, s));
-  } else {
-  uint64_t key_hint = d.key_total;
-  if (d.keyrec) {
-    // the image's key section holds the candidates' RECORDS: decode them, then scan the lengths and gather the keys into the
-    // packed CSR the front end reads — three small launches, the keys never leave HBM
-    const KeyrecLayout& K = w.kb.L;
-    uint8_t* ko = w.kb.out.as<uint8_t>();
-    uint8_t* pk = w.kb.pack.as<uint8_t>();
-    const KeyrecArgs ka{n, d.keyrec->mode, dv.key_blob, dv.key_off, reinterpret_cast<zke_key_info*>(ko), ko + K.keys};
-    hipLaunchKernelGGL(keyrec_kernel, dim3(n), dim3(64), 0, s, ka);
-    const KeyrecPackArgs pa{n, ka.infos, ka.keys, reinterpret_cast<uint64_t*>(pk), pk + K.p_type, pk + K.p_blob};
-    hipLaunchKernelGGL(keyrec_pack_kernel, dim3(1), dim3(64), 0, s, pa);
-    hipLaunchKernelGGL(keyrec_gather_kernel, dim3(n), dim3(64), 0, s, pa);
-    HIPCHK(e, hipGetLastError());
-    dv.key_blob = pa.key_blob; dv.key_off = pa.key_off; dv.key_type = pa.key_type;
-    // (run_device_pipeline reads "the keys average more than an RSA-2048 key's 270 bytes" from the total: a 2048-bit
-    // SubjectPublicKeyInfo record is about 410 characters, a 3072-bit one 580)
-    key_hint = d.key_total > (uint64_t)n * 480 ? (uint64_t)n * 273 : 0;
+  if (d.scan) rc = launch_scan(e, w.sb, dv, batch_clock(e), tm, s);
+  else if (d.body) rc = launch_body(e, w.bb, dv, d.body->flags, tm, s);
+  else if (d.keyrec && !d.sel) rc = launch_keyrec(e, w.kb, dv, d.keyrec->mode, tm, s);
+  else {
+    uint64_t key_hint = d.key_total;
+    if (d.keyrec) {
+      if ((rc = launch_keyrec_prefix(e, w.kb, dv, d.keyrec->mode, s))) return rc;
+      // (run_device_pipeline reads "the keys average more than an RSA-2048 key's 270 bytes" from the total: a 2048-bit
+      // SubjectPublicKeyInfo record is about 410 characters, a 3072-bit one 580)
+      key_hint = d.key_total > (uint64_t)n * 480 ? (uint64_t)n * 273 : 0;
+    }
+    if ((rc = run_device_pipeline(e, w, &dv, d.raw_total, key_hint, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap))) return rc;
+    HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
+    if (d.keyrec) HIPCHK(e, w.kb.t.fetch(w.kb.L.total, s));
   }
-  if (int r = run_device_pipeline(e, w, &dv, d.raw_total, key_hint, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap)) return r;
-  HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
-  if (d.keyrec) HIPCHK(e, hipMemcpyAsync(w.kb.h_out.p, w.kb.out.p, w.kb.L.total, hipMemcpyDeviceToHost, s));
-  }
-  if (d.cap) HIPCHK(e, hipMemcpyAsync(w.cb.h_cap.p, w.cb.cap.p, w.cb.L.fixed_end, hipMemcpyDeviceToHost, s));
-  if (d.cap && d.cap->org && w.ob.launched) HIPCHK(e, hipMemcpyAsync(w.ob.h_org.p, w.ob.org.p, w.ob.L.total, hipMemcpyDeviceToHost, s));
+  if (rc) return rc;
+  if (d.cap) HIPCHK(e, w.cb.t.fetch(w.cb.L.fixed_end, s));
+  if (d.cap && d.cap->org && w.ob.launched) HIPCHK(e, w.ob.t.fetch(w.ob.L.total, s));
   tm.mark(MK_D2H);
   HIPCHK(e, hipEventRecord(w.host_done, s));
   w.host_gen++;
-  w.host_out = (d.scan || d.sel || d.keyrec || d.body) ? nullptr : out; w.host_n = n;
-  w.keyrec_out = d.keyrec ? d.keyrec->out : nullptr;
-  w.body_out = d.body ? d.body->out : nullptr;
-  w.cap_out = d.cap ? d.cap->out : nullptr;
-  w.org_out = d.cap ? d.cap->org : nullptr;
-  w.scan_out = d.scan ? d.scan->out : nullptr;
-  w.sel_off.clear();
-  if (d.sel) {
-    w.sel_off.resize((size_t)d.sel->n + 1);
-    for (uint32_t i = 0; i <= d.sel->n; i++) w.sel_off[i] = d.sel->cand_off[i] - d.sel->cand_off[0];
-    w.sel_out = d.sel->out; w.sel_chosen = d.sel->chosen;
-  }
+  w.owed = pending_delivery(d, out);
   return use.release();
 }
 
@@ -566,6 +496,41 @@ int submit_host_batch(zke_engine* e, const HostBatch& d, zke_result* out, uint64
   return dbg ? copy_debug_out(e, w, d.b, out, dbg) : 0;
 }
 
+// A synchronous entry: its asynchronous one (`submit`, given the ticket), then the wait for the ticket — an empty batch has none.
+template <class Submit> int submit_and_wait(zke_engine* e, uint32_t n, Submit submit) {
+  uint64_t ticket = 0;
+  if (int r = submit(&ticket)) return r;
+  return n ? zke_batch_wait(e, ticket) : 0;
+}
+
+// ---- key selection (zke_select_keys, zke_select_keys_from_records)
+// cand_off of a selection over n e-mails, checked: M candidates in all, the first of them candidate `base` of the caller's list
+int selection_shape(const char* who, const uint32_t* cand_off, uint32_t n, uint32_t& base, uint32_t& M) {
+  if (n && !rising(cand_off, n)) return arg_error(who, "cand_off is not non-decreasing");
+  base = n ? cand_off[0] : 0;
+  M = n ? cand_off[n] - base : 0;
+  return 0;
+}
+// ONE batch of the (e-mail, candidate) pairs: the raw e-mail and the domain by reference, once per candidate; key_of(k, m) puts
+// candidate k's key (or, with `keyrec`, its record: the image's key section then holds records) into the pair m.  The pending
+// delivery folds the pairs' records per e-mail.
+template <class KeyOf> int submit_selection(zke_engine* e, const char* who, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off, uint32_t M,
+                                            zke_result* out, uint32_t* chosen, const KeyrecReq* keyrec, uint64_t* ticket, KeyOf key_of) {
+  std::vector<zke_email_ref> refs(M);
+  for (uint32_t i = 0; i < n; i++)
+    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; k++) {
+      zke_email_ref& m = refs[k - cand_off[0]];
+      m = emails[i];
+      key_of(k, m);
+    }
+  HostBatch d;
+  if (int r = host_batch(d, who, out, refs.data(), M, nullptr)) return r;
+  const SelectReq q{cand_off, n, out, chosen};
+  if (M) { d.sel = &q; d.keyrec = keyrec; }
+  else if (n) fold_selection(nullptr, std::vector<uint32_t>((size_t)n + 1, 0u), out, chosen);      // no candidate anywhere: nothing to run
+  return submit_host_batch(e, d, out, ticket);
+}
+
 }  // namespace
 
 extern "C" {
@@ -615,9 +580,7 @@ int zke_verify_emails_async(zke_engine* e, const zke_email_ref* emails, uint32_t
 }
 
 int zke_verify_emails_with_regex(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_lists* lists, zke_result* out) {
-  uint64_t ticket = 0;
-  if (int r = zke_verify_emails_with_regex_async(e, emails, n, lists, out, &ticket)) return r;
-  return n ? zke_batch_wait(e, ticket) : 0;
+  return submit_and_wait(e, n, [&](uint64_t* t) { return zke_verify_emails_with_regex_async(e, emails, n, lists, out, t); });
 }
 
 int zke_verify_emails(zke_engine* e, const zke_email_ref* emails, uint32_t n, zke_result* out) {
@@ -683,10 +646,7 @@ int zke_scan_signatures_async(zke_engine* e, const zke_email_ref* emails, uint32
   if (max_sigs < 1 || max_sigs > ZKE_SCAN_MAX_SIGS) return arg_error(who, "max_sigs must be 1 .. ZKE_SCAN_MAX_SIGS");
   if ((uint64_t)n * max_sigs >= (1ull << 21)) return arg_error(who, "n * max_sigs must stay below 2^21 (32-bit selector offsets): split the batch");
   out->scan_status_need = (size_t)n * 4; out->sig_off_need = (size_t)n + 1; out->sigs_need = 0; out->sel_blob_need = 0; out->n_sigs = 0;
-  if (out->scan_status_cap < out->scan_status_need || out->sig_off_cap < out->sig_off_need) {
-    g_err = std::string(who) + ": a zke_sig_scan buffer is smaller than its *_need";
-    return ZKE_E_NOMEM;
-  }
+  if (out->scan_status_cap < out->scan_status_need || out->sig_off_cap < out->sig_off_need) return nomem_error(who, "a zke_sig_scan buffer is smaller than its *_need");
   if ((n && !out->scan_status) || !out->sig_off || (out->sigs_cap && !out->sigs) || (out->sel_blob_cap && !out->sel_blob))
     return arg_error(who, "null buffer in zke_sig_scan");
   out->sig_off[0] = 0;
@@ -700,9 +660,7 @@ int zke_scan_signatures_async(zke_engine* e, const zke_email_ref* emails, uint32
 }
 
 int zke_scan_signatures(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t max_sigs, zke_sig_scan* out) {
-  uint64_t ticket = 0;
-  if (int r = zke_scan_signatures_async(e, emails, n, max_sigs, out, &ticket)) return r;
-  return n ? zke_batch_wait(e, ticket) : 0;
+  return submit_and_wait(e, n, [&](uint64_t* t) { return zke_scan_signatures_async(e, emails, n, max_sigs, out, t); });
 }
 
 int zke_select_keys_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off, const zke_key_ref* keys,
@@ -710,35 +668,17 @@ int zke_select_keys_async(zke_engine* e, const zke_email_ref* emails, uint32_t n
   static const char who[] = "zke_select_keys";
   if (!e) return ZKE_E_ARG;
   if (!ticket || (n && (!emails || !cand_off || !out || !chosen))) return arg_error(who, "null pointer");
-  if (n && !rising(cand_off, n)) return arg_error(who, "cand_off is not non-decreasing");
-  const uint32_t base = n ? cand_off[0] : 0, M = n ? cand_off[n] - base : 0;
+  uint32_t base = 0, M = 0;
+  if (int r = selection_shape(who, cand_off, n, base, M)) return r;
   if (M >> 31) return arg_error(who, "2^31 candidates or more");
   if (M && !keys) return arg_error(who, "null pointer");
-  // ONE batch of the (e-mail, candidate key) pairs: the raw e-mail and the domain by reference, once per candidate
-  std::vector<zke_email_ref> refs(M);
-  for (uint32_t i = 0; i < n; i++)
-    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; k++) {
-      zke_email_ref& m = refs[k - base];
-      m = emails[i];
-      m.key = keys[k].key; m.key_len = keys[k].key_len; m.key_type = keys[k].key_type;
-    }
-  HostBatch d;
-  if (int r = host_batch(d, who, out, refs.data(), M, nullptr)) return r;
-  if (!M) {            // no candidate anywhere: nothing to run
-    const std::vector<uint32_t> off((size_t)n + 1, 0u);
-    if (n) fold_selection(nullptr, off, out, chosen);
-    return submit_host_batch(e, d, out, ticket);
-  }
-  const SelectReq q{cand_off, n, out, chosen};
-  d.sel = &q;
-  return submit_host_batch(e, d, out, ticket);
+  return submit_selection(e, who, emails, n, cand_off, M, out, chosen, nullptr, ticket,
+                          [&](uint32_t k, zke_email_ref& m) { m.key = keys[k].key; m.key_len = keys[k].key_len; m.key_type = keys[k].key_type; });
 }
 
 int zke_select_keys(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off, const zke_key_ref* keys,
                     zke_result* out, uint32_t* chosen) {
-  uint64_t ticket = 0;
-  if (int r = zke_select_keys_async(e, emails, n, cand_off, keys, out, chosen, &ticket)) return r;
-  return n ? zke_batch_wait(e, ticket) : 0;
+  return submit_and_wait(e, n, [&](uint64_t* t) { return zke_select_keys_async(e, emails, n, cand_off, keys, out, chosen, t); });
 }
 
 // ---- key records (include/zkemail_amd.h; kernels: keyrec.hip.h)
@@ -752,7 +692,7 @@ int keyrec_args(const char* who, const zke_keyrec_ref* recs, uint32_t m, uint32_
   for (uint32_t i = 0; i < m; i++)
     if (recs[i].len && !recs[i].txt) return arg_error(who, "null buffer with a length");
   out->infos_need = m; out->keys_need = 0;
-  if (out->infos_cap < m) { g_err = std::string(who) + ": zke_keyrec_out.infos is smaller than infos_need"; return ZKE_E_NOMEM; }
+  if (out->infos_cap < m) return nomem_error(who, "zke_keyrec_out.infos is smaller than infos_need");
   if ((m && !out->infos) || (out->keys_cap && !out->keys)) return arg_error(who, "null buffer in zke_keyrec_out");
   return 0;
 }
@@ -774,9 +714,7 @@ int zke_decode_key_records_async(zke_engine* e, const zke_keyrec_ref* recs, uint
 }
 
 int zke_decode_key_records(zke_engine* e, const zke_keyrec_ref* recs, uint32_t m, uint32_t mode, zke_keyrec_out* out) {
-  uint64_t ticket = 0;
-  if (int r = zke_decode_key_records_async(e, recs, m, mode, out, &ticket)) return r;
-  return m ? zke_batch_wait(e, ticket) : 0;
+  return submit_and_wait(e, m, [&](uint64_t* t) { return zke_decode_key_records_async(e, recs, m, mode, out, t); });
 }
 
 int zke_select_keys_from_records_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off,
@@ -785,35 +723,17 @@ int zke_select_keys_from_records_async(zke_engine* e, const zke_email_ref* email
   static const char who[] = "zke_select_keys_from_records";
   if (!e) return ZKE_E_ARG;
   if (!ticket || !keys_out || (n && (!emails || !cand_off || !out || !chosen))) return arg_error(who, "null pointer");
-  if (n && !rising(cand_off, n)) return arg_error(who, "cand_off is not non-decreasing");
-  const uint32_t base = n ? cand_off[0] : 0, M = n ? cand_off[n] - base : 0;
+  uint32_t base = 0, M = 0;
+  if (int r = selection_shape(who, cand_off, n, base, M)) return r;
   if (int r = keyrec_args(who, recs ? recs + base : nullptr, M, mode, keys_out)) return r;
-  // ONE batch of the (e-mail, candidate) pairs, as zke_select_keys; the key section of its image holds the candidates' records
-  std::vector<zke_email_ref> refs(M);
-  for (uint32_t i = 0; i < n; i++)
-    for (uint32_t k = cand_off[i]; k < cand_off[i + 1]; k++) {
-      zke_email_ref& m = refs[k - base];
-      m = emails[i];
-      m.key = recs[k].txt; m.key_len = keyrec_staged(recs[k].len); m.key_type = ZKE_KEY_RSA;
-    }
-  HostBatch d;
-  if (int r = host_batch(d, who, out, refs.data(), M, nullptr)) return r;
-  if (!M) {            // no candidate anywhere: nothing to run
-    const std::vector<uint32_t> off((size_t)n + 1, 0u);
-    if (n) fold_selection(nullptr, off, out, chosen);
-    return submit_host_batch(e, d, out, ticket);
-  }
-  const SelectReq q{cand_off, n, out, chosen};
   const KeyrecReq kq{mode, keys_out};
-  d.sel = &q; d.keyrec = &kq;
-  return submit_host_batch(e, d, out, ticket);
+  return submit_selection(e, who, emails, n, cand_off, M, out, chosen, &kq, ticket,
+                          [&](uint32_t k, zke_email_ref& m) { m.key = recs[k].txt; m.key_len = keyrec_staged(recs[k].len); m.key_type = ZKE_KEY_RSA; });
 }
 
 int zke_select_keys_from_records(zke_engine* e, const zke_email_ref* emails, uint32_t n, const uint32_t* cand_off,
                                  const zke_keyrec_ref* recs, uint32_t mode, zke_result* out, uint32_t* chosen, zke_keyrec_out* keys_out) {
-  uint64_t ticket = 0;
-  if (int r = zke_select_keys_from_records_async(e, emails, n, cand_off, recs, mode, out, chosen, keys_out, &ticket)) return r;
-  return n ? zke_batch_wait(e, ticket) : 0;
+  return submit_and_wait(e, n, [&](uint64_t* t) { return zke_select_keys_from_records_async(e, emails, n, cand_off, recs, mode, out, chosen, keys_out, t); });
 }
 
 // ---- extract_email_body for whole batches (include/zkemail_amd.h; kernel: bodyext.hip.h)
@@ -827,7 +747,7 @@ int zke_extract_bodies_async(zke_engine* e, const zke_email_ref* emails, uint32_
     if (emails[i].raw_len >= (1ull << 31)) return arg_error(who, "an e-mail of 2^31 bytes or more");
   }
   out->infos_need = n; out->bytes_need = 0;
-  if (out->infos_cap < n) { g_err = std::string(who) + ": zke_body_out.infos is smaller than infos_need"; return ZKE_E_NOMEM; }
+  if (out->infos_cap < n) return nomem_error(who, "zke_body_out.infos is smaller than infos_need");
   if ((n && !out->infos) || (out->bytes_cap && !out->bytes)) return arg_error(who, "null buffer in zke_body_out");
   std::vector<zke_email_ref> refs(n);                 // only the raw e-mails travel: no domains, no keys
   for (uint32_t i = 0; i < n; i++) { refs[i] = zke_email_ref{}; refs[i].raw = emails[i].raw; refs[i].raw_len = emails[i].raw_len; }
@@ -839,9 +759,7 @@ int zke_extract_bodies_async(zke_engine* e, const zke_email_ref* emails, uint32_
 }
 
 int zke_extract_bodies(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t flags, zke_body_out* out) {
-  uint64_t ticket = 0;
-  if (int r = zke_extract_bodies_async(e, emails, n, flags, out, &ticket)) return r;
-  return n ? zke_batch_wait(e, ticket) : 0;
+  return submit_and_wait(e, n, [&](uint64_t* t) { return zke_extract_bodies_async(e, emails, n, flags, out, t); });
 }
 
 namespace {
@@ -853,10 +771,8 @@ int check_capture_out(zke_capture_out* o, uint32_t n, uint32_t P, uint32_t G, co
   o->cap_blob_need = 0; o->n_strings = 0;
   // string offsets are 32-bit, as the verify entry's tables are: what n * G spans of ZKE_CAP_MAX_SPAN bytes could not address is refused
   if ((uint64_t)NG * ZKE_CAP_MAX_SPAN > 0xFFFFFFFFull) return arg_error(who, "n x groups beyond what 32-bit string offsets address (n * G * ZKE_CAP_MAX_SPAN must stay below 4 GiB): split the batch");
-  if (o->spans_cap < o->spans_need || o->flags_cap < o->flags_need || o->cap_off_cap < o->cap_off_need || o->cap_str_off_cap < o->cap_str_off_need) {
-    g_err = std::string(who) + ": a zke_capture_out buffer is smaller than its *_need";
-    return ZKE_E_NOMEM;
-  }
+  if (o->spans_cap < o->spans_need || o->flags_cap < o->flags_need || o->cap_off_cap < o->cap_off_need || o->cap_str_off_cap < o->cap_str_off_need)
+    return nomem_error(who, "a zke_capture_out buffer is smaller than its *_need");
   if (!o->spans || !o->flags || !o->cap_off || !o->cap_str_off || (o->cap_blob_cap && !o->cap_blob)) return arg_error(who, "null buffer in zke_capture_out");
   return 0;
 }
@@ -865,10 +781,7 @@ int check_capture_origin(zke_capture_origin* o, uint32_t n, uint32_t G, const ch
   if (!o) return arg_error(who, "null zke_capture_origin");
   const size_t NG = (size_t)n * G;
   o->spans_need = NG * 2; o->flags_need = NG;
-  if (o->spans_cap < o->spans_need || o->flags_cap < o->flags_need) {
-    g_err = std::string(who) + ": a zke_capture_origin buffer is smaller than its *_need";
-    return ZKE_E_NOMEM;
-  }
+  if (o->spans_cap < o->spans_need || o->flags_cap < o->flags_need) return nomem_error(who, "a zke_capture_origin buffer is smaller than its *_need");
   if (NG && (!o->spans || !o->flags)) return arg_error(who, "null buffer in zke_capture_origin");
   return 0;
 }
@@ -906,6 +819,14 @@ int zke_extract_captures_async(zke_engine* e, const zke_email_ref* emails, uint3
                                  "zke_extract_captures");
 }
 
+int zke_extract_captures(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
+                         uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
+                         zke_capture_out* caps) {
+  return submit_and_wait(e, n, [&](uint64_t* t) {
+    return zke_extract_captures_async(e, emails, n, header_parts, n_header_parts, body_parts, n_body_parts, out, caps, t);
+  });
+}
+
 int zke_extract_captures_mapped_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
                                       uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
                                       zke_capture_out* caps, zke_capture_origin* org, uint64_t* ticket) {
@@ -916,9 +837,74 @@ int zke_extract_captures_mapped_async(zke_engine* e, const zke_email_ref* emails
 int zke_extract_captures_mapped(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
                                 uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
                                 zke_capture_out* caps, zke_capture_origin* org) {
-  uint64_t ticket = 0;
-  if (int r = zke_extract_captures_mapped_async(e, emails, n, header_parts, n_header_parts, body_parts, n_body_parts, out, caps, org, &ticket)) return r;
-  return n ? zke_batch_wait(e, ticket) : 0;
+  return submit_and_wait(e, n, [&](uint64_t* t) {
+    return zke_extract_captures_mapped_async(e, emails, n, header_parts, n_header_parts, body_parts, n_body_parts, out, caps, org, t);
+  });
+}
+
+// ---- capture extraction over haystacks of the caller's (registry.hip.h), with the checks and the delivery of the entries above
+int zke_capture_batch(zke_engine* e, uint32_t dfa_id, uint32_t prog_id, const uint32_t* groups, uint32_t n_groups,
+                      const uint8_t* hay_blob, const uint64_t* hay_off, uint32_t n, uint32_t* matches, zke_capture_out* caps) {
+  static const char who[] = "zke_capture_batch";
+  if (!e) return ZKE_E_ARG;
+  if (!caps || (n && (!hay_off || !matches)) || (n && hay_off[n] > hay_off[0] && !hay_blob)) return arg_error(who, "null pointer");
+  if (n && (!rising(hay_off, n) || hay_off[n] - hay_off[0] > (1ull << 32))) return arg_error(who, "offset array is not non-decreasing, or the haystacks exceed 4 GiB");
+  for (uint32_t i = 0; i < n; i++) if (hay_off[i + 1] - hay_off[i] >= (1ull << 31)) return arg_error(who, "haystack of 2 GiB or more");
+  CaptureReq q;
+  q.P = 1; q.n_header_parts = 1; q.out = caps;
+  if (int r = capture_part_shape(q, 0, prog_id, groups, n_groups, who)) return r;
+  if (int r = check_capture_out(caps, n, 1, q.G, who)) return r;
+  if (n == 0) return 0;
+  std::shared_lock<std::shared_mutex> sh(e->big);      // from the registry lookups to the last launch: no table is freed meanwhile
+  std::lock_guard<std::mutex> g(e->misc_mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  capture_resolve(e, q);
+  PartInfo pi{};
+  {
+    std::shared_lock<std::shared_mutex> rl(e->reg_mu);
+    const RegisteredDfa* rd = dfa_id < e->dfas.size() ? e->dfas[dfa_id] : nullptr;
+    if (rd) { pi.detail = rd->detail; pi.dev = rd->valid ? rd->dev.as<RegexDev>() : nullptr; }
+  }
+  // the building blocks run in buffers of their own on slot 0's stream
+  const uint64_t base0 = hay_off[0], total = hay_off[n] - base0;
+  Scoped<CapBufs> tmp;
+  Scoped<DevBuf> dhay, doff, dparts;
+  std::vector<uint8_t> fixed;
+  int r = 0;
+  hipError_t he = hipSuccess;
+  tmp.L = cap_layout(n, 1, q.G, caps->cap_blob_cap);
+  const CapLayout& L = tmp.L;
+  hipStream_t s = e->stream;
+  if ((r = dhay.ensure((size_t)total + 64)) || (r = doff.ensure((size_t)(n + 1) * 8)) || (r = dparts.ensure((size_t)n * sizeof(PartRes))) ||
+      (r = ensure_capture_buffers(e, tmp, L, q.needs_work)))
+    return fail(e, r, "zke_capture_batch: allocation");
+  std::vector<uint64_t> rel(n + 1);
+  for (uint32_t i = 0; i <= n; i++) rel[i] = hay_off[i] - base0;
+  if (total) he = hipMemcpyAsync(dhay.p, hay_blob + base0, (size_t)total, hipMemcpyHostToDevice, s);
+  if (he == hipSuccess) he = hipMemsetAsync(dhay.as<uint8_t>() + total, 0, 64, s);         // the DFA walk loads 16 bytes at a time
+  if (he == hipSuccess) he = hipMemcpyAsync(doff.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s);
+  if (he != hipSuccess) { (void)hipStreamSynchronize(s); return fail(e, ZKE_E_DEVICE, "zke_capture_batch: copy", he); }
+  CapFindArgs fa{};
+  fa.d.re = pi.dev; fa.d.P = 1; fa.d.out = dparts.as<PartRes>(); fa.d.idle = 0xFFFFFFFFu; fa.d.decode_detail = pi.detail;
+  fa.hay_blob = dhay.as<uint8_t>(); fa.hay_off = doff.as<uint64_t>(); fa.n = n;
+  hipLaunchKernelGGL(capture_find_kernel, dim3((n + 255) / 256), dim3(256), 1024, s, fa);
+  r = launch_capture(e, tmp, q, n, true, DfaArgs{}, fa.hay_blob, fa.hay_off, dparts.as<PartRes>(), nullptr, s);
+  std::vector<PartRes> prs(n);
+  if (!r) {
+    he = tmp.t.fetch(L.fixed_end, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(prs.data(), dparts.p, (size_t)n * sizeof(PartRes), hipMemcpyDeviceToHost, s);
+  }
+  const hipError_t hs = hipStreamSynchronize(s);
+  if (r) return r;
+  if (he != hipSuccess || hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "zke_capture_batch", he != hipSuccess ? he : hs);
+  const uint32_t* codes = reinterpret_cast<const uint32_t*>(tmp.t.h.as<uint8_t>() + L.codes);
+  for (uint32_t i = 0; i < n; i++) {
+    const PartRes& pr = prs[i];
+    const bool undecodable = pr.code == PART_DECODE_FAIL;
+    matches[4 * i] = undecodable ? pr.count : (pr.code ? pr.code : codes[i]);
+    matches[4 * i + 1] = undecodable ? 0 : pr.count; matches[4 * i + 2] = pr.start; matches[4 * i + 3] = pr.end;
+  }
+  return deliver_captures(e, tmp, caps, s);
 }
 
 // ---- remove_quoted_printable_soft_breaks with its index map over plain bodies (include/zkemail_amd.h; kernel: qpmap.hip.h).  One
@@ -964,14 +950,6 @@ int zke_qp_clean_batch(zke_engine* e, const uint8_t* body_blob, const uint64_t* 
   if (r) return r;
   if (hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "zke_qp_clean_batch: sync", hs);
   return 0;
-}
-
-int zke_extract_captures(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
-                         uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
-                         zke_capture_out* caps) {
-  uint64_t ticket = 0;
-  if (int r = zke_extract_captures_async(e, emails, n, header_parts, n_header_parts, body_parts, n_body_parts, out, caps, &ticket)) return r;
-  return n ? zke_batch_wait(e, ticket) : 0;
 }
 
 }  // extern "C"

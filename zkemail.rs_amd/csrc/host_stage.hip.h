@@ -27,7 +27,28 @@ struct PinnedBuf {
     return 0;
   }
   void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+  void track(uint64_t*) {}             // (pinned memory is in no captured graph: DevBuf::track)
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// The shape of a side output's buffers (captures, scan, key records, bodies, origins): a device buffer the kernels write and a pinned
+// twin of the same layout; a prefix of it comes back as ONE copy on the batch's stream.
+struct TwinBuf {
+  DevBuf d;
+  PinnedBuf h;
+  int ensure(size_t device_bytes, size_t pinned_bytes) { if (int r = d.ensure(device_bytes)) return r; return h.ensure(pinned_bytes); }
+  void release() { d.release(); h.release(); }
+  hipError_t fetch(size_t bytes, hipStream_t s) const { return hipMemcpyAsync(h.p, d.p, bytes, hipMemcpyDeviceToHost, s); }
+};
+// Every buffer a struct owns, once: f(DevBuf&) or f(PinnedBuf&).  One overload per struct, next to it; Slot::each_buffer walks them all.
+template <class F> void each_buffer(DevBuf& b, F& f) { f(b); }
+template <class F> void each_buffer(PinnedBuf& b, F& f) { f(b); }
+template <class F> void each_buffer(TwinBuf& b, F& f) { f(b.d); f(b.h); }
+// A building block's temporary: released on every way out of its scope.  (A slot's buffers live as long as the slot and stay plain.)
+template <class B> struct Scoped : B {
+  Scoped() = default;
+  Scoped(const Scoped&) = delete; Scoped& operator=(const Scoped&) = delete;
+  ~Scoped() { this->release(); }
 };
 
 // Pageable -> pinned, streaming: non-temporal stores.  An ordinary memcpy of a piece this size reads the destination lines
@@ -229,14 +250,15 @@ inline ImageLayout image_layout(uint32_t n, size_t raw_total, size_t dom_total, 
 }
 
 // The buffers of one capture extraction (a slot's, or zke_capture_batch's own): spans, flags, codes and the three tables in one
-// device buffer laid out by `L` (dfa_registry.hip.h, CapLayout), the rows of programs too large for LDS, and the pinned twin of
-// everything in front of the blob.
+// device buffer laid out by `L` (dfa_registry.hip.h, CapLayout) with a pinned twin of everything in front of the blob, and the rows
+// of programs too large for LDS.
 struct CapBufs {
-  DevBuf cap, work;
-  PinnedBuf h_cap;
+  TwinBuf t;
+  DevBuf work;
   CapLayout L{};
-  void release() { cap.release(); work.release(); h_cap.release(); }
+  void release() { t.release(); work.release(); }
 };
+template <class F> void each_buffer(CapBufs& b, F& f) { each_buffer(b.t, f); f(b.work); }
 
 // The buffers of one signature scan (a slot's): {counter | statuses | record slots | selector blob} in one device buffer with a
 // pinned twin of the same layout — the whole of it comes back as ONE copy —, and the overflow of the header span tables.
@@ -251,11 +273,11 @@ inline ScanLayout scan_layout(uint32_t n, uint32_t max_sigs, size_t blob_cap) {
   return L;
 }
 struct ScanBufs {
-  DevBuf out, ovf;
-  PinnedBuf h_out;
+  TwinBuf t;
+  DevBuf ovf;
   ScanLayout L{};
-  void release() { out.release(); ovf.release(); h_out.release(); }
 };
+template <class F> void each_buffer(ScanBufs& b, F& f) { each_buffer(b.t, f); f(b.ovf); }
 
 // The buffers of one key-record decode (a slot's): {infos | decoded keys at their records' offsets} in one device buffer with a pinned
 // twin — ONE copy back —, and, for zke_select_keys_from_records, the key section the front end reads: {key_off | key_type | packed blob}.
@@ -271,11 +293,11 @@ inline KeyrecLayout keyrec_layout(uint32_t m, size_t rec_total) {
   return L;
 }
 struct KeyrecBufs {
-  DevBuf out, pack;
-  PinnedBuf h_out;
+  TwinBuf t;
+  DevBuf pack;
   KeyrecLayout L{};
-  void release() { out.release(); pack.release(); h_out.release(); }
 };
+template <class F> void each_buffer(KeyrecBufs& b, F& f) { each_buffer(b.t, f); f(b.pack); }
 
 // The buffers of one body extraction (a slot's; zke_extract_bodies): {infos | first places | second places} in one device buffer
 // with a pinned twin.  E-mail i decodes into the first place at its raw offset; only a quoted-printable body that outgrows its e-mail
@@ -292,11 +314,11 @@ inline BodyLayout body_layout(uint32_t n, size_t raw_total) {
   return L;
 }
 struct BodyBufs {
-  DevBuf out, ovf;
-  PinnedBuf h_out;
+  TwinBuf t;
+  DevBuf ovf;
   BodyLayout L{};
-  void release() { out.release(); ovf.release(); h_out.release(); }
 };
+template <class F> void each_buffer(BodyBufs& b, F& f) { each_buffer(b.t, f); f(b.ovf); }
 // The compaction of a finished extraction, host code only, in two steps around the one copy that may lie between them.
 // body_measure: the device's infos (body_off = the e-mail's raw offset, reserved = its raw length: its place) checked against the
 // layout — an info that points outside its place is refused, nothing is read through it — and delivered with body_off rewritten to
@@ -348,13 +370,30 @@ inline OriginLayout origin_layout(uint32_t n, uint32_t G) {
   return L;
 }
 struct OriginBufs {
-  DevBuf org;
-  PinnedBuf h_org;
+  TwinBuf t;
   OriginLayout L{};
   bool launched = false;
 };
+template <class F> void each_buffer(OriginBufs& b, F& f) { each_buffer(b.t, f); }
 
 // The buffers of zke_qp_clean_batch (a slot's): the bodies and their offsets, cleaned bytes, index map, kept lengths.
 struct QpBufs { DevBuf in, off, clean, map, len; };
+template <class F> void each_buffer(QpBufs& b, F& f) { for (DevBuf* x : {&b.in, &b.off, &b.clean, &b.map, &b.len}) f(*x); }
+
+// What a slot owes the caller of its pending host batch: where each output goes once the batch's last copy has arrived.  A
+// default-constructed one owes nothing.  submit_host files it (pending_delivery), retire_host takes it out whole, deliver_pending
+// pays it (host_entry.hip.h).
+struct PendingDelivery {
+  zke_result* records = nullptr;       // the records as they are (a verify batch, an extraction) ...
+  uint32_t n = 0;
+  std::vector<uint32_t> sel_off;       // ... or folded per e-mail: cand_off of a key selection, rebased to 0 (n + 1 entries; empty: no selection)
+  zke_result* sel_out = nullptr;
+  uint32_t* sel_chosen = nullptr;
+  zke_sig_scan* scan = nullptr;
+  zke_keyrec_out* keyrec = nullptr;
+  zke_body_out* body = nullptr;
+  zke_capture_out* caps = nullptr;
+  zke_capture_origin* org = nullptr;   // (with caps only: a mapped extraction)
+};
 
 }  // namespace

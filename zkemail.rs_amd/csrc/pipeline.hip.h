@@ -1,5 +1,5 @@
 // pipeline.hip.h — the device pipeline of one batch: workspace sizing, the kernel sequence of verify_email /
-// verify_email_with_regex (core/src/circuits.rs:9-68) and the capture launches behind it, timing marks, a slot's acquire / release,
+// verify_email_with_regex (core/src/circuits.rs:9-68), the capture launches behind it and the side launches that run in its place, timing marks, a slot's acquire / release,
 // the entry for device-resident batches (zke_verify_batch_device).  Included by engine.hip (single translation unit).
 #pragma once
 
@@ -67,13 +67,16 @@ struct CaptureReq {
 };
 constexpr uint32_t CAP_WORK_WAVES = 256;      // waves of a capture launch whose rows live in the slot's workspace (one slice each)
 
-int ensure_capture_buffers(zke_engine* e, CapBufs& b, uint32_t n, uint32_t P, uint32_t G, size_t blob_cap, bool work) {
-  const CapLayout L = cap_layout(n, P, G, blob_cap);
+// A side output's buffers, grow only (the first batch of a shape allocates, a later one of the same shape does not): the twin, then
+// the extra device buffer where one is wanted.
+int ensure_side_buffers(zke_engine* e, TwinBuf& t, size_t device_bytes, size_t pinned_bytes, DevBuf* extra, size_t extra_bytes, const char* what) {
   int r = 0;
-  if ((r = b.cap.ensure(L.total)) || (r = b.h_cap.ensure(L.fixed_end)) ||
-      (work && (r = b.work.ensure((size_t)CAP_WORK_WAVES * CAP_WORK_WORDS * 8))))
-    return fail(e, r, "capture workspace allocation");
+  if ((r = t.ensure(device_bytes, pinned_bytes)) || (extra && (r = extra->ensure(extra_bytes)))) return fail(e, r, what);
   return 0;
+}
+// (b.L is the caller's to set: zke_engine_reserve grows a slot's capture buffers without touching the layout of a pending extraction)
+int ensure_capture_buffers(zke_engine* e, CapBufs& b, const CapLayout& L, bool work) {
+  return ensure_side_buffers(e, b.t, L.total, L.fixed_end, work ? &b.work : nullptr, (size_t)CAP_WORK_WAVES * CAP_WORK_WORDS * 8, "capture workspace allocation");
 }
 
 // Part p of a request: the requested groups (no registry involved: the sizes of the output follow from these alone) ...
@@ -110,7 +113,7 @@ void capture_resolve(zke_engine* e, CaptureReq& q) {
 int launch_capture(zke_engine* e, CapBufs& b, const CaptureReq& q, uint32_t n, bool plain, const DfaArgs& base,
                    const uint8_t* hay_blob, const uint64_t* hay_off, const PartRes* parts, zke_result* results, hipStream_t s) {
   const CapLayout& L = b.L;
-  uint8_t* cb = b.cap.as<uint8_t>();
+  uint8_t* cb = b.t.d.as<uint8_t>();
   CapArgs ca{};
   ca.plain = plain ? 1u : 0u; ca.n = n; ca.P = q.P; ca.G = q.G; ca.d = base; ca.n_header_parts = q.n_header_parts;
   ca.hay_blob = hay_blob; ca.hay_off = hay_off; ca.parts = parts;
@@ -135,13 +138,72 @@ int launch_capture(zke_engine* e, CapBufs& b, const CaptureReq& q, uint32_t n, b
 // A mapped extraction's third launch, behind the two above: the origins of the body parts' spans (qpmap.hip.h), one wave per e-mail.
 int launch_capture_origin(zke_engine* e, const CapBufs& b, OriginBufs& ob, const CaptureReq& q, uint32_t n, const DfaArgs& base,
                           const zke_result* results, hipStream_t s) {
-  uint8_t* op = ob.org.as<uint8_t>();
+  uint8_t* op = ob.t.d.as<uint8_t>();
   CapOriginArgs oa{};
   oa.n = n; oa.G = q.G; oa.gb0 = q.gbase[q.n_header_parts]; oa.d = base; oa.results = results;
-  oa.spans = reinterpret_cast<const uint32_t*>(b.cap.as<uint8_t>() + b.L.spans);
+  oa.spans = reinterpret_cast<const uint32_t*>(b.t.d.as<uint8_t>() + b.L.spans);
   oa.org_spans = reinterpret_cast<uint32_t*>(op); oa.org_flags = op + ob.L.flags;
   hipLaunchKernelGGL(capture_origin_kernel, dim3(n), dim3(64), 0, s, oa);
   HIPCHK(e, hipGetLastError());
+  return 0;
+}
+
+// ---- the stand-alone side launches of the host entry: ONE kernel over the batch `in` (the device-side view of the packed image)
+// instead of the verify pipeline, no verify workspace, the output in the side output's own buffers.
+// Their common tail: zke_timings.front_end_us is the launch, the other stages are empty; the twin's first `bytes` come back as one copy.
+int finish_side_launch(zke_engine* e, StageTimer& tm, const TwinBuf& t, size_t bytes, hipStream_t s) {
+  HIPCHK(e, hipGetLastError());
+  tm.mark(MK_FRONT); tm.mark(MK_HASH); tm.mark(MK_VERDICT);
+  HIPCHK(e, t.fetch(bytes, s));
+  return 0;
+}
+// zke_scan_signatures: the counter of selector bytes starts at zero, everything comes back
+int launch_scan(zke_engine* e, ScanBufs& b, const zke_batch& in, uint64_t now, StageTimer& tm, hipStream_t s) {
+  const ScanLayout& S = b.L;
+  uint8_t* so = b.t.d.as<uint8_t>();
+  HIPCHK(e, hipMemsetAsync(so, 0, 64, s));
+  SigScanArgs sa{};
+  sa.n = in.n; sa.max_sigs = S.max_sigs;
+  sa.raw = in.raw_blob; sa.raw_off = in.raw_off; sa.dom = in.domain_blob; sa.dom_off = in.domain_off;
+  sa.strict = e->strict; sa.now = now;
+  sa.status = reinterpret_cast<uint32_t*>(so + S.status);
+  sa.recs = reinterpret_cast<zke_sig_info*>(so + S.recs);
+  sa.sel_blob = so + S.blob; sa.sel_cap = (uint32_t)S.blob_cap;
+  sa.sel_used = reinterpret_cast<uint32_t*>(so);
+  sa.hdr_ovf = b.ovf.as<uint32_t>();
+  hipLaunchKernelGGL(sigscan_kernel, dim3(in.n), dim3(64), 0, s, sa);
+  return finish_side_launch(e, tm, b.t, S.total, s);
+}
+// zke_extract_bodies: over the e-mails (the image's raw section); infos and first places come back (the second places: deliver_body)
+int launch_body(zke_engine* e, BodyBufs& b, const zke_batch& in, uint32_t flags, StageTimer& tm, hipStream_t s) {
+  const BodyLayout& K = b.L;
+  uint8_t* bo = b.t.d.as<uint8_t>();
+  const BodyArgs ba{in.n, flags, in.raw_blob, in.raw_off, reinterpret_cast<zke_body_info*>(bo), bo + K.bytes, (uint64_t)K.region, b.ovf.as<uint32_t>()};
+  hipLaunchKernelGGL(body_extract_kernel, dim3(in.n), dim3(64), 0, s, ba);
+  return finish_side_launch(e, tm, b.t, K.first_copy, s);
+}
+// zke_decode_key_records: over the records (the image's raw section); infos and keys come back
+KeyrecArgs keyrec_args_of(const KeyrecBufs& b, uint32_t n, uint32_t mode, const uint8_t* blob, const uint64_t* off) {
+  uint8_t* ko = b.t.d.as<uint8_t>();
+  return KeyrecArgs{n, mode, blob, off, reinterpret_cast<zke_key_info*>(ko), ko + b.L.keys};
+}
+int launch_keyrec(zke_engine* e, KeyrecBufs& b, const zke_batch& in, uint32_t mode, StageTimer& tm, hipStream_t s) {
+  const KeyrecArgs ka = keyrec_args_of(b, in.n, mode, in.raw_blob, in.raw_off);
+  hipLaunchKernelGGL(keyrec_kernel, dim3(in.n), dim3(64), 0, s, ka);
+  return finish_side_launch(e, tm, b.t, b.L.total, s);
+}
+// zke_select_keys_from_records, in front of the verify pipeline: the image's key section holds the candidates' RECORDS — decode them,
+// then scan the lengths and gather the keys into the packed CSR the front end reads, which `in` points to from here on.  Three small
+// launches, the keys never leave HBM.
+int launch_keyrec_prefix(zke_engine* e, KeyrecBufs& b, zke_batch& in, uint32_t mode, hipStream_t s) {
+  uint8_t* pk = b.pack.as<uint8_t>();
+  const KeyrecArgs ka = keyrec_args_of(b, in.n, mode, in.key_blob, in.key_off);
+  hipLaunchKernelGGL(keyrec_kernel, dim3(in.n), dim3(64), 0, s, ka);
+  const KeyrecPackArgs pa{in.n, ka.infos, ka.keys, reinterpret_cast<uint64_t*>(pk), pk + b.L.p_type, pk + b.L.p_blob};
+  hipLaunchKernelGGL(keyrec_pack_kernel, dim3(1), dim3(64), 0, s, pa);
+  hipLaunchKernelGGL(keyrec_gather_kernel, dim3(in.n), dim3(64), 0, s, pa);
+  HIPCHK(e, hipGetLastError());
+  in.key_blob = pa.key_blob; in.key_off = pa.key_off; in.key_type = pa.key_type;
   return 0;
 }
 
@@ -387,7 +449,7 @@ int zke_engine_reserve(zke_engine* e, uint32_t max_n, uint64_t max_raw_total, ui
       if (int r = ensure_workspace(e, *w, max_n, max_raw_total, max_regex_parts != 0, max_regex_parts, false, w->stream)) return r;
   if (max_n && max_regex_parts)          // the capture workspace: four groups of 32 bytes per part is what a larger extraction regrows from
     for (Slot* w : e->slots)
-      if (int r = ensure_capture_buffers(e, w->cb, max_n, max_regex_parts, 4 * max_regex_parts, (size_t)max_n * max_regex_parts * 128, true)) return r;
+      if (int r = ensure_capture_buffers(e, w->cb, cap_layout(max_n, max_regex_parts, 4 * max_regex_parts, (size_t)max_n * max_regex_parts * 128), true)) return r;
 
   // A stream's hardware queue and the queue's scratch memory (the front end spills a few registers) come into being
   // with the first launch that needs them — milliseconds, and they would land in the first batch of every slot.
