@@ -10,14 +10,120 @@
 //     into exact-size caller buffers, every capacity from none to plenty;
 //   * deliver_pending (a slot's pending-delivery record paid in one call) against those individual calls, every kind of batch, and
 //     the shortfall rule with each variable-size buffer one byte too small;
-//   * zke_shard_bounds, image_layout, pair_hash on edge sizes.
+//   * zke_shard_bounds, image_layout, pair_hash on edge sizes;
+//   * the hash / modexp stage's plan (stage_plan.hip.h) and the launches made from it, over a fixed grid of engines and batches:
+//     kernel launches are recorded instead of made, one line per case, and `--stage-plan OUT` writes the lines to OUT, which
+//     tests/test_host_sanitizers.py compares with tests/golden/stage_plan.txt (recorded before the plan had a module of its own).
 // tests/test_host_sanitizers.py builds and runs it.  (The same source with -fsanitize=thread instead: clean as well, run by hand —
 // the second 40 s build is not worth a place in the suite.)
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+
+#include <string>
+#include <utility>
+
+// Every kernel launch of the translation unit is recorded, not made: the kernel by name, grid x block, the dynamic LDS bytes and,
+// for a launch that takes StageArgs, the workgroups per role.  hipGetLastError() has no device to ask here and would end a
+// sequence of launches after the first.
+namespace plan_rec {
+std::string line;                                    // the launches of the case at hand
+const char* kernel_name(const void* k);              // (defined below, where the kernels are)
+template <class T> auto describe(const T& a, int) -> decltype((void)a.g_oct9, void()) {
+  line += " sha=" + std::to_string(a.g_sha) + " wave=" + std::to_string(a.g_wave) + " quad=" + std::to_string(a.g_quad) +
+          " oct=" + std::to_string(a.g_oct) + " oct9=" + std::to_string(a.g_oct9) + " twin=" + std::to_string(a.twin_kinds);
+}
+template <class T> void describe(const T&, long) {}
+template <class... A> void launch(const void* k, dim3 grid, dim3 block, size_t lds, const A&... a) {
+  line += std::string(" | ") + kernel_name(k) + " " + std::to_string(grid.x) + "x" + std::to_string(block.x) + " lds=" + std::to_string(lds);
+  (describe(a, 0), ...);
+}
+}  // namespace plan_rec
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(k, grid, block, lds, stream, ...) plan_rec::launch(reinterpret_cast<const void*>(k), grid, block, lds, __VA_ARGS__)
+#define hipGetLastError() hipSuccess
+
 #include "../../zkemail.rs_amd/csrc/engine.hip"
 
 #include <array>
 #include <random>
 #include <thread>
+
+const char* plan_rec::kernel_name(const void* k) {
+#define NAMED(kernel) {reinterpret_cast<const void*>(kernel<SHA_TILE>), #kernel}
+  static const std::pair<const void*, const char*> names[] = {
+      NAMED(sha256_batch_kernel), NAMED(sha256_pair_kernel), NAMED(sha256_ring_kernel), NAMED(sha256_twin_kernel),
+      NAMED(hash_modexp_kernel), NAMED(hash_modexp_ring_kernel), NAMED(hash_modexp_twin_kernel)};
+#undef NAMED
+  for (const auto& nm : names) if (nm.first == k) return nm.second;
+  return "another kernel";
+}
+
+// One engine of the grid: what the plan depends on besides the batch.
+struct PlanCase { uint32_t slots, queues; int oct9, ring, twin; uint32_t kinds, lanes, sha_mapping, cache; };
+static void plan_engine(zke_engine& eng, const PlanCase& c) {
+  StageEnv& v = eng.stage;
+  v.slots = c.slots; v.hw_queues = c.queues;
+  v.rsa_oct9 = c.oct9; v.sha_ring = c.ring; v.sha_twin = c.twin; v.twin_kinds = c.kinds;
+  v.rsa_lane_groups = c.lanes; v.sha_mapping = c.sha_mapping; v.key_cache = c.cache != 0;
+}
+// A batch of n e-mails through the plan and the stage's launches, as run_device_pipeline does it; returns the route mask
+static uint32_t plan_run_stage(zke_engine& eng, uint32_t n, bool any_big, bool have_order, uint32_t last_wave_jobs) {
+  static const uint32_t some_words[4] = {};
+  const uint32_t n_pad = (n + 63) & ~63u;
+  const StagePlan plan = plan_stage(eng.stage, n, 4 * n_pad, any_big, have_order, last_wave_jobs);
+  if (launch_hash_modexp(&eng, plan, nullptr, 4 * n_pad, nullptr, n, nullptr, nullptr, some_words, some_words, have_order ? some_words : nullptr, nullptr)) exit(1);
+  return plan.route_mask;
+}
+static void plan_run_sha(zke_engine& eng, uint32_t n) {
+  if (launch_sha(&eng, plan_sha(eng.stage, n), nullptr, n, nullptr)) exit(1);
+}
+// The grid.  The option axes vary one at a time around the defaults, on both sides of the in-flight bound.
+static std::string stage_plan_table() {
+  const uint32_t U = 0xFFFFFFFFu;
+  std::vector<PlanCase> engines;
+  for (auto sq : {std::pair<uint32_t, uint32_t>{1, 4}, {4, 23}, {5, 4}, {5, 8}, {22, 23}}) engines.push_back({sq.first, sq.second, -1, -1, -1, 3, 0, 0, 1});
+  for (auto sq : {std::pair<uint32_t, uint32_t>{1, 4}, {22, 23}}) {
+    const PlanCase d{sq.first, sq.second, -1, -1, -1, 3, 0, 0, 1};
+    auto with = [&](auto change) { PlanCase c = d; change(c); engines.push_back(c); };
+    for (int f : {0, 1}) { with([&](PlanCase& c) { c.oct9 = f; }); with([&](PlanCase& c) { c.ring = f; }); with([&](PlanCase& c) { c.twin = f; }); }
+    with([](PlanCase& c) { c.ring = 0; c.twin = 1; });
+    with([](PlanCase& c) { c.ring = 1; c.twin = 0; });
+    for (uint32_t k : {1u, 0u}) { with([&](PlanCase& c) { c.kinds = k; }); with([&](PlanCase& c) { c.kinds = k; c.ring = 1; c.twin = 1; }); }
+    for (uint32_t l : {1u, 2u}) with([&](PlanCase& c) { c.lanes = l; });
+    for (int f : {0, 1}) with([&](PlanCase& c) { c.lanes = 2; c.oct9 = f; });
+    for (uint32_t m : {1u, 2u}) with([&](PlanCase& c) { c.sha_mapping = m; });
+    with([](PlanCase& c) { c.cache = 0; });
+  }
+  std::string table = "# e = slots / hardware queues / forced oct9 / ring / twin (-1: not forced) / twin_kinds / rsa_lane_groups / sha_mapping / key cache;"
+                      " last = -1: nothing known; ring, twin: zke_engine_sha_ring / _twin; then the launches: kernel grid x block, LDS bytes, StageArgs\n";
+  char buf[160];
+  for (size_t k = 0; k < engines.size(); k++) {
+    const PlanCase& c = engines[k];
+    zke_engine eng;
+    plan_engine(eng, c);
+    snprintf(buf, sizeof buf, "e=%u/%u/%d/%d/%d/%u/%u/%u/%u", c.slots, c.queues, c.oct9, c.ring, c.twin, c.kinds, c.lanes, c.sha_mapping, c.cache);
+    const std::string env = buf;
+    snprintf(buf, sizeof buf, " ring=%d twin=%d", zke_engine_sha_ring(&eng), zke_engine_sha_twin(&eng));
+    const std::string abi = buf;
+    auto stage = [&](uint32_t n, int big, int order, uint32_t last) {
+      plan_rec::line.clear();
+      const uint32_t mask = plan_run_stage(eng, n, big != 0, order != 0, last);
+      snprintf(buf, sizeof buf, " n=%u big=%d order=%d last=%d mask=%u", n, big, order, (int)last, mask);
+      table += "stage " + env + buf + abi + plan_rec::line + "\n";
+    };
+    for (uint32_t n : {1u, 127u, 128u, 255u, 256u, 1000u, 8192u, 8256u}) {
+      stage(n, 0, 1, U); stage(n, 1, 1, U); stage(n, 0, 0, U);
+      if (k < 5) { stage(n, 1, 0, U); for (uint32_t last : {0u, 5u, 100000u}) stage(n, 0, 1, last); }       // (the walkers' count depends on nothing else)
+    }
+    for (uint32_t n : {0u, 1u, 32u, 33u, 64u, 32768u, 32769u}) {
+      plan_rec::line.clear();
+      plan_run_sha(eng, n);
+      snprintf(buf, sizeof buf, " n=%u", n);
+      table += "sha " + env + buf + abi + plan_rec::line + "\n";
+    }
+  }
+  return table;
+}
 
 static std::vector<uint8_t> slurp(const char* path) {
   std::vector<uint8_t> v;
@@ -30,7 +136,59 @@ static std::vector<uint8_t> slurp(const char* path) {
 }
 
 int main(int argc, char** argv) {
-  if (argc < 4) { fprintf(stderr, "usage: host_fuzz fwd.dfa rev.dfa record.bin [record2.bin ...]\n"); return 2; }
+  // ---- the stage plan over its grid (`--stage-plan OUT` alone: only this section, to regenerate the table)
+  {
+    const std::string table = stage_plan_table();
+    if (argc >= 3 && !strcmp(argv[1], "--stage-plan")) {
+      FILE* f = fopen(argv[2], "wb");
+      if (!f || fwrite(table.data(), 1, table.size(), f) != table.size() || fclose(f)) { fprintf(stderr, "cannot write %s\n", argv[2]); return 2; }
+      if (argc == 3) return 0;
+      argv += 2; argc -= 2;
+    }
+  }
+  // ---- the environment's part of a StageEnv: each variable alone, unreadable queue counts, the two thresholds in builds with the knobs only
+  {
+    const char* const names[] = {"GPU_MAX_HW_QUEUES", "ZKE_RSA_OCT9", "ZKE_SHA_RING", "ZKE_SHA_TWIN", "ZKE_SHA_TWIN_KINDS", "ZKE_RSA_QUAD_MIN", "ZKE_RSA_OCT_MIN"};
+    std::vector<std::pair<const char*, std::string>> kept;
+    for (const char* nm : names) if (const char* v = getenv(nm)) kept.emplace_back(nm, v);
+    auto read = [&](const char* name, const char* value) {
+      for (const char* nm : names) unsetenv(nm);
+      if (name) setenv(name, value, 1);
+      StageEnv v;
+      stage_env_from_environment(v);
+      return v;
+    };
+    auto same = [](const StageEnv& a, const StageEnv& b) {
+      return a.slots == b.slots && a.hw_queues == b.hw_queues && a.rsa_oct9 == b.rsa_oct9 && a.sha_ring == b.sha_ring && a.sha_twin == b.sha_twin && a.twin_kinds == b.twin_kinds &&
+             a.rsa_quad_min == b.rsa_quad_min && a.rsa_oct_min == b.rsa_oct_min && a.sha_mapping == b.sha_mapping && a.rsa_lane_groups == b.rsa_lane_groups && a.key_cache == b.key_cache;
+    };
+    auto expect = [&](const char* name, const char* value, auto change) {
+      StageEnv want; change(want);
+      if (!same(read(name, value), want)) { fprintf(stderr, "stage_env_from_environment: %s=%s\n", name ? name : "(nothing set)", value ? value : ""); exit(1); }
+    };
+    expect(nullptr, nullptr, [](StageEnv&) {});
+    expect("GPU_MAX_HW_QUEUES", "23", [](StageEnv& v) { v.hw_queues = 23; });
+    for (const char* bad : {"", "0", "-3", "many"}) expect("GPU_MAX_HW_QUEUES", bad, [](StageEnv& v) { v.hw_queues = 4; });
+    for (int f : {0, 1}) {
+      const char* val = f ? "1" : "0";
+      expect("ZKE_RSA_OCT9", val, [&](StageEnv& v) { v.rsa_oct9 = f; });
+      expect("ZKE_SHA_RING", val, [&](StageEnv& v) { v.sha_ring = f; });
+      expect("ZKE_SHA_TWIN", val, [&](StageEnv& v) { v.sha_twin = f; });
+    }
+    expect("ZKE_SHA_RING", "7", [](StageEnv& v) { v.sha_ring = 1; });
+    expect("ZKE_SHA_TWIN_KINDS", "0", [](StageEnv& v) { v.twin_kinds = 0; });
+    expect("ZKE_SHA_TWIN_KINDS", "6", [](StageEnv& v) { v.twin_kinds = 2; });
+#ifdef ZKE_DEV_KNOBS
+    expect("ZKE_RSA_QUAD_MIN", "64", [](StageEnv& v) { v.rsa_quad_min = 64; });
+    expect("ZKE_RSA_OCT_MIN", "32", [](StageEnv& v) { v.rsa_oct_min = 32; });
+#else
+    expect("ZKE_RSA_QUAD_MIN", "64", [](StageEnv&) {});
+    expect("ZKE_RSA_OCT_MIN", "32", [](StageEnv&) {});
+#endif
+    for (const char* nm : names) unsetenv(nm);
+    for (const auto& kv : kept) setenv(kv.first, kv.second.c_str(), 1);
+  }
+  if (argc < 4) { fprintf(stderr, "usage: host_fuzz [--stage-plan out.txt] fwd.dfa rev.dfa record.bin [record2.bin ...]\n"); return 2; }
   std::mt19937_64 rng(12345);
   size_t cases = 0;
   // ---- dense DFA blobs

@@ -62,7 +62,6 @@ struct DevBuf {
 
 inline uint32_t e_k(uint32_t bits) { return (bits + 7) / 8; }
 constexpr int SHA_TILE = 128;                      // bytes of a message per LDS tile (sha256.hip.h)
-constexpr uint32_t SHA_PAIR_MAX_GROUPS = 512;      // launches of up to 32 768 messages use two waves per 64 messages (zke_options.sha_mapping forces either)
 
 }  // namespace
 
@@ -153,24 +152,7 @@ struct zke_engine {
   std::atomic<uint64_t> reg_clock{0};
   size_t dfa_lds_attr = 0, dfa_wave_lds_attr = 0;
   CopyPool* pool = nullptr;
-  uint32_t rsa_quad_min = 256;      // lane-group RSA routines join batches of at least this many e-mails (four lanes; moduli <= 2048 bits).
-                                    // Low since the modexp runs beside SHA-256 (fused.hip.h): its longer chain no longer sits behind the
-                                    // hashes of a small batch; a handful of e-mails is still answered sooner by one signature per wave
-  uint32_t rsa_oct_min = 128;       // ... eight lanes (moduli above 2048 bits)
-  uint32_t hw_queues = 4;           // GPU_MAX_HW_QUEUES as read once, at creation (unset: HIP's default of 4).  Streams beyond HIP's queue pool
-                                    // share a queue, and a queue runs its kernels one after the other: min(slots that exist, hw_queues)
-                                    // batches of this engine can be on the chip at once (rsa_route_mask)
-  int rsa_oct9 = -1;                // moduli <= 2048 bits on eight lanes of nine limbs instead of four of eighteen (rsa_quad.hip.h):
-                                    // -1 by the in-flight bound (rsa_route_mask), 0 never, 1 always (ZKE_RSA_OCT9 in the environment)
-  int sha_ring = -1;                // the two-wave SHA-256 groups run sha256_ring_group (two K+W buffers, 45 KB of LDS per group) instead of
-                                    // sha256_pair_group (one, 28 KB): -1 by the same in-flight bound (sha_takes_ring), 0 never, 1 always
-                                    // (ZKE_SHA_RING in the environment)
-  int sha_twin = -1;                // where the ring is taken, bodies and header preimages run sha256_twin_group (two lanes per message in the
-                                    // rounds wave, 32 messages per group): -1 the default (SHA_TWIN_DEFAULT), 0 never, 1 wherever the ring is
-                                    // taken (ZKE_SHA_TWIN in the environment)
-  uint32_t sha_twin_kinds = 3;      // which kinds of the hash / modexp launch the twin takes (bit 0 bodies, bit 1 header preimages; domains and
-                                    // keys are one block each and keep 64-wide ring groups: 32 more workgroups per batch would keep the RSA
-                                    // roles waiting for room).  ZKE_SHA_TWIN_KINDS in the environment, for A/B runs
+  StageEnv stage;                   // what the choice of the hash / modexp stage's routines depends on besides the batch (stage_plan.hip.h)
 #ifdef ZKE_DEV_KNOBS
   uint32_t debug_skip_rsa = 0, debug_skip_ed = 0, debug_parse_stop = 0, debug_skip_launch = 0;
 #else
@@ -190,40 +172,23 @@ int fail(zke_engine* e, int code, const char* what, hipError_t he = hipSuccess) 
 }
 #define HIPCHK(e, call) do { hipError_t _r = (call); if (_r != hipSuccess) return fail((e), ZKE_E_DEVICE, #call, _r); } while (0)
 
-// Two waves per 64 messages (sha256_pair_group) or one (sha256_batch_kernel) for a hash launch of `groups` groups of 64 messages.
-// zke_options.sha_mapping: 0 = by launch size, 1 always one wave, 2 always two.
-bool sha_takes_pairs(const zke_engine* e, uint32_t groups) {
-  return e->opt.sha_mapping ? e->opt.sha_mapping == 2 : groups <= SHA_PAIR_MAX_GROUPS;
-}
+// The kernels that take dynamic LDS, one column per SHA-256 routine (stage_plan.hip.h says which routine a launch takes): the routine as a
+// launch of its own, the hash / modexp stage whose SHA-256 groups run it (fused.hip.h; the one-wave kernel has no stage), and the routine's
+// workgroup size and LDS bytes — a stage's RSA roles borrow the front of the same LDS.  set_kernel_attrs and the launches both read this table.
+// (The columns stand in ShaRoutine's order, which is also the order in which the kernels have always been emitted into the code object.)
+using ShaKernel = void (*)(const ShaJob*, uint32_t);
+using StageKernel = void (*)(StageArgs);
+constexpr size_t N_ROUTINES = (size_t)ShaRoutine::BATCH + 1;
+//                                                  TWIN                               RING                               PAIR                               BATCH
+const ShaKernel   SHA_KERNEL[N_ROUTINES]   = {sha256_twin_kernel<SHA_TILE>,      sha256_ring_kernel<SHA_TILE>,      sha256_pair_kernel<SHA_TILE>,      sha256_batch_kernel<SHA_TILE>};
+const StageKernel STAGE_KERNEL[N_ROUTINES] = {hash_modexp_twin_kernel<SHA_TILE>, hash_modexp_ring_kernel<SHA_TILE>, hash_modexp_kernel<SHA_TILE>,      nullptr};
+const uint32_t    ROUTINE_BLOCK[N_ROUTINES] = {128,                              128,                               128,                               256};
+const size_t      ROUTINE_LDS[N_ROUTINES]  = {sha256_ring_lds_bytes<SHA_TILE>(), sha256_ring_lds_bytes<SHA_TILE>(), sha256_pair_lds_bytes<SHA_TILE>(), sha256_lds_bytes<SHA_TILE>()};
 
-// Which two-wave routine.  The ring takes the K+W hand-over off the rounds wave's chain (sha256.hip.h) for 17 KB more LDS per group: the
-// choice where a batch's time is its dependency chain, i.e. with at most SHA_RING_MAX_IN_FLIGHT batches on the chip — min(slots that
-// exist now, hardware queues), as for the eight-lane RSA role (rsa_route_mask).  With more the chip is issue- and LDS-bound: the pair.
-constexpr uint32_t SHA_RING_MAX_IN_FLIGHT = 4;
-bool sha_takes_ring(const zke_engine* e) {
-  if (e->sha_ring >= 0) return e->sha_ring == 1;
-  return std::min<uint32_t>((uint32_t)e->slots.size(), e->hw_queues) <= SHA_RING_MAX_IN_FLIGHT;
-}
-
-// The twin is a refinement of the ring: the same roles, buffers and LDS, a shorter rounds chain (sha256.hip.h).
-constexpr bool SHA_TWIN_DEFAULT = true;
-bool sha_takes_twin(const zke_engine* e) {
-  return sha_takes_ring(e) && (e->sha_twin >= 0 ? e->sha_twin == 1 : SHA_TWIN_DEFAULT);
-}
-
-int launch_sha(zke_engine* e, const ShaJob* jobs, uint32_t n, hipStream_t s) {
-  if (n == 0) return 0;
-  // Few messages: the launch is as long as one wave's chain of compressions, so split the chain over two waves
-  // (sha256_pair_kernel).  Many messages: the chip is full and the one-wave kernel does less LDS work per byte.
-  const uint32_t groups = (n + 63) / 64;
-  if (sha_takes_pairs(e, groups)) {
-    if (sha_takes_twin(e))
-      hipLaunchKernelGGL(sha256_twin_kernel<SHA_TILE>, dim3((n + SHA_TWIN_WIDTH - 1) / SHA_TWIN_WIDTH), dim3(128), sha256_ring_lds_bytes<SHA_TILE>(), s, jobs, n);
-    else if (sha_takes_ring(e)) hipLaunchKernelGGL(sha256_ring_kernel<SHA_TILE>, dim3(groups), dim3(128), sha256_ring_lds_bytes<SHA_TILE>(), s, jobs, n);
-    else hipLaunchKernelGGL(sha256_pair_kernel<SHA_TILE>, dim3(groups), dim3(128), sha256_pair_lds_bytes<SHA_TILE>(), s, jobs, n);
-  } else {
-    hipLaunchKernelGGL(sha256_batch_kernel<SHA_TILE>, dim3((n + 255) / 256), dim3(256), sha256_lds_bytes<SHA_TILE>(), s, jobs, n);
-  }
+int launch_sha(zke_engine* e, const ShaPlan& plan, const ShaJob* jobs, uint32_t n, hipStream_t s) {
+  if (!plan.grid) return 0;
+  const size_t r = (size_t)plan.routine;
+  hipLaunchKernelGGL(SHA_KERNEL[r], dim3(plan.grid), dim3(ROUTINE_BLOCK[r]), ROUTINE_LDS[r], s, jobs, n);
   HIPCHK(e, hipGetLastError());
   return 0;
 }
@@ -269,104 +234,34 @@ int drain_engine(zke_engine* e, bool copy_streams) {
   return 0;
 }
 
-// Which lane-group RSA kernels take part in a batch of n e-mails.  Bit 0: four lanes per signature (moduli <= 2048 bits),
-// bit 1: eight lanes (2049..4096 bits; any_big = the caller's hint that the batch's keys average more than an RSA-2048 key).
-// The front end routes signatures by this mask and the hash / modexp launch gets the matching workgroups: the same value
-// must go to both.  zke_options.rsa_lane_groups: 0 = by batch size, 1 never, 2 always.
-// Bit 2 instead of bit 0: moduli <= 2048 bits take eight lanes of nine limbs.  That routine's chain per product is a third shorter
-// (2 520 instead of 3 684 instructions, profiles/oct9_static.txt) and it issues 1.4 times the instructions per signature, so it is
-// the choice when the engine cannot fill the chip's issue slots: with at most RSA_OCT9_MAX_IN_FLIGHT batches on the chip a batch's
-// time is its dependency chain (DESIGN.md §5 has the sweep over the queue count).  The bound is min(slots, hardware queues) with the
-// slots that exist NOW — zke_engine_reserve only appends, and an engine created with one slot and grown to 22 counts 22 — so an
-// engine with more than four slots on more than four queues keeps four lanes.  Only the choice by batch size is made this way:
-// rsa_lane_groups = 2 asks for the routines by name and keeps four lanes unless the environment says otherwise.
-constexpr uint32_t RSA_OCT9_MAX_IN_FLIGHT = 4;
-uint32_t rsa_route_mask(const zke_engine* e, uint32_t n, bool any_big) {
-  if (!e->key_cache.p || e->opt.rsa_lane_groups == 1) return 0;
-  const bool always = e->opt.rsa_lane_groups == 2;
-  const uint32_t in_flight_max = std::min<uint32_t>((uint32_t)e->slots.size(), e->hw_queues);
-  const bool oct9 = e->rsa_oct9 >= 0 ? e->rsa_oct9 == 1 : !always && in_flight_max <= RSA_OCT9_MAX_IN_FLIGHT;
-  uint32_t m = 0;
-  if (always || n >= e->rsa_quad_min) m |= oct9 ? 4u : 1u;
-  if (any_big && (always || n >= e->rsa_oct_min)) m |= 2u;
-  return m;
-}
-
-int launch_stage(zke_engine* e, const StageArgs& A, hipStream_t s) {
-  const uint32_t grid = A.g_sha + A.g_wave + A.g_quad + A.g_oct + A.g_oct9;
-  if (!grid) return 0;
-  if (A.g_sha && A.twin_kinds) hipLaunchKernelGGL(hash_modexp_twin_kernel<SHA_TILE>, dim3(grid), dim3(128), sha256_ring_lds_bytes<SHA_TILE>(), s, A);
-  else if (A.g_sha && sha_takes_ring(e)) hipLaunchKernelGGL(hash_modexp_ring_kernel<SHA_TILE>, dim3(grid), dim3(128), sha256_ring_lds_bytes<SHA_TILE>(), s, A);
-  else hipLaunchKernelGGL(hash_modexp_kernel<SHA_TILE>, dim3(grid), dim3(128), sha256_pair_lds_bytes<SHA_TILE>(), s, A);
-  HIPCHK(e, hipGetLastError());
-  return 0;
-}
-
-// The hash / modexp stage of a batch (fused.hip.h): SHA-256 of the 4 * n_pad messages and the RSA operation of the n jobs.
-// Launches of up to SHA_PAIR_MAX_GROUPS SHA-256 groups (every BASELINE-sized batch) are ONE kernel; beyond that the chip
-// is full of SHA-256 waves anyway: sha256_batch_kernel first, then the RSA roles as a launch of their own.
-// The one-signature-per-wave role walks the front end's job list: the e-mails whose key is not cached yet (or that the
-// lane-group routines do not take).  Once a stream of batches has its keys cached the list is empty, and every workgroup of the
-// role still has to be given LDS and registers on a full chip just to look and leave (57 % of the launch's waves did nothing
-// else).  So the role is sized by what the slot's PREVIOUS batch needed — its verdict launch leaves the list's length in a
-// pinned word, no synchronisation, one batch stale —: 8 workgroups when that was empty, up to 128 (256 waves: a batch of 1 024
-// uncached keys takes four rounds of them) when every key was new.  The walkers loop, so a wrong guess costs time, never work.
-#ifndef ZKE_WAVE_ROLE_MAX_GROUPS
-#define ZKE_WAVE_ROLE_MAX_GROUPS 128
-#endif
-#ifndef ZKE_WAVE_ROLE_MIN_GROUPS
-#define ZKE_WAVE_ROLE_MIN_GROUPS 8
-#endif
-int launch_hash_modexp(zke_engine* e, const ShaJob* sha, uint32_t n_sha, const RsaJob* rsa, uint32_t n, EmailMeta* meta,
-                       uint8_t* em_out, uint32_t route_mask, const uint32_t* wave_count, const uint32_t* wave_list, const uint32_t* order,
-                       uint32_t last_wave_jobs, hipStream_t s) {
+// The hash / modexp stage of a batch (fused.hip.h) as its plan says: SHA-256 of the 4 * n_pad messages and the RSA operation of the n jobs,
+// one launch — or, beyond the plan's threshold, SHA-256 in front and the RSA roles as a launch of their own.
+int launch_hash_modexp(zke_engine* e, const StagePlan& plan, const ShaJob* sha, uint32_t n_sha, const RsaJob* rsa, uint32_t n, EmailMeta* meta,
+                       uint8_t* em_out, const uint32_t* wave_count, const uint32_t* wave_list, const uint32_t* order, hipStream_t s) {
   StageArgs A{};
   A.order = order; A.n_pad = n_sha / 4;
   A.sha = sha; A.n_sha = n_sha; A.rsa = rsa; A.n = n; A.meta = meta;
   A.cache = e->key_cache.as<KeyCacheEntry>();
   A.em_out = em_out;
   A.wave_count = wave_count; A.wave_list = wave_list;
-  A.g_wave = (n + 1) / 2;
-  if (wave_list) {
-    const uint32_t want = last_wave_jobs == 0xFFFFFFFFu ? ZKE_WAVE_ROLE_MAX_GROUPS
-                                                        : std::max<uint32_t>(ZKE_WAVE_ROLE_MIN_GROUPS, (std::min<uint32_t>(last_wave_jobs, n) + 1) / 2);
-    A.g_wave = std::min<uint32_t>(A.g_wave, std::min<uint32_t>(want, ZKE_WAVE_ROLE_MAX_GROUPS));
-  }
-  A.g_quad = (route_mask & 1u) ? (n + 31) / 32 : 0;
-  A.g_oct = (route_mask & 2u) ? (n + 15) / 16 : 0;
-  A.g_oct9 = (route_mask & 4u) ? (n + 15) / 16 : 0;
+  A.g_sha = plan.g_sha; A.g_wave = plan.g_wave; A.g_quad = plan.g_quad; A.g_oct = plan.g_oct; A.g_oct9 = plan.g_oct9;
+  A.twin_kinds = plan.twin_kinds;
   A.debug_skip_rsa = e->debug_skip_rsa;
-  const uint32_t groups = (n_sha + 63) / 64;
-  if (sha_takes_pairs(e, groups)) {
-    // Launches without a kind layout keep 64-wide groups.  Launches with the RSA-4096 role (route bit 1) take the twin like the
-    // others: keeping them on the ring was tried and measured slower (profiles/sha_twin_bench_ab.txt, section 4).
-    if (order && sha_takes_twin(e)) A.twin_kinds = e->sha_twin_kinds;
-    A.g_sha = A.twin_kinds ? sha_stage_groups(A.n_pad, A.twin_kinds) : groups;
-    return launch_stage(e, A, s);
-  }
-  if (int r = launch_sha(e, sha, n_sha, s)) return r;      // (beyond 512 groups: arrival order; the chip is full either way)
-  A.g_sha = 0;
-  return launch_stage(e, A, s);
+  if (int r = launch_sha(e, plan.front, sha, n_sha, s)) return r;
+  if (!plan.grid()) return 0;
+  const size_t r = (size_t)plan.routine;
+  hipLaunchKernelGGL(STAGE_KERNEL[r], dim3(plan.grid()), dim3(ROUTINE_BLOCK[r]), ROUTINE_LDS[r], s, A);
+  HIPCHK(e, hipGetLastError());
+  return 0;
 }
 
 // Every hipFuncSetAttribute the pipeline needs, once per engine (= per device) at creation — never lazily in the submit
 // path, where a first use would land inside somebody's timed region.  The DFA kernels' LDS sizes depend on the registered
 // tables: zke_dfa_register raises them.
 int set_kernel_attrs(zke_engine* e) {
-  HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&sha256_batch_kernel<SHA_TILE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_lds_bytes<SHA_TILE>()));
-  HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&sha256_pair_kernel<SHA_TILE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_pair_lds_bytes<SHA_TILE>()));
-  HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&hash_modexp_kernel<SHA_TILE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_pair_lds_bytes<SHA_TILE>()));
-  HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&sha256_ring_kernel<SHA_TILE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_ring_lds_bytes<SHA_TILE>()));
-  HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&hash_modexp_ring_kernel<SHA_TILE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_ring_lds_bytes<SHA_TILE>()));
-  HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&sha256_twin_kernel<SHA_TILE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_ring_lds_bytes<SHA_TILE>()));
-  HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&hash_modexp_twin_kernel<SHA_TILE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sha256_ring_lds_bytes<SHA_TILE>()));
+  for (size_t r = 0; r < N_ROUTINES; r++)
+    for (const void* kernel : {reinterpret_cast<const void*>(SHA_KERNEL[r]), reinterpret_cast<const void*>(STAGE_KERNEL[r])})
+      if (kernel) HIPCHK(e, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROUTINE_LDS[r]));
   return 0;
 }
 
@@ -518,22 +413,11 @@ int zke_engine_create(const zke_options* opt, zke_engine** out) {
     }
   }
   if (o.host_threads > 1) e->pool = new CopyPool(o.host_threads - 1);     // the caller's thread is one of them
-  {
-    // What HIP's queue pool is sized by was read (or is about to be read) by the runtime from the same variable; zke_process_init
-    // above has set it unless the host had.  Unset or unreadable: HIP's default of 4.
-    const char* q = getenv("GPU_MAX_HW_QUEUES");
-    const int hwq = q ? atoi(q) : 0;
-    e->hw_queues = hwq > 0 ? (uint32_t)hwq : 4u;
-    // ZKE_RSA_OCT9 = 0 / 1 forces the RSA role for moduli <= 2048 bits.  Unlike the knobs below it is read by the shipped library,
-    // not only under ZKE_DEV_KNOBS: the tests of the role and A/B runs of one build need it there (INTEGRATION.md §5 lists it).
-    if (const char* r9 = getenv("ZKE_RSA_OCT9")) e->rsa_oct9 = atoi(r9) != 0 ? 1 : 0;
-    if (const char* sr = getenv("ZKE_SHA_RING")) e->sha_ring = atoi(sr) != 0 ? 1 : 0;      // likewise: which two-wave SHA-256 routine
-    if (const char* st = getenv("ZKE_SHA_TWIN")) e->sha_twin = atoi(st) != 0 ? 1 : 0;      // ... and whether the ring's rounds wave takes two lanes per message
-    if (const char* tk = getenv("ZKE_SHA_TWIN_KINDS")) e->sha_twin_kinds = (uint32_t)atoi(tk) & 3u;
-  }
+  stage_env_from_environment(e->stage);     // (GPU_MAX_HW_QUEUES: zke_process_init above has set it unless the host had)
+  e->stage.slots = (uint32_t)e->slots.size();
+  e->stage.sha_mapping = o.sha_mapping; e->stage.rsa_lane_groups = o.rsa_lane_groups;
+  e->stage.key_cache = e->key_cache.p != nullptr;
 #ifdef ZKE_DEV_KNOBS
-  if (const char* rm = getenv("ZKE_RSA_QUAD_MIN")) e->rsa_quad_min = (uint32_t)atoi(rm);
-  if (const char* ro = getenv("ZKE_RSA_OCT_MIN")) e->rsa_oct_min = (uint32_t)atoi(ro);
   if (getenv("ZKE_DEBUG_SKIP_RSA")) e->debug_skip_rsa = 1;              // ablation experiments: results are then meaningless
   if (getenv("ZKE_DEBUG_SKIP_ED")) e->debug_skip_ed = 1;
   if (const char* ds = getenv("ZKE_DEBUG_PARSE_STOP")) e->debug_parse_stop = (uint32_t)atoi(ds);
@@ -568,13 +452,13 @@ void zke_engine_destroy(zke_engine* e) {
 int zke_engine_sha_ring(zke_engine* e) {
   if (!e) return ZKE_E_ARG;
   std::shared_lock<std::shared_mutex> sh(e->big);
-  return sha_takes_ring(e) ? 1 : 0;
+  return sha_takes_ring(e->stage) ? 1 : 0;
 }
 
 int zke_engine_sha_twin(zke_engine* e) {
   if (!e) return ZKE_E_ARG;
   std::shared_lock<std::shared_mutex> sh(e->big);
-  return sha_takes_twin(e) ? 1 : 0;
+  return sha_takes_twin(e->stage) ? 1 : 0;
 }
 
 const char* zke_last_error(const zke_engine* e) { (void)e; return g_err.c_str(); }
@@ -644,7 +528,7 @@ int sha256_batch_device_locked(zke_engine* e, const uint8_t* blob_dev, const uin
   hipLaunchKernelGGL(sha_jobs_from_csr_kernel, dim3((n + 255) / 256), dim3(256), 0, s, blob_dev, off_dev, n, digests_dev,
                      e->misc.as<ShaJob>());
   HIPCHK(e, hipGetLastError());
-  return launch_sha(e, e->misc.as<ShaJob>(), n, s);
+  return launch_sha(e, plan_sha(e->stage, n), e->misc.as<ShaJob>(), n, s);
 }
 }  // namespace
 

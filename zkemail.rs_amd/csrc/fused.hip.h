@@ -5,13 +5,15 @@
 // depend on any hash — only the final EMSA compare does (call site core/src/email.rs:31-33: cfdkim computes bh, the
 // header hash and the signature check one after the other; nothing orders the arithmetic inside).  One stream runs
 // its kernels in order, so the two can only overlap inside one launch: workgroups [0, g_sha) are SHA-256 groups
-// (sha256_pair_group: two waves per 64 messages), the rest are RSA roles — one signature per wave for keys whose
+// (two waves each: sha256_pair_group, sha256_ring_group or sha256_twin_group, one kernel per routine below; stage_plan.hip.h
+// says which a batch takes and how many workgroups each role gets), the rest are RSA roles — one signature per wave for keys whose
 // Montgomery constants are not cached yet (it fills the cache) or that the lane-group kernels do not take, four / eight
-// lanes per signature (rsa_group_wave) for everything the front end routed there.  RSA leaves EM's shape verdict and its
+// lanes per signature (rsa_group_wave<4>, <8> and <8, 9>) for everything the front end routed there.  RSA leaves EM's shape verdict and its
 // digest bytes in EmailMeta; verdict_kernel joins them with the hashes.  The batch's chain becomes
 // front end -> max(SHA-256, RSA) -> verdict instead of front end -> SHA-256 -> RSA.
 #pragma once
 #include "rsa_quad.hip.h"
+#include "stage_plan.hip.h"      // the layout of the SHA-256 groups (sha_stage_kind) and the plan the host fills StageArgs from
 
 namespace zke {
 
@@ -29,29 +31,6 @@ struct StageArgs {
   uint32_t twin_kinds;                     // bit k: kind k is hashed by sha256_twin_group in groups of 32 (launches with `order` only)
   uint32_t debug_skip_rsa;
 };
-
-// The SHA-256 groups of a launch with a kind layout (kind-major job list, n_pad jobs per kind, n_pad a multiple of 64): kind k takes
-// n_pad / width(k) consecutive workgroups, width 32 for the kinds of twin_kinds and 64 otherwise.  The host sizes g_sha by
-// sha_stage_groups and the kernel finds its kind by sha_stage_kind: the one place that knows the layout.
-constexpr uint32_t SHA_KINDS = 4;          // bodies, header preimages, domains, keys
-__host__ __device__ inline uint32_t sha_kind_groups(uint32_t n_pad, uint32_t twin_kinds, uint32_t kind) {
-  return n_pad / ((twin_kinds >> kind & 1u) ? SHA_TWIN_WIDTH : 64u);
-}
-__host__ __device__ inline uint32_t sha_stage_groups(uint32_t n_pad, uint32_t twin_kinds) {
-  uint32_t g = 0;
-  for (uint32_t k = 0; k < SHA_KINDS; k++) g += sha_kind_groups(n_pad, twin_kinds, k);
-  return g;
-}
-// workgroup b < g_sha -> its kind; b becomes the group within the kind
-__host__ __device__ inline uint32_t sha_stage_kind(uint32_t n_pad, uint32_t twin_kinds, uint32_t& b) {
-  uint32_t kind = 0;
-  for (; kind + 1 < SHA_KINDS; kind++) {
-    const uint32_t g = sha_kind_groups(n_pad, twin_kinds, kind);
-    if (b < g) break;
-    b -= g;
-  }
-  return kind;
-}
 
 template <int G, int L> constexpr uint32_t group_lds_dwords() { return (64 / G) * (G * L + 4); }      // per wave: rsa_group_wave's Llimb
 constexpr uint32_t QUAD_LDS_DWORDS = group_lds_dwords<4, QL>(), OCT_LDS_DWORDS = group_lds_dwords<8, QL>(), OCT9_LDS_DWORDS = group_lds_dwords<8, QL9>();

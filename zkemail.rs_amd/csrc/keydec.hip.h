@@ -5,6 +5,7 @@
 #include "zkemail_amd.h"
 #include "rsa.hip.h"
 #include "bytes.hip.h"
+#include "stage_plan.hip.h"      // ROUTE_*
 
 namespace zke {
 
@@ -86,13 +87,13 @@ __device__ __forceinline__ uint32_t decode_rsa_key(const Str& k, RsaJob* J, Pkcs
 }
 
 // Which RSA routine takes this key's signatures: RSA_F_QUAD / RSA_F_OCT when the lane-group kernel for its size is part of
-// the batch's launch (mask bit 0 / 1; bit 2: the launch has the eight-lane role for moduli <= 2048 bits, RSA_F_OCT9, in place of
-// the four-lane one) and the key's Montgomery constants are in the cache — the modulus [np, np + nl) of
+// the batch's launch (mask: ROUTE_QUAD / ROUTE_OCT; ROUTE_OCT9: the launch has the eight-lane role for moduli <= 2048 bits, RSA_F_OCT9, in
+// place of the four-lane one) and the key's Montgomery constants are in the cache — the modulus [np, np + nl) of
 // the DER key compared limb by limb with the entry, so a hit is exact; 0 = the one-signature-per-wave routine (which
 // fills the cache for the next batch).
 __device__ __forceinline__ uint32_t rsa_route(const Str& k, uint32_t np, uint32_t nl, uint32_t bits, const KeyCacheEntry* cache, uint32_t mask) {
   // (the bits above RSA_F_* say why a key was not routed: zke_debug_out.rsa_route shows them to the tests)
-  if (bits < 512 || !(mask & (bits <= 2048 ? 5u : 2u))) return 0x100;
+  if (bits < 512 || !(mask & (bits <= 2048 ? ROUTE_QUAD | ROUTE_OCT9 : ROUTE_OCT))) return 0x100;
   const uint32_t lane = (uint32_t)lane_id();
   auto limb = [&](uint32_t L) -> uint32_t {       // little-endian 32-bit limb L of the big-endian modulus
     uint32_t v = 0;
@@ -110,7 +111,7 @@ __device__ __forceinline__ uint32_t rsa_route(const Str& k, uint32_t np, uint32_
   if (st != 2u) return 0x200;                                       // not cached (yet)
   if (eb != bits) return 0x400;                                     // the slot belongs to another key
   const bool same = m0 == l0 && m1 == l1;
-  return __ballot(!same) == 0 ? (bits > 2048 ? (uint32_t)RSA_F_OCT : (mask & 4u) ? (uint32_t)RSA_F_OCT9 : (uint32_t)RSA_F_QUAD) : 0x400u;
+  return __ballot(!same) == 0 ? (bits > 2048 ? (uint32_t)RSA_F_OCT : (mask & ROUTE_OCT9) ? (uint32_t)RSA_F_OCT9 : (uint32_t)RSA_F_QUAD) : 0x400u;
 }
 
 // ------------------------------------------------------------------ base64 STANDARD, strict

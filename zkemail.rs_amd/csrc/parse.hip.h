@@ -156,7 +156,7 @@ struct ParseArgs {
   uint32_t strict;                  // ZKE_STRICT_*: zke_options' strictness flags
   uint64_t now;                     // the time x= is compared with (ZKE_STRICT_EXPIRY_X)
   const KeyCacheEntry* cache;       // per-key Montgomery constants (nullptr: no cache, every signature takes the wave routine)
-  uint32_t route_mask;              // bit 0 / 1: the four- / eight-lane RSA kernel is part of this batch's hash / modexp launch
+  uint32_t route_mask;              // ROUTE_* (stage_plan.hip.h): the lane-group RSA roles of this batch's hash / modexp launch (StagePlan::route_mask)
   uint32_t* wave_count;             // job list of the one-signature-per-wave RSA routine: the e-mails not routed to a lane-group kernel
   uint32_t* wave_list;              // (nullptr: no list, the routine looks at every job).  Appended here, consumed by the next launch.
 };

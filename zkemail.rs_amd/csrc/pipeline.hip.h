@@ -246,18 +246,17 @@ int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t ra
 
   const uint32_t rounds = e->opt.max_sig_rounds;
   // an RSA-2048 key is 270 bytes of DER: a batch whose keys average more holds some larger modulus
-  const uint32_t route_mask = rsa_route_mask(e, n, key_total > (uint64_t)n * 272);
+  const StagePlan plan = plan_stage(e->stage, n, 4 * n_pad, key_total > (uint64_t)n * 272, B.order != nullptr, __atomic_load_n(w.wave_feedback, __ATOMIC_RELAXED));
   {
     const uint32_t round = 0;
     uint32_t* wave_count = w.pending.as<uint32_t>() + 2;
     uint32_t* wave_list = w.rsa_ok.as<uint32_t>();
-    ParseArgs pa{B, round, 0, e->debug_parse_stop, e->strict, now, e->key_cache.as<KeyCacheEntry>(), route_mask, wave_count, wave_list};
+    ParseArgs pa{B, round, 0, e->debug_parse_stop, e->strict, now, e->key_cache.as<KeyCacheEntry>(), plan.route_mask, wave_count, wave_list};
     hipLaunchKernelGGL(parse_kernel, dim3((n + ZKE_PARSE_WG_WAVES - 1) / ZKE_PARSE_WG_WAVES), dim3(64 * ZKE_PARSE_WG_WAVES), PARSE_DYN_LDS, s, pa);
     tm.mark(MK_FRONT);
     // hash / modexp stage: the four SHA-256 jobs and the RSA operation of every e-mail, one launch (fused.hip.h)
     if (!(e->debug_skip_launch & 1) &&
-        (r = launch_hash_modexp(e, B.sha, 4 * n_pad, B.rsa, n, B.meta, want_em ? w.em_dbg.as<uint8_t>() : nullptr, route_mask, wave_count, wave_list, B.order,
-                                __atomic_load_n(w.wave_feedback, __ATOMIC_RELAXED), s)))
+        (r = launch_hash_modexp(e, plan, B.sha, 4 * n_pad, B.rsa, n, B.meta, want_em ? w.em_dbg.as<uint8_t>() : nullptr, wave_count, wave_list, B.order, s)))
       return r;
     tm.mark(MK_HASH);
     // Ed25519 stage + verdicts (verdict.hip.h): bh compare, EM digest against the header hash, status / detail, pending counter
@@ -443,6 +442,7 @@ int zke_engine_reserve(zke_engine* e, uint32_t max_n, uint64_t max_raw_total, ui
     Slot* w = new_slot(e);
     if (!w) return ZKE_E_DEVICE;
     e->slots.push_back(w);
+    e->stage.slots = (uint32_t)e->slots.size();
   }
   if (max_n)
     for (Slot* w : e->slots)

@@ -40,9 +40,9 @@ static_assert(sizeof(RsaJob) == 1056, "RsaJob layout");
 enum : uint32_t {
   RSA_F_ACTIVE = 1,             // run the modexp
   RSA_F_SHA1 = 2,               // EMSA block carries the SHA-1 DigestInfo and a 20-byte hash (a=rsa-sha1)
-  RSA_F_QUAD = 4,               // set by rsa_verify_kernel: rsa_group_kernel<4> (four lanes per signature) takes this job
-  RSA_F_OCT = 8,                // ... rsa_group_kernel<8> (eight lanes per signature: moduli of 2049..4096 bits)
-  RSA_F_OCT9 = 16,              // ... rsa_group_kernel<8, 9> (eight lanes of nine limbs: moduli <= 2048 bits, in place of RSA_F_QUAD)
+  RSA_F_QUAD = 4,               // set by the front end (rsa_route, keydec.hip.h): rsa_group_wave<4> (four lanes per signature) takes this job
+  RSA_F_OCT = 8,                // ... rsa_group_wave<8> (eight lanes per signature: moduli of 2049..4096 bits)
+  RSA_F_OCT9 = 16,              // ... rsa_group_wave<8, 9> (eight lanes of nine limbs: moduli <= 2048 bits, in place of RSA_F_QUAD)
   RSA_F_GROUPS = RSA_F_QUAD | RSA_F_OCT | RSA_F_OCT9,
 };
 

@@ -1,5 +1,5 @@
 // rsa_kernel.hip.h — the RSA public-key operation of one signature per wavefront (bigint core in rsa.hip.h), as a
-// device routine (rsa_wave) and as a stand-alone kernel, and the verdict kernel that follows the hash / modexp stage.
+// device routine (rsa_wave) and as a stand-alone kernel.  (The verdict kernel that follows the hash / modexp stage: verdict.hip.h.)
 //
 // The modular exponentiation needs the key and b= only — not the hashes — so it runs BESIDE the SHA-256 launch of its
 // batch (fused.hip.h), not behind it: it leaves "EM has the EMSA-PKCS1-v1_5 shape" and EM's trailing digest bytes in

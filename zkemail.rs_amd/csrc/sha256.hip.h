@@ -42,6 +42,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "stage_plan.hip.h"      // SHA_TWIN_WIDTH: a group's width is part of the launch layout
+
 // A message is a serial chain of compressions, so a hash launch's duration is set by its longest message, not by
 // the chip: with several batches in flight its few waves share SIMDs with thousands of front-end / RSA waves and
 // the chain stretches ~2x.  Raising the wave priority keeps the chain near its unloaded latency; the other
@@ -713,7 +715,7 @@ __global__ __launch_bounds__(128) void sha256_ring_kernel(const ShaJob* __restri
 // two steps of the rounds wave, and there is one barrier per pass.  K+W row 32 h + p of buffer j & 1 is block 2 j + h of message p.
 // Slab rows 32..63 hold no message (their descriptors say nblk 0); the first 256 bytes of row 32 are the zeros the B lanes read.
 // LDS and workgroup shape are the ring's.  Groups with a SHA-1 job take the one-wave path, here, 32 wide.
-constexpr uint32_t SHA_TWIN_WIDTH = 32;                       // messages per group
+// (SHA_TWIN_WIDTH, the messages per group: stage_plan.hip.h)
 constexpr uint32_t SHA_TWIN_SH[2][3] = {{6, 11, 25}, {2, 13, 22}};      // [A | B]: Σ1, Σ0
 constexpr uint32_t SHA_TWIN_MASKB[2] = {0u, 0xFFFFFFFFu};
 

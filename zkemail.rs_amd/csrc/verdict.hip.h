@@ -21,7 +21,7 @@ struct EdVerdictArgs {
   uint32_t strict;           // ZKE_STRICT_* and the x= clock, for the front end of later signature rounds
   uint64_t now;
   uint32_t* wave_feedback;   // pinned host word of the slot: how long the wave-routine job list of this batch was (sizes the next
-                             // batch's walkers: engine.hip, launch_hash_modexp); nullptr: nobody listens
+                             // batch's walkers: stage_plan.hip.h, plan_stage); nullptr: nobody listens
 };
 
 // SHA-256 / SHA-1 of one message by ONE LANE (later signature rounds only: two messages per e-mail, a rare path; the
