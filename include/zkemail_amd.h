@@ -722,6 +722,11 @@ int zke_engine_sha_ring(zke_engine* e);
  * zke_engine_sha_ring answers 1; ZKE_SHA_TWIN = 0 / 1 in the environment at zke_engine_create turns it off / asks for it wherever the
  * ring is taken.  Negative: an error code. */
 int zke_engine_sha_twin(zke_engine* e);
+/* Whether the round-0 front end of a batch of n e-mails runs two waves per e-mail as the engine stands now: 1 a helper wave
+ * canonicalises the body beside the header-hash preimage, 0 one wave does both.  Chosen like the ring — min(slots that exist,
+ * GPU_MAX_HW_QUEUES as read at creation) <= 4 — for batches of at most 1 024 e-mails, or forced by ZKE_FRONT_HELPER = 0 / 1 in the
+ * environment at zke_engine_create.  Negative: an error code. */
+int zke_engine_front_helper(zke_engine* e, uint32_t n);
 /* Enable per-launch HIP-event timing (adds event records between the launches). */
 int zke_set_timing(zke_engine* e, int enabled);
 

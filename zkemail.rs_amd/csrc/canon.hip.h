@@ -47,18 +47,25 @@ __device__ __forceinline__ uint32_t trailing_crlf_pairs(LD load, uint32_t len, b
 // (no launch boundary, no trip through EmailMeta); regex_prep_kernel (regex.hip.h) reads them from EmailMeta for the rare
 // e-mail whose canonicalize_signed_email pass cannot reuse the verify pass.
 // `lds`: CANON_LDS_BYTES of 16-byte aligned LDS the wave may overwrite (the front end hands over its staging buffer).
-constexpr uint32_t CANON_LDS_TRASH = 3504, CANON_LDS_BYTES = 3504 + 64;
+//
+// Two parts.  canon_body_compute writes the canonical bytes to region B of the e-mail's scratch slot (simple canonicalisation:
+// nothing but the CRLF of an empty body) and returns the canonical length and whether the hash reads the raw bytes; it touches
+// no record.  canon_body_publish applies l= and writes EmailMeta, the record, the body's SHA job and the two length-bucket keys.
+// canon_body_wave is the two back to back.  The round-0 front end runs compute on the e-mail's helper wave and publish on
+// the front-end wave (parse.hip.h).
+// (CANON_LDS_TRASH, CANON_LDS_BYTES: parse.hip.h, whose two-wave kernel reserves such a buffer for the helper wave)
 static_assert(CANON_LDS_BYTES <= PARSE_STAGE_BYTES, "the front end lends its staging buffer to the canonicaliser");
-__device__ __forceinline__ void canon_body_wave(const BatchDev& B, uint32_t i, uint32_t mode, uint32_t flags, uint32_t boff,
-                                                uint32_t blen, uint64_t len_tag, uint8_t* lds, bool ignore_l, bool bucket,
-                                                uint32_t hdr_len) {
-  const int lane = lane_id();
-  EmailMeta* M = B.meta + i;
-  zke_result* R = B.results + i;
+// (CanonWhere: the body and region B of the e-mail, looked up once for both parts — parse.hip.h)
+__device__ __forceinline__ CanonWhere canon_where(const BatchDev& B, uint32_t i, uint32_t boff) {
   const uint64_t r0 = B.raw_off[i];
   const uint32_t raw_len = (uint32_t)(B.raw_off[i + 1] - r0);
-  const uint8_t* body = B.raw + r0 + boff;
-  uint8_t* regB = B.scratch + scratch_offset(r0 - B.raw_off[0], i) + (((size_t)raw_len + PRE_SLACK + 15) & ~(size_t)15);
+  return CanonWhere{B.raw + r0 + boff, B.scratch + scratch_offset(r0 - B.raw_off[0], i) + (((size_t)raw_len + PRE_SLACK + 15) & ~(size_t)15)};
+}
+__device__ __forceinline__ void canon_body_compute(const CanonWhere W, uint32_t flags, uint32_t blen, uint8_t* lds,
+                                                   uint32_t& full_out, uint32_t& src_is_raw_out) {
+  const int lane = lane_id();
+  const uint8_t* body = W.body;
+  uint8_t* regB = W.regB;
   uint32_t full = 0, src_is_raw = 0;
 
   if (!(flags & ZKE_F_BODY_RELAXED)) {
@@ -283,6 +290,16 @@ __device__ __forceinline__ void canon_body_wave(const BatchDev& B, uint32_t i, u
     }
     full = o;
   }
+  full_out = full; src_is_raw_out = src_is_raw;
+}
+
+__device__ __forceinline__ void canon_body_publish(const BatchDev& B, uint32_t i, const CanonWhere W, uint32_t mode, uint32_t flags, uint64_t len_tag,
+                                                   bool ignore_l, bool bucket, uint32_t hdr_len, uint32_t full, uint32_t src_is_raw) {
+  const int lane = lane_id();
+  EmailMeta* M = B.meta + i;
+  zke_result* R = B.results + i;
+  const uint8_t* body = W.body;
+  uint8_t* regB = W.regB;
   uint32_t hashed = full;
   // STRICTNESS SITE canon_ignores_l (mode 1 only: ignore_l): canonicalize_signed_email returns the whole canonical body
   if ((flags & ZKE_F_HAS_LENGTH) && !ignore_l) {
@@ -298,6 +315,15 @@ __device__ __forceinline__ void canon_body_wave(const BatchDev& B, uint32_t i, u
     }
   }
   if (bucket && lane < 2) sha_bucket(B.order, (uint32_t)lane, B.n_pad, i, lane ? hdr_len : hashed);      // body and header preimage
+}
+
+__device__ __forceinline__ void canon_body_wave(const BatchDev& B, uint32_t i, uint32_t mode, uint32_t flags, uint32_t boff,
+                                                uint32_t blen, uint64_t len_tag, uint8_t* lds, bool ignore_l, bool bucket,
+                                                uint32_t hdr_len) {
+  uint32_t full, src_is_raw;
+  const CanonWhere W = canon_where(B, i, boff);
+  canon_body_compute(W, flags, blen, lds, full, src_is_raw);
+  canon_body_publish(B, i, W, mode, flags, len_tag, ignore_l, bucket, hdr_len, full, src_is_raw);
 }
 
 // ---- verdict of one signature round, by the wave that ran the e-mail's RSA job -----------------------

@@ -461,6 +461,12 @@ int zke_engine_sha_twin(zke_engine* e) {
   return sha_takes_twin(e->stage) ? 1 : 0;
 }
 
+int zke_engine_front_helper(zke_engine* e, uint32_t n) {
+  if (!e) return ZKE_E_ARG;
+  std::shared_lock<std::shared_mutex> sh(e->big);
+  return ZKE_PARSE_HELPER && front_takes_helper(e->stage, n) ? 1 : 0;
+}
+
 const char* zke_last_error(const zke_engine* e) { (void)e; return g_err.c_str(); }
 
 int zke_engine_join(zke_engine* e, void* stream) {

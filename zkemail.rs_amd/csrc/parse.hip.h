@@ -1,5 +1,5 @@
-// parse.hip.h — device-side restatement of the e-mail front end of verify_dkim, one e-mail per
-// wavefront (blockDim = 64).
+// parse.hip.h — device-side restatement of the e-mail front end of verify_dkim.  One e-mail per wavefront parses; in round 0
+// (parse_kernel<true>, blockDim = 128) a second wave per e-mail, the helper, canonicalises the body meanwhile.
 //
 // Replaces, on the verify path (call sites core/src/email.rs:26-33, core/src/circuits.rs:34-35):
 //   * mailparse 0.15.0 parse_headers / parse_header (header list) and parse_mail_recursive's walk over the MIME
@@ -15,8 +15,10 @@
 // turns per-byte predicates into 64-bit ballot masks (find first / find last / stream
 // compaction by popcount prefix).  The head of the e-mail (3.5 KB: the header block of ordinary mail) is staged
 // in LDS with 16-byte lane-contiguous loads; the per-e-mail tables (header spans, tag records, the FWS-stripped
-// tag values) live in LDS too.  In round 0 the kernel also does the batch's bookkeeping (batch_prologue), and
-// after the parse the same wave canonicalises the body (canon.hip.h) — one launch for the whole front end.
+// tag values) live in LDS too.  In round 0 the kernel also does the batch's bookkeeping (batch_prologue), and the body is
+// canonicalised in the same launch (canon.hip.h): by the e-mail's helper wave, beside the header-hash preimage, in round 0 ("the
+// helper wave of the round-0 front end" below); by the parsing wave itself, after the parse, everywhere else (later signature
+// rounds, mode 1) and on round 0's fallback paths — one launch for the whole front end.
 //
 // This file is the kernel: the batch's records, the phases only the verify path has (c= / l=, the b= removal) and
 // parse_email, the list of reference calls with the header-hash preimage written out.  What the signature scan and the key
@@ -168,9 +170,49 @@ struct ParseArgs {
 #endif
 
 // canon.hip.h
+constexpr uint32_t CANON_LDS_TRASH = 3504, CANON_LDS_BYTES = 3504 + 64;     // LDS the canonicaliser is lent (canon_body_compute's `lds`)
 __device__ __forceinline__ void canon_body_wave(const BatchDev& B, uint32_t i, uint32_t mode, uint32_t flags, uint32_t boff,
                                                 uint32_t blen, uint64_t len_tag, uint8_t* lds, bool ignore_l, bool bucket,
                                                 uint32_t hdr_len = 0);
+struct CanonWhere { const uint8_t* body; uint8_t* regB; };      // the e-mail's body and region B of its scratch slot
+__device__ __forceinline__ CanonWhere canon_where(const BatchDev& B, uint32_t i, uint32_t boff);
+__device__ __forceinline__ void canon_body_compute(const CanonWhere W, uint32_t flags, uint32_t blen, uint8_t* lds,
+                                                   uint32_t& full_out, uint32_t& src_is_raw_out);
+__device__ __forceinline__ void canon_body_publish(const BatchDev& B, uint32_t i, const CanonWhere W, uint32_t mode, uint32_t flags, uint64_t len_tag,
+                                                   bool ignore_l, bool bucket, uint32_t hdr_len, uint32_t full, uint32_t src_is_raw);
+
+// ------------------------------------------------------------------ the helper wave of the round-0 front end
+// parse_kernel<true> gives every e-mail a workgroup of two waves.  Wave 0 is the front end (parse_email<true, 0, true>); wave 1,
+// the helper, canonicalises the body (canon_body_compute) while wave 0 selects the headers and writes the header-hash preimage,
+// the longest stage of the chain, which needs nothing the canonicaliser produces.  The two meet at exactly two workgroup
+// barriers, on every path through the kernel:
+//   post  wave 0 has decoded the candidate's b= and knows whether the excised header went to region B (`copied`).  It leaves
+//         (flags, body_off, blen, l=) in the mailbox with go = 1, or go = 0 when region B is in use (`copied`) — then it
+//         canonicalises by itself at the end, as the one-wave front end does.
+//   join  where the one-wave front end calls canon_body_wave.  The helper has left (full, src_is_raw) in the mailbox; wave 0
+//         publishes them (canon_body_publish) if what it posted is still the candidate's (flags, l=).  It is not when the posted
+//         candidate's preimage overflowed and a later signature took its place: wave 0 then runs compute + publish itself.
+// The helper publishes nothing: the only global memory it writes is the canonical bytes in region B, dead unless a ShaJob points
+// at them.  Every record, EmailMeta field, job and bucket key is written by wave 0 where the one-wave front end writes it.
+// A path of wave 0 that ends before a barrier (every finish(...); return, ZKE_DEV_STOP) leaves it to parse_kernel, which executes
+// the barriers the mailbox says are missing, with go = 0.  Region B has one writer at a time: wave 0 writes it (the excised header
+// of a later candidate, the fallback) only behind the join.
+struct HelperBox {                 // the mailbox, in LDS
+  uint32_t go;                     // 1: canonicalise with the four values below
+  uint32_t flags, body_off, blen;
+  uint32_t len_tag_lo, len_tag_hi;
+  uint32_t full, src_is_raw;       // the helper's answer (canon_body_compute)
+  // wave 0's own: which of its two barriers it has executed.  (Here and not in registers: the signature loop's control flow is
+  // divergent to the compiler, which would carry them through it in vector registers the front end does not have to spare.)
+  uint32_t posted, joined;
+};
+
+// s_barrier with the workgroup fences __syncthreads() has: LDS traffic in front of it is complete and none behind it moves up
+__device__ __forceinline__ void wg_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
 // File e-mail i's message of `len` bytes (kind 0 body, 1 header preimage) under its length class.  One lane per kind: lanes 0
 // and 1 file the body and the header preimage with ONE atomic instruction at the very end of the front end — the positions
 // come back after a round trip to the memory side that nothing else waits for.
@@ -183,8 +225,10 @@ __device__ __forceinline__ void sha_bucket(uint32_t* order, uint32_t kind, uint3
 // The front end of e-mail i by the calling wave (L: the wave's LDS image).  parse_kernel runs it for every e-mail of a
 // batch (round 0, and mode 1); the verdict launch runs it again, round by round, for the rare e-mail whose candidate
 // signature failed while a later same-domain signature is still untried (verdict.hip.h).
-template <bool FAST = true, int MODE = 0>
-__device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i, ParseLds& L) {
+// HELPER (round 0, mode 0, parse_kernel<true> only): the e-mail has a helper wave, H is the mailbox the two share.
+template <bool FAST = true, int MODE = 0, bool HELPER = false>
+__device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i, ParseLds& L, HelperBox* H = nullptr) {
+  static_assert(!HELPER || (FAST && MODE == 0), "the helper wave belongs to the round-0 verify front end");
   const BatchDev& B = A.b;
   const int lane = lane_id();
   EmailMeta* M = B.meta + i;
@@ -396,6 +440,14 @@ __device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i
       // STRICTNESS SITE b_removes_own_span_only (oracle: build_preimage, same name).  Default: String::replace — every occurrence
       // of the raw b= value goes.  ZKE_STRICT_B_OWN_SPAN: only the tag's own span is emptied.
       if (!(A.strict & ZKE_STRICT_B_OWN_SPAN) && next_occurrence(0, b_rs) != NONE) {
+        if constexpr (HELPER) {
+          // a later candidate (the posted one overflowed the preimage): the helper may still be writing region B — join first
+          // (and what it left there is about to be overwritten: go = 0 makes the join below take the fallback)
+          if (uni(H->posted)) {
+            if (!uni(H->joined)) wg_barrier();
+            if (lane == 0) { H->joined = 1; H->go = 0; }
+          }
+        }
         uint32_t pos = 0;
         while (pos < v.len) {
           const uint32_t q = next_occurrence(pos, NONE);
@@ -419,6 +471,18 @@ __device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i
     if (copied) sv = mkstr(tmp, tn);
     else if (bl) { sv.len = v.len - bl; sv.cut = b_rs; sv.skip = bl; }
     ZKE_DEV_STOP(6);
+    if constexpr (HELPER) {
+      if (!uni(H->posted)) {
+        // ---- hand-off: the body canonicalisation of this candidate starts on the helper wave, unless region B holds `tmp`
+        if (lane == 0) {
+          H->flags = flags; H->body_off = body_off; H->blen = raw.len - body_off;
+          H->len_tag_lo = (uint32_t)len_tag; H->len_tag_hi = (uint32_t)(len_tag >> 32);
+          H->go = copied ? 0u : 1u;
+          H->posted = 1;
+        }
+        wg_barrier();
+      }
+    }
     // ---- header-hash preimage (cfdkim hash::compute_headers_hash)
     // (This block and the b= scan above stay written out in parse_email.  With the scan in a function that returns `copied`, the join
     // described above comes out wrong again: tests/test_gpu_hdr_split.py, the S-hbm routes, fail.)
@@ -493,6 +557,8 @@ __device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i
       unsupported = ZKE_D_U_PREIMAGE_OVERFLOW;
       if (MODE == 1) { finish(ZKE_UNSUPPORTED, unsupported); return; }
       have_cand = false; cand_count--;
+      // (HELPER: the only way on to a second hand-off point.  The post is behind this wave, so a later candidate posts nothing; its
+      // copy into region B joins first, and the join at the end finds go = 0 or other (flags, l=) and takes the fallback.)
       continue;
     }
     cand_flags = flags; cand_len_tag = len_tag;
@@ -532,8 +598,24 @@ __device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i
     M->em_ok = 0;
     if ((jf & RSA_F_ACTIVE) && !(jf & RSA_F_GROUPS) && A.wave_list) A.wave_list[atomicAdd(A.wave_count, 1u)] = i;
   }
-  // ---- body canonicalisation of the candidate (cfdkim hash::compute_body_hash), same wave, no launch boundary
-  canon_body_wave(B, i, 0, cand_flags, body_off, raw.len - body_off, cand_len_tag, L.stage, false, bucket, cand_hdr_len);   // parsing is over: the staged head is dead
+  // ---- body canonicalisation of the candidate (cfdkim hash::compute_body_hash), no launch boundary
+  if constexpr (HELPER) {
+    // ---- join (a candidate has passed the hand-off, so the post barrier is behind this wave)
+    const bool posted = uni(H->posted) != 0;
+    if (posted && !uni(H->joined)) wg_barrier();
+    if (lane == 0 && posted) H->joined = 1;
+    uint32_t full, src_is_raw;
+    const CanonWhere W{raw.base + body_off, regA + (((size_t)raw.len + PRE_SLACK + 15) & ~(size_t)15)};      // (from registers: no look-up)
+    if (posted && uni(H->go) && uni(H->flags) == cand_flags && uni(H->len_tag_lo) == (uint32_t)cand_len_tag && uni(H->len_tag_hi) == (uint32_t)(cand_len_tag >> 32)) {
+      full = uni(H->full); src_is_raw = uni(H->src_is_raw);
+    } else {
+      // the fallback: the posted candidate is not the final one, or region B was in use — this wave, as in the one-wave front end
+      canon_body_compute(W, cand_flags, raw.len - body_off, L.stage, full, src_is_raw);
+    }
+    canon_body_publish(B, i, W, 0, cand_flags, cand_len_tag, false, bucket, cand_hdr_len, full, src_is_raw);
+  } else {
+    canon_body_wave(B, i, 0, cand_flags, body_off, raw.len - body_off, cand_len_tag, L.stage, false, bucket, cand_hdr_len);   // parsing is over: the staged head is dead
+  }
 }
 
 #ifndef ZKE_PARSE_PRIO
@@ -557,20 +639,59 @@ constexpr size_t PARSE_DYN_LDS = ZKE_PARSE_WG_WAVES > 1 ? ZKE_PARSE_WG_WAVES * s
 #else
 #define ZKE_PARSE_VGPR_ATTR
 #endif
-__global__ __launch_bounds__(64 * ZKE_PARSE_WG_WAVES, ZKE_PARSE_WAVES) ZKE_PARSE_VGPR_ATTR void parse_kernel(ParseArgs A) {
-#if ZKE_PARSE_WG_WAVES > 1
-  // dynamic LDS (W * sizeof(ParseLds), given at launch): with the size in sight the compiler takes the kernel's occupancy
-  // for LDS-bound at 4 waves per SIMD and spends 109 registers — the point of W is that the front end stays at 80
-  extern __shared__ __attribute__((aligned(16))) uint8_t parse_lds_raw[];
-  ParseLds* L = reinterpret_cast<ParseLds*>(parse_lds_raw);
-#else
-  __shared__ ParseLds L[1];
+// ZKE_PARSE_HELPER: 1 (default) the pipeline launches parse_kernel<true>, two waves per e-mail (above), where the batch's plan takes it
+// (stage_plan.hip.h, front_takes_helper); 0: parse_kernel<true> is not built (needed for ZKE_PARSE_WG_WAVES > 1).
+#ifndef ZKE_PARSE_HELPER
+#define ZKE_PARSE_HELPER 1
 #endif
-  const uint32_t wave = ZKE_PARSE_WG_WAVES > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
-  const uint32_t email = blockIdx.x * ZKE_PARSE_WG_WAVES + wave;
-  if (email >= A.b.n) return;
-  if (ZKE_PARSE_PRIO) __builtin_amdgcn_s_setprio(ZKE_PARSE_PRIO);
-  parse_email(A, email, L[wave]);
+static_assert(sizeof(ParseLds) + CANON_LDS_BYTES + sizeof(HelperBox) == 10840, "LDS per workgroup of parse_kernel<true>: DESIGN §3, profiles/kernel_resource_usage.txt");
+template <bool HELPER>
+__global__ __launch_bounds__(HELPER ? 128 : 64 * ZKE_PARSE_WG_WAVES, ZKE_PARSE_WAVES) ZKE_PARSE_VGPR_ATTR void parse_kernel(ParseArgs A) {
+  if constexpr (HELPER) {
+    static_assert(!HELPER || ZKE_PARSE_WG_WAVES == 1, "the helper wave takes the place of a second e-mail in the workgroup");
+    __shared__ ParseLds L;
+    __shared__ __attribute__((aligned(16))) uint8_t canon_lds[CANON_LDS_BYTES];      // the helper's own: L.stage is alive in wave 0 until the join
+    __shared__ HelperBox box;
+    const uint32_t email = blockIdx.x;
+    if (email >= A.b.n) return;                        // (the whole workgroup)
+    if (ZKE_PARSE_PRIO) __builtin_amdgcn_s_setprio(ZKE_PARSE_PRIO);
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // Two barriers per wave on every path: the helper's are the two below; wave 0 executes here whichever of its two
+    // parse_email did not reach.
+    if (wave == 0) {
+      if (lane_id() == 0) { box.posted = 0; box.joined = 0; }
+      parse_email<true, 0, true>(A, email, L, &box);
+      if (!uni(box.posted)) {
+        if (lane_id() == 0) box.go = 0;
+        wg_barrier();
+      }
+      if (!uni(box.joined)) wg_barrier();
+    } else {
+      wg_barrier();                                    // post
+      if (uni(box.go)) {
+        uint32_t full, src_is_raw;
+        canon_body_compute(canon_where(A.b, email, uni(box.body_off)), uni(box.flags), uni(box.blen), canon_lds, full, src_is_raw);
+        if (lane_id() == 0) { box.full = full; box.src_is_raw = src_is_raw; }
+        // region B is complete before wave 0 may write it (the fallback)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      wg_barrier();                                    // join
+    }
+  } else {
+#if ZKE_PARSE_WG_WAVES > 1
+    // dynamic LDS (W * sizeof(ParseLds), given at launch): with the size in sight the compiler takes the kernel's occupancy
+    // for LDS-bound at 4 waves per SIMD and spends 109 registers — the point of W is that the front end stays at 80
+    extern __shared__ __attribute__((aligned(16))) uint8_t parse_lds_raw[];
+    ParseLds* L = reinterpret_cast<ParseLds*>(parse_lds_raw);
+#else
+    __shared__ ParseLds L[1];
+#endif
+    const uint32_t wave = ZKE_PARSE_WG_WAVES > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
+    const uint32_t email = blockIdx.x * ZKE_PARSE_WG_WAVES + wave;
+    if (email >= A.b.n) return;
+    if (ZKE_PARSE_PRIO) __builtin_amdgcn_s_setprio(ZKE_PARSE_PRIO);
+    parse_email(A, email, L[wave]);
+  }
 }
 
 // CSR (blob, off[n+1]) -> ShaJob list with digests packed 32 B apart (building-block entry point)

@@ -252,7 +252,13 @@ int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t ra
     uint32_t* wave_count = w.pending.as<uint32_t>() + 2;
     uint32_t* wave_list = w.rsa_ok.as<uint32_t>();
     ParseArgs pa{B, round, 0, e->debug_parse_stop, e->strict, now, e->key_cache.as<KeyCacheEntry>(), plan.route_mask, wave_count, wave_list};
-    hipLaunchKernelGGL(parse_kernel, dim3((n + ZKE_PARSE_WG_WAVES - 1) / ZKE_PARSE_WG_WAVES), dim3(64 * ZKE_PARSE_WG_WAVES), PARSE_DYN_LDS, s, pa);
+    // a workgroup of two waves per e-mail, the front-end wave and its helper, which canonicalises the body (parse.hip.h), where the plan says
+    // that pays (stage_plan.hip.h, front_takes_helper); else one wave per e-mail
+#if ZKE_PARSE_HELPER
+    if (plan.front_helper) hipLaunchKernelGGL(parse_kernel<true>, dim3(n), dim3(128), 0, s, pa);
+    else
+#endif
+    hipLaunchKernelGGL(parse_kernel<false>, dim3((n + ZKE_PARSE_WG_WAVES - 1) / ZKE_PARSE_WG_WAVES), dim3(64 * ZKE_PARSE_WG_WAVES), PARSE_DYN_LDS, s, pa);
     tm.mark(MK_FRONT);
     // hash / modexp stage: the four SHA-256 jobs and the RSA operation of every e-mail, one launch (fused.hip.h)
     if (!(e->debug_skip_launch & 1) &&

@@ -74,6 +74,7 @@ struct StageEnv {
   int rsa_oct9 = -1;               // ZKE_RSA_OCT9: ROUTE_OCT9 instead of ROUTE_QUAD
   int sha_ring = -1;               // ZKE_SHA_RING: the ring instead of the pair
   int sha_twin = -1;               // ZKE_SHA_TWIN: the twin wherever the ring is taken
+  int front_helper = -1;           // ZKE_FRONT_HELPER: the two-wave front end (a helper wave per e-mail canonicalises the body)
   uint32_t twin_kinds = 3;         // ZKE_SHA_TWIN_KINDS: which kinds of the stage the twin takes (bit 0 bodies, bit 1 header preimages; domains
                                    // and keys are one block each and keep 64-wide groups: 32 more workgroups per batch would keep the RSA
                                    // roles waiting for room)
@@ -97,6 +98,7 @@ inline void stage_env_from_environment(StageEnv& v) {
   forced("ZKE_RSA_OCT9", v.rsa_oct9);
   forced("ZKE_SHA_RING", v.sha_ring);
   forced("ZKE_SHA_TWIN", v.sha_twin);
+  forced("ZKE_FRONT_HELPER", v.front_helper);
   if (const char* tk = getenv("ZKE_SHA_TWIN_KINDS")) v.twin_kinds = (uint32_t)atoi(tk) & 3u;
 #ifdef ZKE_DEV_KNOBS
   if (const char* rm = getenv("ZKE_RSA_QUAD_MIN")) v.rsa_quad_min = (uint32_t)atoi(rm);
@@ -119,6 +121,21 @@ inline bool sha_takes_pairs(const StageEnv& v, uint32_t groups) { return v.sha_m
 // same roles, buffers and LDS, a shorter rounds chain) and on by default.
 inline bool sha_takes_ring(const StageEnv& v) { return v.sha_ring >= 0 ? v.sha_ring == 1 : chain_bound(v); }
 inline bool sha_takes_twin(const StageEnv& v) { return sha_takes_ring(v) && v.sha_twin != 0; }
+
+// The round-0 front end with a helper wave per e-mail (parse.hip.h, parse_kernel<true>) or with one wave.  The helper shortens the front end's
+// chain by the body canonicaliser's length and doubles the launch's waves (+ 3.5 KB of LDS per e-mail).  That pays where a batch's time is its
+// chain and the launch leaves the chip room; where 23 hardware queues keep the chip's issue slots busy, or the batch alone fills the chip, the
+// extra residents cost more than the chain gains.  The bound on the batch is the chip's SIMD count (256 CUs x 4): the front end is compiled for
+// five waves per SIMD (96 registers), so up to one e-mail per SIMD the two-wave launch holds two of those five and leaves the other three, and
+// the registers beside them, to the hash / modexp and verdict waves of the other batches in flight, as the one-wave launch of twice the batch
+// would.  At 2 048 e-mails it holds four of five; at 4 096 its 8 192 waves exceed the 5 120 the chip holds of this kernel and the launch runs in
+// two passes, the chain twice.  Measured (profiles/frontend_helper_bench_ab.txt, section 3: the helper for every batch): batches of 1 024 gain
+// 6.8 % with four queues and lose 17 % with 23; with four queues batches of 4 096 and 8 192 lose 17 and 7 %, and the two workloads of 2 048 go
+// one each way (+ 3 %, - 4 %).
+constexpr uint32_t FRONT_HELPER_MAX_BATCH = 1024;      // = SIMDs of the chip
+inline bool front_takes_helper(const StageEnv& v, uint32_t n) {
+  return v.front_helper >= 0 ? v.front_helper == 1 : chain_bound(v) && n <= FRONT_HELPER_MAX_BATCH;
+}
 
 // Which lane-group RSA roles take part in a batch of n e-mails; any_big = the caller's hint that the batch's keys average more than an
 // RSA-2048 key.  Eight lanes of nine limbs is the choice when the engine cannot fill the chip's issue slots.  Only the choice by batch size is
@@ -161,6 +178,7 @@ inline ShaPlan plan_sha(const StageEnv& v, uint32_t n) {
 // that the chip is full of SHA-256 waves anyway: `front` runs first (arrival order), then the RSA roles as a launch without SHA-256 groups.
 struct StagePlan {
   uint32_t route_mask;             // ROUTE_*: to the front end as well
+  bool front_helper;               // the front end's kernel: parse_kernel<true> (two waves per e-mail) or parse_kernel<false>
   ShaPlan front;                   // SHA-256 as a launch of its own in front; grid == 0: none, the stage's own groups hash
   ShaRoutine routine;              // of the stage's kernel: what its SHA-256 groups run and the LDS it carries (no groups: the pair's)
   uint32_t twin_kinds;             // StageArgs::twin_kinds; launches without a kind layout (`order`) keep 64-wide groups
@@ -170,6 +188,7 @@ struct StagePlan {
 inline StagePlan plan_stage(const StageEnv& v, uint32_t n, uint32_t n_sha, bool any_big, bool have_order, uint32_t last_wave_jobs) {
   StagePlan p{};
   p.route_mask = rsa_route_mask(v, n, any_big);
+  p.front_helper = front_takes_helper(v, n);
   const uint32_t want = last_wave_jobs == 0xFFFFFFFFu ? ZKE_WAVE_ROLE_MAX_GROUPS
                                                       : plan_max(ZKE_WAVE_ROLE_MIN_GROUPS, (plan_min(last_wave_jobs, n) + 1) / 2);
   p.g_wave = plan_min((n + 1) / 2, plan_min(want, ZKE_WAVE_ROLE_MAX_GROUPS));

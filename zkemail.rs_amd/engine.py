@@ -176,6 +176,9 @@ def load_library(path: Optional[str] = None):
     if hasattr(lib, "zke_engine_sha_twin"):         # (likewise)
         lib.zke_engine_sha_twin.argtypes = [vp]
         lib.zke_engine_sha_twin.restype = C.c_int
+    if hasattr(lib, "zke_engine_front_helper"):     # (likewise)
+        lib.zke_engine_front_helper.argtypes = [vp, C.c_uint32]
+        lib.zke_engine_front_helper.restype = C.c_int
     lib.zke_version.argtypes = []
     lib.zke_version.restype = C.c_char_p
     lib.zke_device_available.argtypes = []
@@ -198,7 +201,7 @@ EXPORTED_SYMBOLS = [
     "zke_extract_captures_async", "zke_capture_batch",
     "zke_scan_signatures", "zke_scan_signatures_async", "zke_select_keys", "zke_select_keys_async",
     "zke_decode_key_records", "zke_decode_key_records_async", "zke_select_keys_from_records", "zke_select_keys_from_records_async",
-    "zke_engine_sha_ring", "zke_engine_sha_twin",
+    "zke_engine_sha_ring", "zke_engine_sha_twin", "zke_engine_front_helper",
     "zke_qp_clean_batch", "zke_extract_captures_mapped", "zke_extract_captures_mapped_async",
     "zke_extract_bodies", "zke_extract_bodies_async",
 ]
@@ -707,6 +710,12 @@ class Engine:
         """Whether the ring's rounds wave takes two lanes per message as the engine stands now (zke_engine_sha_twin)."""
         r = self.lib.zke_engine_sha_twin(self.h)
         self._check(min(r, 0), "zke_engine_sha_twin")
+        return r == 1
+
+    def front_helper(self, n: int) -> bool:
+        """Whether a batch of n e-mails takes the two-wave front end as the engine stands now (zke_engine_front_helper)."""
+        r = self.lib.zke_engine_front_helper(self.h, n)
+        self._check(min(r, 0), "zke_engine_front_helper")
         return r == 1
 
     def join(self, stream: int = 0):
