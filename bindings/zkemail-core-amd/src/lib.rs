@@ -452,6 +452,108 @@ impl Engine {
             .collect())
     }
 
+    /// `verify_email_with_regex` over a slice as the reference has it: every value with a `RegexInfo` of its own
+    /// (core/src/structs.rs:59-62), so one batch may mix regex configs (`zke_verify_emails_mixed`).  The configs are the
+    /// distinct id lists in order of first appearance; the capture tables are e-mail-major.  Result `i` is what
+    /// `verify_emails_with_regex` gives input `i` in a batch of its own config.
+    pub fn verify_emails_mixed(
+        &self,
+        inputs: &[EmailWithRegex],
+    ) -> Result<Vec<Result<EmailWithRegexVerifierOutput, Panic>>, EngineError> {
+        if inputs.is_empty() {
+            return Ok(Vec::new());
+        }
+        let empty: Vec<CompiledRegex> = Vec::new();
+        let ids = |engine: &Engine, parts: &Option<Vec<CompiledRegex>>| -> Result<Vec<u32>, EngineError> {
+            let mut v = Vec::new();
+            for p in parts.as_ref().unwrap_or(&empty) {
+                let mut id = 0u32;
+                // SAFETY: the slices outlive the call; the engine copies what it keeps.
+                let rc = unsafe {
+                    sys::zke_dfa_register(
+                        engine.raw,
+                        p.verify_re.fwd.as_ptr(),
+                        p.verify_re.fwd.len(),
+                        p.verify_re.bwd.as_ptr(),
+                        p.verify_re.bwd.len(),
+                        &mut id,
+                    )
+                };
+                if rc != 0 {
+                    return Err(engine.last_error(rc));
+                }
+                v.push(id);
+            }
+            Ok(v)
+        };
+        let mut lists: Vec<(Vec<u32>, Vec<u32>)> = Vec::new();
+        let mut config_of: Vec<u32> = Vec::with_capacity(inputs.len());
+        let mut cap_off: Vec<u32> = vec![0];
+        let mut cap_str_off: Vec<u32> = vec![0];
+        let mut cap_blob: Vec<u8> = Vec::new();
+        for inp in inputs {
+            let key = (ids(self, &inp.regex_info.header_parts)?, ids(self, &inp.regex_info.body_parts)?);
+            let c = match lists.iter().position(|k| *k == key) {
+                Some(c) => c,
+                None => {
+                    if lists.len() == sys::ZKE_MIXED_MAX_CONFIGS as usize {
+                        return Err(EngineError { code: sys::ZKE_E_ARG, message: "more than ZKE_MIXED_MAX_CONFIGS regex configs in one batch; split it".into() });
+                    }
+                    lists.push(key);
+                    lists.len() - 1
+                }
+            };
+            config_of.push(c as u32);
+            for parts in [&inp.regex_info.header_parts, &inp.regex_info.body_parts] {
+                for p in parts.as_ref().unwrap_or(&empty) {
+                    for s in p.captures.as_ref().map(|v| v.as_slice()).unwrap_or(&[]) {
+                        cap_blob.extend_from_slice(s.as_bytes());
+                        cap_str_off.push(cap_blob.len() as u32);
+                    }
+                    cap_off.push((cap_str_off.len() - 1) as u32);
+                }
+            }
+        }
+        if cap_blob.is_empty() {
+            cap_blob.push(0);
+        }
+        let configs: Vec<sys::zke_regex_config> = lists
+            .iter()
+            .map(|(h, b)| sys::zke_regex_config {
+                n_header_parts: h.len() as u32,
+                header_part_ids: h.as_ptr(),
+                n_body_parts: b.len() as u32,
+                body_part_ids: b.as_ptr(),
+            })
+            .collect();
+        let refs: Vec<sys::zke_email_ref> = inputs.iter().map(|i| email_ref(&i.email)).collect();
+        let mixed = sys::zke_regex_mixed {
+            n_configs: configs.len() as u32,
+            configs: configs.as_ptr(),
+            config_of: config_of.as_ptr(),
+            cap_off: if cap_off.len() > 1 { cap_off.as_ptr() } else { ptr::null() },
+            cap_str_off: cap_str_off.as_ptr(),
+            cap_blob: cap_blob.as_ptr(),
+        };
+        let mut out = vec![zeroed_result(); inputs.len()];
+        // SAFETY: as in verify_emails; the configs, their id lists and the capture tables live until the call returns.
+        let rc = unsafe { sys::zke_verify_emails_mixed(self.raw, refs.as_ptr(), refs.len() as u32, &mixed, out.as_mut_ptr()) };
+        if rc != 0 {
+            return Err(self.last_error(rc));
+        }
+        Ok(inputs
+            .iter()
+            .zip(out.iter())
+            .map(|(inp, r)| {
+                if r.status == sys::ZKE_OK {
+                    Ok(EmailWithRegexVerifierOutput { email: email_output(&inp.email, r), regex_matches: regex_matches_of(&inp.regex_info) })
+                } else {
+                    Err(Panic { status: r.status, detail: r.detail })
+                }
+            })
+            .collect())
+    }
+
     /// One e-mail through the single-e-mail C entry point `zke_verify_email` (core/src/circuits.rs:9).
     pub fn try_verify_email(&self, email: &Email) -> Result<Result<EmailVerifierOutput, Panic>, EngineError> {
         let mut r = zeroed_result();

@@ -399,7 +399,8 @@ typedef struct zke_email_ref {
 int zke_verify_emails(zke_engine* e, const zke_email_ref* emails, uint32_t n, zke_result* out);
 int zke_verify_emails_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, zke_result* out, uint64_t* ticket);
 /* ... and verify_email_with_regex over `&[EmailWithRegex]` that share one part list (one regex_config per batch): the e-mails as
- * above, the part lists and the per-e-mail capture tables exactly as zke_batch has them (host arrays; small). */
+ * above, the part lists and the per-e-mail capture tables exactly as zke_batch has them (host arrays; small).  A slice that mixes
+ * part lists: zke_verify_emails_mixed below. */
 typedef struct zke_regex_lists {
   uint32_t n_header_parts; const uint32_t* header_part_ids;   /* ids from zke_dfa_register, RegexInfo.header_parts order */
   uint32_t n_body_parts;   const uint32_t* body_part_ids;
@@ -410,6 +411,41 @@ typedef struct zke_regex_lists {
 int zke_verify_emails_with_regex(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_lists* lists, zke_result* out);
 int zke_verify_emails_with_regex_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_lists* lists,
                                        zke_result* out, uint64_t* ticket);
+
+/* ... and over `&[EmailWithRegex]` as the reference has it: every value carries its own RegexInfo (core/src/structs.rs:32-35,59-62;
+ * core/src/circuits.rs:31-68 takes one at a time), so one batch may mix regex configs — a relayer's queue of receipts, invitations
+ * and password resets, each with its own regex_config.json — and e-mails that are verify_email only.  `configs` are the distinct
+ * part lists, config_of[i] names e-mail i's.  out[i] is exactly the record zke_verify_emails_with_regex gives e-mail i in a batch
+ * that holds only its own config — status, detail, regex_part, match_*, the fold order "header parts, then body parts, stop at the
+ * first failing part" — and for config_of[i] == ZKE_CONFIG_NONE the record of zke_verify_emails (circuits.rs:9): the regex stage
+ * neither reads nor writes it.  A config with ZERO parts is not ZKE_CONFIG_NONE: it is verify_email_with_regex with both lists
+ * None, which still runs canonicalize_signed_email(..).unwrap() (circuits.rs:34-35) and can report that failure.
+ * On the device: the verify launches, one preparation launch, ONE lane-mapped and ONE wave-mapped DFA launch whatever the number of
+ * configs and parts (a block is told by a segment table which config's e-mails and which automaton it owns), one verdict launch.
+ * ZKE_E_ARG, before anything is staged: a config_of[i] that is neither below n_configs nor ZKE_CONFIG_NONE, n_configs above
+ * ZKE_MIXED_MAX_CONFIGS, more than ZKE_MIXED_MAX_PARTS parts in a config, a null list with a non-zero count, capture offsets that
+ * decrease.  An unknown or undecodable DFA id stays a per-e-mail matter: the e-mails of the configs that use it report
+ * ZKE_DFA_DECODE_FAIL with the section.  Same slots, tickets and zke_batch_wait as zke_verify_emails_async; everything `mixed`
+ * points to has been read when the call returns. */
+#define ZKE_MIXED_MAX_CONFIGS 64u
+#define ZKE_MIXED_MAX_PARTS 64u
+#define ZKE_CONFIG_NONE 4294967295u
+typedef struct zke_regex_config {     /* one RegexInfo's part lists */
+  uint32_t n_header_parts; const uint32_t* header_part_ids;   /* ids from zke_dfa_register, RegexInfo.header_parts order */
+  uint32_t n_body_parts;   const uint32_t* body_part_ids;
+} zke_regex_config;
+typedef struct zke_regex_mixed {
+  uint32_t n_configs; const zke_regex_config* configs;
+  const uint32_t* config_of;       /* [n]: index into configs, or ZKE_CONFIG_NONE: this e-mail is verify_email only */
+  const uint32_t* cap_off;         /* [J + 1] or NULL: no captures anywhere.  J = the sum over the e-mails of P(config_of[i]) (0 for
+                                      ZKE_CONFIG_NONE), e-mail-major: e-mail i's part p is job job_off[i] + p, header parts first,
+                                      job_off the prefix sum of P; the captures of job j are the strings cap_off[j] .. cap_off[j + 1] */
+  const uint32_t* cap_str_off;     /* [n_strings + 1], as zke_regex_lists */
+  const uint8_t*  cap_blob;
+} zke_regex_mixed;
+int zke_verify_emails_mixed(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_mixed* mixed, zke_result* out);
+int zke_verify_emails_mixed_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_mixed* mixed,
+                                  zke_result* out, uint64_t* ticket);
 
 /* ---- capture extraction: the compute half of the reference's input generation (helpers/src/generator.rs:55-87 ->
  * helpers/src/regex.rs:16-51) — canonicalise, remove the QP soft breaks, require exactly one match per pattern, run the capturing

@@ -251,6 +251,63 @@ class Engine {
     return out;
   }
 
+  // verify_email_with_regex over a vector as the reference has it — every value with a RegexInfo of its own — and verify_email for
+  // the entries without one (nullopt), in ONE batch (zke_verify_emails_mixed): the pairs are registered, the configs are the distinct
+  // id lists in order of first appearance, the capture tables are e-mail-major.  Record i is what verify_emails_with_regex gives
+  // input i in a batch of its own config, or what verify_emails gives it.
+  std::vector<zke_result> verify_emails_mixed(const std::vector<std::pair<Email, std::optional<RegexInfo>>>& in) {
+    if (in.empty()) return {};
+    auto ids_of = [&](const std::optional<std::vector<CompiledRegex>>& parts) {
+      std::vector<uint32_t> v;
+      if (parts)
+        for (const auto& p : *parts) {
+          uint32_t id = 0;
+          if (int r = zke_dfa_register(e_, p.verify_re.fwd.data(), p.verify_re.fwd.size(), p.verify_re.bwd.data(), p.verify_re.bwd.size(), &id))
+            throw EngineError("zke_dfa_register failed: " + std::to_string(r) + " " + zke_last_error(e_));
+          v.push_back(id);
+        }
+      return v;
+    };
+    std::vector<std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> lists;       // the configs' id lists (stable addresses below)
+    std::vector<zke_email_ref> refs(in.size());
+    std::vector<uint32_t> config_of(in.size()), cap_off{0}, cap_str_off{0};
+    std::vector<uint8_t> cap_blob;
+    for (size_t i = 0; i < in.size(); i++) {
+      const Email& em = in[i].first;
+      uint32_t ext = 0;
+      for (const auto& x : em.external_inputs) if (!x.value) ext = 1;
+      refs[i] = zke_email_ref{em.raw_email.data(), em.raw_email.size(), em.from_domain.data(), em.from_domain.size(),
+                              em.public_key.key.data(), em.public_key.key.size(), key_type_code(em.public_key.key_type), ext};
+      if (!in[i].second) { config_of[i] = ZKE_CONFIG_NONE; continue; }
+      const RegexInfo& ri = *in[i].second;
+      auto key = std::make_pair(ids_of(ri.header_parts), ids_of(ri.body_parts));
+      size_t c = 0;
+      while (c < lists.size() && lists[c] != key) c++;
+      if (c == lists.size()) {
+        if (c == ZKE_MIXED_MAX_CONFIGS) throw EngineError("more than ZKE_MIXED_MAX_CONFIGS regex configs in one batch; split it");
+        lists.push_back(std::move(key));
+      }
+      config_of[i] = (uint32_t)c;
+      for (const auto* parts : {&ri.header_parts, &ri.body_parts})
+        if (*parts)
+          for (const auto& p : **parts) {
+            if (p.captures)
+              for (const auto& s : *p.captures) { cap_blob.insert(cap_blob.end(), s.begin(), s.end()); cap_str_off.push_back((uint32_t)cap_blob.size()); }
+            cap_off.push_back((uint32_t)cap_str_off.size() - 1);
+          }
+    }
+    if (cap_blob.empty()) cap_blob.push_back(0);
+    std::vector<zke_regex_config> configs(lists.size());
+    for (size_t c = 0; c < lists.size(); c++)
+      configs[c] = zke_regex_config{(uint32_t)lists[c].first.size(), lists[c].first.data(), (uint32_t)lists[c].second.size(), lists[c].second.data()};
+    zke_regex_mixed mixed{(uint32_t)configs.size(), configs.data(), config_of.data(), cap_off.size() > 1 ? cap_off.data() : nullptr,
+                          cap_str_off.data(), cap_blob.data()};
+    std::vector<zke_result> out(in.size());
+    if (int r = zke_verify_emails_mixed(e_, refs.data(), (uint32_t)refs.size(), &mixed, out.data()))
+      throw EngineError("zke_verify_emails_mixed failed: " + std::to_string(r) + " " + zke_last_error(e_));
+    return out;
+  }
+
   // zke_extract_captures over a vector of e-mails that share one part list: verify_email + canonicalise + QP clean + exactly one
   // match per part + the requested groups.  One record per e-mail; `caps` as zke_capture_out describes it.
   std::vector<zke_result> extract_captures(const std::vector<Email>& emails, const std::vector<CapturePart>& header_parts,

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -286,6 +286,63 @@ class zke_regex_lists(C.Structure):
         ("n_header_parts", C.c_uint32), ("header_part_ids", C.c_void_p), ("n_body_parts", C.c_uint32), ("body_part_ids", C.c_void_p),
         ("cap_off", C.c_void_p), ("cap_str_off", C.c_void_p), ("cap_blob", C.c_void_p),
     ]
+
+
+MIXED_MAX_CONFIGS = 64           # ZKE_MIXED_MAX_CONFIGS
+MIXED_MAX_PARTS = 64             # ZKE_MIXED_MAX_PARTS
+CONFIG_NONE = 0xFFFFFFFF         # ZKE_CONFIG_NONE: config_of[i] of an e-mail that is verify_email only
+
+
+class zke_regex_config(C.Structure):
+    """One RegexInfo's part lists (zke_verify_emails_mixed)."""
+    _fields_ = [
+        ("n_header_parts", C.c_uint32), ("header_part_ids", C.c_void_p), ("n_body_parts", C.c_uint32), ("body_part_ids", C.c_void_p),
+    ]
+
+
+class zke_regex_mixed(C.Structure):
+    _fields_ = [
+        ("n_configs", C.c_uint32), ("configs", C.POINTER(zke_regex_config)), ("config_of", C.c_void_p),
+        ("cap_off", C.c_void_p), ("cap_str_off", C.c_void_p), ("cap_blob", C.c_void_p),
+    ]
+
+
+class MixedLists:
+    """The tables of one zke_verify_emails_mixed call: the distinct configs (id lists), config_of[n], job_off[n + 1] (the prefix sum
+    of the e-mails' part counts: e-mail i's part p is job job_off[i] + p, header parts first) and the capture strings per job as CSR.
+    `configs`: [(header ids, body ids)]; `config_of`: per e-mail an index into it or CONFIG_NONE; `captures`: per e-mail the list
+    (one entry per part, header parts first) of its parts' capture strings — [] or None for an e-mail without a config.
+    Keeps the numpy buffers alive and exposes a ``zke_regex_mixed``."""
+
+    def __init__(self, configs: Sequence[Tuple[Sequence[int], Sequence[int]]], config_of: Sequence[int],
+                 captures: Optional[Sequence[Optional[Sequence[Sequence[str]]]]] = None):
+        self.n = len(config_of)
+        self.configs = [(list(h), list(b)) for h, b in configs]
+        self.config_of = np.array(list(config_of) or [0], dtype=np.uint32)
+        self._ids = [(np.array(h or [0], np.uint32), np.array(b or [0], np.uint32)) for h, b in self.configs]
+        self.arr = (zke_regex_config * max(len(self.configs), 1))()
+        for k, ((h, b), (ha, ba)) in enumerate(zip(self.configs, self._ids)):
+            self.arr[k].n_header_parts, self.arr[k].header_part_ids = len(h), ha.ctypes.data
+            self.arr[k].n_body_parts, self.arr[k].body_part_ids = len(b), ba.ctypes.data
+        parts_of = [0 if c == CONFIG_NONE else len(self.configs[c][0]) + len(self.configs[c][1]) for c in config_of]
+        self.job_off = np.zeros(self.n + 1, np.uint32)
+        if self.n:
+            self.job_off[1:] = np.cumsum(parts_of)
+        strs: List[bytes] = []
+        cap_off = [0]
+        for i, P in enumerate(parts_of):
+            per_email = list((captures[i] if captures is not None else None) or [[]] * P)
+            assert len(per_email) == P, (i, len(per_email), P)
+            for part_caps in per_email:
+                strs.extend(s.encode("utf-8") if isinstance(s, str) else s for s in (part_caps or []))
+                cap_off.append(len(strs))
+        self.cap_off = np.array(cap_off, dtype=np.uint32)
+        self.cap_blob, str_off = _csr(strs)
+        self.cap_str_off = str_off.astype(np.uint32)
+        m = self.c = zke_regex_mixed()
+        m.n_configs, m.configs, m.config_of = len(self.configs), self.arr, self.config_of.ctypes.data
+        if int(self.job_off[self.n]):
+            m.cap_off, m.cap_str_off, m.cap_blob = self.cap_off.ctypes.data, self.cap_str_off.ctypes.data, self.cap_blob.ctypes.data
 
 
 class EmailRefs:

@@ -72,6 +72,7 @@ CPP_SIGSCAN = os.path.join(ROOT, "tests", "cpp", "sigscan_test")
 CPP_KEYREC = os.path.join(ROOT, "tests", "cpp", "keyrec_test")
 CPP_QPMAP = os.path.join(ROOT, "tests", "cpp", "qpmap_test")
 CPP_BODY = os.path.join(ROOT, "tests", "cpp", "body_test")
+CPP_MIXED = os.path.join(ROOT, "tests", "cpp", "mixed_test")
 ED_PROBE = os.path.join(ROOT, "tests", "cpp", "ed_probe")
 SHA_PROBE = os.path.join(ROOT, "tests", "cpp", "sha_probe")
 
@@ -101,6 +102,8 @@ def build_cpp_example(force: bool = False) -> str:
         build_cpp_qpmap(force)
     if os.path.exists(CPP_BODY + ".cpp"):
         build_cpp_body(force)
+    if os.path.exists(CPP_MIXED + ".cpp"):
+        build_cpp_mixed(force)
     if os.path.exists(ED_PROBE + ".hip"):       # test infrastructure that lives in tests/: a tree whose tests/ does not carry the probe
         build_ed_probe(force)                   # has nothing that runs it, and the three programs below do not depend on it
     if os.path.exists(SHA_PROBE + ".hip"):
@@ -126,6 +129,11 @@ def build_cpp_qpmap(force: bool = False) -> str:
 def build_cpp_body(force: bool = False) -> str:
     """tests/cpp/body_test: extract_email_bodies / extract_email_body of the C++ mirror."""
     return _build_cpp(CPP_BODY, force)
+
+
+def build_cpp_mixed(force: bool = False) -> str:
+    """tests/cpp/mixed_test: verify_emails_mixed of the C++ mirror."""
+    return _build_cpp(CPP_MIXED, force)
 
 
 def build_ed_probe(force: bool = False) -> str:

@@ -35,6 +35,7 @@
 #include "fused.hip.h"
 #include "ed25519.hip.h"
 #include "verdict.hip.h"
+#include "regex_mixed.hip.h"      // (behind the others: the earlier kernels keep their places in the code object)
 
 using namespace zke;
 

@@ -31,6 +31,38 @@ struct KeyrecReq { uint32_t mode; zke_keyrec_out* out; };
 // ---- body extraction (bodyext.hip.h): the batch's raw section holds the e-mails, body_extract_kernel runs instead of the verify pipeline
 struct BodyReq { uint32_t flags; zke_body_out* out; };
 
+// ---- mixed regex batches (zke_verify_emails_mixed; plan: mixed_plan.hip.h, kernels: regex_mixed.hip.h).  The entry checks the
+// arguments and measures (`shape`, `counts`); mixed_resolve builds the plan once the registry can be read; submit_host stages it.
+struct MixedReq {
+  const zke_regex_mixed* in = nullptr;
+  uint32_t n = 0;
+  std::vector<MixedConfigIn> counts;    // [n_configs]
+  MixedShape shape;
+  MixedPlan plan;
+};
+// The configs' parts resolved against the registry and the plan built from them.  The caller holds `big` (shared) from here until the
+// batch is enqueued, as for capture_resolve: the tables the segments point to cannot be freed before the launches that read them.
+int mixed_resolve(zke_engine* e, MixedReq& q) {
+  std::vector<MixedPartIn> parts;
+  parts.reserve(q.shape.n_segs);
+  {
+    std::shared_lock<std::shared_mutex> rl(e->reg_mu);
+    for (uint32_t c = 0; c < q.in->n_configs; c++) {
+      const zke_regex_config& cf = q.in->configs[c];
+      for (uint32_t p = 0; p < cf.n_header_parts + cf.n_body_parts; p++) {
+        const uint32_t id = p >= cf.n_header_parts ? cf.body_part_ids[p - cf.n_header_parts] : cf.header_part_ids[p];
+        const RegisteredDfa* rd = id < e->dfas.size() ? e->dfas[id] : nullptr;
+        PartInfo pi{};
+        if (rd) { pi.detail = rd->detail; pi.lds_bytes = rd->lds_bytes; pi.idle = rd->idle; pi.dev = rd->valid ? rd->dev.as<RegexDev>() : nullptr; }
+        parts.push_back(MixedPartIn{(uint64_t)(uintptr_t)pi.dev, pi.lds_bytes, pi.idle, pi.detail});
+      }
+    }
+  }
+  if (const char* why = mixed_plan_build(q.in->config_of, q.n, q.counts.data(), q.in->n_configs, parts.data(), e->opt.dfa_mapping, q.plan))
+    return fail(e, ZKE_E_ARG, why);
+  return 0;
+}
+
 // A slot's buffers for one side output of a batch of n: the layout, then the buffers it asks for (ensure_side_buffers).
 // `pack`: zke_select_keys_from_records, the decoded keys are packed for the front end.
 int ensure_keyrec_buffers(zke_engine* e, KeyrecBufs& b, uint32_t m, size_t rec_total, bool pack) {
@@ -231,6 +263,7 @@ struct HostBatch {
   const SelectReq* sel = nullptr;       // zke_select_keys: the batch's entries are (e-mail, candidate key) pairs, folded on delivery
   const KeyrecReq* keyrec = nullptr;    // key records: decoded instead of the verify pipeline, or (with sel) in front of it
   const BodyReq* body = nullptr;        // zke_extract_bodies: body_extract_kernel runs instead of the verify pipeline
+  MixedReq* mixed = nullptr;            // zke_verify_emails_mixed: a regex batch whose part lists are the configs' (b's own are empty)
   uint64_t raw_total = 0, dom_total = 0, key_total = 0, raw_base = 0, dom_base = 0, key_base = 0;   // blob bytes; off[0] of packed offsets
   size_t cap_words = 0, cap_strs = 0, cap_bytes = 0;      // entries of cap_off and cap_str_off, bytes of cap_blob (0: no tables)
   ImageLayout L{};
@@ -239,7 +272,7 @@ struct HostBatch {
 int measure_host_batch(HostBatch& d, const char* who) {
   zke_batch& b = d.b;
   if (d.raw_total > (1ull << 40)) return arg_error(who, "raw e-mails beyond 1 TiB");
-  const size_t NP = b.with_regex ? (size_t)b.n * (b.n_header_parts + b.n_body_parts) : 0;
+  const size_t NP = d.mixed ? (size_t)d.mixed->shape.J : b.with_regex ? (size_t)b.n * (b.n_header_parts + b.n_body_parts) : 0;
   if (NP && b.cap_off) {
     if (!rising(b.cap_off, NP)) return arg_error(who, "capture offset array is not non-decreasing");
     if (const uint32_t strs = b.cap_off[NP]) {
@@ -249,7 +282,7 @@ int measure_host_batch(HostBatch& d, const char* who) {
     }
   }
   if (!d.cap_words) b.cap_off = nullptr, b.cap_str_off = nullptr, b.cap_blob = nullptr;
-  d.L = image_layout(b.n, d.raw_total, d.dom_total, d.key_total, d.cap_words, d.cap_strs, d.cap_bytes);
+  d.L = image_layout(b.n, d.raw_total, d.dom_total, d.key_total, d.cap_words, d.cap_strs, d.cap_bytes, d.mixed ? mixed_image(b.n, d.mixed->shape).total : 0);
   return 0;
 }
 // The packed shape.  Its offsets are in host memory here, so they are checked (three passes over n + 1 words): a negative length
@@ -264,10 +297,17 @@ int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_b
   }
   return measure_host_batch(d, who);
 }
-// The gathered shape: the e-mails one by one, lists == nullptr for verify_email.
-int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_email_ref* refs, uint32_t n, const zke_regex_lists* lists) {
+// The gathered shape: the e-mails one by one, lists == nullptr for verify_email; `mixed` (checked and measured by its entry) instead
+// of lists: the capture tables are its.
+int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_email_ref* refs, uint32_t n, const zke_regex_lists* lists,
+               MixedReq* mixed = nullptr) {
   if (n && (!refs || !out)) return arg_error(who, "null pointer");
   d = HostBatch{zke_batch{n}, refs};
+  if (mixed) {
+    d.mixed = mixed;
+    d.b.with_regex = 1;
+    d.b.cap_off = mixed->in->cap_off; d.b.cap_str_off = mixed->in->cap_str_off; d.b.cap_blob = mixed->in->cap_blob;
+  }
   if (lists) {
     d.b.with_regex = 1; d.b.n_header_parts = lists->n_header_parts; d.b.header_part_ids = lists->header_part_ids;
     d.b.n_body_parts = lists->n_body_parts; d.b.body_part_ids = lists->body_part_ids;
@@ -351,6 +391,15 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
     stage_copy(hp + L.cap_str_off, d.b.cap_str_off, d.cap_strs * 4);
     stage_copy(hp + L.cap_blob, d.b.cap_blob, d.cap_bytes);
   }
+  const MixedImage ML = d.mixed ? mixed_image(n, d.mixed->shape) : MixedImage{};
+  if (d.mixed) {           // the plan of a mixed batch rides in the same image: the batch is still ONE copy
+    const MixedPlan& P = d.mixed->plan;
+    uint8_t* mp = hp + L.mixed;
+    stage_copy(mp + ML.job_off, P.job_off.data(), P.job_off.size() * 4);
+    stage_copy(mp + ML.email_cfg, P.email_cfg.data(), P.email_cfg.size() * 4);
+    stage_copy(mp + ML.perm, P.perm.data(), P.perm.size() * 4);
+    stage_copy(mp + ML.segs, P.segs.data(), P.segs.size() * sizeof(MixedSeg));
+  }
   hipStream_t s = w.stream;
   SlotUse use(e, w, s);
   if ((rc = use.acquire())) return rc;
@@ -396,7 +445,11 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
       // SubjectPublicKeyInfo record is about 410 characters, a 3072-bit one 580)
       key_hint = d.key_total > (uint64_t)n * 480 ? (uint64_t)n * 273 : 0;
     }
-    if ((rc = run_device_pipeline(e, w, &dv, d.raw_total, key_hint, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap))) return rc;
+    const uint8_t* mp = dp + L.mixed;
+    const MixedLaunch ml{d.mixed ? &d.mixed->plan : nullptr, reinterpret_cast<const uint32_t*>(mp + ML.job_off), reinterpret_cast<const uint32_t*>(mp + ML.email_cfg),
+                         reinterpret_cast<const uint32_t*>(mp + ML.perm), reinterpret_cast<const MixedSeg*>(mp + ML.segs)};
+    if ((rc = run_device_pipeline(e, w, &dv, d.raw_total, key_hint, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap,
+                                  d.mixed ? &ml : nullptr))) return rc;
     HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
     if (d.keyrec) HIPCHK(e, w.kb.t.fetch(w.kb.L.total, s));
   }
@@ -484,6 +537,7 @@ int submit_host_batch(zke_engine* e, const HostBatch& d, zke_result* out, uint64
   std::shared_lock<std::shared_mutex> sh(e->big);
   HIPCHK(e, hipSetDevice(e->device));
   if (d.cap) capture_resolve(e, *d.cap);             // under `big`: the programs' tables cannot be freed before the batch is enqueued
+  if (d.mixed && n) if (int r = mixed_resolve(e, *d.mixed)) return r;      // likewise the DFA pairs' tables a mixed batch's segments point to
   uint32_t slot;
   Slot& w = next_slot(e, slot);
   std::lock_guard<std::mutex> g(w.mu);
@@ -577,6 +631,33 @@ int zke_verify_emails_with_regex_async(zke_engine* e, const zke_email_ref* email
 
 int zke_verify_emails_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, zke_result* out, uint64_t* ticket) {
   return zke_verify_emails_with_regex_async(e, emails, n, nullptr, out, ticket);
+}
+
+// `&[EmailWithRegex]` with a RegexInfo per value (include/zkemail_amd.h): the checks and the sizes here, before anything is staged;
+// the plan once the registry can be read (mixed_resolve); its tables in the slot's image (submit_host).
+int zke_verify_emails_mixed_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_mixed* mixed, zke_result* out,
+                                  uint64_t* ticket) {
+  static const char who[] = "zke_verify_emails_mixed";
+  if (!e) return ZKE_E_ARG;
+  if (!mixed || !ticket) return arg_error(who, "null pointer");
+  if (mixed->n_configs > ZKE_MIXED_MAX_CONFIGS) return arg_error(who, "more than ZKE_MIXED_MAX_CONFIGS configs");
+  if ((mixed->n_configs && !mixed->configs) || (n && !mixed->config_of)) return arg_error(who, "null pointer");
+  MixedReq q;
+  q.in = mixed; q.n = n;
+  q.counts.resize(mixed->n_configs);
+  for (uint32_t c = 0; c < mixed->n_configs; c++) {
+    const zke_regex_config& cf = mixed->configs[c];
+    if ((cf.n_header_parts && !cf.header_part_ids) || (cf.n_body_parts && !cf.body_part_ids)) return arg_error(who, "part-id list is null");
+    q.counts[c] = MixedConfigIn{cf.n_header_parts, cf.n_body_parts};
+  }
+  if (const char* why = mixed_plan_check(mixed->config_of, n, q.counts.data(), mixed->n_configs, q.shape)) return arg_error(who, why);
+  HostBatch d;
+  if (int r = host_batch(d, who, out, emails, n, nullptr, &q)) return r;
+  return submit_host_batch(e, d, out, ticket);
+}
+
+int zke_verify_emails_mixed(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_mixed* mixed, zke_result* out) {
+  return submit_and_wait(e, n, [&](uint64_t* t) { return zke_verify_emails_mixed_async(e, emails, n, mixed, out, t); });
 }
 
 int zke_verify_emails_with_regex(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_lists* lists, zke_result* out) {

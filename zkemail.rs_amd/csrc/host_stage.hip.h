@@ -227,10 +227,11 @@ class CopyPool {
 // the image; blobs start 64-byte aligned and are followed by 64 bytes of slack (the kernels read 16 bytes at a time).
 struct ImageLayout {
   size_t raw_off, dom_off, key_off, key_type, ext_null, cap_off, cap_str_off, raw, dom, key, cap_blob, total;
+  size_t mixed;       // a mixed regex batch's plan (mixed_plan.hip.h, MixedImage); no bytes otherwise
 };
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) & ~(a - 1); }
 inline ImageLayout image_layout(uint32_t n, size_t raw_total, size_t dom_total, size_t key_total, size_t n_cap_off, size_t n_cap_str,
-                                size_t cap_bytes) {
+                                size_t cap_bytes, size_t mixed_bytes = 0) {
   ImageLayout L{};
   size_t o = 0;
   auto put = [&](size_t bytes, size_t slack) { const size_t at = o; o = align_up(o + bytes + slack, 64); return at; };
@@ -241,6 +242,7 @@ inline ImageLayout image_layout(uint32_t n, size_t raw_total, size_t dom_total, 
   L.ext_null = put(n, 0);
   L.cap_off = put(n_cap_off * 4, 0);
   L.cap_str_off = put(n_cap_str * 4, 0);
+  L.mixed = put(mixed_bytes, 0);
   L.raw = put(raw_total, 64);
   L.dom = put(dom_total, 64);
   L.key = put(key_total, 64);

@@ -207,18 +207,66 @@ int launch_keyrec_prefix(zke_engine* e, KeyrecBufs& b, zke_batch& in, uint32_t m
   return 0;
 }
 
+// ---- the regex stage of a mixed batch (zke_verify_emails_mixed; kernels: regex_mixed.hip.h, plan: mixed_plan.hip.h)
+// The plan of the batch and where its tables lie in the slot's staged image (device pointers).
+struct MixedLaunch {
+  const MixedPlan* plan;
+  const uint32_t* job_off; const uint32_t* email_cfg; const uint32_t* perm; const MixedSeg* segs;
+};
+// Behind the verify launches: the preparation (e-mails without a config left out), ONE lane-mapped and ONE wave-mapped DFA launch
+// over the plan's segments, the fold.  B: the verify pass's view of the batch; `in`: its capture tables (indexed by job).
+int run_mixed_regex_stage(zke_engine* e, Slot& w, const BatchDev& B, const zke_batch& in, const MixedLaunch& mx, uint64_t* clean_off, uint64_t now,
+                          bool want_clean, StageTimer& tm, hipStream_t s) {
+  const MixedPlan& P = *mx.plan;
+  const uint32_t n = B.n;
+  BatchDev B2 = B;
+  B2.meta = w.meta2.as<EmailMeta>();
+  B2.scratch = w.scratch2.as<uint8_t>();
+  B2.meta_verify = B.meta;
+  B2.order = nullptr;
+  // want_clean stays what a parity buffer asks for: whether a config has body parts is decided per e-mail (email_cfg)
+  PrepMixedArgs pr{PrepArgs{ParseArgs{B2, 0, 1, 0, e->strict, now, nullptr, 0, nullptr, nullptr},
+                            QpArgs{B2, B.meta, w.clean.as<uint8_t>(), clean_off, B.scratch, B.scratch_off}, want_clean ? 1u : 0u},
+                   mx.email_cfg};
+  hipLaunchKernelGGL(regex_prep_mixed_kernel, dim3(n), dim3(64), 0, s, pr);
+  tm.mark(MK_PREP);
+  DfaMixedArgs ma{};
+  ma.common.b = B2;
+  ma.common.scratch_v = B.scratch; ma.common.scratch_v_off = B.scratch_off;
+  ma.common.clean = w.clean.as<uint8_t>(); ma.common.clean_off = clean_off;
+  ma.common.cap_off = in.cap_off; ma.common.cap_str_off = in.cap_str_off; ma.common.cap_blob = in.cap_blob;
+  ma.common.out = w.parts.as<PartRes>();
+  ma.perm = mx.perm; ma.job_off = mx.job_off;
+  if (P.lane_blocks) {
+    ma.segs = mx.segs; ma.n_segs = P.n_lane;
+    hipLaunchKernelGGL(dfa_mixed_kernel, dim3(P.lane_blocks), dim3(256), P.lane_lds, s, ma);
+  }
+  if (P.wave_blocks) {
+    ma.segs = mx.segs + P.n_lane; ma.n_segs = (uint32_t)P.segs.size() - P.n_lane;
+    hipLaunchKernelGGL(dfa_mixed_wave_kernel, dim3(P.wave_blocks), dim3(256), P.wave_lds, s, ma);
+  }
+  RegexFoldMixedArgs rf{B2, w.parts.as<PartRes>(), mx.job_off, mx.email_cfg};
+  hipLaunchKernelGGL(regex_fold_mixed_kernel, dim3((n + 255) / 256), dim3(256), 0, s, rf);
+  tm.mark(MK_DFA);
+  HIPCHK(e, hipGetLastError());
+  return 0;
+}
+
 // The device pipeline.  Every pointer in `in` / out_dev is device memory, except the part-id lists (host arrays in both
 // entry points).  Three launches — front end, hash / modexp stage, Ed25519 + verdict (which also runs the later signature
 // rounds of the rare e-mail that needs them) — and, for verify_email_with_regex, the regex stage behind them.
 // Caller holds the slot's lock; everything the call needs is in its arguments or in the slot.
 int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t raw_total, uint64_t key_total, zke_result* out_dev,
-                        hipStream_t s, bool want_em, uint64_t now, bool want_clean = false, const CaptureReq* cap = nullptr) {
+                        hipStream_t s, bool want_em, uint64_t now, bool want_clean = false, const CaptureReq* cap = nullptr,
+                        const MixedLaunch* mixed = nullptr) {
   const uint32_t n = in->n;
   if (n == 0) return 0;
   const uint32_t n_pad = (n + 63) & ~63u;
   const uint32_t P = in->with_regex ? in->n_header_parts + in->n_body_parts : 0;
   int r = 0;
   if ((r = ensure_workspace(e, w, n, raw_total, in->with_regex != 0, P, want_em, s))) return r;
+  // a mixed batch (with_regex, no list of its own): one PartRes per (e-mail, part) job
+  if (mixed && (r = w.parts.ensure((size_t)std::max<uint32_t>(mixed->plan->shape.J, 1) * sizeof(PartRes)))) return fail(e, r, "workspace allocation");
   uint64_t* scratch_off = w.scratch_off.as<uint64_t>();
   uint64_t* clean_off = scratch_off + (n + 1);
 
@@ -273,7 +321,9 @@ int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t ra
   }
   HIPCHK(e, hipGetLastError());
 
-  if (in->with_regex) {
+  if (in->with_regex && mixed) {
+    if ((r = run_mixed_regex_stage(e, w, B, *in, *mixed, clean_off, now, want_clean, tm, s))) return r;
+  } else if (in->with_regex) {
     // the parts of this batch, copied out of the registry (the entries themselves stay put until the engine is idle)
     PartInfo parts_small[16];
     std::vector<PartInfo> parts_big;

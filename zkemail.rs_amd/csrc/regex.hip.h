@@ -74,11 +74,10 @@ __device__ __forceinline__ void qp_wave(const uint8_t* src, uint32_t n, uint8_t*
 //   remove_quoted_printable_soft_breaks (circuits.rs:37) — only when somebody will read the cleaned body: a batch without
 //   body parts never looks at it (circuits.rs:48-56), so `want_clean` is off unless body parts or a parity buffer ask for it.
 struct PrepArgs { ParseArgs parse; QpArgs qp; uint32_t want_clean; };
-__global__ __launch_bounds__(64, ZKE_PARSE_WAVES) void regex_prep_kernel(PrepArgs A) {
-  __shared__ ParseLds L;
+// E-mail i by the calling wave (`want_clean`: somebody reads this e-mail's cleaned body).  Two entry kernels call it: regex_prep_kernel
+// below, and regex_prep_mixed_kernel (regex_mixed.hip.h), which leaves out the e-mails that have no regex config.
+__device__ __forceinline__ void regex_prep_email(const PrepArgs& A, const uint32_t i, ParseLds& L, const uint32_t want_clean) {
   const BatchDev& B = A.parse.b;
-  const uint32_t i = blockIdx.x;
-  if (i >= B.n) return;
   // what parse_email<_, 1> is going to decide, from the verify pass's state (written by earlier launches: plain loads)
   const EmailMeta* V = B.meta_verify + i;
   const bool ok = B.results[i].status == ZKE_OK;
@@ -89,7 +88,7 @@ __global__ __launch_bounds__(64, ZKE_PARSE_WAVES) void regex_prep_kernel(PrepArg
   const uint32_t raw_len = (uint32_t)(B.raw_off[i + 1] - r0);
   uint8_t* dst = A.qp.clean + A.qp.clean_off[i];
   if (reuse) {
-    if (!A.want_clean) return;
+    if (!want_clean) return;
     const uint32_t n = (A.parse.strict & ZKE_STRICT_CANON_IGNORES_L) ? V->canon_full_len : V->hashed_len;
     const uint8_t* src = V->body_src_is_raw ? B.raw + r0 + V->body_off : region_b(A.qp.scratch_v, A.qp.scratch_v_off, i, raw_len);
     qp_wave(src, n, dst);
@@ -105,11 +104,17 @@ __global__ __launch_bounds__(64, ZKE_PARSE_WAVES) void regex_prep_kernel(PrepArg
   if (ld(&M->state) != ST_CAND) return;
   canon_body_wave(B, i, 1, ld(&M->flags), ld(&M->body_off), ld(&M->body_len), ((uint64_t)ld(&M->len_tag_hi) << 32) | ld(&M->len_tag_lo),
                   L.stage, (A.parse.strict & ZKE_STRICT_CANON_IGNORES_L) != 0, false);
-  if (!A.want_clean) return;
+  if (!want_clean) return;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   const uint8_t* src = ld(&M->body_src_is_raw) ? B.raw + r0 + ld(&M->body_off) : region_b(B.scratch, B.scratch_off, i, raw_len);
   qp_wave(src, ld(&M->hashed_len), dst);
+}
+__global__ __launch_bounds__(64, ZKE_PARSE_WAVES) void regex_prep_kernel(PrepArgs A) {
+  __shared__ ParseLds L;
+  const uint32_t i = blockIdx.x;
+  if (i >= A.parse.b.n) return;
+  regex_prep_email(A, i, L, A.want_clean);
 }
 
 // ---- dense DFA search ------------------------------------------------------------------------
@@ -470,6 +475,36 @@ __global__ __launch_bounds__(256) void dfa_kernel(DfaMultiArgs MA) {
   if (MA.finalize) regex_fold_part(fold, R, A.part, MA.n_header_parts, pr);
 }
 
+// The chunk map of one haystack (DfaAccel) by the calling wave: lane l walks chunk l from the idle state X (~0: no map).
+__device__ __forceinline__ DfaAccel dfa_chunk_map(const DfaLds& F, const uint8_t* hay, const uint32_t hlen, const uint32_t X, const int lane) {
+  DfaAccel acc{0, 0, 0, false};
+  if (X != 0xFFFFFFFFu && hlen >= 256) {
+    // chunk size: a multiple of 16 (the walk loads 16 bytes at a time), 64 chunks cover the haystack
+    const uint32_t C = ((hlen + 63) / 64 + 15) & ~15u;
+    const uint32_t lo = (uint32_t)lane * C;
+    bool clean = true;
+    if (lo < hlen) {
+      const uint32_t hi = lo + C < hlen ? lo + C : hlen;
+      uint32_t sid = X;
+      for (uint32_t at = lo; at < hi && clean; at += 16) {
+        const uint4 v = *(const uint4_u1*)(hay + at);
+        const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
+        const uint32_t nb = hi - at < 16 ? hi - at : 16;
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+          if ((uint32_t)j < nb) {
+            sid = dfa_tr(F, sid, F.classes[(wv[j >> 2] >> (8 * (j & 3))) & 0xff]);
+            if (sid <= F.sp_max && (dfa_is_match(F, sid) || sid == 0 || dfa_is_quit(F, sid))) clean = false;
+          }
+        }
+      }
+      clean = clean && sid == X;
+    }
+    acc.clean = __ballot(clean); acc.C = C; acc.X = X; acc.on = true;
+  }
+  return acc;
+}
+
 // One e-mail per WAVE (blockDim = 256: four e-mails share the staged tables).  A DFA walk is a serial chain, but
 // where the chain can be cut is knowable in parallel: the 64 lanes first walk one chunk of the haystack each from
 // the automaton's idle state `A.idle` and report which chunks are "clean" (DfaAccel); the exact search that follows
@@ -501,33 +536,7 @@ __global__ __launch_bounds__(256) void dfa_wave_kernel(DfaMultiArgs MA) {
     } else {
       const uint8_t* hay; uint32_t hlen;
       dfa_haystack(A, i, M, hay, hlen);
-      DfaAccel acc{0, 0, 0, false};
-      const uint32_t X = A.idle;
-      if (X != 0xFFFFFFFFu && hlen >= 256) {
-        // chunk size: a multiple of 16 (the walk loads 16 bytes at a time), 64 chunks cover the haystack
-        const uint32_t C = ((hlen + 63) / 64 + 15) & ~15u;
-        const uint32_t lo = (uint32_t)lane * C;
-        bool clean = true;
-        if (lo < hlen) {
-          const uint32_t hi = lo + C < hlen ? lo + C : hlen;
-          uint32_t sid = X;
-          for (uint32_t at = lo; at < hi && clean; at += 16) {
-            const uint4 v = *(const uint4_u1*)(hay + at);
-            const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
-            const uint32_t nb = hi - at < 16 ? hi - at : 16;
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-              if ((uint32_t)j < nb) {
-                sid = dfa_tr(F, sid, F.classes[(wv[j >> 2] >> (8 * (j & 3))) & 0xff]);
-                if (sid <= F.sp_max && (dfa_is_match(F, sid) || sid == 0 || dfa_is_quit(F, sid))) clean = false;
-              }
-            }
-          }
-          clean = clean && sid == X;
-        }
-        acc.clean = __ballot(clean); acc.C = C; acc.X = X; acc.on = true;
-      }
-      pr = dfa_part(A, F, Rv, i, hay, hlen, acc);
+      pr = dfa_part(A, F, Rv, i, hay, hlen, dfa_chunk_map(F, hay, hlen, A.idle, lane));
     }
   }
   if (lane == 0) {

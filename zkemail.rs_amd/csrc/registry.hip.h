@@ -7,12 +7,15 @@ namespace {
 
 // (caller holds reg_mu exclusively or is creating the engine)
 int raise_dfa_lds_attrs(zke_engine* e, size_t lds) {
+  // (each mapping's two kernels together: the single-config launch and the mixed batch's, regex_mixed.hip.h)
   if (lds > e->dfa_wave_lds_attr) {
     HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&dfa_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&dfa_mixed_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     e->dfa_wave_lds_attr = lds;
   }
   if (lds > e->dfa_lds_attr) {
     HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&dfa_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&dfa_mixed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     e->dfa_lds_attr = lds;
   }
   return 0;

@@ -68,6 +68,11 @@ def load_library(path: Optional[str] = None):
     lib.zke_verify_emails_with_regex.restype = C.c_int
     lib.zke_verify_emails_with_regex_async.argtypes = [vp, C.POINTER(A.zke_email_ref), C.c_uint32, C.POINTER(A.zke_regex_lists), vp, C.POINTER(C.c_uint64)]
     lib.zke_verify_emails_with_regex_async.restype = C.c_int
+    if hasattr(lib, "zke_verify_emails_mixed"):     # (a ZKE_LIB build of an older tree, for an A/B run, has no such entry)
+        lib.zke_verify_emails_mixed.argtypes = [vp, C.POINTER(A.zke_email_ref), C.c_uint32, C.POINTER(A.zke_regex_mixed), vp]
+        lib.zke_verify_emails_mixed.restype = C.c_int
+        lib.zke_verify_emails_mixed_async.argtypes = [vp, C.POINTER(A.zke_email_ref), C.c_uint32, C.POINTER(A.zke_regex_mixed), vp, C.POINTER(C.c_uint64)]
+        lib.zke_verify_emails_mixed_async.restype = C.c_int
     lib.zke_status_name.argtypes = [C.c_uint32]
     lib.zke_status_name.restype = C.c_char_p
     lib.zke_dfa_status.argtypes = [vp, C.c_uint32, u32p]
@@ -196,7 +201,7 @@ EXPORTED_SYMBOLS = [
     "zke_abi_encode", "zke_engine_join", "zke_verify_batch_async", "zke_batch_wait", "zke_dfa_status", "zke_dfa_unregister",
     "zke_process_init", "zke_abi_version", "zke_engine_reserve_host", "zke_wire_decode", "zke_wire_free", "zke_wire_view",
     "zke_wire_external_input", "zke_verify_wire", "zke_shard_bounds", "zke_status_name", "zke_verify_emails", "zke_verify_emails_async",
-    "zke_verify_emails_with_regex", "zke_verify_emails_with_regex_async",
+    "zke_verify_emails_with_regex", "zke_verify_emails_with_regex_async", "zke_verify_emails_mixed", "zke_verify_emails_mixed_async",
     "zke_capture_validate", "zke_capture_register", "zke_capture_status", "zke_capture_unregister", "zke_extract_captures",
     "zke_extract_captures_async", "zke_capture_batch",
     "zke_scan_signatures", "zke_scan_signatures_async", "zke_select_keys", "zke_select_keys_async",
@@ -823,6 +828,51 @@ class Engine:
         out = np.zeros(max(refs.n, 1), dtype=A.RESULT_DTYPE)
         self._check(self.lib.zke_verify_emails_with_regex(self.h, refs.arr, refs.n, C.byref(lists), out.ctypes.data), "zke_verify_emails_with_regex")
         return out[:refs.n]
+
+    def pack_mixed(self, inputs: Sequence) -> "A.MixedLists":
+        """The tables of zke_verify_emails_mixed for a sequence of ``Email`` / ``EmailWithRegex`` values: registers every pair, derives
+        the configs by equal id lists (first appearance first), config_of (an ``Email`` is ``_abi.CONFIG_NONE``: verify_email only)
+        and the e-mail-major capture tables."""
+        index: Dict[Tuple[Tuple[int, ...], Tuple[int, ...]], int] = {}
+        configs, config_of, caps = [], [], []
+        for inp in inputs:
+            if isinstance(inp, Email):
+                config_of.append(A.CONFIG_NONE)
+                caps.append(None)
+                continue
+            hp, bp = list(inp.regex_info.header_parts or []), list(inp.regex_info.body_parts or [])
+            key = (tuple(self.dfa_register(p.verify_re.fwd, p.verify_re.bwd) for p in hp),
+                   tuple(self.dfa_register(p.verify_re.fwd, p.verify_re.bwd) for p in bp))
+            if key not in index:
+                if len(configs) == A.MIXED_MAX_CONFIGS:
+                    raise EngineError("more than ZKE_MIXED_MAX_CONFIGS regex configs in one batch; split it")
+                index[key] = len(configs)
+                configs.append(key)
+            config_of.append(index[key])
+            caps.append([list(p.captures or []) for p in hp + bp])
+        return A.MixedLists(configs, config_of, caps)
+
+    @staticmethod
+    def _mixed_refs(inputs: Sequence) -> "A.EmailRefs":
+        return A.EmailRefs([i if isinstance(i, Email) else i.email for i in inputs])
+
+    def verify_emails_mixed(self, inputs: Sequence) -> np.ndarray:
+        """zke_verify_emails_mixed: ``Email`` and ``EmailWithRegex`` values in one batch, every EmailWithRegex with its own RegexInfo
+        (core/src/circuits.rs:31-68 takes them one at a time).  Record i is what verify_emails_with_regex gives input i in a batch
+        of its own config, or what verify_emails gives an ``Email``."""
+        lists, refs = self.pack_mixed(inputs), self._mixed_refs(inputs)
+        out = np.zeros(max(refs.n, 1), dtype=A.RESULT_DTYPE)
+        self._check(self.lib.zke_verify_emails_mixed(self.h, refs.arr, refs.n, C.byref(lists.c), out.ctypes.data), "zke_verify_emails_mixed")
+        return out[:refs.n]
+
+    def verify_emails_mixed_async(self, inputs: Sequence):
+        """zke_verify_emails_mixed_async: (ticket, records); the records are valid once ``wait(ticket)`` has returned."""
+        lists, refs = self.pack_mixed(inputs), self._mixed_refs(inputs)
+        out = np.zeros(max(refs.n, 1), dtype=A.RESULT_DTYPE)
+        t = C.c_uint64()
+        self._check(self.lib.zke_verify_emails_mixed_async(self.h, refs.arr, refs.n, C.byref(lists.c), out.ctypes.data, C.byref(t)),
+                    "zke_verify_emails_mixed_async")
+        return t.value, out[:refs.n]
 
     def verify_emails_async(self, refs: "A.EmailRefs"):
         """zke_verify_emails_async: (ticket, records); the records are valid once ``wait(ticket)`` has returned."""
