@@ -85,6 +85,31 @@ __device__ __forceinline__ uint32_t decode_rsa_key(const Str& k, RsaJob* J, Pkcs
   if (lane_id() == 0) { J->e = pk.e; J->k = nl; J->bits = bits; }
   return 0;
 }
+// The same decode in two parts, as the body canonicaliser is (canon_body_compute / canon_body_publish), for the round-0 front end with
+// a helper wave (parse.hip.h): the helper runs the first before anything is known about the e-mail and the second behind a barrier,
+// when the front-end wave has come through the key site.  Together they compute and store exactly what decode_rsa_key does; that one
+// keeps its text (the modulus stored before the last byte is looked at for `even`), and with it the one-wave kernels their instruction streams.
+//   compute  returns 0 or ZKE_D_KEY_*; pk, `even`, and byte lane + 64 t of the 512-byte modulus field in mb[t].  Reads the key, writes nothing.
+//   store    the RSA job's modulus / exponent
+struct RsaModBytes { uint8_t mb[8]; };
+__device__ __forceinline__ uint32_t decode_rsa_key_compute(const Str& k, Pkcs1& pk, uint32_t& even, RsaModBytes& m) {
+  Win w; w.wpos = WNONE; w.c = 0;
+  const uint32_t r = pkcs1_walk(k, w, 0, k.len, pk);
+  if (r) return r == PKCS1_DER ? ZKE_D_KEY_DER : ZKE_D_KEY_RANGE;
+  const uint32_t np = pk.np, nl = pk.nl;
+#pragma unroll
+  for (uint32_t t = 0; t < 8; t++) {
+    const uint32_t o = (uint32_t)lane_id() + 64 * t;
+    m.mb[t] = o >= 512 - nl ? (uint8_t)ldb(k, np + (o - (512 - nl))) : (uint8_t)0;
+  }
+  even = !(at(k, w, np + nl - 1) & 1) && pk.bits != 0;
+  return 0;
+}
+__device__ __forceinline__ void decode_rsa_key_store(RsaJob* J, const Pkcs1& pk, const RsaModBytes& m) {
+#pragma unroll
+  for (uint32_t t = 0; t < 8; t++) J->mod[(uint32_t)lane_id() + 64 * t] = m.mb[t];
+  if (lane_id() == 0) { J->e = pk.e; J->k = pk.nl; J->bits = pk.bits; }
+}
 
 // Which RSA routine takes this key's signatures: RSA_F_QUAD / RSA_F_OCT when the lane-group kernel for its size is part of
 // the batch's launch (mask: ROUTE_QUAD / ROUTE_OCT; ROUTE_OCT9: the launch has the eight-lane role for moduli <= 2048 bits, RSA_F_OCT9, in

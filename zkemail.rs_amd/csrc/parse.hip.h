@@ -1,5 +1,5 @@
 // parse.hip.h — device-side restatement of the e-mail front end of verify_dkim.  One e-mail per wavefront parses; in round 0
-// (parse_kernel<true>, blockDim = 128) a second wave per e-mail, the helper, canonicalises the body meanwhile.
+// (parse_kernel<true>, blockDim = 128) a second wave per e-mail, the helper, decodes the key and canonicalises the body meanwhile.
 //
 // Replaces, on the verify path (call sites core/src/email.rs:26-33, core/src/circuits.rs:34-35):
 //   * mailparse 0.15.0 parse_headers / parse_header (header list) and parse_mail_recursive's walk over the MIME
@@ -184,27 +184,46 @@ __device__ __forceinline__ void canon_body_publish(const BatchDev& B, uint32_t i
 // ------------------------------------------------------------------ the helper wave of the round-0 front end
 // parse_kernel<true> gives every e-mail a workgroup of two waves.  Wave 0 is the front end (parse_email<true, 0, true>); wave 1,
 // the helper, canonicalises the body (canon_body_compute) while wave 0 selects the headers and writes the header-hash preimage,
-// the longest stage of the chain, which needs nothing the canonicaliser produces.  The two meet at exactly two workgroup
-// barriers, on every path through the kernel:
+// the longest stage of the chain, which needs nothing the canonicaliser produces.  For the body the two meet at exactly two
+// workgroup barriers, on every path through the kernel:
 //   post  wave 0 has decoded the candidate's b= and knows whether the excised header went to region B (`copied`).  It leaves
 //         (flags, body_off, blen, l=) in the mailbox with go = 1, or go = 0 when region B is in use (`copied`) — then it
 //         canonicalises by itself at the end, as the one-wave front end does.
 //   join  where the one-wave front end calls canon_body_wave.  The helper has left (full, src_is_raw) in the mailbox; wave 0
 //         publishes them (canon_body_publish) if what it posted is still the candidate's (flags, l=).  It is not when the posted
 //         candidate's preimage overflowed and a later signature took its place: wave 0 then runs compute + publish itself.
-// The helper publishes nothing: the only global memory it writes is the canonical bytes in region B, dead unless a ShaJob points
-// at them.  Every record, EmailMeta field, job and bucket key is written by wave 0 where the one-wave front end writes it.
-// A path of wave 0 that ends before a barrier (every finish(...); return, ZKE_DEV_STOP) leaves it to parse_kernel, which executes
-// the barriers the mailbox says are missing, with go = 0.  Region B has one writer at a time: wave 0 writes it (the excised header
-// of a later candidate, the fallback) only behind the join.
+// The helper decides nothing: the global memory it writes is the canonical bytes in region B, dead unless a ShaJob points at them,
+// and (below) the RsaJob's key fields.  Every record, EmailMeta field, job and bucket key is written by wave 0 where the one-wave
+// front end writes it.  A path of wave 0 that ends before a barrier (every finish(...); return, ZKE_DEV_STOP) leaves it to
+// parse_kernel, which executes the barriers the mailbox says are missing, with key_go = 0 and go = 0.  Region B has one writer at a
+// time: wave 0 writes it (the excised header of a later candidate, the fallback) only behind the join.
+//
+// ZKE_HELPER_KEYDEC (default 1): a third barrier, in front of the other two, takes the key stage off wave 0's chain as well.  The
+// stage needs the key, its type, the key cache and the route mask — nothing of the e-mail —, so the helper, idle until the post,
+// runs it at kernel entry while wave 0 splits the headers: decode_rsa_key_compute and rsa_route, both without a store.
+//   key   where the key stage stands in the one-wave front end (behind the MIME check).  The helper has left (kr, bits, even,
+//         route) in the mailbox; wave 0 leaves key_go = 1 for an RSA key and, behind the barrier, does what it did with the values
+//         it computed itself: finish(ZKE_KEY_DECODE_FAIL, kr) or R->rsa_bits, M->key_ok / even_modulus / rsa_route.  The helper
+//         then stores the RsaJob's modulus / exponent (decode_rsa_key_store) if key_go && !kr: exactly when the one-wave front end
+//         stores them — an e-mail that fails earlier (parse, MIME) never comes through the key site and its job stays as it was.
+//         Wave 0's zeroing of J->bits / k / e at entry lies in front of its key barrier, whose release orders it before these stores.
+//         An Ed25519 or unknown key type: the helper computes nothing, wave 0 decides as before (key_go = 0).
+// Every wave then executes exactly three barriers on every path, in the order key, post, join.  (0: the two-barrier kernel above.)
+#ifndef ZKE_HELPER_KEYDEC
+#define ZKE_HELPER_KEYDEC 1
+#endif
 struct HelperBox {                 // the mailbox, in LDS
   uint32_t go;                     // 1: canonicalise with the four values below
   uint32_t flags, body_off, blen;
   uint32_t len_tag_lo, len_tag_hi;
   uint32_t full, src_is_raw;       // the helper's answer (canon_body_compute)
-  // wave 0's own: which of its two barriers it has executed.  (Here and not in registers: the signature loop's control flow is
+  // wave 0's own: which of its barriers it has executed.  (Here and not in registers: the signature loop's control flow is
   // divergent to the compiler, which would carry them through it in vector registers the front end does not have to spare.)
   uint32_t posted, joined;
+  // ZKE_HELPER_KEYDEC (unused, but there, in the two-barrier build: the switch stays out of the layout)
+  uint32_t keyed;
+  uint32_t key_go;                 // 1: wave 0 came through the key site with an RSA key
+  uint32_t kr, bits, even, route;  // the helper's answer: ZKE_D_KEY_* or 0 (decode_rsa_key_compute), Pkcs1::bits, even modulus, rsa_route or 0x800
 };
 
 // s_barrier with the workgroup fences __syncthreads() has: LDS traffic in front of it is complete and none behind it moves up
@@ -249,7 +268,11 @@ __device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i
   if (MODE == 0) stage_head(raw, L);
   const Str dom = mkstr(B.dom + B.dom_off[i], (uint32_t)(B.dom_off[i + 1] - B.dom_off[i]));
   const Str key = mkstr(B.key + B.key_off[i], (uint32_t)(B.key_off[i + 1] - B.key_off[i]));
-  uint8_t* regA = B.scratch + scratch_offset(r0 - B.raw_off[0], i);
+  uint64_t rel0 = r0 - B.raw_off[0];
+  // (the three-barrier kernel: the slot's address as a scalar.  As a vector pair — the offsets come from vector loads — it was the
+  // value the compiler spilled across the signature loop once the helper's key stage was in the kernel: 8 VGPR spills, 20 B of scratch)
+  if constexpr (HELPER && ZKE_HELPER_KEYDEC) rel0 = ((uint64_t)uni((uint32_t)(rel0 >> 32)) << 32) | uni((uint32_t)rel0);
+  uint8_t* regA = B.scratch + scratch_offset(rel0, i);
   const uint32_t capA = raw.len + PRE_SLACK;
 
   auto sha_job = [&](uint32_t kind, const void* src, uint32_t len, void* dst, uint32_t algo = 0) {
@@ -325,19 +348,30 @@ __device__ __forceinline__ void parse_email(const ParseArgs& A, const uint32_t i
   // ---- DkimPublicKey::try_from_bytes (core/src/email.rs:28-29)
   if (round == 0 && MODE == 0) {
     const uint32_t kt = B.key_type[i];
+    if constexpr (HELPER && ZKE_HELPER_KEYDEC) {
+      // ---- key: the helper has decoded and routed an RSA key meanwhile (HelperBox); it stores the job's key fields behind this barrier
+      if (lane == 0) { H->key_go = kt == ZKE_KEY_RSA ? 1u : 0u; H->keyed = 1; }
+      wg_barrier();
+    }
     if (kt == ZKE_KEY_ED25519) {
       // raw 32 bytes (helpers/src/dkim.rs:103-108); whether they are a curve point is decided by ed25519_email_kernel
       if (key.len != 32) { finish(ZKE_KEY_DECODE_FAIL, ZKE_D_KEY_DER); return; }
       if (lane == 0) M->key_ok = 2;
     } else {
       if (kt != ZKE_KEY_RSA) { finish(ZKE_KEY_DECODE_FAIL, ZKE_D_KEY_TYPE); return; }
-      Pkcs1 pk{0, 0, 0, 0};
-      uint32_t even = 0;
-      const uint32_t kr = decode_rsa_key(key, J, pk, even);
-      if (kr) { finish(ZKE_KEY_DECODE_FAIL, kr); return; }
-      uint32_t route = 0x800;           // no cache, no lane-group kernel in this launch, or an exponent / modulus they do not take
-      if (A.cache && A.route_mask && pk.e == 65537 && !even) route = rsa_route(key, pk.np, pk.nl, pk.bits, A.cache, A.route_mask);
-      if (lane == 0) { R->rsa_bits = pk.bits; M->key_ok = 1; M->even_modulus = even; M->rsa_route = route; }
+      if constexpr (HELPER && ZKE_HELPER_KEYDEC) {
+        const uint32_t kr = uni(H->kr);
+        if (kr) { finish(ZKE_KEY_DECODE_FAIL, kr); return; }
+        if (lane == 0) { R->rsa_bits = H->bits; M->key_ok = 1; M->even_modulus = H->even; M->rsa_route = H->route; }
+      } else {
+        Pkcs1 pk{0, 0, 0, 0};
+        uint32_t even = 0;
+        const uint32_t kr = decode_rsa_key(key, J, pk, even);
+        if (kr) { finish(ZKE_KEY_DECODE_FAIL, kr); return; }
+        uint32_t route = 0x800;           // no cache, no lane-group kernel in this launch, or an exponent / modulus they do not take
+        if (A.cache && A.route_mask && pk.e == 65537 && !even) route = rsa_route(key, pk.np, pk.nl, pk.bits, A.cache, A.route_mask);
+        if (lane == 0) { R->rsa_bits = pk.bits; M->key_ok = 1; M->even_modulus = even; M->rsa_route = route; }
+      }
     }
     // the two output witnesses (core/src/circuits.rs:16-17)
     sha_job(2, dom.base, dom.len, R->from_domain_hash);
@@ -644,7 +678,7 @@ constexpr size_t PARSE_DYN_LDS = ZKE_PARSE_WG_WAVES > 1 ? ZKE_PARSE_WG_WAVES * s
 #ifndef ZKE_PARSE_HELPER
 #define ZKE_PARSE_HELPER 1
 #endif
-static_assert(sizeof(ParseLds) + CANON_LDS_BYTES + sizeof(HelperBox) == 10840, "LDS per workgroup of parse_kernel<true>: DESIGN §3, profiles/kernel_resource_usage.txt");
+static_assert(sizeof(ParseLds) + CANON_LDS_BYTES + sizeof(HelperBox) == 10864, "LDS per workgroup of parse_kernel<true>: DESIGN §3, profiles/kernel_resource_usage.txt");
 template <bool HELPER>
 __global__ __launch_bounds__(HELPER ? 128 : 64 * ZKE_PARSE_WG_WAVES, ZKE_PARSE_WAVES) ZKE_PARSE_VGPR_ATTR void parse_kernel(ParseArgs A) {
   if constexpr (HELPER) {
@@ -656,17 +690,36 @@ __global__ __launch_bounds__(HELPER ? 128 : 64 * ZKE_PARSE_WG_WAVES, ZKE_PARSE_W
     if (email >= A.b.n) return;                        // (the whole workgroup)
     if (ZKE_PARSE_PRIO) __builtin_amdgcn_s_setprio(ZKE_PARSE_PRIO);
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // Two barriers per wave on every path: the helper's are the two below; wave 0 executes here whichever of its two
-    // parse_email did not reach.
+    // Three barriers per wave on every path (two with ZKE_HELPER_KEYDEC = 0), in the order key, post, join: the helper's are the
+    // ones below, straight-line; wave 0 executes here whichever of its own parse_email did not reach.
     if (wave == 0) {
-      if (lane_id() == 0) { box.posted = 0; box.joined = 0; }
+      if (lane_id() == 0) { box.keyed = ZKE_HELPER_KEYDEC ? 0 : 1; box.key_go = 0; box.posted = 0; box.joined = 0; }      // (two-barrier build: the key counts as done)
       parse_email<true, 0, true>(A, email, L, &box);
+      if (!uni(box.keyed)) wg_barrier();               // (key_go = 0 since the initialisation above)
       if (!uni(box.posted)) {
         if (lane_id() == 0) box.go = 0;
         wg_barrier();
       }
       if (!uni(box.joined)) wg_barrier();
     } else {
+      if constexpr (ZKE_HELPER_KEYDEC) {
+        // the key stage, on nothing but the batch's key columns: decoded and routed before wave 0 has split the headers
+        Pkcs1 pk{0, 0, 0, 0};
+        RsaModBytes mod{};
+        uint32_t kr = 0;
+        const bool rsa_key = uni(A.b.key_type[email]) == ZKE_KEY_RSA;
+        if (rsa_key) {
+          const uint64_t k0 = A.b.key_off[email], k1 = A.b.key_off[email + 1];
+          const Str key = mkstr(A.b.key + k0, (uint32_t)(k1 - k0));
+          uint32_t even = 0;
+          kr = uni(decode_rsa_key_compute(key, pk, even, mod));
+          uint32_t route = 0x800;         // no cache, no lane-group kernel in this launch, or an exponent / modulus they do not take
+          if (!kr && A.cache && A.route_mask && pk.e == 65537 && !even) route = rsa_route(key, pk.np, pk.nl, pk.bits, A.cache, A.route_mask);
+          if (lane_id() == 0) { box.kr = kr; box.bits = pk.bits; box.even = even; box.route = route; }
+        }
+        wg_barrier();                                    // key
+        if (rsa_key && !kr && uni(box.key_go)) decode_rsa_key_store(A.b.rsa + email, pk, mod);
+      }
       wg_barrier();                                    // post
       if (uni(box.go)) {
         uint32_t full, src_is_raw;
