@@ -1155,6 +1155,80 @@ impl Engine {
         }
         Ok(m)
     }
+
+    /// `zke_extract_captures_mixed`: the extraction over e-mails that carry different regex configs, in ONE batch.  `configs`: the
+    /// distinct configs (header parts, body parts); `config_of[i]`: e-mail i's, or `ZKE_CONFIG_NONE` (verify_email only).  The tables
+    /// are ragged — `cap_off` has J + 1 entries, spans / flags / origins are indexed by column (the header's job_off / col_off) —
+    /// and `cap_off` / `cap_str_off` / `cap_blob` are what `verify_emails_mixed`'s C entry takes.
+    pub fn extract_captures_mixed(&self, emails: &[Email], configs: &[(Vec<CapturePart>, Vec<CapturePart>)], config_of: &[u32]) -> Result<MappedCaptures, EngineError> {
+        let n = emails.len();
+        assert_eq!(config_of.len(), n, "one config index (or ZKE_CONFIG_NONE) per e-mail");
+        let refs: Vec<sys::zke_email_ref> = emails.iter().map(email_ref).collect();
+        let part = |p: &CapturePart| sys::zke_capture_part { dfa_id: p.dfa_id, prog_id: p.prog_id, n_groups: p.groups.len() as u32, groups: p.groups.as_ptr() };
+        let parts: Vec<Vec<sys::zke_capture_part>> = configs.iter().map(|(h, b)| h.iter().chain(b).map(part).collect()).collect();
+        let cfgs: Vec<sys::zke_capture_config> = configs
+            .iter()
+            .zip(&parts)
+            .map(|((h, b), p)| sys::zke_capture_config {
+                n_header_parts: h.len() as u32,
+                header_parts: p.as_ptr(),
+                n_body_parts: b.len() as u32,
+                body_parts: p[h.len()..].as_ptr(),
+            })
+            .collect();
+        let groups: Vec<usize> = configs.iter().map(|(h, b)| h.iter().chain(b).map(|p| p.groups.len()).sum()).collect();
+        let (mut nj, mut ng) = (0usize, 0usize);
+        for &c in config_of {
+            if c != sys::ZKE_CONFIG_NONE {
+                let c = c as usize;
+                assert!(c < configs.len(), "config_of names no config");
+                nj += parts[c].len();
+                ng += groups[c];
+            }
+        }
+        let mixed = sys::zke_capture_mixed { n_configs: cfgs.len() as u32, configs: cfgs.as_ptr(), config_of: config_of.as_ptr() };
+        let mut m = MappedCaptures {
+            records: vec![zeroed_result(); n],
+            spans: vec![0; ng * 2],
+            flags: vec![0; ng],
+            cap_off: vec![0; nj + 1],
+            cap_str_off: vec![0; ng + 1],
+            cap_blob: vec![0; ng * 32 + 1],
+            origin_spans: vec![0; ng * 2],
+            origin_flags: vec![0; ng],
+        };
+        for attempt in 0..2 {
+            let mut caps: sys::zke_capture_out = unsafe { std::mem::zeroed() };
+            caps.spans = m.spans.as_mut_ptr();
+            caps.spans_cap = ng * 2;
+            caps.flags = m.flags.as_mut_ptr();
+            caps.flags_cap = ng;
+            caps.cap_off = m.cap_off.as_mut_ptr();
+            caps.cap_off_cap = nj + 1;
+            caps.cap_str_off = m.cap_str_off.as_mut_ptr();
+            caps.cap_str_off_cap = ng + 1;
+            caps.cap_blob = m.cap_blob.as_mut_ptr();
+            caps.cap_blob_cap = m.cap_blob.len();
+            let mut org: sys::zke_capture_origin = unsafe { std::mem::zeroed() };
+            org.spans = m.origin_spans.as_mut_ptr();
+            org.spans_cap = ng * 2;
+            org.flags = m.origin_flags.as_mut_ptr();
+            org.flags_cap = ng;
+            // SAFETY: every pointer refers into the arguments, `parts`, `cfgs` or `m`, alive and unmoved until the synchronous call returns.
+            let rc = unsafe { sys::zke_extract_captures_mixed(self.raw, refs.as_ptr(), n as u32, &mixed, m.records.as_mut_ptr(), &mut caps, &mut org) };
+            if rc == sys::ZKE_E_NOMEM && attempt == 0 && caps.cap_blob_need > m.cap_blob.len() {
+                m.cap_blob = vec![0; caps.cap_blob_need];
+                continue;
+            }
+            if rc != 0 {
+                return Err(self.last_error(rc));
+            }
+            m.cap_str_off.truncate(caps.n_strings + 1);
+            m.cap_blob.truncate(caps.cap_blob_need);
+            break;
+        }
+        Ok(m)
+    }
 }
 
 impl Drop for Engine {

@@ -550,6 +550,42 @@ int zke_extract_captures_mapped_async(zke_engine* e, const zke_email_ref* emails
                                       const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out, zke_capture_out* caps,
                                       zke_capture_origin* org, uint64_t* ticket);
 
+/* The extraction over `&[Email]` whose e-mails carry DIFFERENT regex configs — what produces, in one call, the values
+ * zke_verify_emails_mixed consumes: `configs` are the distinct RegexConfigs (parts with their programs and requested groups),
+ * config_of[i] names e-mail i's, ZKE_CONFIG_NONE an e-mail that is verify_email only.
+ * Layout.  With P_i and G_i the part count and the requested-group count of e-mail i's config (both 0 for ZKE_CONFIG_NONE), job_off
+ * and col_off their prefix sums, J = job_off[n] and Gt = col_off[n]: part p of e-mail i is job job_off[i] + p, header parts first,
+ * exactly as in zke_regex_mixed; requested group k of that part is column col_off[i] + gbase[p] + k, gbase the prefix sum of the
+ * config's per-part group counts.  `caps` sizes are known up front — spans 2*Gt, flags Gt, cap_off J+1, cap_str_off Gt+1 — and so
+ * are `org`'s (NULL: no origins): spans 2*Gt, flags Gt.  Both follow the conventions of zke_capture_out / zke_capture_origin: too
+ * small fails at once with ZKE_E_NOMEM and the *_need fields set; a short cap_blob delivers everything else and reports
+ * cap_blob_need exactly.  cap_off / cap_str_off / cap_blob are byte for byte what zke_regex_mixed takes.
+ * Records.  out[i], the e-mail's spans, flags, strings and origins are exactly what zke_extract_captures[_mapped] gives e-mail i in a
+ * batch that holds only its own config, the single fold included (the first failing part in verify order, for either reason).  For
+ * ZKE_CONFIG_NONE out[i] is the record of zke_verify_emails: the e-mail has no job and no column, and the regex and capture stages
+ * neither read nor write it.
+ * ZKE_E_ARG, before anything is staged (`out` and `caps` untouched): n_configs above ZKE_MIXED_MAX_CONFIGS; a config with 0 parts or
+ * more than ZKE_CAP_MAX_PARTS (the single-config entry's rule: ZKE_CONFIG_NONE is the way to say "no regex"); a part asking for more
+ * than ZKE_CAP_MAX_GROUPS groups; a null list with a non-zero count; a config_of[i] that is neither below n_configs nor
+ * ZKE_CONFIG_NONE; Gt * ZKE_CAP_MAX_SPAN >= 4 GiB (Gt >= 2^20).
+ * An unknown or undecodable DFA or program id fails only the e-mails of the configs that use it: ZKE_DFA_DECODE_FAIL with the
+ * section, or ZKE_UNSUPPORTED / ZKE_D_U_CAPTURE_*.  Slots, tickets, zke_batch_wait and the lifetimes of `caps` / `org` are as for
+ * zke_extract_captures_async; everything `mixed` points to has been read when the call returns.  The slot's capture buffers are
+ * sized by J and Gt and only grow; zke_engine_reserve's sizing is unchanged, so a mixed extraction larger than the reserved shape
+ * (max_n * max_regex_parts jobs, four groups per part) regrows them once, as a larger batch does. */
+typedef struct zke_capture_config {          /* one RegexConfig: the parts with their programs and requested groups */
+  uint32_t n_header_parts; const zke_capture_part* header_parts;
+  uint32_t n_body_parts;   const zke_capture_part* body_parts;
+} zke_capture_config;
+typedef struct zke_capture_mixed {
+  uint32_t n_configs; const zke_capture_config* configs;
+  const uint32_t* config_of;                 /* [n]: index into configs, or ZKE_CONFIG_NONE: verify_email only */
+} zke_capture_mixed;
+int zke_extract_captures_mixed(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_mixed* mixed, zke_result* out,
+                               zke_capture_out* caps, zke_capture_origin* org /* NULL: no origins */);
+int zke_extract_captures_mixed_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_mixed* mixed, zke_result* out,
+                                     zke_capture_out* caps, zke_capture_origin* org, uint64_t* ticket);
+
 /* ---- DKIM-Signature scan and key selection: the compute on both sides of the caller's DNS fetch in the reference's
  * generate_email_inputs (helpers/src/generator.rs:11-53).  The fetch itself, like all IO, stays with the caller:
  *     zke_scan_signatures   raw e-mails + from_domain -> per e-mail every DKIM-Signature header with its validate_header verdict,

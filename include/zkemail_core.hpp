@@ -320,6 +320,61 @@ class Engine {
                                            const std::vector<CapturePart>& body_parts, CaptureTables& caps, CaptureOrigins& origins) {
     return extract(emails, header_parts, body_parts, caps, &origins);
   }
+  // zke_extract_captures_mixed: the extraction over e-mails that carry different regex configs, in ONE batch.  `configs`: the
+  // distinct configs (header parts, body parts); config_of[i]: e-mail i's, or ZKE_CONFIG_NONE (verify_email only).  `caps` is ragged:
+  // cap_off has J + 1 entries, spans / flags / cap_str_off are indexed by column (the header's job_off / col_off) — the tables
+  // zke_verify_emails_mixed takes.  origins: nullptr, or where the spans lie before the QP filter (the same columns).
+  std::vector<zke_result> extract_captures_mixed(const std::vector<Email>& emails,
+                                                 const std::vector<std::pair<std::vector<CapturePart>, std::vector<CapturePart>>>& configs,
+                                                 const std::vector<uint32_t>& config_of, CaptureTables& caps, CaptureOrigins* origins = nullptr) {
+    if (config_of.size() != emails.size()) throw EngineError("one config index (or ZKE_CONFIG_NONE) per e-mail");
+    const uint32_t n = (uint32_t)emails.size();
+    std::vector<zke_email_ref> refs(n);
+    for (uint32_t i = 0; i < n; i++) {
+      const Email& em = emails[i];
+      uint32_t ext = 0;
+      for (const auto& x : em.external_inputs) if (!x.value) ext = 1;
+      refs[i] = zke_email_ref{em.raw_email.data(), em.raw_email.size(), em.from_domain.data(), em.from_domain.size(),
+                              em.public_key.key.data(), em.public_key.key.size(), key_type_code(em.public_key.key_type), ext};
+    }
+    std::vector<std::vector<zke_capture_part>> parts(configs.size());
+    std::vector<zke_capture_config> cfgs(configs.size());
+    std::vector<size_t> P(configs.size()), G(configs.size(), 0);
+    for (size_t c = 0; c < configs.size(); c++) {
+      for (const auto* side : {&configs[c].first, &configs[c].second})
+        for (const auto& p : *side) { parts[c].push_back(zke_capture_part{p.dfa_id, p.prog_id, (uint32_t)p.groups.size(), p.groups.data()}); G[c] += p.groups.size(); }
+      P[c] = parts[c].size();
+      cfgs[c] = zke_capture_config{(uint32_t)configs[c].first.size(), parts[c].data(), (uint32_t)configs[c].second.size(),
+                                   parts[c].data() + configs[c].first.size()};
+    }
+    size_t J = 0, Gt = 0;
+    for (uint32_t c : config_of) {
+      if (c == ZKE_CONFIG_NONE) continue;
+      if (c >= configs.size()) throw EngineError("config_of names no config");
+      J += P[c]; Gt += G[c];
+    }
+    caps.spans.assign(Gt * 2 + 1, 0); caps.flags.assign(Gt + 1, 0); caps.cap_off.assign(J + 1, 0); caps.cap_str_off.assign(Gt + 1, 0);
+    caps.cap_blob.assign(Gt * 32 + 1, 0);
+    zke_capture_origin org{};
+    if (origins) {
+      origins->spans.assign(Gt * 2 + 1, 0); origins->flags.assign(Gt + 1, 0);
+      org = zke_capture_origin{origins->spans.data(), Gt * 2, origins->flags.data(), Gt, 0, 0};
+    }
+    const zke_capture_mixed mixed{(uint32_t)cfgs.size(), cfgs.data(), config_of.data()};
+    std::vector<zke_result> out(n);
+    zke_capture_out o{};
+    for (int attempt = 0; attempt < 2; attempt++) {
+      o = zke_capture_out{caps.spans.data(), Gt * 2, caps.flags.data(), Gt, caps.cap_off.data(), J + 1, caps.cap_str_off.data(), Gt + 1,
+                          caps.cap_blob.data(), caps.cap_blob.size(), 0, 0, 0, 0, 0, 0};
+      const int r = zke_extract_captures_mixed(e_, refs.data(), n, &mixed, out.data(), &o, origins ? &org : nullptr);
+      if (r == ZKE_E_NOMEM && attempt == 0 && o.cap_blob_need > caps.cap_blob.size()) { caps.cap_blob.resize(o.cap_blob_need); continue; }
+      if (r) throw EngineError("zke_extract_captures_mixed failed: " + std::to_string(r) + " " + zke_last_error(e_));
+      break;
+    }
+    caps.spans.resize(Gt * 2); caps.flags.resize(Gt); caps.cap_str_off.resize(o.n_strings + 1); caps.cap_blob.resize(o.cap_blob_need);
+    if (origins) { origins->spans.resize(Gt * 2); origins->flags.resize(Gt); }
+    return out;
+  }
 
   // helpers/src/generator.rs:17-30 for a batch (zke_scan_signatures): every DKIM-Signature header of every e-mail with
   // validate_header's verdict, whether d= names from_domain, a= classified and the selector.

@@ -11,10 +11,12 @@ from ._abi import (  # noqa: F401
     RESULT_DTYPE, STATUS_NAMES, STATUS_SITE,
 )
 from .engine import (BodyInfo, Engine, EngineError, KeyInfo, SigInfo, SigScan, VerifyPanic, extract_email_body,  # noqa: F401
-                     generate_email_inputs, generate_email_inputs_from_records, generate_email_with_regex_inputs, verify_email, verify_email_with_regex)
+                     generate_email_inputs, generate_email_inputs_from_records, generate_email_with_regex_inputs, generate_email_with_regex_inputs_mixed,
+                     verify_email, verify_email_with_regex)
 
 __all__ = [
     "Engine", "EngineError", "VerifyPanic", "verify_email", "verify_email_with_regex", "generate_email_with_regex_inputs",
+    "generate_email_with_regex_inputs_mixed",
     "generate_email_inputs", "SigInfo", "SigScan", "generate_email_inputs_from_records", "KeyInfo",
     "extract_email_body", "BodyInfo",
     "Email", "EmailWithRegex", "PublicKey", "ExternalInput", "DFA", "CompiledRegex", "RegexInfo",

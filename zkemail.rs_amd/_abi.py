@@ -345,6 +345,56 @@ class MixedLists:
             m.cap_off, m.cap_str_off, m.cap_blob = self.cap_off.ctypes.data, self.cap_str_off.ctypes.data, self.cap_blob.ctypes.data
 
 
+class zke_capture_config(C.Structure):
+    """One RegexConfig of a mixed extraction (zke_extract_captures_mixed): the parts with their programs and requested groups."""
+    _fields_ = [
+        ("n_header_parts", C.c_uint32), ("header_parts", C.POINTER(zke_capture_part)),
+        ("n_body_parts", C.c_uint32), ("body_parts", C.POINTER(zke_capture_part)),
+    ]
+
+
+class zke_capture_mixed(C.Structure):
+    _fields_ = [("n_configs", C.c_uint32), ("configs", C.POINTER(zke_capture_config)), ("config_of", C.c_void_p)]
+
+
+class CaptureMixedLists:
+    """The tables of one zke_extract_captures_mixed call.  `configs`: [(header parts, body parts)], a part (dfa_id, prog_id, groups);
+    `config_of`: per e-mail an index into it or CONFIG_NONE.  Derived, as the header lays them out: job_off / col_off [n + 1] (the
+    prefix sums of the e-mails' part and requested-group counts), J, Gt, and per config gbase (the first column of each part among
+    the config's G).  Keeps the buffers alive and exposes a ``zke_capture_mixed``."""
+
+    def __init__(self, configs, config_of: Sequence[int]):
+        self.n = len(config_of)
+        self.configs = [([(int(d), int(p), [int(g) for g in gs]) for d, p, gs in h], [(int(d), int(p), [int(g) for g in gs]) for d, p, gs in b])
+                        for h, b in configs]
+        self.config_of = np.array(list(config_of) or [0], dtype=np.uint32)
+        self.arr = (zke_capture_config * max(len(self.configs), 1))()
+        self._keep = []
+        self.gbase: List[List[int]] = []
+        for k, (h, b) in enumerate(self.configs):
+            parts = (zke_capture_part * max(len(h) + len(b), 1))()
+            gb = [0]
+            for j, (dfa_id, prog_id, gs) in enumerate(h + b):
+                g = np.array(gs or [0], np.uint32)
+                self._keep.append(g)
+                parts[j].dfa_id, parts[j].prog_id, parts[j].n_groups, parts[j].groups = dfa_id, prog_id, len(gs), g.ctypes.data
+                gb.append(gb[-1] + len(gs))
+            self._keep.append(parts)
+            self.gbase.append(gb)
+            self.arr[k].n_header_parts, self.arr[k].header_parts = len(h), parts
+            self.arr[k].n_body_parts = len(b)
+            self.arr[k].body_parts = C.cast(C.byref(parts, len(h) * C.sizeof(zke_capture_part)), C.POINTER(zke_capture_part))
+        parts_of = [0 if c == CONFIG_NONE else len(self.configs[c][0]) + len(self.configs[c][1]) for c in config_of]
+        groups_of = [0 if c == CONFIG_NONE else self.gbase[c][-1] for c in config_of]
+        self.job_off, self.col_off = np.zeros(self.n + 1, np.uint32), np.zeros(self.n + 1, np.uint32)
+        if self.n:
+            self.job_off[1:] = np.cumsum(parts_of)
+            self.col_off[1:] = np.cumsum(groups_of)
+        self.J, self.Gt = int(self.job_off[self.n]), int(self.col_off[self.n])
+        m = self.c = zke_capture_mixed()
+        m.n_configs, m.configs, m.config_of = len(self.configs), self.arr, self.config_of.ctypes.data
+
+
 class EmailRefs:
     """An array of zke_email_ref over a list of Email values, pointing INTO their bytes objects (nothing is copied; the list is
     kept alive by this object)."""

@@ -222,6 +222,53 @@ __device__ __forceinline__ uint32_t cap_walk(const CapProgDev& Pg, const uint8_t
   return ZKE_D_U_CAPTURE_WALK;
 }
 
+// Item `item` of a capture launch — one (e-mail, part) — by one wave: the walk over the match `pr` the search left, the requested
+// groups into the part's columns (`row`: the e-mail's first column; the part's follow from its gbase), the capture verdict into
+// codes[item].  hay_of(hay, hlen): the part's haystack, asked for only when the part is walked.  Rows: lds_rows for programs of at
+// most CAP_LDS_STATES states, else this wave's slice of `work`.
+template <class HayOf>
+__device__ __forceinline__ void cap_item(const CapPartDev& part, const PartRes pr, HayOf hay_of, uint64_t* lds_rows, uint64_t* work,
+                                         uint32_t* spans, uint8_t* flags, size_t row, uint32_t* codes, uint32_t item, int lane) {
+  uint32_t code = 0;
+  // every part the search left with exactly one match is walked, whatever the regex fold has written into the record meanwhile:
+  // the fold of the gather launch needs the capture verdict of the parts IN FRONT of a part that fails on its match count
+  const bool run = pr.code == 0 && pr.count == 1;
+  uint32_t slot = CAP_NONE;
+  const uint8_t* hay = nullptr; uint32_t hlen = 0;
+  if (run) {
+    if (part.code) code = part.code;
+    else if (pr.end - pr.start > ZKE_CAP_MAX_SPAN) code = ZKE_D_U_CAPTURE_SPAN;
+    else {
+      hay_of(hay, hlen);
+      uint64_t* rows = part.prog.words64 <= CAP_LDS_WORDS ? lds_rows : work + (size_t)blockIdx.x * CAP_WORK_WORDS;
+      code = cap_walk(part.prog, hay, hlen, pr.start, pr.end, rows, slot, lane);
+    }
+  }
+  // the requested groups: lane k answers for groups[k]
+  const uint32_t ng = part.n_groups;
+  uint32_t gs = CAP_NONE, ge = CAP_NONE;
+  bool missing = false;
+  {
+    const uint32_t g = (uint32_t)lane < ng ? part.groups[lane] : 0;
+    const bool inprog = g < part.prog.n_groups;
+    const uint32_t a = __shfl(slot, (2 * g) & 63), b = __shfl(slot, (2 * g + 1) & 63);
+    if (run && !code && (uint32_t)lane < ng) {
+      if (inprog && a != CAP_NONE && b != CAP_NONE && a <= b) { gs = a; ge = b; }
+      else missing = true;                         // "Capture group not found"  helpers/src/regex.rs:31
+    }
+  }
+  if (run && !code && __ballot(missing)) code = ZKE_D_RE_GROUP_MISSING;
+  if ((uint32_t)lane < ng) {
+    const size_t col = row + part.gbase + lane;
+    const bool have = run && !code;
+    spans[2 * col] = have ? gs : CAP_NONE;
+    spans[2 * col + 1] = have ? ge : CAP_NONE;
+    flags[col] = have && !utf8_valid(hay + gs, ge - gs) ? CAPF_NOT_UTF8 : 0;
+  }
+  if (lane == 0) codes[item] = code;
+  cap_sync();                                      // the next item reuses the rows
+}
+
 // One wave per (e-mail, part); the host bounds the grid (CAP_WORK_WAVES when rows live in the workspace) and each wave loops.  blockDim = 64.
 __global__ __launch_bounds__(64) void capture_kernel(CapArgs A) {
   __shared__ uint64_t lds_rows[CAP_ROWS * CAP_LDS_WORDS];
@@ -230,46 +277,12 @@ __global__ __launch_bounds__(64) void capture_kernel(CapArgs A) {
   for (uint32_t item = blockIdx.x; item < items; item += gridDim.x) {
     const uint32_t i = item / A.P, p = item % A.P;
     const CapPartDev& part = A.part[p];
-    const PartRes pr = A.parts[item];
-    uint32_t code = 0;
-    // every part the search left with exactly one match is walked, whatever the regex fold has written into the record meanwhile:
-    // the fold of capture_gather_kernel needs the capture verdict of the parts IN FRONT of a part that fails on its match count
-    const bool run = pr.code == 0 && pr.count == 1;
-    uint32_t slot = CAP_NONE;
-    const uint8_t* hay = nullptr; uint32_t hlen = 0;
-    if (run) {
-      if (part.code) code = part.code;
-      else if (pr.end - pr.start > ZKE_CAP_MAX_SPAN) code = ZKE_D_U_CAPTURE_SPAN;
-      else {
-        if (A.plain) { hay = A.hay_blob + A.hay_off[i]; hlen = (uint32_t)(A.hay_off[i + 1] - A.hay_off[i]); }
-        else { DfaArgs D = A.d; D.is_body = p >= A.n_header_parts ? 1u : 0u; dfa_haystack(D, i, A.d.b.meta + i, hay, hlen); }
-        uint64_t* rows = part.prog.words64 <= CAP_LDS_WORDS ? lds_rows : A.work + (size_t)blockIdx.x * CAP_WORK_WORDS;
-        code = cap_walk(part.prog, hay, hlen, pr.start, pr.end, rows, slot, lane);
-      }
-    }
-    // the requested groups: lane k answers for groups[k]
-    const uint32_t ng = part.n_groups;
-    uint32_t gs = CAP_NONE, ge = CAP_NONE;
-    bool missing = false;
-    {
-      const uint32_t g = (uint32_t)lane < ng ? part.groups[lane] : 0;
-      const bool inprog = g < part.prog.n_groups;
-      const uint32_t a = __shfl(slot, (2 * g) & 63), b = __shfl(slot, (2 * g + 1) & 63);
-      if (run && !code && (uint32_t)lane < ng) {
-        if (inprog && a != CAP_NONE && b != CAP_NONE && a <= b) { gs = a; ge = b; }
-        else missing = true;                         // "Capture group not found"  helpers/src/regex.rs:31
-      }
-    }
-    if (run && !code && __ballot(missing)) code = ZKE_D_RE_GROUP_MISSING;
-    if ((uint32_t)lane < ng) {
-      const size_t col = (size_t)i * A.G + part.gbase + lane;
-      const bool have = run && !code;
-      A.spans[2 * col] = have ? gs : CAP_NONE;
-      A.spans[2 * col + 1] = have ? ge : CAP_NONE;
-      A.flags[col] = have && !utf8_valid(hay + gs, ge - gs) ? CAPF_NOT_UTF8 : 0;
-    }
-    if (lane == 0) A.codes[item] = code;
-    cap_sync();                                      // the next item reuses the rows
+    cap_item(part, A.parts[item],
+             [&](const uint8_t*& hay, uint32_t& hlen) {
+               if (A.plain) { hay = A.hay_blob + A.hay_off[i]; hlen = (uint32_t)(A.hay_off[i + 1] - A.hay_off[i]); }
+               else { DfaArgs D = A.d; D.is_body = p >= A.n_header_parts ? 1u : 0u; dfa_haystack(D, i, A.d.b.meta + i, hay, hlen); }
+             },
+             lds_rows, A.work, A.spans, A.flags, (size_t)i * A.G, A.codes, item, lane);
   }
 }
 
@@ -319,41 +332,61 @@ __device__ __forceinline__ uint64_t cap_block_scan(uint32_t* v, size_t cnt, uint
   return total;
 }
 
+// Verdict of one e-mail, ONE fold over its P parts in verify order as compile_regex_parts walks them (helpers/src/regex.rs:21-47:
+// the match count of a part, then its groups, then the next part).  The regex fold in front of the gather launch has named the first
+// part whose SEARCH fails (decode, quit, match count); a part in front of that one whose capture fails takes the record over.
+// regex_part == 0xFFFFFFFF: the regex fold never looked at a part (DKIM or canonicalisation failed) — the record stands.
+// `parts`, `codes`: the e-mail's own P entries; nh: its config's header parts.  Returns whether the e-mail yields strings.
+__device__ __forceinline__ bool cap_fold_email(zke_result* R, const PartRes* parts, const uint32_t* codes, uint32_t P, uint32_t nh) {
+  bool ok = true;
+  if (R->regex_part == CAP_NONE) ok = false;
+  for (uint32_t p = 0; p < P && ok; p++) {
+    const PartRes pr = parts[p];
+    const uint32_t code = codes[p];
+    if (pr.code != 0 || pr.count != 1) ok = false;            // the part the regex fold named (or one it skipped behind it)
+    else if (code) {
+      R->status = code == ZKE_D_RE_GROUP_MISSING ? (p < nh ? ZKE_HEADER_REGEX_FAIL : ZKE_BODY_REGEX_FAIL) : ZKE_UNSUPPORTED;
+      R->detail = code;
+      R->regex_part = p; R->match_count = pr.count; R->match_start = pr.start; R->match_end = pr.end;
+      ok = false;
+    }
+  }
+  return ok;
+}
+// The lengths of one (e-mail, part): the strings it yields into *nstr, the bytes of each of its ng columns into nbytes[0, ng);
+// spans: the {start, end} pairs of those columns — a part that yields no strings yields no span either.
+__device__ __forceinline__ void cap_part_lengths(bool part_ok, uint32_t ng, uint32_t* nstr, uint32_t* nbytes, uint32_t* spans) {
+  *nstr = part_ok ? ng : 0;
+  for (uint32_t c = 0; c < ng; c++) {
+    const uint32_t s = spans[2 * c], e = spans[2 * c + 1];
+    nbytes[c] = part_ok && s != CAP_NONE ? e - s : 0;
+    if (!part_ok) { spans[2 * c] = CAP_NONE; spans[2 * c + 1] = CAP_NONE; }
+  }
+}
+// One column's string into the tables: string `sidx` of `strings` starts at byte `at` of `bytes`; its bytes are hay[s, e) of the
+// haystack hay_of() names (asked for only when the bytes fit the caller's blob).
+template <class HayOf>
+__device__ __forceinline__ void cap_put_string(uint32_t sidx, uint32_t at, uint32_t s, uint32_t e, uint64_t strings, uint64_t bytes,
+                                               uint32_t* cap_str_off, uint8_t* cap_blob, uint64_t blob_cap, HayOf hay_of) {
+  cap_str_off[sidx] = at;
+  if (sidx + 1 == strings) cap_str_off[strings] = (uint32_t)bytes;
+  const uint32_t len = e - s;
+  if ((uint64_t)at + len > blob_cap) return;          // the caller's blob is too small: sizes are reported, nothing is cut short silently
+  const uint8_t* hay = hay_of();
+  for (uint32_t k = 0; k < len; k++) cap_blob[at + k] = hay[s + k];
+}
+
 __global__ __launch_bounds__(1024) void capture_gather_kernel(CapGatherArgs A) {
   __shared__ uint64_t sh[1025];
   const uint32_t T = blockDim.x, t = threadIdx.x;
   uint32_t* nstr = A.tmp;                              // [n * P]
   uint32_t* nbytes = A.tmp + (size_t)A.n * A.P;        // [n * G]
-  // Verdict per e-mail, ONE fold over the parts in verify order as compile_regex_parts walks them (helpers/src/regex.rs:21-47:
-  // the match count of a part, then its groups, then the next part).  The regex fold in front of this launch has named the first
-  // part whose SEARCH fails (decode, quit, match count); a part in front of that one whose capture fails takes the record over.
-  // regex_part == 0xFFFFFFFF: the regex fold never looked at a part (DKIM or canonicalisation failed) — the record stands.
   for (uint32_t i = t; i < A.n; i += T) {
-    bool ok = true;
-    if (!A.plain) {
-      zke_result* R = A.results + i;
-      if (R->regex_part == CAP_NONE) ok = false;
-      for (uint32_t p = 0; p < A.P && ok; p++) {
-        const PartRes pr = A.parts[(size_t)i * A.P + p];
-        const uint32_t code = A.codes[(size_t)i * A.P + p];
-        if (pr.code != 0 || pr.count != 1) ok = false;            // the part the regex fold named (or one it skipped behind it)
-        else if (code) {
-          R->status = code == ZKE_D_RE_GROUP_MISSING ? (p < A.n_header_parts ? ZKE_HEADER_REGEX_FAIL : ZKE_BODY_REGEX_FAIL) : ZKE_UNSUPPORTED;
-          R->detail = code;
-          R->regex_part = p; R->match_count = pr.count; R->match_start = pr.start; R->match_end = pr.end;
-          ok = false;
-        }
-      }
-    }
+    const bool ok = A.plain ? true : cap_fold_email(A.results + i, A.parts + (size_t)i * A.P, A.codes + (size_t)i * A.P, A.P, A.n_header_parts);
     for (uint32_t p = 0; p < A.P; p++) {
       const bool part_ok = A.plain ? (A.codes[(size_t)i * A.P + p] == 0 && A.parts[(size_t)i * A.P + p].code == 0 && A.parts[(size_t)i * A.P + p].count == 1) : ok;
-      nstr[(size_t)i * A.P + p] = part_ok ? A.gbase[p + 1] - A.gbase[p] : 0;
-      for (uint32_t c = A.gbase[p]; c < A.gbase[p + 1]; c++) {
-        const size_t col = (size_t)i * A.G + c;
-        const uint32_t s = A.spans[2 * col], e = A.spans[2 * col + 1];
-        nbytes[col] = part_ok && s != CAP_NONE ? e - s : 0;
-        if (!part_ok) { A.spans[2 * col] = CAP_NONE; A.spans[2 * col + 1] = CAP_NONE; }     // an e-mail that fails yields no span either
-      }
+      const size_t col = (size_t)i * A.G + A.gbase[p];
+      cap_part_lengths(part_ok, A.gbase[p + 1] - A.gbase[p], nstr + (size_t)i * A.P + p, nbytes + col, A.spans + 2 * col);
     }
   }
   __syncthreads();
@@ -372,18 +405,14 @@ __global__ __launch_bounds__(1024) void capture_gather_kernel(CapGatherArgs A) {
     const size_t ip = (size_t)i * A.P + p;
     const uint32_t first = A.cap_off[ip], cnt = A.cap_off[ip + 1] - first;
     if (!cnt) continue;
-    const uint32_t sidx = first + (c - A.gbase[p]);
-    const uint32_t at = nbytes[col];
-    const uint32_t s = A.spans[2 * col], e = A.spans[2 * col + 1];
-    A.cap_str_off[sidx] = at;
-    if (sidx + 1 == strings) A.cap_str_off[strings] = (uint32_t)bytes;
-    const uint32_t len = e - s;
-    if ((uint64_t)at + len > A.blob_cap) continue;     // the caller's blob is too small: sizes are reported, nothing is cut short silently
-    const uint8_t* hay; uint32_t hlen;
-    if (A.plain) { hay = A.hay_blob + A.hay_off[i]; hlen = 0; }
-    else { DfaArgs D = A.d; D.is_body = p >= A.n_header_parts ? 1u : 0u; dfa_haystack(D, i, A.d.b.meta + i, hay, hlen); }
-    (void)hlen;
-    for (uint32_t k = 0; k < len; k++) A.cap_blob[at + k] = hay[s + k];
+    cap_put_string(first + (c - A.gbase[p]), nbytes[col], A.spans[2 * col], A.spans[2 * col + 1], strings, bytes, A.cap_str_off, A.cap_blob, A.blob_cap,
+                   [&]() -> const uint8_t* {
+                     const uint8_t* hay; uint32_t hlen;
+                     if (A.plain) { hay = A.hay_blob + A.hay_off[i]; hlen = 0; }
+                     else { DfaArgs D = A.d; D.is_body = p >= A.n_header_parts ? 1u : 0u; dfa_haystack(D, i, A.d.b.meta + i, hay, hlen); }
+                     (void)hlen;
+                     return hay;
+                   });
   }
   if (t == 0 && strings == 0) A.cap_str_off[0] = 0;
 }

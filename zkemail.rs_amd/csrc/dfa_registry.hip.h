@@ -239,16 +239,17 @@ struct CapLayout {
   size_t hdr, codes, spans, flags, cap_off, cap_str_off, fixed_end, tmp, blob, total;
   size_t blob_cap;
 };
-inline CapLayout cap_layout(uint32_t n, uint32_t P, uint32_t G, size_t blob_cap) {
+// NP (e-mail, part) jobs and NG columns: n * P and n * G of one part list per batch, J and Gt of a mixed extraction
+inline CapLayout cap_layout_sized(size_t NP, size_t NG, size_t blob_cap) {
   CapLayout L{};
   size_t o = 0;
   auto put = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 63) & ~(size_t)63; return at; };
-  const size_t NP = (size_t)n * P, NG = (size_t)n * G;
   L.hdr = put(64); L.codes = put(NP * 4); L.spans = put(NG * 8); L.flags = put(NG); L.cap_off = put((NP + 1) * 4);
   L.cap_str_off = put((NG + 1) * 4); L.fixed_end = o; L.tmp = put((NP + NG) * 4); L.blob = put(blob_cap + 64); L.total = o;
   L.blob_cap = blob_cap;
   return L;
 }
+inline CapLayout cap_layout(uint32_t n, uint32_t P, uint32_t G, size_t blob_cap) { return cap_layout_sized((size_t)n * P, (size_t)n * G, blob_cap); }
 
 struct RegisteredCapture {
   uint32_t detail = 0;              // 0, ZKE_D_U_CAPTURE_PROGRAM or ZKE_D_U_CAPTURE_STATES

@@ -36,6 +36,7 @@
 #include "ed25519.hip.h"
 #include "verdict.hip.h"
 #include "regex_mixed.hip.h"      // (behind the others: the earlier kernels keep their places in the code object)
+#include "capture_mixed.hip.h"
 
 using namespace zke;
 

@@ -63,6 +63,30 @@ int mixed_resolve(zke_engine* e, MixedReq& q) {
   return 0;
 }
 
+// ---- mixed extractions (zke_extract_captures_mixed; plan: mixed_plan.hip.h, kernels: capture_mixed.hip.h).  The regex stage in front
+// of the capture launches is a mixed batch's (`verify`, over the parts' DFA ids, no capture tables); on top of it the ragged columns
+// (`plan`) and the config-major part table, whose programs capmix_resolve copies out of the registry.
+struct CapMixedReq {
+  MixedReq verify;
+  zke_regex_mixed lists{};               // what `verify` plans over: the configs' DFA ids, the caller's config_of
+  std::vector<zke_regex_config> id_lists;
+  std::vector<uint32_t> dfa_ids, prog_ids, n_groups;      // config-major, header parts first
+  std::vector<CapPartDev> part;          // the device part table (groups and gbase: the entry; code and prog: capmix_resolve)
+  CapMixedPlan plan;
+  bool needs_work = false;               // some program's rows do not fit LDS
+  zke_capture_out* out = nullptr;
+  zke_capture_origin* org = nullptr;
+  bool origin_launch() const { return org && plan.shape.body_groups; }
+  CapMixedImage image(uint32_t n) const { return capmix_image(n, lists.n_configs, plan.shape, sizeof(CapPartDev)); }
+};
+// Under `big` (shared), like capture_resolve: the pointers copied here stay valid until the batch is enqueued.
+void capmix_resolve(zke_engine* e, CapMixedReq& q) {
+  std::shared_lock<std::shared_mutex> rl(e->reg_mu);
+  q.needs_work = false;
+  for (size_t k = 0; k < q.part.size(); k++)
+    if (capture_resolve_part(e, q.part[k], q.prog_ids[k])) q.needs_work = true;
+}
+
 // A slot's buffers for one side output of a batch of n: the layout, then the buffers it asks for (ensure_side_buffers).
 // `pack`: zke_select_keys_from_records, the decoded keys are packed for the front end.
 int ensure_keyrec_buffers(zke_engine* e, KeyrecBufs& b, uint32_t m, size_t rec_total, bool pack) {
@@ -80,9 +104,9 @@ int ensure_scan_buffers(zke_engine* e, ScanBufs& b, uint32_t n, uint32_t max_sig
   return ensure_side_buffers(e, b.t, b.L.total, b.L.total, &b.ovf, (size_t)n * HDR_OVF_BYTES, "signature-scan buffer allocation");
 }
 // `launched`: capture_origin_kernel runs for this batch; where it does not, nothing is allocated
-int ensure_origin_buffers(zke_engine* e, OriginBufs& b, uint32_t n, const CaptureReq& q) {
-  b.L = origin_layout(n, q.G);
-  b.launched = q.origin_launch();
+int ensure_origin_buffers(zke_engine* e, OriginBufs& b, size_t NG, bool launched) {
+  b.L = origin_layout_sized(NG);
+  b.launched = launched;
   return b.launched ? ensure_side_buffers(e, b.t, b.L.total, b.L.total, nullptr, 0, "capture-origin buffer allocation") : 0;
 }
 
@@ -264,6 +288,7 @@ struct HostBatch {
   const KeyrecReq* keyrec = nullptr;    // key records: decoded instead of the verify pipeline, or (with sel) in front of it
   const BodyReq* body = nullptr;        // zke_extract_bodies: body_extract_kernel runs instead of the verify pipeline
   MixedReq* mixed = nullptr;            // zke_verify_emails_mixed: a regex batch whose part lists are the configs' (b's own are empty)
+  CapMixedReq* capmix = nullptr;        // zke_extract_captures_mixed: the extraction that rides on this mixed batch (mixed == &capmix->verify)
   uint64_t raw_total = 0, dom_total = 0, key_total = 0, raw_base = 0, dom_base = 0, key_base = 0;   // blob bytes; off[0] of packed offsets
   size_t cap_words = 0, cap_strs = 0, cap_bytes = 0;      // entries of cap_off and cap_str_off, bytes of cap_blob (0: no tables)
   ImageLayout L{};
@@ -282,7 +307,8 @@ int measure_host_batch(HostBatch& d, const char* who) {
     }
   }
   if (!d.cap_words) b.cap_off = nullptr, b.cap_str_off = nullptr, b.cap_blob = nullptr;
-  d.L = image_layout(b.n, d.raw_total, d.dom_total, d.key_total, d.cap_words, d.cap_strs, d.cap_bytes, d.mixed ? mixed_image(b.n, d.mixed->shape).total : 0);
+  d.L = image_layout(b.n, d.raw_total, d.dom_total, d.key_total, d.cap_words, d.cap_strs, d.cap_bytes,
+                     (d.mixed ? mixed_image(b.n, d.mixed->shape).total : 0) + (d.capmix ? d.capmix->image(b.n).total : 0));
   return 0;
 }
 // The packed shape.  Its offsets are in host memory here, so they are checked (three passes over n + 1 words): a negative length
@@ -298,11 +324,12 @@ int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_b
   return measure_host_batch(d, who);
 }
 // The gathered shape: the e-mails one by one, lists == nullptr for verify_email; `mixed` (checked and measured by its entry) instead
-// of lists: the capture tables are its.
+// of lists: the capture tables are its; `capmix`: the mixed extraction whose regex stage `mixed` is.
 int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_email_ref* refs, uint32_t n, const zke_regex_lists* lists,
-               MixedReq* mixed = nullptr) {
+               MixedReq* mixed = nullptr, CapMixedReq* capmix = nullptr) {
   if (n && (!refs || !out)) return arg_error(who, "null pointer");
   d = HostBatch{zke_batch{n}, refs};
+  d.capmix = capmix;
   if (mixed) {
     d.mixed = mixed;
     d.b.with_regex = 1;
@@ -336,6 +363,7 @@ PendingDelivery pending_delivery(const HostBatch& d, zke_result* out) {
   if (d.keyrec) p.keyrec = d.keyrec->out;
   if (d.body) p.body = d.body->out;
   if (d.cap) { p.caps = d.cap->out; p.org = d.cap->org; }
+  if (d.capmix) { p.caps = d.capmix->out; p.org = d.capmix->org; }
   return p;
 }
 
@@ -350,7 +378,10 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   if ((rc = ensure_host_buffers(e, w, L.total, n))) return rc;      // (a no-op: submit_host_batch has grown every slot's staging)
   if (d.cap) w.cb.L = cap_layout(n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap);
   if (d.cap && (rc = ensure_capture_buffers(e, w.cb, w.cb.L, d.cap->needs_work))) return rc;
-  if (d.cap && d.cap->org && (rc = ensure_origin_buffers(e, w.ob, n, *d.cap))) return rc;
+  if (d.cap && d.cap->org && (rc = ensure_origin_buffers(e, w.ob, (size_t)n * d.cap->G, d.cap->origin_launch()))) return rc;
+  if (d.capmix) w.cb.L = cap_layout_sized(d.capmix->plan.shape.J, d.capmix->plan.shape.Gt, d.capmix->out->cap_blob_cap);
+  if (d.capmix && (rc = ensure_capture_buffers(e, w.cb, w.cb.L, d.capmix->needs_work))) return rc;
+  if (d.capmix && d.capmix->org && (rc = ensure_origin_buffers(e, w.ob, d.capmix->plan.shape.Gt, d.capmix->origin_launch()))) return rc;
   if (d.scan && (rc = ensure_scan_buffers(e, w.sb, n, d.scan->max_sigs, d.scan->out->sel_blob_cap))) return rc;
   if (d.keyrec && (rc = ensure_keyrec_buffers(e, w.kb, n, (size_t)(d.sel ? d.key_total : d.raw_total), d.sel != nullptr))) return rc;
   if (d.body && (rc = ensure_body_buffers(e, w.bb, n, (size_t)d.raw_total))) return rc;
@@ -400,6 +431,15 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
     stage_copy(mp + ML.perm, P.perm.data(), P.perm.size() * 4);
     stage_copy(mp + ML.segs, P.segs.data(), P.segs.size() * sizeof(MixedSeg));
   }
+  const CapMixedImage CL = d.capmix ? d.capmix->image(n) : CapMixedImage{};
+  if (d.capmix) {          // a mixed extraction's columns and its part table, one more section behind the plan
+    const CapMixedPlan& P = d.capmix->plan;
+    uint8_t* cp = hp + L.mixed + ML.total;
+    stage_copy(cp + CL.col_off, P.col_off.data(), P.col_off.size() * 4);
+    stage_copy(cp + CL.cap_cfg, P.cap_cfg.data(), P.cap_cfg.size() * 4);
+    stage_copy(cp + CL.cfgs, P.cfgs.data(), P.cfgs.size() * sizeof(CapMixedCfg));
+    stage_copy(cp + CL.parts, d.capmix->part.data(), d.capmix->part.size() * sizeof(CapPartDev));
+  }
   hipStream_t s = w.stream;
   SlotUse use(e, w, s);
   if ((rc = use.acquire())) return rc;
@@ -448,14 +488,19 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
     const uint8_t* mp = dp + L.mixed;
     const MixedLaunch ml{d.mixed ? &d.mixed->plan : nullptr, reinterpret_cast<const uint32_t*>(mp + ML.job_off), reinterpret_cast<const uint32_t*>(mp + ML.email_cfg),
                          reinterpret_cast<const uint32_t*>(mp + ML.perm), reinterpret_cast<const MixedSeg*>(mp + ML.segs)};
+    const uint8_t* cp = mp + ML.total;
+    const CapMixedLaunch cl{d.capmix ? d.capmix->plan.shape.J : 0u, d.capmix ? d.capmix->plan.shape.Gt : 0u, d.capmix && d.capmix->needs_work,
+                            d.capmix && d.capmix->origin_launch(),
+                            CapMixedTables{ml.job_off, reinterpret_cast<const uint32_t*>(cp + CL.col_off), reinterpret_cast<const uint32_t*>(cp + CL.cap_cfg),
+                                           reinterpret_cast<const CapMixedCfg*>(cp + CL.cfgs), reinterpret_cast<const CapPartDev*>(cp + CL.parts)}};
     if ((rc = run_device_pipeline(e, w, &dv, d.raw_total, key_hint, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap,
-                                  d.mixed ? &ml : nullptr))) return rc;
+                                  d.mixed ? &ml : nullptr, d.capmix ? &cl : nullptr))) return rc;
     HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
     if (d.keyrec) HIPCHK(e, w.kb.t.fetch(w.kb.L.total, s));
   }
   if (rc) return rc;
-  if (d.cap) HIPCHK(e, w.cb.t.fetch(w.cb.L.fixed_end, s));
-  if (d.cap && d.cap->org && w.ob.launched) HIPCHK(e, w.ob.t.fetch(w.ob.L.total, s));
+  if (d.cap || d.capmix) HIPCHK(e, w.cb.t.fetch(w.cb.L.fixed_end, s));
+  if (((d.cap && d.cap->org) || (d.capmix && d.capmix->org)) && w.ob.launched) HIPCHK(e, w.ob.t.fetch(w.ob.L.total, s));
   tm.mark(MK_D2H);
   HIPCHK(e, hipEventRecord(w.host_done, s));
   w.host_gen++;
@@ -537,6 +582,7 @@ int submit_host_batch(zke_engine* e, const HostBatch& d, zke_result* out, uint64
   std::shared_lock<std::shared_mutex> sh(e->big);
   HIPCHK(e, hipSetDevice(e->device));
   if (d.cap) capture_resolve(e, *d.cap);             // under `big`: the programs' tables cannot be freed before the batch is enqueued
+  if (d.capmix && n) capmix_resolve(e, *d.capmix);   // likewise the part table of a mixed extraction
   if (d.mixed && n) if (int r = mixed_resolve(e, *d.mixed)) return r;      // likewise the DFA pairs' tables a mixed batch's segments point to
   uint32_t slot;
   Slot& w = next_slot(e, slot);
@@ -845,9 +891,9 @@ int zke_extract_bodies(zke_engine* e, const zke_email_ref* emails, uint32_t n, u
 
 namespace {
 // the sizes an extraction over n e-mails needs, written back; ZKE_E_NOMEM when a buffer of known size is too small
-int check_capture_out(zke_capture_out* o, uint32_t n, uint32_t P, uint32_t G, const char* who) {
+// (NP jobs and NG columns: n * P and n * G of one part list per batch, J and Gt of a mixed extraction)
+int check_capture_out_sized(zke_capture_out* o, size_t NP, size_t NG, const char* who) {
   if (!o) return arg_error(who, "null zke_capture_out");
-  const size_t NP = (size_t)n * P, NG = (size_t)n * G;
   o->spans_need = NG * 2; o->flags_need = NG; o->cap_off_need = NP + 1; o->cap_str_off_need = NG + 1;
   o->cap_blob_need = 0; o->n_strings = 0;
   // string offsets are 32-bit, as the verify entry's tables are: what n * G spans of ZKE_CAP_MAX_SPAN bytes could not address is refused
@@ -857,15 +903,16 @@ int check_capture_out(zke_capture_out* o, uint32_t n, uint32_t P, uint32_t G, co
   if (!o->spans || !o->flags || !o->cap_off || !o->cap_str_off || (o->cap_blob_cap && !o->cap_blob)) return arg_error(who, "null buffer in zke_capture_out");
   return 0;
 }
+int check_capture_out(zke_capture_out* o, uint32_t n, uint32_t P, uint32_t G, const char* who) { return check_capture_out_sized(o, (size_t)n * P, (size_t)n * G, who); }
 // the same for the origins of a mapped extraction: both sizes are known up front
-int check_capture_origin(zke_capture_origin* o, uint32_t n, uint32_t G, const char* who) {
+int check_capture_origin_sized(zke_capture_origin* o, size_t NG, const char* who) {
   if (!o) return arg_error(who, "null zke_capture_origin");
-  const size_t NG = (size_t)n * G;
   o->spans_need = NG * 2; o->flags_need = NG;
   if (o->spans_cap < o->spans_need || o->flags_cap < o->flags_need) return nomem_error(who, "a zke_capture_origin buffer is smaller than its *_need");
   if (NG && (!o->spans || !o->flags)) return arg_error(who, "null buffer in zke_capture_origin");
   return 0;
 }
+int check_capture_origin(zke_capture_origin* o, uint32_t n, uint32_t G, const char* who) { return check_capture_origin_sized(o, (size_t)n * G, who); }
 
 // zke_extract_captures_async and its mapped form (`mapped`: org is wanted, and checked behind caps)
 int extract_captures_submit(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
@@ -921,6 +968,60 @@ int zke_extract_captures_mapped(zke_engine* e, const zke_email_ref* emails, uint
   return submit_and_wait(e, n, [&](uint64_t* t) {
     return zke_extract_captures_mapped_async(e, emails, n, header_parts, n_header_parts, body_parts, n_body_parts, out, caps, org, t);
   });
+}
+
+// ---- the extraction over `&[Email]` with a RegexConfig per e-mail (include/zkemail_amd.h): the checks, the plan's ragged half and the
+// sizes here, before anything is staged; the programs and the DFA pairs once the registry can be read (capmix_resolve, mixed_resolve).
+int zke_extract_captures_mixed_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_mixed* mixed, zke_result* out,
+                                     zke_capture_out* caps, zke_capture_origin* org, uint64_t* ticket) {
+  static const char who[] = "zke_extract_captures_mixed";
+  if (!e) return ZKE_E_ARG;
+  if (!mixed || !ticket || !caps) return arg_error(who, "null pointer");
+  if (mixed->n_configs > ZKE_MIXED_MAX_CONFIGS) return arg_error(who, "more than ZKE_MIXED_MAX_CONFIGS configs");
+  if ((mixed->n_configs && !mixed->configs) || (n && !mixed->config_of)) return arg_error(who, "null pointer");
+  CapMixedReq q;
+  q.out = caps; q.org = org;
+  q.verify.counts.resize(mixed->n_configs);
+  for (uint32_t c = 0; c < mixed->n_configs; c++) {
+    const zke_capture_config& cf = mixed->configs[c];
+    if (cf.n_header_parts > ZKE_CAP_MAX_PARTS || cf.n_body_parts > ZKE_CAP_MAX_PARTS - cf.n_header_parts || cf.n_header_parts + cf.n_body_parts == 0)
+      return arg_error(who, "a config needs 1 .. ZKE_CAP_MAX_PARTS parts (ZKE_CONFIG_NONE is the way to say: no regex)");
+    if ((cf.n_header_parts && !cf.header_parts) || (cf.n_body_parts && !cf.body_parts)) return arg_error(who, "part list is null");
+    q.verify.counts[c] = MixedConfigIn{cf.n_header_parts, cf.n_body_parts};
+    for (uint32_t p = 0; p < cf.n_header_parts + cf.n_body_parts; p++) {
+      const zke_capture_part& cp = p < cf.n_header_parts ? cf.header_parts[p] : cf.body_parts[p - cf.n_header_parts];
+      if (cp.n_groups > ZKE_CAP_MAX_GROUPS) return arg_error(who, "more than ZKE_CAP_MAX_GROUPS groups requested for a part");
+      if (cp.n_groups && !cp.groups) return arg_error(who, "null group list");
+      CapPartDev d{};
+      d.code = ZKE_D_U_CAPTURE_PROGRAM;
+      d.n_groups = cp.n_groups;
+      for (uint32_t k = 0; k < cp.n_groups; k++) d.groups[k] = cp.groups[k];
+      q.part.push_back(d);
+      q.dfa_ids.push_back(cp.dfa_id); q.prog_ids.push_back(cp.prog_id); q.n_groups.push_back(cp.n_groups);
+    }
+  }
+  if (const char* why = capmix_plan_build(mixed->config_of, n, q.verify.counts.data(), mixed->n_configs, q.n_groups.data(), q.plan)) return arg_error(who, why);
+  for (size_t k = 0; k < q.part.size(); k++) q.part[k].gbase = q.plan.gbase[k];
+  // the regex stage's half: zke_verify_emails_mixed's request over the same configs, without capture tables
+  q.id_lists.resize(mixed->n_configs);
+  for (uint32_t c = 0; c < mixed->n_configs; c++) {
+    const uint32_t* ids = q.dfa_ids.data() + q.plan.cfgs[c].part0;
+    q.id_lists[c] = zke_regex_config{q.verify.counts[c].n_header_parts, ids, q.verify.counts[c].n_body_parts, ids + q.verify.counts[c].n_header_parts};
+  }
+  q.lists = zke_regex_mixed{mixed->n_configs, q.id_lists.data(), mixed->config_of, nullptr, nullptr, nullptr};
+  q.verify.in = &q.lists; q.verify.n = n;
+  if (const char* why = mixed_plan_check(mixed->config_of, n, q.verify.counts.data(), mixed->n_configs, q.verify.shape)) return arg_error(who, why);
+  HostBatch d;
+  if (int r = host_batch(d, who, out, emails, n, nullptr, &q.verify, &q)) return r;
+  if (int r = check_capture_out_sized(caps, q.plan.shape.J, q.plan.shape.Gt, who)) return r;
+  if (org) if (int r = check_capture_origin_sized(org, q.plan.shape.Gt, who)) return r;
+  if (!n) { caps->cap_off[0] = 0; caps->cap_str_off[0] = 0; }      // (nothing is launched: the empty tables are written here)
+  return submit_host_batch(e, d, out, ticket);
+}
+
+int zke_extract_captures_mixed(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_mixed* mixed, zke_result* out,
+                               zke_capture_out* caps, zke_capture_origin* org) {
+  return submit_and_wait(e, n, [&](uint64_t* t) { return zke_extract_captures_mixed_async(e, emails, n, mixed, out, caps, org, t); });
 }
 
 // ---- capture extraction over haystacks of the caller's (registry.hip.h), with the checks and the delivery of the entries above

@@ -227,7 +227,7 @@ class CopyPool {
 // the image; blobs start 64-byte aligned and are followed by 64 bytes of slack (the kernels read 16 bytes at a time).
 struct ImageLayout {
   size_t raw_off, dom_off, key_off, key_type, ext_null, cap_off, cap_str_off, raw, dom, key, cap_blob, total;
-  size_t mixed;       // a mixed regex batch's plan (mixed_plan.hip.h, MixedImage); no bytes otherwise
+  size_t mixed;       // a mixed regex batch's plan (mixed_plan.hip.h, MixedImage) and, behind it, a mixed extraction's tables (CapMixedImage); no bytes otherwise
 };
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) & ~(a - 1); }
 inline ImageLayout image_layout(uint32_t n, size_t raw_total, size_t dom_total, size_t key_total, size_t n_cap_off, size_t n_cap_str,
@@ -364,13 +364,14 @@ inline void body_compact(const BodyLayout& K, const uint8_t* twin, zke_body_out*
 // with a pinned twin — a plain extraction never sees it.  `launched`: capture_origin_kernel ran for the pending batch (it does not
 // when no body part asks for a group: the origins are then the spans themselves).
 struct OriginLayout { size_t flags, total; size_t NG; };
-inline OriginLayout origin_layout(uint32_t n, uint32_t G) {
+inline OriginLayout origin_layout_sized(size_t NG) {      // NG columns: n * G, or a mixed extraction's Gt
   OriginLayout L{};
-  L.NG = (size_t)n * G;
+  L.NG = NG;
   L.flags = align_up(L.NG * 8, 64);
   L.total = align_up(L.flags + L.NG, 64);
   return L;
 }
+inline OriginLayout origin_layout(uint32_t n, uint32_t G) { return origin_layout_sized((size_t)n * G); }
 struct OriginBufs {
   TwinBuf t;
   OriginLayout L{};

@@ -180,4 +180,115 @@ inline MixedImage mixed_image(uint32_t n, const MixedShape& s) {
   return L;
 }
 
+// ---- what a mixed EXTRACTION needs on top of that (zke_extract_captures_mixed; kernels: capture_mixed.hip.h).  The verify plan above is
+// built as for zke_verify_emails_mixed from the same config_of and the configs' part counts; this half adds the ragged columns:
+//   col_off[n + 1]   prefix sum of G(config_of[i]), the requested groups of the e-mail's config (0 for ZKE_CONFIG_NONE): requested
+//                    group k of the e-mail's part p is column col_off[i] + gbase[p] + k, gbase the prefix sum of the config's
+//                    per-part group counts;
+//   cap_cfg[n]       the e-mail's config index, or MIXED_NONE — a job is mapped to its e-mail by a binary search of job_off, the
+//                    e-mail to its config by this word;
+//   cfgs[n_configs]  per config {first part in the config-major part table, n_header_parts, G, first body column};
+//   gbase[n_parts]   per entry of the part table the first column of the part among its config's G.
+// Like the plan above a pure function: every check precedes the first write.
+constexpr uint32_t CAPMIX_MAX_PARTS = 16;            // = ZKE_CAP_MAX_PARTS: parts of one config of an extraction
+constexpr uint32_t CAPMIX_MAX_GROUPS = 16;           // = ZKE_CAP_MAX_GROUPS: groups requested of one part
+constexpr uint64_t CAPMIX_MAX_COLUMNS = 1ull << 20;  // Gt * ZKE_CAP_MAX_SPAN must stay below 4 GiB (32-bit string offsets)
+
+struct CapMixedCfg { uint32_t part0, nh, G, gb0; };  // device image, 16 bytes
+static_assert(sizeof(CapMixedCfg) == 16, "CapMixedCfg is a device image");
+struct CapMixedShape { uint32_t J = 0, Gt = 0, n_parts = 0; bool body_groups = false; };   // body_groups: some body part asks for a group
+struct CapMixedPlan {
+  CapMixedShape shape;
+  std::vector<uint32_t> col_off, cap_cfg, gbase;
+  std::vector<CapMixedCfg> cfgs;
+};
+
+// `groups`: the requested-group count of every part, config-major, header parts first (the sum of the configs' part counts entries).
+// 0, or a message (nothing has been written).
+inline const char* capmix_plan_check(const uint32_t* config_of, uint32_t n, const MixedConfigIn* cfgs, uint32_t n_configs, const uint32_t* groups,
+                                     CapMixedShape& out) {
+  if (n_configs > MIXED_MAX_CONFIGS) return "more than ZKE_MIXED_MAX_CONFIGS configs";
+  if ((n_configs && !cfgs) || (n && !config_of)) return "null pointer";
+  uint32_t P[MIXED_MAX_CONFIGS], G[MIXED_MAX_CONFIGS];
+  CapMixedShape s;
+  for (uint32_t c = 0; c < n_configs; c++) {
+    if (cfgs[c].n_header_parts > CAPMIX_MAX_PARTS || cfgs[c].n_body_parts > CAPMIX_MAX_PARTS - cfgs[c].n_header_parts ||
+        cfgs[c].n_header_parts + cfgs[c].n_body_parts == 0)
+      return "a config needs 1 .. ZKE_CAP_MAX_PARTS parts (ZKE_CONFIG_NONE is the way to say: no regex)";
+    P[c] = cfgs[c].n_header_parts + cfgs[c].n_body_parts;
+    if (!groups) return "null pointer";
+    G[c] = 0;
+    for (uint32_t p = 0; p < P[c]; p++) {
+      const uint32_t g = groups[s.n_parts + p];
+      if (g > CAPMIX_MAX_GROUPS) return "more than ZKE_CAP_MAX_GROUPS groups requested for a part";
+      G[c] += g;
+      if (p >= cfgs[c].n_header_parts && g) s.body_groups = true;
+    }
+    s.n_parts += P[c];
+  }
+  uint64_t J = 0, Gt = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t c = config_of[i];
+    if (c == MIXED_NONE) continue;
+    if (c >= n_configs) return "config_of names no config (neither below n_configs nor ZKE_CONFIG_NONE)";
+    J += P[c]; Gt += G[c];
+  }
+  if (Gt >= CAPMIX_MAX_COLUMNS)
+    return "requested groups beyond what 32-bit string offsets address (their sum over the e-mails times ZKE_CAP_MAX_SPAN must stay below 4 GiB): split the batch";
+  if (J >= (1ull << 31)) return "2^31 (e-mail, part) jobs or more: split the batch";
+  s.J = (uint32_t)J; s.Gt = (uint32_t)Gt;
+  out = s;
+  return nullptr;
+}
+
+// 0, or the message of capmix_plan_check — then `out` is as it was.
+inline const char* capmix_plan_build(const uint32_t* config_of, uint32_t n, const MixedConfigIn* cfgs, uint32_t n_configs, const uint32_t* groups,
+                                     CapMixedPlan& out) {
+  CapMixedShape shape;
+  if (const char* why = capmix_plan_check(config_of, n, cfgs, n_configs, groups, shape)) return why;
+  out.shape = shape;
+  out.cfgs.assign(n_configs, CapMixedCfg{});
+  out.gbase.assign(shape.n_parts, 0);
+  uint32_t part0 = 0;
+  for (uint32_t c = 0; c < n_configs; c++) {
+    const uint32_t nh = cfgs[c].n_header_parts, P = nh + cfgs[c].n_body_parts;
+    uint32_t g = 0, gb0 = 0;
+    for (uint32_t p = 0; p < P; p++) {
+      if (p == nh) gb0 = g;
+      out.gbase[part0 + p] = g;
+      g += groups[part0 + p];
+    }
+    if (nh == P) gb0 = g;
+    out.cfgs[c] = CapMixedCfg{part0, nh, g, gb0};
+    part0 += P;
+  }
+  out.col_off.assign((size_t)n + 1, 0);
+  out.cap_cfg.assign(n, MIXED_NONE);
+  uint32_t col = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    out.col_off[i] = col;
+    const uint32_t c = config_of[i];
+    if (c == MIXED_NONE) continue;
+    out.cap_cfg[i] = c;
+    col += out.cfgs[c].G;
+  }
+  out.col_off[n] = col;
+  return nullptr;
+}
+
+// Its section of the staged image, behind the verify plan's: col_off | cap_cfg | cfgs | the part table (part_bytes per entry: the
+// device's CapPartDev, resolved against the registry when the batch is submitted), each 16-byte aligned.
+struct CapMixedImage { size_t col_off, cap_cfg, cfgs, parts, total; };
+inline CapMixedImage capmix_image(uint32_t n, uint32_t n_configs, const CapMixedShape& s, size_t part_bytes) {
+  CapMixedImage L{};
+  size_t o = 0;
+  auto put = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
+  L.col_off = put(((size_t)n + 1) * 4);
+  L.cap_cfg = put((size_t)n * 4);
+  L.cfgs = put((size_t)n_configs * sizeof(CapMixedCfg));
+  L.parts = put((size_t)s.n_parts * part_bytes);
+  L.total = o;
+  return L;
+}
+
 }  // namespace zke

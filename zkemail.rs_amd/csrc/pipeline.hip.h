@@ -96,17 +96,19 @@ int capture_part_shape(CaptureReq& q, uint32_t p, uint32_t prog_id, const uint32
 // ... and the programs' device tables.  The caller holds `big` (shared) from here until the batch is enqueued: unregistering a
 // program takes `big` exclusively and drains the engine before it frees a table, so the pointers copied here stay valid for as
 // long as a launch can read them — the same order in which run_device_pipeline resolves the DFA pairs of a batch.
+// One part against the registry (the caller holds reg_mu): its code and program; returns whether its rows need the workspace.
+bool capture_resolve_part(const zke_engine* e, CapPartDev& d, uint32_t id) {
+  const RegisteredCapture* rc = id < e->captures.size() ? e->captures[id] : nullptr;
+  d.code = rc ? rc->detail : (uint32_t)ZKE_D_U_CAPTURE_PROGRAM;
+  d.prog = CapProgDev{};
+  if (rc && !rc->detail) { d.prog = rc->dev; return d.prog.words64 > CAP_LDS_WORDS; }
+  return false;
+}
 void capture_resolve(zke_engine* e, CaptureReq& q) {
   std::shared_lock<std::shared_mutex> rl(e->reg_mu);
   q.needs_work = false;
-  for (uint32_t p = 0; p < q.P; p++) {
-    CapPartDev& d = q.part[p];
-    const uint32_t id = q.prog_ids[p];
-    const RegisteredCapture* rc = id < e->captures.size() ? e->captures[id] : nullptr;
-    d.code = rc ? rc->detail : (uint32_t)ZKE_D_U_CAPTURE_PROGRAM;
-    d.prog = CapProgDev{};
-    if (rc && !rc->detail) { d.prog = rc->dev; if (d.prog.words64 > CAP_LDS_WORDS) q.needs_work = true; }
-  }
+  for (uint32_t p = 0; p < q.P; p++)
+    if (capture_resolve_part(e, q.part[p], q.prog_ids[p])) q.needs_work = true;
 }
 
 // The two launches of an extraction: the walk per (e-mail, part), then verdict + tables.  `parts`: the PartRes the search left.
@@ -215,8 +217,9 @@ struct MixedLaunch {
 };
 // Behind the verify launches: the preparation (e-mails without a config left out), ONE lane-mapped and ONE wave-mapped DFA launch
 // over the plan's segments, the fold.  B: the verify pass's view of the batch; `in`: its capture tables (indexed by job).
+// base_out: the launches' common DfaArgs, for the capture launches of a mixed extraction behind this stage.
 int run_mixed_regex_stage(zke_engine* e, Slot& w, const BatchDev& B, const zke_batch& in, const MixedLaunch& mx, uint64_t* clean_off, uint64_t now,
-                          bool want_clean, StageTimer& tm, hipStream_t s) {
+                          bool want_clean, StageTimer& tm, hipStream_t s, DfaArgs* base_out = nullptr) {
   const MixedPlan& P = *mx.plan;
   const uint32_t n = B.n;
   BatchDev B2 = B;
@@ -237,6 +240,7 @@ int run_mixed_regex_stage(zke_engine* e, Slot& w, const BatchDev& B, const zke_b
   ma.common.cap_off = in.cap_off; ma.common.cap_str_off = in.cap_str_off; ma.common.cap_blob = in.cap_blob;
   ma.common.out = w.parts.as<PartRes>();
   ma.perm = mx.perm; ma.job_off = mx.job_off;
+  if (base_out) *base_out = ma.common;
   if (P.lane_blocks) {
     ma.segs = mx.segs; ma.n_segs = P.n_lane;
     hipLaunchKernelGGL(dfa_mixed_kernel, dim3(P.lane_blocks), dim3(256), P.lane_lds, s, ma);
@@ -252,13 +256,54 @@ int run_mixed_regex_stage(zke_engine* e, Slot& w, const BatchDev& B, const zke_b
   return 0;
 }
 
+// ---- capture extraction behind the mixed regex stage (zke_extract_captures_mixed; kernels: capture_mixed.hip.h)
+// The shape of the extraction and where its tables lie in the slot's staged image (device pointers).
+struct CapMixedLaunch {
+  uint32_t J, Gt;
+  bool needs_work;              // some part of some config keeps its rows in the slot's workspace: the grid is bounded by CAP_WORK_WAVES
+  bool origin;                  // the origin launch runs (org is wanted and some body part asks for a group)
+  CapMixedTables t;
+};
+// The walk per job, then verdict + tables, as launch_capture; b.L is laid out for J jobs and Gt columns.
+int launch_capture_mixed(zke_engine* e, CapBufs& b, const CapMixedLaunch& cm, uint32_t n, const DfaArgs& base, const PartRes* parts,
+                         zke_result* results, hipStream_t s) {
+  const CapLayout& L = b.L;
+  uint8_t* cb = b.t.d.as<uint8_t>();
+  CapMixedArgs ca{};
+  ca.n = n; ca.J = cm.J; ca.d = base; ca.t = cm.t; ca.parts = parts;
+  ca.spans = reinterpret_cast<uint32_t*>(cb + L.spans); ca.flags = cb + L.flags; ca.codes = reinterpret_cast<uint32_t*>(cb + L.codes);
+  ca.work = b.work.as<uint64_t>();
+  const uint32_t grid = std::min<uint32_t>(cm.J, cm.needs_work ? CAP_WORK_WAVES : 16384u);
+  if (grid) hipLaunchKernelGGL(capture_mixed_kernel, dim3(grid), dim3(64), 0, s, ca);
+  CapGatherMixedArgs ga{};
+  ga.n = n; ga.J = cm.J; ga.Gt = cm.Gt; ga.d = base; ga.t = cm.t;
+  ga.parts = parts; ga.codes = ca.codes; ga.spans = ca.spans; ga.results = results;
+  ga.cap_off = reinterpret_cast<uint32_t*>(cb + L.cap_off); ga.cap_str_off = reinterpret_cast<uint32_t*>(cb + L.cap_str_off);
+  ga.cap_blob = cb + L.blob; ga.blob_cap = L.blob_cap; ga.hdr = reinterpret_cast<uint64_t*>(cb + L.hdr);
+  ga.tmp = reinterpret_cast<uint32_t*>(cb + L.tmp);
+  hipLaunchKernelGGL(capture_gather_mixed_kernel, dim3(1), dim3(1024), 0, s, ga);
+  HIPCHK(e, hipGetLastError());
+  return 0;
+}
+int launch_capture_origin_mixed(zke_engine* e, const CapBufs& b, OriginBufs& ob, const CapMixedLaunch& cm, uint32_t n, const DfaArgs& base,
+                                const zke_result* results, hipStream_t s) {
+  uint8_t* op = ob.t.d.as<uint8_t>();
+  CapOriginMixedArgs oa{};
+  oa.n = n; oa.d = base; oa.t = cm.t; oa.results = results;
+  oa.spans = reinterpret_cast<const uint32_t*>(b.t.d.as<uint8_t>() + b.L.spans);
+  oa.org_spans = reinterpret_cast<uint32_t*>(op); oa.org_flags = op + ob.L.flags;
+  hipLaunchKernelGGL(capture_origin_mixed_kernel, dim3(n), dim3(64), 0, s, oa);
+  HIPCHK(e, hipGetLastError());
+  return 0;
+}
+
 // The device pipeline.  Every pointer in `in` / out_dev is device memory, except the part-id lists (host arrays in both
 // entry points).  Three launches — front end, hash / modexp stage, Ed25519 + verdict (which also runs the later signature
 // rounds of the rare e-mail that needs them) — and, for verify_email_with_regex, the regex stage behind them.
 // Caller holds the slot's lock; everything the call needs is in its arguments or in the slot.
 int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t raw_total, uint64_t key_total, zke_result* out_dev,
                         hipStream_t s, bool want_em, uint64_t now, bool want_clean = false, const CaptureReq* cap = nullptr,
-                        const MixedLaunch* mixed = nullptr) {
+                        const MixedLaunch* mixed = nullptr, const CapMixedLaunch* capmix = nullptr) {
   const uint32_t n = in->n;
   if (n == 0) return 0;
   const uint32_t n_pad = (n + 63) & ~63u;
@@ -322,7 +367,14 @@ int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t ra
   HIPCHK(e, hipGetLastError());
 
   if (in->with_regex && mixed) {
-    if ((r = run_mixed_regex_stage(e, w, B, *in, *mixed, clean_off, now, want_clean, tm, s))) return r;
+    DfaArgs base{};
+    if ((r = run_mixed_regex_stage(e, w, B, *in, *mixed, clean_off, now, want_clean, tm, s, &base))) return r;
+    // capture extraction (zke_extract_captures_mixed): the stage above ran without capture tables, as the single-config extraction's does
+    if (capmix) {
+      if ((r = launch_capture_mixed(e, w.cb, *capmix, n, base, w.parts.as<PartRes>(), out_dev, s))) return r;
+      if (capmix->origin && (r = launch_capture_origin_mixed(e, w.cb, w.ob, *capmix, n, base, out_dev, s))) return r;
+      tm.mark(MK_DFA);
+    }
   } else if (in->with_regex) {
     // the parts of this batch, copied out of the registry (the entries themselves stay put until the engine is idle)
     PartInfo parts_small[16];

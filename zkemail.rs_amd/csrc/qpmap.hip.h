@@ -89,42 +89,40 @@ struct CapOriginArgs {
   uint8_t* org_flags;             // [n * G]
 };
 
-// One wave per e-mail, behind capture_gather_kernel.  Header columns and e-mails without strings keep their pair, flags 0.  For
+// One wave per e-mail, behind the gather launch (capture_origin_kernel here; capture_origin_mixed_kernel, capture_mixed.hip.h, with
+// the e-mail's own column range).  Header columns and e-mails without strings keep their pair, flags 0.  For
 // the body columns of an e-mail whose record is ZKE_OK, with im = the index map of the e-mail's regex haystack (the canonical
 // body regex_prep_kernel feeds to qp_wave, n bytes) and {s, e} the span:
 //     start = s < n ? im[s] : NO_INDEX;   end = e == s ? start : (im[e - 1] == NO_INDEX ? NO_INDEX : im[e - 1] + 1)
 // Query k of the e-mail (k = 2 * body column + {0: s, 1: e - 1}) belongs to lane k & 63, slot k >> 6: a column's two queries sit
 // in neighbouring lanes of one slot.
-__global__ __launch_bounds__(64) void capture_origin_kernel(CapOriginArgs A) {
-  const int lane = lane_id();
-  const uint32_t i = blockIdx.x;
-  if (i >= A.n) return;
-  const size_t row = (size_t)i * A.G;
-  const bool ok = A.results[i].status == ZKE_OK;
-  const uint32_t ident_to = ok ? A.gb0 : A.G;          // columns [0, ident_to): origin = span
+// The origins of one e-mail by one wave: its G columns start at column `row`, the body parts' at row + gb0; ok: its record is ZKE_OK.
+__device__ __forceinline__ void cap_origin_email(const DfaArgs& d, uint32_t i, size_t row, uint32_t G, uint32_t gb0, bool ok, const uint32_t* spans,
+                                                 uint32_t* org_spans, uint8_t* org_flags, int lane) {
+  const uint32_t ident_to = ok ? gb0 : G;          // columns [0, ident_to): origin = span
   for (uint32_t c = lane; c < ident_to; c += 64) {
-    A.org_spans[2 * (row + c)] = A.spans[2 * (row + c)];
-    A.org_spans[2 * (row + c) + 1] = A.spans[2 * (row + c) + 1];
-    A.org_flags[row + c] = 0;
+    org_spans[2 * (row + c)] = spans[2 * (row + c)];
+    org_spans[2 * (row + c) + 1] = spans[2 * (row + c) + 1];
+    org_flags[row + c] = 0;
   }
   if (!ok) return;
-  const uint32_t Gb = A.G - A.gb0;
+  const uint32_t Gb = G - gb0;
   const uint32_t slots = (2 * Gb + 63) / 64;
   // the haystack before the QP filter: the src / n choice of regex_prep_kernel, read from what that pass left in its EmailMeta
-  const BatchDev& B = A.d.b;
+  const BatchDev& B = d.b;
   const EmailMeta* M = B.meta + i;
   const uint64_t r0 = B.raw_off[i];
   const uint32_t raw_len = (uint32_t)(B.raw_off[i + 1] - r0);
   const uint32_t n = M->hashed_len;
   const uint8_t* src = M->body_src_is_raw ? B.raw + r0 + M->body_off
-                     : (M->reuse ? region_b(A.d.scratch_v, A.d.scratch_v_off, i, raw_len) : region_b(B.scratch, B.scratch_off, i, raw_len));
+                     : (M->reuse ? region_b(d.scratch_v, d.scratch_v_off, i, raw_len) : region_b(B.scratch, B.scratch_off, i, raw_len));
   uint32_t q[ORG_SLOTS], res[ORG_SLOTS];
 #pragma unroll
   for (uint32_t j = 0; j < ORG_SLOTS; j++) {
     q[j] = QP_NO_INDEX; res[j] = QP_NO_INDEX;
     const uint32_t k = j * 64 + lane, c = k >> 1;
     if (j < slots && c < Gb) {
-      const uint32_t s = A.spans[2 * (row + A.gb0 + c)], e = A.spans[2 * (row + A.gb0 + c) + 1];
+      const uint32_t s = spans[2 * (row + gb0 + c)], e = spans[2 * (row + gb0 + c) + 1];
       if (!(k & 1)) q[j] = s;
       else if (e > s && e != CAP_NONE) q[j] = e - 1;
     }
@@ -146,17 +144,24 @@ __global__ __launch_bounds__(64) void capture_origin_kernel(CapOriginArgs A) {
     const uint32_t k = j * 64 + lane, c = k >> 1;
     const uint32_t last = (uint32_t)__shfl_xor((int)res[j], 1);                       // even lanes: im[e - 1]
     if (!(k & 1) && c < Gb) {
-      const size_t col = row + A.gb0 + c;
-      const uint32_t s = A.spans[2 * col], e = A.spans[2 * col + 1];
+      const size_t col = row + gb0 + c;
+      const uint32_t s = spans[2 * col], e = spans[2 * col + 1];
       uint32_t start = res[j], end = e == s ? start : (last == QP_NO_INDEX ? QP_NO_INDEX : last + 1);
       uint8_t flag = 0;
       if (s == CAP_NONE && e == CAP_NONE) { start = s; end = e; }                     // no string: the pair stands
       else if (start == QP_NO_INDEX || end == QP_NO_INDEX) flag = ZKE_ORGF_PADDING;
       else if (end - start != e - s) flag = ZKE_ORGF_SPLIT;
-      A.org_spans[2 * col] = start; A.org_spans[2 * col + 1] = end;
-      A.org_flags[col] = flag;
+      org_spans[2 * col] = start; org_spans[2 * col + 1] = end;
+      org_flags[col] = flag;
     }
   }
+}
+
+__global__ __launch_bounds__(64) void capture_origin_kernel(CapOriginArgs A) {
+  const int lane = lane_id();
+  const uint32_t i = blockIdx.x;
+  if (i >= A.n) return;
+  cap_origin_email(A.d, i, (size_t)i * A.G, A.G, A.gb0, A.results[i].status == ZKE_OK, A.spans, A.org_spans, A.org_flags, lane);
 }
 
 }  // namespace zke

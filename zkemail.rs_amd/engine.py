@@ -152,6 +152,12 @@ def load_library(path: Optional[str] = None):
         lib.zke_extract_captures_mapped_async.argtypes = [vp, C.POINTER(A.zke_email_ref), C.c_uint32, cpp, C.c_uint32, cpp, C.c_uint32, vp, cop, orp,
                                                           C.POINTER(C.c_uint64)]
         lib.zke_extract_captures_mapped_async.restype = C.c_int
+    if hasattr(lib, "zke_extract_captures_mixed"):  # (likewise)
+        cmp_, orp = C.POINTER(A.zke_capture_mixed), C.POINTER(A.zke_capture_origin)
+        lib.zke_extract_captures_mixed.argtypes = [vp, C.POINTER(A.zke_email_ref), C.c_uint32, cmp_, vp, cop, orp]
+        lib.zke_extract_captures_mixed.restype = C.c_int
+        lib.zke_extract_captures_mixed_async.argtypes = [vp, C.POINTER(A.zke_email_ref), C.c_uint32, cmp_, vp, cop, orp, C.POINTER(C.c_uint64)]
+        lib.zke_extract_captures_mixed_async.restype = C.c_int
     erp =C.POINTER(A.zke_email_ref)
     lib.zke_scan_signatures.argtypes = [vp, erp, C.c_uint32, C.c_uint32, C.POINTER(A.zke_sig_scan)]
     lib.zke_scan_signatures.restype = C.c_int
@@ -209,6 +215,7 @@ EXPORTED_SYMBOLS = [
     "zke_engine_sha_ring", "zke_engine_sha_twin", "zke_engine_front_helper",
     "zke_qp_clean_batch", "zke_extract_captures_mapped", "zke_extract_captures_mapped_async",
     "zke_extract_bodies", "zke_extract_bodies_async",
+    "zke_extract_captures_mixed", "zke_extract_captures_mixed_async",
 ]
 
 
@@ -434,7 +441,11 @@ class Engine:
 
     def _run_captures(self, n: int, P: int, G: int, call, blob_bytes: int):
         """The caller-sized buffers of a zke_capture_out, one retry with the blob size the engine reports."""
-        NP, NG = n * P, n * G
+        rc, spans, flags, cap_off, cap_str_off, blob = self._run_captures_sized(n * P, n * G, call, blob_bytes)
+        return rc, spans.reshape(n, G, 2), flags.reshape(n, G), cap_off, cap_str_off, blob
+
+    def _run_captures_sized(self, NP: int, NG: int, call, blob_bytes: int):
+        """The same for NP (e-mail, part) jobs and NG columns, spans [NG, 2] and flags [NG] as they lie."""
         spans = np.zeros(max(NG * 2, 1), np.uint32)
         flags = np.zeros(max(NG, 1), np.uint8)
         cap_off = np.zeros(NP + 1, np.uint32)
@@ -449,7 +460,7 @@ class Engine:
             if rc == -3 and attempt == 0 and o.cap_blob_need > blob_bytes:        # ZKE_E_NOMEM: the strings need a larger blob
                 blob_bytes = int(o.cap_blob_need)
                 continue
-            return rc, spans[:NG * 2].reshape(n, G, 2), flags[:NG].reshape(n, G), cap_off, cap_str_off[:int(o.n_strings) + 1], blob[:int(o.cap_blob_need)]
+            return rc, spans[:NG * 2].reshape(NG, 2), flags[:NG], cap_off, cap_str_off[:int(o.n_strings) + 1], blob[:int(o.cap_blob_need)]
 
     def capture_batch(self, dfa_id: int, prog_id: int, groups: Sequence[int], haystacks: Sequence[bytes]):
         """zke_capture_batch: one pattern over plain haystacks.  Returns (matches [n, 4] = code, count, start, end;
@@ -536,6 +547,79 @@ class Engine:
         if origins:
             return out[:n], infos, (ospans[:n * G * 2].reshape(n, G, 2), oflags[:n * G].reshape(n, G))
         return out[:n], infos
+
+    def pack_capture_mixed(self, regex_configs: Sequence, *, unicode: bool = True):
+        """The tables of zke_extract_captures_mixed for one ``RegexConfig`` (or its JSON dict, or None: verify_email only) per
+        e-mail: compiles and registers every pattern, deduplicates the configs by content (patterns and capture_indices, first
+        appearance first).  Returns (``_abi.CaptureMixedLists``, the distinct RegexConfig values in its order)."""
+        from . import regex_compile as rc
+        index: Dict[object, int] = {}
+        distinct, configs, config_of = [], [], []
+        for cfg in regex_configs:
+            if cfg is None:
+                config_of.append(A.CONFIG_NONE)
+                continue
+            if isinstance(cfg, dict):
+                cfg = rc.RegexConfig.from_json(cfg)
+            side = lambda parts: None if parts is None else tuple((p.pattern, tuple(p.capture_indices or [])) for p in parts)
+            key = (side(cfg.header_parts), side(cfg.body_parts))
+            if key not in index:
+                if len(configs) == A.MIXED_MAX_CONFIGS:
+                    raise EngineError("more than ZKE_MIXED_MAX_CONFIGS regex configs in one batch; split it")
+                index[key] = len(configs)
+                distinct.append(cfg)
+                part = lambda p: (*self.compile_pattern(p.pattern, unicode)[1:], list(p.capture_indices or []))
+                configs.append(([part(p) for p in cfg.header_parts or []], [part(p) for p in cfg.body_parts or []]))
+            config_of.append(index[key])
+        return A.CaptureMixedLists(configs, config_of), distinct
+
+    def _capture_mixed_call(self, refs, lists, origins: bool, blob_bytes: Optional[int] = None):
+        """One synchronous zke_extract_captures_mixed with caller-sized buffers (one retry with the blob size the engine reports)."""
+        n, J, Gt = refs.n, lists.J, lists.Gt
+        out = np.zeros(max(n, 1), dtype=A.RESULT_DTYPE)
+        ospans, oflags = np.zeros(max(Gt * 2, 1), np.uint32), np.zeros(max(Gt, 1), np.uint8)
+        org = A.zke_capture_origin()
+        org.spans, org.spans_cap, org.flags, org.flags_cap = ospans.ctypes.data, Gt * 2, oflags.ctypes.data, Gt
+        call = lambda o: self.lib.zke_extract_captures_mixed(self.h, refs.arr, n, C.byref(lists.c), out.ctypes.data, C.byref(o),
+                                                             C.byref(org) if origins else None)
+        rcode, spans, flags, cap_off, cap_str_off, cblob = self._run_captures_sized(J, Gt, call, 32 * Gt if blob_bytes is None else blob_bytes)
+        self._check(rcode, "zke_extract_captures_mixed")
+        return out[:n], spans, flags, cap_off, cap_str_off, cblob, (ospans[:Gt * 2].reshape(Gt, 2), oflags[:Gt])
+
+    def extract_captures_mixed(self, emails: Sequence[Email], regex_configs: Sequence, *, unicode: bool = True, origins: bool = False):
+        """zke_extract_captures_mixed: `extract_captures` for e-mails that carry different regex configs, one batch on the GPU.
+        `regex_configs[i]`: e-mail i's RegexConfig (or its JSON dict), or None for an e-mail that is verify_email only.  Returns
+        (records, regex_infos): regex_infos[i] is the RegexInfo of e-mail i, or None where the record is not OK or the e-mail has no
+        config.  origins=True: a third value (origin_spans, origin_flags), per e-mail ragged arrays [G_i, 2] and [G_i] — where
+        each requested group lies in its haystack BEFORE the QP filter."""
+        if len(emails) != len(regex_configs):
+            raise ValueError("one regex config (or None) per e-mail")
+        lists, distinct = self.pack_capture_mixed(regex_configs, unicode=unicode)
+        refs = emails if isinstance(emails, A.EmailRefs) else A.EmailRefs(emails)
+        out, spans, flags, cap_off, cap_str_off, cblob, (ospans, oflags) = self._capture_mixed_call(refs, lists, origins)
+        raw = cblob.tobytes()
+        infos: List[Optional[A.RegexInfo]] = []
+        for i in range(refs.n):
+            c = int(lists.config_of[i])
+            if c == A.CONFIG_NONE or out[i]["status"] != A.ZKE_OK:
+                infos.append(None)
+                continue
+            cfg, j0, col = distinct[c], int(lists.job_off[i]), int(lists.col_off[i])
+            pats = list(cfg.header_parts or []) + list(cfg.body_parts or [])
+            parts = []
+            for p, pat in enumerate(pats):
+                strs = []
+                for k in range(cap_off[j0 + p], cap_off[j0 + p + 1]):
+                    b = raw[cap_str_off[k]:cap_str_off[k + 1]]
+                    strs.append(b.decode("utf-8", errors="replace") if flags[col] & A.CAPF_NOT_UTF8 else b.decode("utf-8"))
+                    col += 1
+                parts.append(CompiledRegex(self.compile_pattern(pat.pattern, unicode)[0], strs))
+            nh = len(cfg.header_parts or [])
+            infos.append(A.RegexInfo(parts[:nh] if cfg.header_parts is not None else None, parts[nh:] if cfg.body_parts is not None else None))
+        if origins:
+            cut = lambda a: [a[int(lists.col_off[i]):int(lists.col_off[i + 1])].copy() for i in range(refs.n)]
+            return out, infos, (cut(ospans), cut(oflags))
+        return out, infos
 
     # ---- DKIM-Signature scan and key selection (helpers/src/generator.rs:11-53 around the caller's DNS fetch)
     @staticmethod
@@ -982,7 +1066,20 @@ def generate_email_with_regex_inputs(emails: Sequence[Email], regex_config, *, u
     return [EmailWithRegex(e, info) for e, info in zip(emails, infos)]
 
 
-NO_SIGNATURES = "No DKIM signatures found"                         # helpers/src/generator.rs:21
+def generate_email_with_regex_inputs_mixed(emails: Sequence[Email], regex_configs: Sequence, *, unicode: bool = True,
+                                           engine: Optional[Engine] = None):
+    """generate_email_with_regex_inputs for e-mails that carry different regex configs (`regex_configs[i]`: a RegexConfig, its JSON
+    dict, or None), one batch: an EmailWithRegex per e-mail with a config, the Email itself for one without — values
+    `Engine.verify_emails_mixed` accepts.  Raises VerifyPanic as generate_email_with_regex_inputs does."""
+    eng = engine or default_engine()
+    records, infos = eng.extract_captures_mixed(emails, regex_configs, unicode=unicode)
+    for i, r in enumerate(records):
+        if r["status"] != A.ZKE_OK:
+            raise VerifyPanic(int(r["status"]), int(r["detail"]), i)
+    return [e if cfg is None else EmailWithRegex(e, info) for e, cfg, info in zip(emails, regex_configs, infos)]
+
+
+NO_SIGNATURES = "No DKIM signatures found"                        # helpers/src/generator.rs:21
 NO_VALID_KEY = "No valid DKIM key found for any signature"        # helpers/src/generator.rs:52
 
 
