@@ -1008,6 +1008,76 @@ pub struct MappedCaptures {
     pub origin_flags: Vec<u8>,
 }
 
+/// One e-mail's verifier output as a batch encodes it on the device (`zke_encoded_info`, the encoding as bytes):
+/// `VerificationOutput::from_parts(email, None).abi_encode()` (`core/src/io.rs:28-44`) — what a zkVM front end commits as public
+/// values — and the SHA-256 of those bytes, the value a proof binds to.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct EncodedOutput {
+    pub bytes: Vec<u8>,
+    pub digest: [u8; 32],
+}
+
+impl Engine {
+    /// `verify_email` over a slice with the outputs encoded and hashed on the device (`zke_verify_emails_encoded`, both list forms
+    /// NULL): one `Result` per e-mail, in order — the encoding and its digest, or the panic the reference would have raised.  The
+    /// external inputs travel flattened `[name1, value1, ...]` as `circuits.rs:18-27` flattens them; a `None` value travels as `""`
+    /// (its e-mail reports `ZKE_EXTERNAL_INPUT_NULL` and is not encoded).  Both buffer sizes follow from the inputs' lengths alone:
+    /// a first call that stages nothing asks for them, the second runs the batch.
+    pub fn verify_emails_encoded(&self, emails: &[Email]) -> Result<Vec<Result<EncodedOutput, Panic>>, EngineError> {
+        let n = emails.len();
+        if n == 0 {
+            return Ok(Vec::new());
+        }
+        let refs: Vec<sys::zke_email_ref> = emails.iter().map(email_ref).collect();
+        let (mut ext_off, mut ext_str_off, mut ext_blob) = (vec![0u32], vec![0u32], Vec::<u8>::new());
+        for e in emails {
+            for x in &e.external_inputs {
+                ext_blob.extend_from_slice(x.name.as_bytes());
+                ext_str_off.push(ext_blob.len() as u32);
+                ext_blob.extend_from_slice(x.value.as_deref().unwrap_or("").as_bytes());
+                ext_str_off.push(ext_blob.len() as u32);
+            }
+            ext_off.push(ext_str_off.len() as u32 - 1);
+        }
+        ext_blob.push(0); // (a valid pointer also when every string is empty)
+        let input = sys::zke_encode_in {
+            lists: ptr::null(),
+            mixed: ptr::null(),
+            ext_off: ext_off.as_ptr(),
+            ext_str_off: ext_str_off.as_ptr(),
+            ext_blob: ext_blob.as_ptr(),
+        };
+        let mut out = vec![zeroed_result(); n];
+        let mut enc = sys::zke_encoded_out { infos: ptr::null_mut(), infos_cap: 0, bytes: ptr::null_mut(), bytes_cap: 0, infos_need: 0, bytes_need: 0 };
+        // SAFETY: every pointer refers into `emails`, `refs`, the three tables or `out`, alive until the synchronous call returns;
+        // with zero capacities the call writes the two sizes and returns ZKE_E_NOMEM before anything is staged.
+        let rc = unsafe { sys::zke_verify_emails_encoded(self.raw, refs.as_ptr(), n as u32, &input, out.as_mut_ptr(), &mut enc) };
+        if rc != sys::ZKE_E_NOMEM {
+            return Err(self.last_error(if rc == 0 { sys::ZKE_E_ARG } else { rc }));
+        }
+        // SAFETY: zke_encoded_info is plain integers and bytes; all-zero is a value of it.
+        let mut infos: Vec<sys::zke_encoded_info> = vec![unsafe { std::mem::zeroed() }; enc.infos_need];
+        let mut bytes = vec![0u8; enc.bytes_need];
+        enc = sys::zke_encoded_out { infos: infos.as_mut_ptr(), infos_cap: infos.len(), bytes: bytes.as_mut_ptr(), bytes_cap: bytes.len(), infos_need: 0, bytes_need: 0 };
+        // SAFETY: as above; `infos` and `bytes` have exactly the sizes the first call asked for.
+        let rc = unsafe { sys::zke_verify_emails_encoded(self.raw, refs.as_ptr(), n as u32, &input, out.as_mut_ptr(), &mut enc) };
+        if rc != 0 {
+            return Err(self.last_error(rc));
+        }
+        Ok(out
+            .iter()
+            .zip(infos.iter())
+            .map(|(r, f)| {
+                if r.status == sys::ZKE_OK {
+                    Ok(EncodedOutput { bytes: bytes[f.off as usize..f.off as usize + f.len as usize].to_vec(), digest: f.digest })
+                } else {
+                    Err(Panic { status: r.status, detail: r.detail })
+                }
+            })
+            .collect())
+    }
+}
+
 /// One e-mail's `extract_email_body` as an extraction reports it (`zke_body_info`, the decoded body as bytes).
 #[derive(Debug, Clone, PartialEq, Eq)]
 pub struct BodyInfo {

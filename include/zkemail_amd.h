@@ -767,6 +767,52 @@ typedef struct zke_body_out {
 int zke_extract_bodies(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t flags, zke_body_out* out);
 int zke_extract_bodies_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t flags, zke_body_out* out, uint64_t* ticket);
 
+/* ---- the verifier outputs encoded on the device: per e-mail VerificationOutput::from_parts(email, matches).abi_encode()
+ * (core/src/io.rs:28-44; the layout: zke_abi_encode below) — the bytes a zkVM front end commits as public values — and their SHA-256,
+ * the value a proof binds to.  One e-mail per wavefront (encode_outputs_kernel, csrc/encode.hip.h), then the engine's ordinary hash
+ * launch over the encodings; both follow the verify launches on the batch's stream.
+ *   zke_verify_emails_encoded   runs the pipeline of zke_verify_emails (in == NULL, or both of its lists NULL), of
+ *                               zke_verify_emails_with_regex (in->lists) or of zke_verify_emails_mixed (in->mixed); out[i] is byte for
+ *                               byte the record that entry gives.  An e-mail whose record is ZKE_OK is encoded: kind 0
+ *                               (SolEmailOutput) where it is verify_email only — no list form, or config_of[i] == ZKE_CONFIG_NONE —,
+ *                               else kind 1 (SolEmailWithRegexOutput), whose matches are ALL its parts' capture strings in part order
+ *                               (circuits.rs:58-62): with `lists` the strings cap_off[i * P] .. cap_off[(i + 1) * P], with `mixed`
+ *                               cap_off[job_off[i]] .. cap_off[job_off[i + 1]]; possibly none.  Any other status: not encoded —
+ *                               len 0, a zero digest, its place in `bytes` left as it was.  external_input_null stays in
+ *                               zke_email_ref: such an e-mail reports ZKE_EXTERNAL_INPUT_NULL as always and is not encoded.
+ *   external inputs             flattened as the reference does, [name1, value1, name2, value2, ...] (circuits.rs:18-27): e-mail i's
+ *                               are the strings ext_off[i] .. ext_off[i + 1] of the CSR table ext_str_off / ext_blob.
+ * Strings are bytes with lengths and are NOT validated as UTF-8: the reference's Strings are valid by type, a caller that hands
+ * over other bytes gets them encoded as they are.
+ * Buffers.  The size of an encoding follows from the kind and the string lengths alone, so off, infos_need and bytes_need are exact
+ * and are set BEFORE anything is staged: a call whose infos or bytes is too small fails at once with ZKE_E_NOMEM and both *_need
+ * set (the zke_body_out protocol, without its second chance: nothing here depends on the e-mails).  E-mail i's place is
+ * bytes[off, off + planned length) whatever its verdict; places follow each other in e-mail order without a gap.
+ * ZKE_E_ARG, before anything is staged: both lists and mixed set; offsets that decrease (ext_off, ext_str_off, the capture tables);
+ * a null table with a non-zero tail (ext_off names strings and ext_str_off is NULL, or they have bytes and ext_blob is NULL);
+ * an encoding of 2^32 bytes or more; and whatever the entry chosen by `in` refuses.
+ * Slots, tickets and zke_batch_wait are zke_verify_emails_async's; everything `in` points to has been read when the call returns,
+ * `out`, `enc` and its buffers must stay valid until the batch has been waited for. */
+typedef struct zke_encoded_info {   /* 48 bytes */
+  uint64_t off;        /* the e-mail's place in zke_encoded_out.bytes (planned from the inputs' lengths: known before the batch runs) */
+  uint32_t len;        /* bytes of the encoding; 0: not encoded (status != ZKE_OK) */
+  uint32_t kind;       /* 0 SolEmailOutput, 1 SolEmailWithRegexOutput */
+  uint8_t  digest[32]; /* SHA-256 of bytes[off, off+len); zero when len == 0 */
+} zke_encoded_info;
+typedef struct zke_encoded_out { zke_encoded_info* infos; size_t infos_cap; uint8_t* bytes; size_t bytes_cap;
+                                 size_t infos_need, bytes_need; } zke_encoded_out;
+typedef struct zke_encode_in {
+  const zke_regex_lists* lists;    /* at most one of lists / mixed; both NULL: verify_email for every e-mail (kind 0) */
+  const zke_regex_mixed* mixed;    /* kind 0 where config_of[i] == ZKE_CONFIG_NONE, else 1 */
+  const uint32_t* ext_off;         /* [n+1] or NULL: no external inputs anywhere; e-mail i's strings ext_off[i] .. ext_off[i+1] */
+  const uint32_t* ext_str_off;     /* [n_strings+1] */
+  const uint8_t*  ext_blob;
+} zke_encode_in;
+int zke_verify_emails_encoded(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_encode_in* in, zke_result* out,
+                              zke_encoded_out* enc);
+int zke_verify_emails_encoded_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_encode_in* in, zke_result* out,
+                                    zke_encoded_out* enc, uint64_t* ticket);
+
 /* Device-resident batch: every pointer in `in` and `out_dev` is device memory (the part-id lists stay host arrays);
  * `raw_total`, `domain_total`, `key_total` are the blob sizes (the CSR tails), which the
  * host needs for workspace sizing without a device read.  Takes the engine's next submission slot (round-robin),
@@ -891,6 +937,17 @@ int zke_ed25519_verify_batch(zke_engine* e, const uint8_t* keys, const uint8_t* 
 /* Device-resident SHA-256 micro-benchmark entry: messages already in HBM. */
 int zke_sha256_batch_device(zke_engine* e, const uint8_t* msg_blob_dev, const uint64_t* off_dev,
                             uint32_t n, uint8_t* digests_dev, void* stream);
+
+/* The encode and digest launches of zke_verify_emails_encoded alone, over records and tables of the caller's (host pointers): for
+ * parity tests, and for a caller that already holds a batch's records.  records[n]: status, from_domain_hash and public_key_hash are
+ * read; kinds[n]: 0 / 1 as zke_encoded_info.kind.  Two CSR string tables of the same shape: e-mail i's external inputs are the
+ * strings ext_off[i] .. ext_off[i + 1] of ext_str_off / ext_blob, its matches (kind 1 only) the strings match_off[i] ..
+ * match_off[i + 1] of match_str_off / match_blob; ext_off / match_off NULL: none anywhere.  `enc`, the checks (ZKE_E_ARG, also for a
+ * kind above 1) and the exact sizes (ZKE_E_NOMEM at once) are zke_verify_emails_encoded's.  Synchronous; runs in one slot, whose
+ * output buffer is the one that entry uses. */
+int zke_encode_outputs(zke_engine* e, const zke_result* records, uint32_t n, const uint32_t* kinds,
+                       const uint32_t* ext_off, const uint32_t* ext_str_off, const uint8_t* ext_blob,
+                       const uint32_t* match_off, const uint32_t* match_str_off, const uint8_t* match_blob, zke_encoded_out* enc);
 
 /* Solidity ABI encoding of a verifier output — what VerificationOutput::from_parts(email, matches).abi_encode()
  * returns (core/src/io.rs:28-44): abi.encode of

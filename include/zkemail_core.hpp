@@ -7,6 +7,8 @@
 // status that names the panic site; a caller that wants drop-in abort semantics lets it propagate
 // to std::terminate.
 #pragma once
+#include <algorithm>
+#include <array>
 #include <cstdint>
 #include <functional>
 #include <map>
@@ -130,6 +132,14 @@ struct BodyInfo {
   uint32_t src_off, src_len;               // body_bytes of the chosen part in the raw e-mail, before decoding
   std::vector<uint8_t> body;               // empty unless status is ZKE_OK
 };
+// One e-mail's verifier output as a batch encodes it on the device (zke_encoded_info, the encoding as bytes): the record's verdict
+// and, when that is ZKE_OK, VerificationOutput::from_parts(..).abi_encode() and its SHA-256; else no bytes and a zero digest.
+struct EncodedOutput {
+  uint32_t status, detail;                 // of the e-mail's record
+  uint32_t kind;                           // 0 SolEmailOutput, 1 SolEmailWithRegexOutput
+  std::vector<uint8_t> bytes;
+  std::array<uint8_t, 32> digest;
+};
 // The resolver of generate_email_inputs_from_records: (from_domain, selector) -> the RAW answer — the TXT record of
 // selector._domainkey.domain (its character-strings joined) or the archive's value —, or nullopt when the fetch fails.
 using FetchRecord = std::function<std::optional<std::string>(const std::string& domain, const std::string& selector)>;
@@ -209,46 +219,31 @@ class Engine {
   // the pairs are registered once (zke_dfa_register), the e-mails stay where they are (zke_verify_emails_with_regex).
   std::vector<zke_result> verify_emails_with_regex(const std::vector<EmailWithRegex>& in) {
     if (in.empty()) return {};
-    std::vector<uint32_t> hids, bids;
-    auto ids_of = [&](const std::optional<std::vector<CompiledRegex>>& parts) {
-      std::vector<uint32_t> v;
-      if (parts)
-        for (const auto& p : *parts) {
-          uint32_t id = 0;
-          if (int r = zke_dfa_register(e_, p.verify_re.fwd.data(), p.verify_re.fwd.size(), p.verify_re.bwd.data(), p.verify_re.bwd.size(), &id))
-            throw EngineError("zke_dfa_register failed: " + std::to_string(r) + " " + zke_last_error(e_));
-          v.push_back(id);                       // an equal pair registered again gets the id it already has
-        }
-      return v;
-    };
-    hids = ids_of(in[0].regex_info.header_parts);
-    bids = ids_of(in[0].regex_info.body_parts);
-    std::vector<zke_email_ref> refs(in.size());
-    std::vector<uint32_t> cap_off{0}, cap_str_off{0};
-    std::vector<uint8_t> cap_blob;
-    for (size_t i = 0; i < in.size(); i++) {
-      const Email& em = in[i].email;
-      if (ids_of(in[i].regex_info.header_parts) != hids || ids_of(in[i].regex_info.body_parts) != bids)
-        throw EngineError("a batch must share one part list; split it per regex_config");
-      uint32_t ext = 0;
-      for (const auto& x : em.external_inputs) if (!x.value) ext = 1;
-      refs[i] = zke_email_ref{em.raw_email.data(), em.raw_email.size(), em.from_domain.data(), em.from_domain.size(),
-                              em.public_key.key.data(), em.public_key.key.size(), key_type_code(em.public_key.key_type), ext};
-      for (const auto* parts : {&in[i].regex_info.header_parts, &in[i].regex_info.body_parts})
-        if (*parts)
-          for (const auto& p : **parts) {
-            if (p.captures)
-              for (const auto& s : *p.captures) { cap_blob.insert(cap_blob.end(), s.begin(), s.end()); cap_str_off.push_back((uint32_t)cap_blob.size()); }
-            cap_off.push_back((uint32_t)cap_str_off.size() - 1);
-          }
-    }
-    if (cap_blob.empty()) cap_blob.push_back(0);
-    zke_regex_lists lists{(uint32_t)hids.size(), hids.data(), (uint32_t)bids.size(), bids.data(),
-                          hids.size() + bids.size() ? cap_off.data() : nullptr, cap_str_off.data(), cap_blob.data()};
+    ListsPack p;
+    pack_lists(in, p);
     std::vector<zke_result> out(in.size());
-    if (int r = zke_verify_emails_with_regex(e_, refs.data(), (uint32_t)refs.size(), &lists, out.data()))
+    if (int r = zke_verify_emails_with_regex(e_, p.refs.data(), (uint32_t)p.refs.size(), &p.lists, out.data()))
       throw EngineError("zke_verify_emails_with_regex failed: " + std::to_string(r) + " " + zke_last_error(e_));
     return out;
+  }
+
+  // verify_email over a vector of e-mails with the outputs encoded on the device (zke_verify_emails_encoded): per e-mail the record's
+  // verdict and, where it is ZKE_OK, VerificationOutput::from_parts(email, None).abi_encode() (core/src/io.rs:28-44) and its SHA-256 —
+  // what abi_encode(verify_email(email)) gives, for the whole batch.  Never a throw for a bad e-mail.
+  std::vector<EncodedOutput> verify_emails_encoded(const std::vector<Email>& emails) {
+    std::vector<zke_email_ref> refs(emails.size());
+    std::vector<const Email*> ems(emails.size());
+    for (size_t i = 0; i < emails.size(); i++) { refs[i] = ref_of(emails[i]); ems[i] = &emails[i]; }
+    return encoded_call(refs, ems, nullptr);
+  }
+  // ... and verify_email_with_regex over a vector that shares one part list: SolEmailWithRegexOutput, the matches the e-mail's captures
+  std::vector<EncodedOutput> verify_emails_with_regex_encoded(const std::vector<EmailWithRegex>& in) {
+    if (in.empty()) return {};
+    ListsPack p;
+    pack_lists(in, p);
+    std::vector<const Email*> ems(in.size());
+    for (size_t i = 0; i < in.size(); i++) ems[i] = &in[i].email;
+    return encoded_call(p.refs, ems, &p.lists);
   }
 
   // verify_email_with_regex over a vector as the reference has it — every value with a RegexInfo of its own — and verify_email for
@@ -638,6 +633,85 @@ class Engine {
   }
   static uint32_t key_type_code(const std::string& t) {
     return t == "rsa" ? ZKE_KEY_RSA : (t == "ed25519" ? ZKE_KEY_ED25519 : ZKE_KEY_OTHER);
+  }
+  static zke_email_ref ref_of(const Email& em) {
+    uint32_t ext = 0;
+    for (const auto& x : em.external_inputs) if (!x.value) ext = 1;                      // circuits.rs:24
+    return zke_email_ref{em.raw_email.data(), em.raw_email.size(), em.from_domain.data(), em.from_domain.size(),
+                         em.public_key.key.data(), em.public_key.key.size(), key_type_code(em.public_key.key_type), ext};
+  }
+  // A vector of EmailWithRegex that shares one part list as zke_verify_emails_with_regex takes it: the pairs registered, the e-mails
+  // where they are, the captures as CSR tables.  `lists` points into the pack.
+  struct ListsPack {
+    std::vector<uint32_t> hids, bids, cap_off{0}, cap_str_off{0};
+    std::vector<uint8_t> cap_blob;
+    std::vector<zke_email_ref> refs;
+    zke_regex_lists lists{};
+  };
+  void pack_lists(const std::vector<EmailWithRegex>& in, ListsPack& p) {
+    auto ids_of = [&](const std::optional<std::vector<CompiledRegex>>& parts) {
+      std::vector<uint32_t> v;
+      if (parts)
+        for (const auto& q : *parts) {
+          uint32_t id = 0;
+          if (int r = zke_dfa_register(e_, q.verify_re.fwd.data(), q.verify_re.fwd.size(), q.verify_re.bwd.data(), q.verify_re.bwd.size(), &id))
+            throw EngineError("zke_dfa_register failed: " + std::to_string(r) + " " + zke_last_error(e_));
+          v.push_back(id);                       // an equal pair registered again gets the id it already has
+        }
+      return v;
+    };
+    p.hids = ids_of(in[0].regex_info.header_parts);
+    p.bids = ids_of(in[0].regex_info.body_parts);
+    p.refs.resize(in.size());
+    for (size_t i = 0; i < in.size(); i++) {
+      if (ids_of(in[i].regex_info.header_parts) != p.hids || ids_of(in[i].regex_info.body_parts) != p.bids)
+        throw EngineError("a batch must share one part list; split it per regex_config");
+      p.refs[i] = ref_of(in[i].email);
+      for (const auto* parts : {&in[i].regex_info.header_parts, &in[i].regex_info.body_parts})
+        if (*parts)
+          for (const auto& q : **parts) {
+            if (q.captures)
+              for (const auto& s : *q.captures) { p.cap_blob.insert(p.cap_blob.end(), s.begin(), s.end()); p.cap_str_off.push_back((uint32_t)p.cap_blob.size()); }
+            p.cap_off.push_back((uint32_t)p.cap_str_off.size() - 1);
+          }
+    }
+    if (p.cap_blob.empty()) p.cap_blob.push_back(0);
+    p.lists = zke_regex_lists{(uint32_t)p.hids.size(), p.hids.data(), (uint32_t)p.bids.size(), p.bids.data(),
+                              p.hids.size() + p.bids.size() ? p.cap_off.data() : nullptr, p.cap_str_off.data(), p.cap_blob.data()};
+  }
+  // zke_verify_emails_encoded over refs (and `lists`, or nullptr for verify_email): the external inputs flattened [name, value, ...]
+  // (circuits.rs:18-27; a None value travels as "": its e-mail reports ZKE_EXTERNAL_INPUT_NULL and is not encoded), a first call
+  // that asks for the sizes — they are exact and known before anything runs —, the call itself.
+  std::vector<EncodedOutput> encoded_call(const std::vector<zke_email_ref>& refs, const std::vector<const Email*>& ems, const zke_regex_lists* lists) {
+    const uint32_t n = (uint32_t)refs.size();
+    std::vector<uint32_t> ext_off{0}, ext_str_off{0};
+    std::vector<uint8_t> ext_blob;
+    for (const Email* em : ems) {
+      for (const auto& x : em->external_inputs)
+        for (const std::string* s : {&x.name, x.value ? &*x.value : nullptr}) {
+          if (s) ext_blob.insert(ext_blob.end(), s->begin(), s->end());
+          ext_str_off.push_back((uint32_t)ext_blob.size());
+        }
+      ext_off.push_back((uint32_t)ext_str_off.size() - 1);
+    }
+    if (ext_blob.empty()) ext_blob.push_back(0);
+    const zke_encode_in in{lists, nullptr, ext_off.data(), ext_str_off.data(), ext_blob.data()};
+    std::vector<zke_result> recs(n);
+    zke_encoded_out enc{};
+    int r = zke_verify_emails_encoded(e_, refs.data(), n, &in, recs.data(), &enc);
+    if (r && r != ZKE_E_NOMEM) throw EngineError("zke_verify_emails_encoded failed: " + std::to_string(r) + " " + zke_last_error(e_));
+    std::vector<zke_encoded_info> infos(enc.infos_need + 1);
+    std::vector<uint8_t> bytes(enc.bytes_need + 1);
+    enc = zke_encoded_out{infos.data(), enc.infos_need, bytes.data(), enc.bytes_need, 0, 0};
+    if ((r = zke_verify_emails_encoded(e_, refs.data(), n, &in, recs.data(), &enc)))
+      throw EngineError("zke_verify_emails_encoded failed: " + std::to_string(r) + " " + zke_last_error(e_));
+    std::vector<EncodedOutput> out(n);
+    for (uint32_t i = 0; i < n; i++) {
+      out[i].status = recs[i].status; out[i].detail = recs[i].detail; out[i].kind = infos[i].kind;
+      out[i].bytes.assign(bytes.begin() + infos[i].off, bytes.begin() + infos[i].off + infos[i].len);
+      std::copy(infos[i].digest, infos[i].digest + 32, out[i].digest.begin());
+    }
+    return out;
   }
   // One e-mail through the single-e-mail entry points of the C-ABI (zke_verify_email / zke_verify_email_with_regex).
   zke_result run(const Email& em, const RegexInfo* ri) {

@@ -345,6 +345,94 @@ class MixedLists:
             m.cap_off, m.cap_str_off, m.cap_blob = self.cap_off.ctypes.data, self.cap_str_off.ctypes.data, self.cap_blob.ctypes.data
 
 
+# the verifier outputs encoded on the device (zke_verify_emails_encoded, zke_encode_outputs)
+ENC_KIND_EMAIL, ENC_KIND_WITH_REGEX = 0, 1       # zke_encoded_info.kind: SolEmailOutput, SolEmailWithRegexOutput
+
+
+class zke_encoded_info(C.Structure):
+    """One e-mail's encoding: its place in the byte blob, its length (0: not encoded), its kind, the SHA-256 of its bytes."""
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint32), ("kind", C.c_uint32), ("digest", C.c_uint8 * 32)]
+
+
+ENCODED_INFO_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("kind", "<u4"), ("digest", "u1", 32)])
+assert C.sizeof(zke_encoded_info) == 48 == ENCODED_INFO_DTYPE.itemsize
+
+
+class zke_encoded_out(C.Structure):
+    """Caller-sized buffers of an encoding; capacities in entries, the (exact) sizes needed written back."""
+    _fields_ = [("infos", C.c_void_p), ("infos_cap", C.c_size_t), ("bytes", C.c_void_p), ("bytes_cap", C.c_size_t),
+                ("infos_need", C.c_size_t), ("bytes_need", C.c_size_t)]
+
+
+class zke_encode_in(C.Structure):
+    _fields_ = [("lists", C.POINTER(zke_regex_lists)), ("mixed", C.POINTER(zke_regex_mixed)),
+                ("ext_off", C.c_void_p), ("ext_str_off", C.c_void_p), ("ext_blob", C.c_void_p)]
+
+
+def flat_external_inputs(inputs: Sequence["ExternalInput"]) -> List[str]:
+    """Email.external_inputs as the output carries them: [name1, value1, name2, value2, ...] (circuits.rs:18-27).  (A None value
+    is the reference's panic, ZKE_EXTERNAL_INPUT_NULL: such an e-mail is never encoded, and its value travels as "".)"""
+    return [s for x in inputs for s in (x.name, x.value if x.value is not None else "")]
+
+
+class StringTable:
+    """A CSR string table as the encode entries take it: ``lists[i]`` are entry i's strings (str or bytes).  off[n + 1] indexes
+    str_off[n_strings + 1], which indexes blob.  Keeps the numpy buffers alive."""
+
+    def __init__(self, lists: Sequence[Sequence]):
+        strs = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for xs in lists for s in xs]
+        self.off = np.zeros(len(lists) + 1, np.uint32)
+        if len(lists):
+            self.off[1:] = np.cumsum([len(xs) for xs in lists])
+        self.blob, so = _csr(strs)
+        self.str_off = so.astype(np.uint32)
+        self.n_strings = len(strs)
+
+
+class EncodeTables:
+    """The tables of one zke_encode_outputs call from a list of verifier outputs — EmailVerifierOutput (kind 0) or
+    EmailWithRegexVerifierOutput (kind 1) values: kinds[n], the external inputs and the matches as two StringTables, and the
+    hashes laid into zke_result records (status ZKE_OK unless `statuses` says otherwise)."""
+
+    def __init__(self, outputs: Sequence, statuses: Optional[Sequence[int]] = None):
+        self.n = len(outputs)
+        emails = [o.email if isinstance(o, EmailWithRegexVerifierOutput) else o for o in outputs]
+        self.kinds = np.array([ENC_KIND_WITH_REGEX if isinstance(o, EmailWithRegexVerifierOutput) else ENC_KIND_EMAIL for o in outputs] or [0],
+                              np.uint32)
+        self.ext = StringTable([e.external_inputs for e in emails])
+        self.matches = StringTable([o.regex_matches if isinstance(o, EmailWithRegexVerifierOutput) else [] for o in outputs])
+        self.records = np.zeros(max(self.n, 1), RESULT_DTYPE)
+        for i, e in enumerate(emails):
+            self.records[i]["from_domain_hash"] = np.frombuffer(bytes(e.from_domain_hash), np.uint8)
+            self.records[i]["public_key_hash"] = np.frombuffer(bytes(e.public_key_hash), np.uint8)
+            self.records[i]["status"] = statuses[i] if statuses is not None else ZKE_OK
+
+
+class EncodedBuffers:
+    """The caller-sized buffers of a zke_encoded_out (kept alive by this object) and their reading."""
+
+    def __init__(self, n: int, nbytes: int, guard: int = 0, fill: int = 0):
+        self.n, self.nbytes = n, nbytes
+        self.infos = np.zeros(max(n, 1), ENCODED_INFO_DTYPE)
+        self.bytes = np.full(max(nbytes + guard, 1), fill, np.uint8)
+        o = self.c = zke_encoded_out()
+        o.infos, o.infos_cap, o.bytes, o.bytes_cap = self.infos.ctypes.data, n, self.bytes.ctypes.data, nbytes
+
+    def encoding(self, i: int) -> bytes:
+        f = self.infos[i]
+        return self.bytes[int(f["off"]):int(f["off"]) + int(f["len"])].tobytes()
+
+    def result(self) -> List[Tuple[bytes, bytes]]:
+        """Per e-mail (encoding, digest); (b"", 32 zero bytes) for an e-mail that was not encoded."""
+        return [(self.encoding(i), self.infos[i]["digest"].tobytes()) for i in range(self.n)]
+
+
+def encoded_len(kind: int, ext_lens: Sequence[int], match_lens: Sequence[int] = ()) -> int:
+    """The plan's size rule (csrc/encode_plan.hip.h): the bytes of an encoding from its kind and its strings' lengths."""
+    arr = lambda lens: 32 + sum(64 + (int(ln) + 31) // 32 * 32 for ln in lens)
+    return 32 + 96 + arr(ext_lens) + ((64 + arr(match_lens)) if kind == ENC_KIND_WITH_REGEX else 0)
+
+
 class zke_capture_config(C.Structure):
     """One RegexConfig of a mixed extraction (zke_extract_captures_mixed): the parts with their programs and requested groups."""
     _fields_ = [

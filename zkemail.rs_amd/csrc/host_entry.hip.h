@@ -87,6 +87,17 @@ void capmix_resolve(zke_engine* e, CapMixedReq& q) {
     if (capture_resolve_part(e, q.part[k], q.prog_ids[k])) q.needs_work = true;
 }
 
+// ---- output encoding (zke_verify_emails_encoded; plan: encode_plan.hip.h, kernel: encode.hip.h): the plan — the jobs, the places, the
+// exact size of the blob — is built by the entry before anything is staged; the jobs and the external-input table ride in the batch's
+// input image (EncImage, behind a mixed batch's plan), the matches are the capture tables the regex stage reads.
+struct EncodeReq {
+  zke_encoded_out* out = nullptr;
+  EncodePlan plan;
+  const uint32_t* ext_str_off = nullptr;
+  const uint8_t* ext_blob = nullptr;
+  EncImage image() const { return enc_image((uint32_t)plan.jobs.size(), plan.ext_strs, plan.ext_bytes); }
+};
+
 // A slot's buffers for one side output of a batch of n: the layout, then the buffers it asks for (ensure_side_buffers).
 // `pack`: zke_select_keys_from_records, the decoded keys are packed for the front end.
 int ensure_keyrec_buffers(zke_engine* e, KeyrecBufs& b, uint32_t m, size_t rec_total, bool pack) {
@@ -96,6 +107,11 @@ int ensure_keyrec_buffers(zke_engine* e, KeyrecBufs& b, uint32_t m, size_t rec_t
 int ensure_body_buffers(zke_engine* e, BodyBufs& b, uint32_t n, size_t raw_total) {
   b.L = body_layout(n, raw_total);
   return ensure_side_buffers(e, b.t, b.L.total, b.L.total, &b.ovf, (size_t)n * HDR_OVF_BYTES, "body-extraction buffer allocation");
+}
+// `staged`: bytes of the building block's input (zke_encode_outputs), 0 where the batch's image carries it
+int ensure_encode_buffers(zke_engine* e, EncBufs& b, uint32_t n, uint64_t blob, size_t staged) {
+  b.L = enc_layout(n, blob);
+  return ensure_side_buffers(e, b.t, b.L.total, b.L.prefix, staged ? &b.in : nullptr, staged, "output-encoding buffer allocation");
 }
 // max_sigs record slots per e-mail and the caller's sel_blob_cap bytes of selectors (a selector is at most ZKE_MAX_TAGBUF bytes: a
 // larger blob than that per record slot is never used)
@@ -208,6 +224,28 @@ int deliver_body(zke_engine* e, const BodyBufs& b, zke_body_out* o, hipStream_t 
   return 0;
 }
 
+// The encodings from the slot's pinned twin into the caller's zke_encoded_out (both buffers were checked against the plan's exact
+// sizes before the batch was staged): the infos as they are, the bytes in runs of encoded e-mails that follow each other — the place
+// of an e-mail that was not encoded holds whatever the slot's buffer held, and the caller's bytes stay as they were there.  An info
+// that points outside the blob is refused and nothing is read through it.
+int deliver_encoded(zke_engine* e, const EncBufs& b, zke_encoded_out* o) {
+  const EncLayout& K = b.L;
+  const uint8_t* hp = b.t.h.as<uint8_t>();
+  const zke_encoded_info* src = reinterpret_cast<const zke_encoded_info*>(hp);
+  for (uint32_t i = 0; i < K.n; i++)
+    if (src[i].off > K.blob || src[i].len > K.blob - src[i].off) return fail(e, ZKE_E_DEVICE, "output encoding: an info points outside the blob");
+  if (K.n) memcpy(o->infos, src, (size_t)K.n * sizeof(zke_encoded_info));
+  uint64_t r0 = 0, r1 = 0;
+  auto flush = [&] { if (r1 > r0) memcpy(o->bytes + r0, hp + K.bytes + r0, (size_t)(r1 - r0)); };
+  for (uint32_t i = 0; i < K.n; i++) {
+    if (!src[i].len) continue;
+    if (src[i].off != r1) { flush(); r0 = src[i].off; }
+    r1 = src[i].off + src[i].len;
+  }
+  flush();
+  return 0;
+}
+
 // A key selection's fold: the records of the (e-mail, candidate) pairs are in the pinned buffer; per e-mail the first ZKE_OK.
 void fold_selection(const zke_result* R, const std::vector<uint32_t>& off, zke_result* out, uint32_t* chosen) {
   for (size_t i = 0; i + 1 < off.size(); i++) {
@@ -229,8 +267,8 @@ void fold_selection(const zke_result* R, const std::vector<uint32_t>& off, zke_r
 }
 
 // Pay what a slot owes for a batch whose last copy has arrived, from the slot's pinned buffers into the caller's.  The order: the
-// records, the selection fold, the scan, the key records, the bodies, the captures, the origins.  Needs no device where nothing is
-// left in HBM (a body that did not spill, no capture strings).
+// records, the selection fold, the scan, the key records, the bodies, the captures, the origins, the encodings.  Needs no device where
+// nothing is left in HBM (a body that did not spill, no capture strings).
 // The shortfall rule: an output whose variable-size buffer is too small is ZKE_E_NOMEM to whoever waits — `cap_rc` (zke_batch_wait,
 // the synchronous entries) — and nobody's business otherwise: a slot that retires a batch nobody waited for has nobody to tell, and
 // zke_last_error stays what it was.  Everything of fixed size and every *_need is delivered either way; any other error ends the delivery.
@@ -248,6 +286,7 @@ int deliver_pending(zke_engine* e, Slot& w, const PendingDelivery& d, int* cap_r
   if (d.body && (r = settled(deliver_body(e, w.bb, d.body, w.stream)))) return r;
   if (d.caps && (r = settled(deliver_captures(e, w.cb, d.caps, w.stream)))) return r;
   if (d.org) deliver_origins(w.cb, w.ob, d.org);
+  if (d.enc && (r = deliver_encoded(e, w.eb, d.enc))) return r;
   return 0;
 }
 
@@ -289,10 +328,21 @@ struct HostBatch {
   const BodyReq* body = nullptr;        // zke_extract_bodies: body_extract_kernel runs instead of the verify pipeline
   MixedReq* mixed = nullptr;            // zke_verify_emails_mixed: a regex batch whose part lists are the configs' (b's own are empty)
   CapMixedReq* capmix = nullptr;        // zke_extract_captures_mixed: the extraction that rides on this mixed batch (mixed == &capmix->verify)
+  const EncodeReq* enc = nullptr;       // zke_verify_emails_encoded: the encode and digest launches behind this batch's records
   uint64_t raw_total = 0, dom_total = 0, key_total = 0, raw_base = 0, dom_base = 0, key_base = 0;   // blob bytes; off[0] of packed offsets
   size_t cap_words = 0, cap_strs = 0, cap_bytes = 0;      // entries of cap_off and cap_str_off, bytes of cap_blob (0: no tables)
   ImageLayout L{};
 };
+// The plan sections of a batch's image, one behind the other: a mixed batch's plan, a mixed extraction's tables, an encoding's jobs
+// and external inputs (which start 64-byte aligned: a blob lies in them).
+size_t enc_image_at(const HostBatch& d) {
+  return align_up((d.mixed ? mixed_image(d.b.n, d.mixed->shape).total : 0) + (d.capmix ? d.capmix->image(d.b.n).total : 0), 64);
+}
+void layout_host_batch(HostBatch& d) {
+  const size_t plans = d.enc ? enc_image_at(d) + d.enc->image().total
+                             : (d.mixed ? mixed_image(d.b.n, d.mixed->shape).total : 0) + (d.capmix ? d.capmix->image(d.b.n).total : 0);
+  d.L = image_layout(d.b.n, d.raw_total, d.dom_total, d.key_total, d.cap_words, d.cap_strs, d.cap_bytes, plans);
+}
 // Both shapes.  Capture tables: a cap_off whose last entry is 0 holds no string and is no table (cap_str_off, cap_blob unread).
 int measure_host_batch(HostBatch& d, const char* who) {
   zke_batch& b = d.b;
@@ -307,8 +357,7 @@ int measure_host_batch(HostBatch& d, const char* who) {
     }
   }
   if (!d.cap_words) b.cap_off = nullptr, b.cap_str_off = nullptr, b.cap_blob = nullptr;
-  d.L = image_layout(b.n, d.raw_total, d.dom_total, d.key_total, d.cap_words, d.cap_strs, d.cap_bytes,
-                     (d.mixed ? mixed_image(b.n, d.mixed->shape).total : 0) + (d.capmix ? d.capmix->image(b.n).total : 0));
+  layout_host_batch(d);
   return 0;
 }
 // The packed shape.  Its offsets are in host memory here, so they are checked (three passes over n + 1 words): a negative length
@@ -364,6 +413,7 @@ PendingDelivery pending_delivery(const HostBatch& d, zke_result* out) {
   if (d.body) p.body = d.body->out;
   if (d.cap) { p.caps = d.cap->out; p.org = d.cap->org; }
   if (d.capmix) { p.caps = d.capmix->out; p.org = d.capmix->org; }
+  if (d.enc) p.enc = d.enc->out;
   return p;
 }
 
@@ -385,6 +435,7 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   if (d.scan && (rc = ensure_scan_buffers(e, w.sb, n, d.scan->max_sigs, d.scan->out->sel_blob_cap))) return rc;
   if (d.keyrec && (rc = ensure_keyrec_buffers(e, w.kb, n, (size_t)(d.sel ? d.key_total : d.raw_total), d.sel != nullptr))) return rc;
   if (d.body && (rc = ensure_body_buffers(e, w.bb, n, (size_t)d.raw_total))) return rc;
+  if (d.enc && (rc = ensure_encode_buffers(e, w.eb, n, d.enc->plan.total, 0))) return rc;
   uint8_t* hp = w.h_image.as<uint8_t>();
   if (d.refs) {
     // the CSR arrays are written where they will be read from (prefix sums over the lengths), and every e-mail's three buffers
@@ -439,6 +490,14 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
     stage_copy(cp + CL.cap_cfg, P.cap_cfg.data(), P.cap_cfg.size() * 4);
     stage_copy(cp + CL.cfgs, P.cfgs.data(), P.cfgs.size() * sizeof(CapMixedCfg));
     stage_copy(cp + CL.parts, d.capmix->part.data(), d.capmix->part.size() * sizeof(CapPartDev));
+  }
+  const EncImage EL = d.enc ? d.enc->image() : EncImage{};
+  const size_t enc_at = d.enc ? L.mixed + enc_image_at(d) : 0;
+  if (d.enc) {             // an encoding's jobs and its external-input table, the last of the plan sections
+    const EncodePlan& P = d.enc->plan;
+    stage_copy(hp + enc_at + EL.jobs, P.jobs.data(), P.jobs.size() * sizeof(EncodeJob));
+    if (P.ext_strs) stage_copy(hp + enc_at + EL.ext_str_off, d.enc->ext_str_off, ((size_t)P.ext_strs + 1) * 4);
+    if (P.ext_bytes) stage_copy(hp + enc_at + EL.ext_blob, d.enc->ext_blob, P.ext_bytes);
   }
   hipStream_t s = w.stream;
   SlotUse use(e, w, s);
@@ -495,7 +554,16 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
                                            reinterpret_cast<const CapMixedCfg*>(cp + CL.cfgs), reinterpret_cast<const CapPartDev*>(cp + CL.parts)}};
     if ((rc = run_device_pipeline(e, w, &dv, d.raw_total, key_hint, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap,
                                   d.mixed ? &ml : nullptr, d.capmix ? &cl : nullptr))) return rc;
+    if (d.enc) {           // the encodings of the records just written and their digests, two more launches on the same stream
+      EncodeArgs ea{};
+      ea.records = w.d_results.as<zke_result>();
+      ea.jobs = reinterpret_cast<const EncodeJob*>(dp + enc_at + EL.jobs);
+      ea.ext_str_off = reinterpret_cast<const uint32_t*>(dp + enc_at + EL.ext_str_off); ea.ext_blob = dp + enc_at + EL.ext_blob;
+      ea.match_str_off = dv.cap_str_off; ea.match_blob = dv.cap_blob;
+      if ((rc = launch_encode(e, w.eb, ea, s))) return rc;
+    }
     HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
+    if (d.enc) HIPCHK(e, w.eb.t.fetch(w.eb.L.prefix, s));
     if (d.keyrec) HIPCHK(e, w.kb.t.fetch(w.kb.L.total, s));
   }
   if (rc) return rc;
@@ -681,14 +749,11 @@ int zke_verify_emails_async(zke_engine* e, const zke_email_ref* emails, uint32_t
 
 // `&[EmailWithRegex]` with a RegexInfo per value (include/zkemail_amd.h): the checks and the sizes here, before anything is staged;
 // the plan once the registry can be read (mixed_resolve); its tables in the slot's image (submit_host).
-int zke_verify_emails_mixed_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_mixed* mixed, zke_result* out,
-                                  uint64_t* ticket) {
-  static const char who[] = "zke_verify_emails_mixed";
-  if (!e) return ZKE_E_ARG;
-  if (!mixed || !ticket) return arg_error(who, "null pointer");
+namespace {
+// The request of a mixed batch from the caller's zke_regex_mixed: the checks that need no registry, the configs' part counts, the shape.
+int mixed_request(const char* who, const zke_regex_mixed* mixed, uint32_t n, MixedReq& q) {
   if (mixed->n_configs > ZKE_MIXED_MAX_CONFIGS) return arg_error(who, "more than ZKE_MIXED_MAX_CONFIGS configs");
   if ((mixed->n_configs && !mixed->configs) || (n && !mixed->config_of)) return arg_error(who, "null pointer");
-  MixedReq q;
   q.in = mixed; q.n = n;
   q.counts.resize(mixed->n_configs);
   for (uint32_t c = 0; c < mixed->n_configs; c++) {
@@ -697,6 +762,17 @@ int zke_verify_emails_mixed_async(zke_engine* e, const zke_email_ref* emails, ui
     q.counts[c] = MixedConfigIn{cf.n_header_parts, cf.n_body_parts};
   }
   if (const char* why = mixed_plan_check(mixed->config_of, n, q.counts.data(), mixed->n_configs, q.shape)) return arg_error(who, why);
+  return 0;
+}
+}  // namespace
+
+int zke_verify_emails_mixed_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_regex_mixed* mixed, zke_result* out,
+                                  uint64_t* ticket) {
+  static const char who[] = "zke_verify_emails_mixed";
+  if (!e) return ZKE_E_ARG;
+  if (!mixed || !ticket) return arg_error(who, "null pointer");
+  MixedReq q;
+  if (int r = mixed_request(who, mixed, n, q)) return r;
   HostBatch d;
   if (int r = host_batch(d, who, out, emails, n, nullptr, &q)) return r;
   return submit_host_batch(e, d, out, ticket);
@@ -887,6 +963,120 @@ int zke_extract_bodies_async(zke_engine* e, const zke_email_ref* emails, uint32_
 
 int zke_extract_bodies(zke_engine* e, const zke_email_ref* emails, uint32_t n, uint32_t flags, zke_body_out* out) {
   return submit_and_wait(e, n, [&](uint64_t* t) { return zke_extract_bodies_async(e, emails, n, flags, out, t); });
+}
+
+// ---- the verifier outputs encoded on the device (include/zkemail_amd.h; plan: encode_plan.hip.h, kernel: encode.hip.h)
+namespace {
+// `enc` against a plan's sizes, which are exact: the needs written back, ZKE_E_NOMEM when either buffer is too small
+int check_encoded_out(zke_encoded_out* o, uint32_t n, uint64_t total, const char* who) {
+  o->infos_need = n; o->bytes_need = (size_t)total;
+  if (o->infos_cap < n || o->bytes_cap < total) return nomem_error(who, "a zke_encoded_out buffer is smaller than its *_need");
+  if ((n && !o->infos) || (total && !o->bytes)) return arg_error(who, "null buffer in zke_encoded_out");
+  return 0;
+}
+}  // namespace
+
+// The entry `in` chooses, checked and measured as that entry does it; then the plan over the tables just checked — kinds, places, the
+// exact sizes — and `enc` against it: all of it before anything is staged.
+int zke_verify_emails_encoded_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_encode_in* in, zke_result* out,
+                                    zke_encoded_out* enc, uint64_t* ticket) {
+  static const char who[] = "zke_verify_emails_encoded";
+  if (!e) return ZKE_E_ARG;
+  if (!ticket || !enc) return arg_error(who, "null pointer");
+  const zke_encode_in none{};
+  if (!in) in = &none;
+  if (const char* why = encode_lists_check(in->lists, in->mixed)) return arg_error(who, why);
+  MixedReq mq;
+  if (in->mixed) if (int r = mixed_request(who, in->mixed, n, mq)) return r;
+  HostBatch d;
+  if (int r = host_batch(d, who, out, emails, n, in->lists, in->mixed ? &mq : nullptr)) return r;
+  std::vector<uint32_t> kinds(n, in->lists ? ENC_KIND_WITH_REGEX : ENC_KIND_EMAIL), row_off;
+  EncodeTables t;
+  t.ext_off = in->ext_off; t.ext_str_off = in->ext_str_off; t.ext_blob = in->ext_blob;
+  t.match_off = d.b.cap_off; t.match_str_off = d.b.cap_str_off; t.match_blob = d.b.cap_blob;      // (null where no string is named: measure_host_batch)
+  if (in->lists) t.row_stride = in->lists->n_header_parts + in->lists->n_body_parts;
+  if (in->mixed) {         // a mixed batch's rows are its jobs: job_off, the prefix sum of the configs' part counts
+    row_off.resize((size_t)n + 1);
+    uint32_t j = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t c = in->mixed->config_of[i];
+      row_off[i] = j;
+      if (c == ZKE_CONFIG_NONE) continue;
+      kinds[i] = ENC_KIND_WITH_REGEX;
+      j += mq.counts[c].n_header_parts + mq.counts[c].n_body_parts;
+    }
+    row_off[n] = j;
+    t.row_off = row_off.data();
+  }
+  EncodeReq q;
+  q.out = enc; q.ext_str_off = in->ext_str_off; q.ext_blob = in->ext_blob;
+  if (const char* why = encode_plan_build(n, kinds.data(), t, q.plan)) return arg_error(who, why);
+  if (int r = check_encoded_out(enc, n, q.plan.total, who)) return r;
+  d.enc = &q;
+  layout_host_batch(d);
+  return submit_host_batch(e, d, out, ticket);
+}
+
+int zke_verify_emails_encoded(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_encode_in* in, zke_result* out,
+                              zke_encoded_out* enc) {
+  return submit_and_wait(e, n, [&](uint64_t* t) { return zke_verify_emails_encoded_async(e, emails, n, in, out, enc, t); });
+}
+
+// The two launches alone over the caller's records and tables (host pointers), beside zke_sha256_batch: one staged input
+// {records | jobs | the two tables}, the slot's encoding buffer — the one the entry above uses —, one copy back.  Synchronous.
+int zke_encode_outputs(zke_engine* e, const zke_result* records, uint32_t n, const uint32_t* kinds, const uint32_t* ext_off,
+                       const uint32_t* ext_str_off, const uint8_t* ext_blob, const uint32_t* match_off, const uint32_t* match_str_off,
+                       const uint8_t* match_blob, zke_encoded_out* enc) {
+  static const char who[] = "zke_encode_outputs";
+  if (!e) return ZKE_E_ARG;
+  if (!enc || (n && (!records || !kinds))) return arg_error(who, "null pointer");
+  EncodeTables t;
+  t.ext_off = ext_off; t.ext_str_off = ext_str_off; t.ext_blob = ext_blob;
+  t.match_off = match_off; t.match_str_off = match_str_off; t.match_blob = match_blob;
+  EncodePlan P;
+  if (const char* why = encode_plan_build(n, kinds, t, P)) return arg_error(who, why);
+  if (int r = check_encoded_out(enc, n, P.total, who)) return r;
+  if (n == 0) return 0;
+  size_t o = 0;
+  auto put = [&](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 64); return at; };
+  const size_t at_rec = put((size_t)n * sizeof(zke_result)), at_jobs = put((size_t)n * sizeof(EncodeJob));
+  const size_t at_eso = put(P.ext_strs ? ((size_t)P.ext_strs + 1) * 4 : 0), at_eb = put(P.ext_bytes);
+  const size_t at_mso = put(P.match_strs ? ((size_t)P.match_strs + 1) * 4 : 0), at_mb = put(P.match_bytes);
+  std::vector<uint8_t> img(o);
+  memcpy(img.data() + at_rec, records, (size_t)n * sizeof(zke_result));
+  memcpy(img.data() + at_jobs, P.jobs.data(), (size_t)n * sizeof(EncodeJob));
+  if (P.ext_strs) memcpy(img.data() + at_eso, ext_str_off, ((size_t)P.ext_strs + 1) * 4);
+  if (P.ext_bytes) memcpy(img.data() + at_eb, ext_blob, P.ext_bytes);
+  if (P.match_strs) memcpy(img.data() + at_mso, match_str_off, ((size_t)P.match_strs + 1) * 4);
+  if (P.match_bytes) memcpy(img.data() + at_mb, match_blob, P.match_bytes);
+  std::shared_lock<std::shared_mutex> sh(e->big);
+  HIPCHK(e, hipSetDevice(e->device));
+  uint32_t slot;
+  Slot& w = next_slot(e, slot);
+  std::lock_guard<std::mutex> g(w.mu);
+  int r = 0;
+  if ((r = retire_host(e, w))) return r;             // the buffer's pinned twin may hold encodings nobody has waited for yet
+  if ((r = ensure_encode_buffers(e, w.eb, n, P.total, img.size()))) return r;
+  hipStream_t s = w.stream;
+  SlotUse use(e, w, s);
+  if ((r = use.acquire())) return r;
+  auto enqueue = [&]() -> int {
+    HIPCHK(e, hipMemcpyAsync(w.eb.in.p, img.data(), img.size(), hipMemcpyHostToDevice, s));
+    const uint8_t* ip = w.eb.in.as<uint8_t>();
+    EncodeArgs ea{};
+    ea.records = reinterpret_cast<const zke_result*>(ip + at_rec);
+    ea.jobs = reinterpret_cast<const EncodeJob*>(ip + at_jobs);
+    ea.ext_str_off = reinterpret_cast<const uint32_t*>(ip + at_eso); ea.ext_blob = ip + at_eb;
+    ea.match_str_off = reinterpret_cast<const uint32_t*>(ip + at_mso); ea.match_blob = ip + at_mb;
+    if (int lr = launch_encode(e, w.eb, ea, s)) return lr;
+    HIPCHK(e, w.eb.t.fetch(w.eb.L.prefix, s));
+    return use.release();
+  };
+  r = enqueue();
+  const hipError_t hs = hipStreamSynchronize(s);      // also behind a failed enqueue: no copy outlives `img`
+  if (r) return r;
+  if (hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "zke_encode_outputs: sync", hs);
+  return deliver_encoded(e, w.eb, enc);
 }
 
 namespace {

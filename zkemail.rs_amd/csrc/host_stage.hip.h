@@ -379,6 +379,38 @@ struct OriginBufs {
 };
 template <class F> void each_buffer(OriginBufs& b, F& f) { each_buffer(b.t, f); }
 
+// The buffers of one output encoding (a slot's; zke_verify_emails_encoded, zke_encode_outputs; kernel: encode.hip.h): {infos |
+// encodings} in one device buffer with a pinned twin — that prefix comes back as ONE copy — and behind it, on the device alone, the
+// digest launch's job list.  `blob`: the planned bytes of the encodings (encode_plan.hip.h), exact.  `in`: the building block's
+// staged records and tables (the verify entry's ride in the batch's input image: EncImage).
+struct EncLayout { size_t bytes, prefix, sha, total; uint64_t blob; uint32_t n; };
+inline EncLayout enc_layout(uint32_t n, uint64_t blob) {
+  EncLayout L{};
+  L.n = n; L.blob = blob;
+  L.bytes = align_up((size_t)n * sizeof(zke_encoded_info), 64);
+  L.prefix = L.bytes + (size_t)blob;
+  L.sha = align_up(L.prefix, 64);
+  L.total = L.sha + (size_t)n * sizeof(ShaJob);
+  return L;
+}
+struct EncBufs {
+  TwinBuf t;
+  DevBuf in;
+  EncLayout L{};
+};
+template <class F> void each_buffer(EncBufs& b, F& f) { each_buffer(b.t, f); f(b.in); }
+// What the encode launch reads besides the records and the capture tables, as one section of a batch's input image: the jobs and the
+// external-input table (offsets into the section; the blob 64-byte aligned like the image's others).
+struct EncImage { size_t jobs, ext_str_off, ext_blob, total; };
+inline EncImage enc_image(uint32_t n, uint32_t ext_strs, uint32_t ext_bytes) {
+  EncImage L{};
+  L.jobs = 0;
+  L.ext_str_off = align_up((size_t)n * sizeof(EncodeJob), 64);
+  L.ext_blob = align_up(L.ext_str_off + (ext_strs ? (size_t)ext_strs + 1 : 0) * 4, 64);
+  L.total = align_up(L.ext_blob + ext_bytes, 64);
+  return L;
+}
+
 // The buffers of zke_qp_clean_batch (a slot's): the bodies and their offsets, cleaned bytes, index map, kept lengths.
 struct QpBufs { DevBuf in, off, clean, map, len; };
 template <class F> void each_buffer(QpBufs& b, F& f) { for (DevBuf* x : {&b.in, &b.off, &b.clean, &b.map, &b.len}) f(*x); }
@@ -397,6 +429,7 @@ struct PendingDelivery {
   zke_body_out* body = nullptr;
   zke_capture_out* caps = nullptr;
   zke_capture_origin* org = nullptr;   // (with caps only: a mapped extraction)
+  zke_encoded_out* enc = nullptr;      // (beside the records: zke_verify_emails_encoded)
 };
 
 }  // namespace

@@ -209,6 +209,18 @@ int launch_keyrec_prefix(zke_engine* e, KeyrecBufs& b, zke_batch& in, uint32_t m
   return 0;
 }
 
+// ---- the output encoding behind a batch's records (zke_verify_emails_encoded, zke_encode_outputs; kernel: encode.hip.h): the encode
+// launch over records, jobs and tables (`a`: device pointers; the outputs are filled in here from the slot's buffer), then the SHA-256
+// of the encodings — the engine's hash launch over the job list the kernel left, the call sha256_batch_device_locked makes.
+int launch_encode(zke_engine* e, EncBufs& b, EncodeArgs a, hipStream_t s) {
+  uint8_t* eo = b.t.d.as<uint8_t>();
+  a.n = b.L.n;
+  a.infos = reinterpret_cast<zke_encoded_info*>(eo); a.bytes = eo + b.L.bytes; a.sha = reinterpret_cast<ShaJob*>(eo + b.L.sha);
+  hipLaunchKernelGGL(encode_outputs_kernel, dim3(a.n), dim3(64), 0, s, a);
+  HIPCHK(e, hipGetLastError());
+  return launch_sha(e, plan_sha(e->stage, a.n), a.sha, a.n, s);
+}
+
 // ---- the regex stage of a mixed batch (zke_verify_emails_mixed; kernels: regex_mixed.hip.h, plan: mixed_plan.hip.h)
 // The plan of the batch and where its tables lie in the slot's staged image (device pointers).
 struct MixedLaunch {

@@ -181,6 +181,14 @@ def load_library(path: Optional[str] = None):
     lib.zke_extract_bodies.restype = C.c_int
     lib.zke_extract_bodies_async.argtypes = [vp, erp, C.c_uint32, C.c_uint32, bop, C.POINTER(C.c_uint64)]
     lib.zke_extract_bodies_async.restype = C.c_int
+    if hasattr(lib, "zke_verify_emails_encoded"):   # (a ZKE_LIB build of an older tree, for an A/B run, has none of the three)
+        eip, eop = C.POINTER(A.zke_encode_in), C.POINTER(A.zke_encoded_out)
+        lib.zke_verify_emails_encoded.argtypes = [vp, erp, C.c_uint32, eip, vp, eop]
+        lib.zke_verify_emails_encoded.restype = C.c_int
+        lib.zke_verify_emails_encoded_async.argtypes = [vp, erp, C.c_uint32, eip, vp, eop, C.POINTER(C.c_uint64)]
+        lib.zke_verify_emails_encoded_async.restype = C.c_int
+        lib.zke_encode_outputs.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, eop]
+        lib.zke_encode_outputs.restype = C.c_int
     if hasattr(lib, "zke_engine_sha_ring"):         # (a ZKE_LIB build of an older tree, for an A/B run, has no such entry)
         lib.zke_engine_sha_ring.argtypes = [vp]
         lib.zke_engine_sha_ring.restype = C.c_int
@@ -216,6 +224,7 @@ EXPORTED_SYMBOLS = [
     "zke_qp_clean_batch", "zke_extract_captures_mapped", "zke_extract_captures_mapped_async",
     "zke_extract_bodies", "zke_extract_bodies_async",
     "zke_extract_captures_mixed", "zke_extract_captures_mixed_async",
+    "zke_verify_emails_encoded", "zke_verify_emails_encoded_async", "zke_encode_outputs",
 ]
 
 
@@ -334,6 +343,50 @@ class _BodyBuffers:
         blob = self.bytes.tobytes()
         return [BodyInfo(int(f["status"]), int(f["detail"]), int(f["part"]), int(f["encoding"]), int(f["src_off"]), int(f["src_len"]),
                          blob[int(f["body_off"]):int(f["body_off"]) + int(f["body_len"])]) for f in self.infos[:self.n]]
+
+
+class _EncodedCall:
+    """Everything one zke_verify_emails_encoded call points to, kept alive until the batch has been waited for: the e-mails, the
+    list form (`lists` / `mixed` of a zke_encode_in, or neither), the external-input table, the record array and the encoding buffers."""
+
+    def __init__(self, eng: "Engine", inputs: Sequence, form: Optional[str], bytes_cap: Optional[int], infos_cap: Optional[int]):
+        inputs = list(inputs)
+        emails = [i if isinstance(i, Email) else i.email for i in inputs]
+        if form is None:
+            form = "plain" if all(isinstance(i, Email) for i in inputs) else "mixed" if any(isinstance(i, Email) for i in inputs) else "lists"
+        self.form = form
+        self.refs = A.EmailRefs(emails)
+        n = self.refs.n
+        self.ext = A.StringTable([A.flat_external_inputs(e.external_inputs) for e in emails])
+        c = self.c = A.zke_encode_in()
+        c.ext_off, c.ext_str_off, c.ext_blob = self.ext.off.ctypes.data, self.ext.str_off.ctypes.data, self.ext.blob.ctypes.data
+        matches: List[Optional[List[str]]] = [None] * n
+        if form == "lists":
+            p = self._packed = eng.pack_with_regex(inputs)
+            l = self._lists = A.zke_regex_lists()
+            l.n_header_parts, l.n_body_parts = p.nh, p.nb
+            l.header_part_ids, l.body_part_ids = p.hdr_ids.ctypes.data, p.body_ids.ctypes.data
+            if p.has_caps:
+                l.cap_off, l.cap_str_off, l.cap_blob = p.cap_off.ctypes.data, p.cap_str_off.ctypes.data, p.cap_blob.ctypes.data
+            c.lists = C.pointer(l)
+            matches = [regex_matches_of(i) for i in inputs]
+        elif form == "mixed":
+            self._mixed = eng.pack_mixed(inputs)
+            c.mixed = C.pointer(self._mixed.c)
+            matches = [None if isinstance(i, Email) else regex_matches_of(i) for i in inputs]
+        elif form != "plain":
+            raise ValueError("form must be 'plain', 'lists', 'mixed' or None")
+        u8 = lambda xs: [len(s.encode("utf-8")) for s in xs]
+        self.planned = [A.encoded_len(A.ENC_KIND_EMAIL if m is None else A.ENC_KIND_WITH_REGEX,
+                                      u8(A.flat_external_inputs(e.external_inputs)), u8(m or [])) for e, m in zip(emails, matches)]
+        self.out = np.zeros(max(n, 1), dtype=A.RESULT_DTYPE)
+        self.enc = A.EncodedBuffers(n, sum(self.planned) if bytes_cap is None else bytes_cap)
+        if infos_cap is not None:
+            self.enc.c.infos_cap = infos_cap
+
+    @property
+    def records(self) -> np.ndarray:
+        return self.out[:self.refs.n]
 
 
 class Engine:
@@ -957,6 +1010,52 @@ class Engine:
         self._check(self.lib.zke_verify_emails_mixed_async(self.h, refs.arr, refs.n, C.byref(lists.c), out.ctypes.data, C.byref(t)),
                     "zke_verify_emails_mixed_async")
         return t.value, out[:refs.n]
+
+    # ---- the verifier outputs encoded on the device (core/src/io.rs:28-44): ABI bytes and their SHA-256 per e-mail
+    def _encoded_call(self, inputs: Sequence, form: Optional[str], bytes_cap: Optional[int], infos_cap: Optional[int]) -> "_EncodedCall":
+        return _EncodedCall(self, inputs, form, bytes_cap, infos_cap)
+
+    def verify_emails_encoded(self, inputs: Sequence, *, form: Optional[str] = None, bytes_cap: Optional[int] = None,
+                              infos_cap: Optional[int] = None):
+        """zke_verify_emails_encoded over ``Email`` / ``EmailWithRegex`` values: (records, encoded) with ``encoded[i]`` =
+        (encoding, digest) — VerificationOutput::from_parts(..).abi_encode() and its SHA-256 — or (b"", 32 zero bytes) for an e-mail
+        whose record is not ZKE_OK.  `form`: "plain" (every input an Email: zke_verify_emails' pipeline), "lists" (EmailWithRegex
+        values that share one part list) or "mixed" (any of both, a RegexInfo per value); None picks the first that fits.
+        `bytes_cap` / `infos_cap`: the buffers' sizes (default: exact); too small raises EngineError(ZKE_E_NOMEM)."""
+        c = self._encoded_call(inputs, form, bytes_cap, infos_cap)
+        self._check(self.lib.zke_verify_emails_encoded(self.h, c.refs.arr, c.refs.n, C.byref(c.c), c.out.ctypes.data, C.byref(c.enc.c)),
+                    "zke_verify_emails_encoded")
+        return c.records, c.enc.result()
+
+    def verify_emails_encoded_async(self, inputs: Sequence, *, form: Optional[str] = None, bytes_cap: Optional[int] = None,
+                                    infos_cap: Optional[int] = None):
+        """zke_verify_emails_encoded_async: (ticket, pending); ``pending.records`` and ``pending.enc.result()`` are valid once
+        ``wait(ticket)`` has returned.  `pending` keeps the output arrays (and the input tables) alive: hold on to it until then."""
+        c = self._encoded_call(inputs, form, bytes_cap, infos_cap)
+        t = C.c_uint64()
+        self._check(self.lib.zke_verify_emails_encoded_async(self.h, c.refs.arr, c.refs.n, C.byref(c.c), c.out.ctypes.data, C.byref(c.enc.c),
+                                                             C.byref(t)), "zke_verify_emails_encoded_async")
+        return t.value, c
+
+    def encode_outputs(self, outputs: Sequence, statuses: Optional[Sequence[int]] = None, *, bytes_cap: Optional[int] = None,
+                       guard: int = 0, fill: int = 0) -> "A.EncodedBuffers":
+        """zke_encode_outputs over EmailVerifierOutput / EmailWithRegexVerifierOutput values (or a prepared ``_abi.EncodeTables``): the
+        encode and digest launches alone.  `statuses`: the records' statuses (default ZKE_OK: everything is encoded).  Returns the
+        buffers; ``.result()`` is the (encoding, digest) list.  `guard` / `fill`: bytes behind bytes_cap and the buffer's initial
+        value, for tests that watch what is written."""
+        tb = outputs if isinstance(outputs, A.EncodeTables) else A.EncodeTables(outputs, statuses)
+        need = A.zke_encoded_out()
+        rc = self.lib.zke_encode_outputs(self.h, tb.records.ctypes.data, tb.n, tb.kinds.ctypes.data, tb.ext.off.ctypes.data,
+                                         tb.ext.str_off.ctypes.data, tb.ext.blob.ctypes.data, tb.matches.off.ctypes.data,
+                                         tb.matches.str_off.ctypes.data, tb.matches.blob.ctypes.data, C.byref(need))
+        if rc not in (0, -3):
+            self._check(rc, "zke_encode_outputs")
+        enc = A.EncodedBuffers(tb.n, int(need.bytes_need) if bytes_cap is None else bytes_cap, guard, fill)
+        self._check(self.lib.zke_encode_outputs(self.h, tb.records.ctypes.data, tb.n, tb.kinds.ctypes.data, tb.ext.off.ctypes.data,
+                                                tb.ext.str_off.ctypes.data, tb.ext.blob.ctypes.data, tb.matches.off.ctypes.data,
+                                                tb.matches.str_off.ctypes.data, tb.matches.blob.ctypes.data, C.byref(enc.c)),
+                    "zke_encode_outputs")
+        return enc
 
     def verify_emails_async(self, refs: "A.EmailRefs"):
         """zke_verify_emails_async: (ticket, records); the records are valid once ``wait(ticket)`` has returned."""
