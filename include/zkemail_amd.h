@@ -375,7 +375,8 @@ int zke_dfa_unregister(zke_engine* e, uint32_t id);
  *   zke_verify_batch_async  returns as soon as everything is enqueued; `in` has been read completely (the caller may reuse
  *                           its buffers), `out` must stay valid until zke_batch_wait(e, *ticket) has returned.  With S slots
  *                           reserved, S batches are in flight; a slot whose previous batch was never waited for completes it
- *                           (its records are delivered) before it is reused.
+ *                           (its records are delivered) before it is reused, and at the latest when S further batches have
+ *                           been submitted (slots on a fuller hardware queue come round later than that: zke_engine_slot_queue).
  *   zke_batch_wait          blocks until that batch's records are in `out`.  Waiting twice, or for a ticket a later batch of
  *                           the same slot has already retired, returns 0 at once.
  *   zke_verify_batch        = async + wait; `dbg` != NULL additionally copies the parity intermediates back (tests). */
@@ -815,7 +816,8 @@ int zke_verify_emails_encoded_async(zke_engine* e, const zke_email_ref* emails, 
 
 /* Device-resident batch: every pointer in `in` and `out_dev` is device memory (the part-id lists stay host arrays);
  * `raw_total`, `domain_total`, `key_total` are the blob sizes (the CSR tails), which the
- * host needs for workspace sizing without a device read.  Takes the engine's next submission slot (round-robin),
+ * host needs for workspace sizing without a device read.  Takes the engine's next submission slot (round-robin over the
+ * hardware queues the slot streams share, then over a queue's slots: zke_engine_slot_queue; plain round-robin while that map is unknown),
  * enqueues on `stream` (a hipStream_t; NULL = that slot's own stream) and returns without synchronising: with S slots
  * reserved, S consecutive calls run concurrently.  A slot is reused only behind its previous batch (stream order, or an
  * event wait when the caller's stream changed).  zke_engine_sync waits for every slot. */
@@ -845,6 +847,16 @@ int zke_engine_sha_twin(zke_engine* e);
  * GPU_MAX_HW_QUEUES as read at creation) <= 4 — for batches of at most 1 024 e-mails, or forced by ZKE_FRONT_HELPER = 0 / 1 in the
  * environment at zke_engine_create.  Negative: an error code. */
 int zke_engine_front_helper(zke_engine* e, uint32_t n);
+/* Which slots share a hardware queue, as zke_engine_reserve read it from the device (HIP places the slot streams on GPU_MAX_HW_QUEUES
+ * queues, and a queue runs its kernels one after the other).  zke_engine_queue_count: the number of groups, 0 while the map is unknown
+ * (before the first zke_engine_reserve, or when every slot has a queue to itself); negative: an error code.  zke_engine_slot_queue: the
+ * group of `slot`, numbered in order of the groups' lowest slot index, or -1 if unknown.  Submission ticket t (counted from the engine's
+ * creation, every entry point) goes to group t % count and takes that group's slots in turn, in ascending slot index: every queue gets
+ * the same share of the batches however many slots sit on it.  With the map unknown ticket t goes to slot t % slots.
+ * zke_engine_last_slot: the slot the most recent submission took (the one zke_get_timings reads); negative: an error code. */
+int zke_engine_queue_count(zke_engine* e);
+int zke_engine_slot_queue(zke_engine* e, uint32_t slot);
+int zke_engine_last_slot(zke_engine* e);
 /* Enable per-launch HIP-event timing (adds event records between the launches). */
 int zke_set_timing(zke_engine* e, int enabled);
 

@@ -20,8 +20,41 @@ def short(name: str) -> str:
     return name[:40]
 
 
+def check_map(d: str, probe_log: str):
+    """queue_trace.py DIR --map PROBE_LOG: the hardware queue each slot's kernels ran on, from the trace, against the group the engine
+    reported for the slot (the `queue_probe slot K group G HW_ID by XCC: ...` lines a -DZKE_DEV_KNOBS build prints under
+    ZKE_DEBUG_QUEUE_PROBE=1).  zke_engine_reserve launches one slot_queue_probe_kernel per slot, in slot order: the k-th of them by
+    dispatch id is slot k's, and its Queue_Id is the slot stream's queue."""
+    rows = []
+    for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
+        with open(f, newline="") as fh:
+            for r in csv.DictReader(fh):
+                if "slot_queue_probe_kernel" in r["Kernel_Name"]:
+                    rows.append((int(r.get("Dispatch_Id") or r["Start_Timestamp"]), r["Queue_Id"]))
+    rows.sort()
+    groups, words = {}, {}
+    for line in open(probe_log):
+        if line.startswith("queue_probe slot"):
+            p = line.split()
+            groups[int(p[2])], words[int(p[2])] = int(p[4]), p[8:]
+    S = len(groups)
+    if not S or len(rows) < S:
+        raise SystemExit(f"{S} slots in the probe log, {len(rows)} probe launches in the trace")
+    traced = [q for _, q in rows[-S:]]          # the last reserve's
+    print("slot  trace_queue  engine_group  HW_ID by XCC 0..7")
+    for s in range(S):
+        print(f"{s:4d}  {traced[s]:>11}  {groups[s]:12d}  {' '.join(words[s])}")
+    same_t = [[traced[a] == traced[b] for b in range(S)] for a in range(S)]
+    same_e = [[groups[a] == groups[b] and groups[a] >= 0 for b in range(S)] for a in range(S)]
+    ok = same_t == same_e
+    print(f"trace queues {len(set(traced))}, engine groups {len(set(groups.values()))}: the partitions are {'IDENTICAL' if ok else 'DIFFERENT'}")
+    sys.exit(0 if ok else 1)
+
+
 def main():
     d = sys.argv[1]
+    if len(sys.argv) > 3 and sys.argv[2] == "--map":
+        return check_map(d, sys.argv[3])
     files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
     if not files:
         raise SystemExit(f"no *kernel_trace.csv under {d}")

@@ -70,6 +70,7 @@ constexpr int SHA_TILE = 128;                      // bytes of a message per LDS
 
 #include "dfa_registry.hip.h"
 #include "host_stage.hip.h"
+#include "slot_order.hip.h"
 
 // Timing marks of one batch (HIP events on the stream it ran on; zke_set_timing).
 enum : int { MK_START = 0, MK_H2D, MK_FRONT, MK_HASH, MK_VERDICT, MK_PREP, MK_DFA, MK_D2H, MK_N };
@@ -106,7 +107,8 @@ struct Slot {
 #undef X
   }
   uint32_t* wave_feedback = nullptr;   // pinned host word the verdict launch leaves the job list's length in: the slot's next batch sizes the
-                                       // one-signature-per-wave role of its hash / modexp launch by it (0xFFFFFFFF: nothing known yet)
+                                       // one-signature-per-wave role of its hash / modexp launch by it (0xFFFFFFFF: nothing known yet).
+                                       // Words 8 .. 15 of the same 64-byte block: what slot_queue_probe_kernel read on XCC 0 .. 7
   // host entry: the batch not yet delivered
   hipEvent_t host_done = nullptr;      // recorded behind the D2H of the records
   hipEvent_t h2d_done = nullptr;       // recorded behind the slot's input image on the engine's copy stream
@@ -129,7 +131,9 @@ struct zke_engine {
   // then `reg_mu` (the registry) or `misc_mu` (the building blocks' scratch).
   std::shared_mutex big;
   std::vector<Slot*> slots;         // at least one; grows only under `big` exclusive
-  std::atomic<uint32_t> ticket{0};  // round-robin cursor of the submission entry points
+  std::atomic<uint64_t> ticket{0};  // cursor of the submission entry points (next_slot); 64 bits: it never wraps
+  SlotOrder order;                  // ticket -> slot: round-robin over the hardware queues the slot streams share (slot_order.hip.h);
+                                    // rebuilt by zke_engine_reserve under `big` exclusive, read under `big` shared
   std::atomic<uint32_t> last_slot{0};
   std::atomic<bool> timing{false};
   std::atomic<size_t> host_image_cap{0};   // every slot's pinned staging holds an input image of this many bytes ...
@@ -407,6 +411,7 @@ int zke_engine_create(const zke_options* opt, zke_engine** out) {
     e->slots.push_back(w);
   }
   e->stream = e->slots[0]->stream;
+  slot_order_unknown(e->order, (uint32_t)e->slots.size());      // no stream has a hardware queue yet: zke_engine_reserve reads the map
   if (!o.disable_key_cache) {
     const size_t kc_bytes = (size_t)KEY_CACHE_SLOTS * sizeof(KeyCacheEntry);
     // (cleared on slot 0's stream and waited for: a hipMemset on device memory is not waited for, nor ordered in front of the slots' streams)
@@ -470,6 +475,20 @@ int zke_engine_front_helper(zke_engine* e, uint32_t n) {
   std::shared_lock<std::shared_mutex> sh(e->big);
   return ZKE_PARSE_HELPER && front_takes_helper(e->stage, n) ? 1 : 0;
 }
+
+int zke_engine_queue_count(zke_engine* e) {
+  if (!e) return ZKE_E_ARG;
+  std::shared_lock<std::shared_mutex> sh(e->big);
+  return (int)e->order.n_queues;
+}
+
+int zke_engine_slot_queue(zke_engine* e, uint32_t slot) {
+  if (!e) return -1;
+  std::shared_lock<std::shared_mutex> sh(e->big);
+  return slot < e->order.slots && e->order.n_queues ? (int)e->order.queue_of[slot] : -1;
+}
+
+int zke_engine_last_slot(zke_engine* e) { return e ? (int)e->last_slot.load(std::memory_order_relaxed) : ZKE_E_ARG; }
 
 const char* zke_last_error(const zke_engine* e) { (void)e; return g_err.c_str(); }
 

@@ -653,7 +653,16 @@ int submit_host_batch(zke_engine* e, const HostBatch& d, zke_result* out, uint64
   if (d.capmix && n) capmix_resolve(e, *d.capmix);   // likewise the part table of a mixed extraction
   if (d.mixed && n) if (int r = mixed_resolve(e, *d.mixed)) return r;      // likewise the DFA pairs' tables a mixed batch's segments point to
   uint32_t slot;
-  Slot& w = next_slot(e, slot);
+  uint64_t t;
+  Slot& w = next_slot(e, slot, &t);
+  // A batch nobody waited for is delivered once as many batches as the engine has slots have been submitted behind it.  While tickets went
+  // round the slots that was the slot's own turn; ordered by queue, a slot on a fuller queue comes round later than that, so the batch of
+  // ticket t - slots is delivered here — the wait every submission has always made.  (Before this slot's lock is taken, never under it.)
+  const uint64_t S = e->slots.size();
+  if (e->order.n_queues && t >= S) {
+    const uint32_t due = slot_for_ticket(e->order, t - S);
+    if (due != slot) { Slot& o = *e->slots[due]; std::lock_guard<std::mutex> go(o.mu); if (int r = retire_host(e, o)) return r; }
+  }
   std::lock_guard<std::mutex> g(w.mu);
   if (!n) { *ticket = make_ticket(slot, w.host_retired); return 0; }      // nothing to wait for
   if (int r = submit_host(e, w, d, out, dbg && dbg->em, dbg && dbg->clean_body)) return r;

@@ -536,9 +536,59 @@ struct SlotUse {
   ~SlotUse() { if (armed) { const std::string keep = g_err; (void)release_slot(e, w, s); g_err = keep; } }      // the first error is the one reported
 };
 
-// The slot's next submission ticket (round-robin over the slots that exist: zke_engine_reserve only appends).
-Slot& next_slot(zke_engine* e, uint32_t& index) {
-  index = e->ticket.fetch_add(1, std::memory_order_relaxed) % (uint32_t)e->slots.size();
+// Which hardware queue a slot's stream sits on, read where it is visible: on the device.  HW_ID of a wave names the queue descriptor its
+// dispatch packet came through — ME_ID [31:30], PIPE_ID [7:6], QUEUE_ID [26:24] — and a stream's packets all come through the descriptors of
+// its one hardware queue, one per XCD.  A launch of SLOT_PROBE_GROUPS workgroups puts one on every XCD; each leaves its HW_ID in the word of
+// its XCC (words 8 .. 15 of the slot's pinned block), and the host takes XCC 0's.  The other fields of the word say where the wave ran.
+constexpr uint32_t SLOT_PROBE_GROUPS = 64;
+constexpr uint32_t SLOT_PROBE_WORD0 = 8;               // first of the eight words, in uint32_t of Slot::wave_feedback
+constexpr uint32_t SLOT_PROBE_UNWRITTEN = 0xFFFFFFFFu; // no HW_ID reads all ones: ME_ID 3 does not exist
+constexpr uint32_t SLOT_PROBE_QUEUE_MASK = (3u << 30) | (7u << 24) | (3u << 6);
+__global__ void slot_queue_probe_kernel(uint32_t* block) {
+  if (threadIdx.x != 0) return;
+  const uint32_t hw_id = __builtin_amdgcn_s_getreg(4 | (31 << 11));
+  const uint32_t xcc = __builtin_amdgcn_s_getreg(20 | (31 << 11)) & 7u;          // XCC_ID [3:0]; eight words: the index stays inside the block
+  __hip_atomic_store(block + SLOT_PROBE_WORD0 + xcc, hw_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Rebuild the engine's ticket order from the hardware queues its slot streams sit on (under `big` exclusive, every slot stream idle and
+// its hardware queue in being: no queue is created while the probes run).  A map that does not come out — a word not written, more
+// queues than the pool has, a queue per slot — leaves the order at plain round-robin (slot_order_build).
+int probe_slot_queues(zke_engine* e) {
+  const uint32_t S = (uint32_t)e->slots.size();
+  slot_order_unknown(e->order, S);
+  for (Slot* w : e->slots) {
+    for (uint32_t k = 0; k < 8; k++) w->wave_feedback[SLOT_PROBE_WORD0 + k] = SLOT_PROBE_UNWRITTEN;
+    hipLaunchKernelGGL(slot_queue_probe_kernel, dim3(SLOT_PROBE_GROUPS), dim3(64), 0, w->stream, w->wave_feedback);
+  }
+  HIPCHK(e, hipGetLastError());
+  for (Slot* w : e->slots) HIPCHK(e, hipStreamSynchronize(w->stream));
+  uint32_t id[SLOT_ORDER_MAX_SLOTS];
+  uint8_t known[SLOT_ORDER_MAX_SLOTS];
+  for (uint32_t s = 0; s < S; s++) {
+    const uint32_t word = __atomic_load_n(e->slots[s]->wave_feedback + SLOT_PROBE_WORD0, __ATOMIC_RELAXED);
+    known[s] = word != SLOT_PROBE_UNWRITTEN;
+    id[s] = word & SLOT_PROBE_QUEUE_MASK;
+  }
+  (void)slot_order_build(e->order, id, known, S, e->stage.hw_queues);
+#ifdef ZKE_DEV_KNOBS
+  if (getenv("ZKE_DEBUG_QUEUE_PROBE")) {          // the raw words, for profiles/queue_balance_queues.txt
+    for (uint32_t s = 0; s < S; s++) {
+      fprintf(stderr, "queue_probe slot %2u group %2d HW_ID by XCC:", s, e->order.n_queues ? (int)e->order.queue_of[s] : -1);
+      for (uint32_t k = 0; k < 8; k++) fprintf(stderr, " %08x", e->slots[s]->wave_feedback[SLOT_PROBE_WORD0 + k]);
+      fprintf(stderr, "\n");
+    }
+  }
+#endif
+  return 0;
+}
+
+// The slot's next submission ticket: round-robin over the hardware queues the slot streams share and over a queue's slots within it, or,
+// with the map unknown, over the slots that exist (slot_order.hip.h; zke_engine_reserve only appends).
+Slot& next_slot(zke_engine* e, uint32_t& index, uint64_t* ticket_no = nullptr) {
+  const uint64_t t = e->ticket.fetch_add(1, std::memory_order_relaxed);
+  if (ticket_no) *ticket_no = t;
+  index = slot_for_ticket(e->order, t);
   e->last_slot.store(index, std::memory_order_relaxed);
   return *e->slots[index];
 }
@@ -564,6 +614,7 @@ int zke_engine_reserve(zke_engine* e, uint32_t max_n, uint64_t max_raw_total, ui
     e->slots.push_back(w);
     e->stage.slots = (uint32_t)e->slots.size();
   }
+  if (e->order.slots != e->slots.size()) slot_order_unknown(e->order, (uint32_t)e->slots.size());      // until the probe below has run
   if (max_n)
     for (Slot* w : e->slots)
       if (int r = ensure_workspace(e, *w, max_n, max_raw_total, max_regex_parts != 0, max_regex_parts, false, w->stream)) return r;
@@ -600,6 +651,7 @@ int zke_engine_reserve(zke_engine* e, uint32_t max_n, uint64_t max_raw_total, ui
   e->timing = timing;
   HIPCHK(e, hipGetLastError());
   for (Slot* w : e->slots) HIPCHK(e, hipStreamSynchronize(w->stream));
+  if (int r = probe_slot_queues(e)) return r;          // every slot stream has its hardware queue now: which of them share one
   if (e->host_image_cap.load())          // slots created just now get the staging the others have (everything is drained: see grow_host_staging)
     for (Slot* w : e->slots)
       if (int r = ensure_host_buffers(e, *w, e->host_image_cap.load(), e->host_n_cap.load())) return r;

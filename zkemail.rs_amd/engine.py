@@ -198,6 +198,13 @@ def load_library(path: Optional[str] = None):
     if hasattr(lib, "zke_engine_front_helper"):     # (likewise)
         lib.zke_engine_front_helper.argtypes = [vp, C.c_uint32]
         lib.zke_engine_front_helper.restype = C.c_int
+    if hasattr(lib, "zke_engine_queue_count"):      # (likewise)
+        lib.zke_engine_queue_count.argtypes = [vp]
+        lib.zke_engine_queue_count.restype = C.c_int
+        lib.zke_engine_slot_queue.argtypes = [vp, C.c_uint32]
+        lib.zke_engine_slot_queue.restype = C.c_int
+        lib.zke_engine_last_slot.argtypes = [vp]
+        lib.zke_engine_last_slot.restype = C.c_int
     lib.zke_version.argtypes = []
     lib.zke_version.restype = C.c_char_p
     lib.zke_device_available.argtypes = []
@@ -225,6 +232,7 @@ EXPORTED_SYMBOLS = [
     "zke_extract_bodies", "zke_extract_bodies_async",
     "zke_extract_captures_mixed", "zke_extract_captures_mixed_async",
     "zke_verify_emails_encoded", "zke_verify_emails_encoded_async", "zke_encode_outputs",
+    "zke_engine_queue_count", "zke_engine_slot_queue", "zke_engine_last_slot",
 ]
 
 
@@ -859,6 +867,22 @@ class Engine:
         r = self.lib.zke_engine_front_helper(self.h, n)
         self._check(min(r, 0), "zke_engine_front_helper")
         return r == 1
+
+    def queue_count(self) -> int:
+        """How many groups of slots share a hardware queue each, 0 while the map is unknown (zke_engine_queue_count)."""
+        r = self.lib.zke_engine_queue_count(self.h)
+        self._check(min(r, 0), "zke_engine_queue_count")
+        return r
+
+    def slot_queue(self, slot: int) -> int:
+        """The group of slots `slot` shares its hardware queue with, or -1 if unknown (zke_engine_slot_queue)."""
+        return self.lib.zke_engine_slot_queue(self.h, slot)
+
+    def last_slot(self) -> int:
+        """The slot the most recent submission took (zke_engine_last_slot)."""
+        r = self.lib.zke_engine_last_slot(self.h)
+        self._check(min(r, 0), "zke_engine_last_slot")
+        return r
 
     def join(self, stream: int = 0):
         """Work enqueued on `stream` (a hipStream_t handle; 0 = the null stream) from now on runs behind every batch
