@@ -1171,6 +1171,130 @@ impl Engine {
             .collect())
     }
 
+    /// `String::from_utf8_lossy` (`helpers/src/regex.rs:35`) over a slice of byte strings on the device (`zke_utf8_lossy_batch`): per
+    /// string the repaired text — every ill-formed chunk one U+FFFD — and whether it was changed.
+    pub fn utf8_lossy_batch(&self, strings: &[&[u8]]) -> Result<Vec<(String, bool)>, EngineError> {
+        let mut off: Vec<u64> = vec![0];
+        let mut blob: Vec<u8> = Vec::new();
+        for s in strings {
+            blob.extend_from_slice(s);
+            off.push(blob.len() as u64);
+        }
+        let n = strings.len();
+        let mut out_off = vec![0u32; n + 1];
+        let mut flags = vec![0u8; n + 1];
+        let mut out = vec![0u8; blob.len() + blob.len() / 8 + 64];
+        let mut need: usize = 0;
+        for _attempt in 0..2 {
+            // SAFETY: out_off holds n + 1 entries, flags n, out its length; every pointer is alive until the synchronous call returns.
+            let rc = unsafe {
+                sys::zke_utf8_lossy_batch(self.raw, blob.as_ptr(), off.as_ptr(), n as u32, out_off.as_mut_ptr(), out.as_mut_ptr(), out.len(), &mut need, flags.as_mut_ptr())
+            };
+            if rc == sys::ZKE_E_NOMEM && need > out.len() {
+                out = vec![0u8; need];      // the repaired strings need a larger blob: once more with the size the engine reports
+                continue;
+            }
+            if rc != 0 {
+                return Err(self.last_error(rc));
+            }
+            break;
+        }
+        Ok((0..n)
+            .map(|i| (String::from_utf8_lossy(&out[out_off[i] as usize..out_off[i + 1] as usize]).into_owned(), flags[i] & 1 != 0))
+            .collect())
+    }
+
+    /// `zke_extract_captures_encoded`: from raw e-mails, keys and a part list to the public values in ONE batch — verify_email, the
+    /// extraction, `String::from_utf8_lossy`, `abi_encode` and SHA-256 on the device.  Returns the tables (the strings of `cap_blob`
+    /// are the REPAIRED strings, `CompiledRegex.captures` as the reference holds them; the origins are empty) and one `Result` per
+    /// e-mail: the encoding of its `EmailWithRegexVerifierOutput` and the digest, or the panic the reference would have raised.
+    /// One call when the first guess of the two variable-size buffers holds, else a second with the exact needs.
+    pub fn extract_captures_encoded(
+        &self,
+        emails: &[Email],
+        header_parts: &[CapturePart],
+        body_parts: &[CapturePart],
+    ) -> Result<(MappedCaptures, Vec<Result<EncodedOutput, Panic>>), EngineError> {
+        let n = emails.len();
+        let refs: Vec<sys::zke_email_ref> = emails.iter().map(email_ref).collect();
+        let part = |p: &CapturePart| sys::zke_capture_part { dfa_id: p.dfa_id, prog_id: p.prog_id, n_groups: p.groups.len() as u32, groups: p.groups.as_ptr() };
+        let hp: Vec<sys::zke_capture_part> = header_parts.iter().map(part).collect();
+        let bp: Vec<sys::zke_capture_part> = body_parts.iter().map(part).collect();
+        let g: usize = header_parts.iter().chain(body_parts).map(|p| p.groups.len()).sum();
+        let (np, ng) = (n * (hp.len() + bp.len()), n * g);
+        let (mut ext_off, mut ext_str_off, mut ext_blob) = (vec![0u32], vec![0u32], Vec::<u8>::new());
+        for e in emails {
+            for x in &e.external_inputs {
+                ext_blob.extend_from_slice(x.name.as_bytes());
+                ext_str_off.push(ext_blob.len() as u32);
+                ext_blob.extend_from_slice(x.value.as_deref().unwrap_or("").as_bytes());
+                ext_str_off.push(ext_blob.len() as u32);
+            }
+            ext_off.push(ext_str_off.len() as u32 - 1);
+        }
+        ext_blob.push(0); // (a valid pointer also when every string is empty)
+        let mut m = MappedCaptures {
+            records: vec![zeroed_result(); n],
+            spans: vec![0; ng * 2],
+            flags: vec![0; ng],
+            cap_off: vec![0; np + 1],
+            cap_str_off: vec![0; ng + 1],
+            cap_blob: vec![0; ng * 64 + 1],
+            origin_spans: Vec::new(),
+            origin_flags: Vec::new(),
+        };
+        // SAFETY: zke_encoded_info is plain integers and bytes; all-zero is a value of it.
+        let mut infos: Vec<sys::zke_encoded_info> = vec![unsafe { std::mem::zeroed() }; n];
+        let mut bytes = vec![0u8; n * 512 + 2 * ext_blob.len() + 64 * ext_str_off.len() + ng * 160 + 1];
+        for attempt in 0..2 {
+            let mut caps: sys::zke_capture_out = unsafe { std::mem::zeroed() };
+            caps.spans = m.spans.as_mut_ptr();
+            caps.spans_cap = ng * 2;
+            caps.flags = m.flags.as_mut_ptr();
+            caps.flags_cap = ng;
+            caps.cap_off = m.cap_off.as_mut_ptr();
+            caps.cap_off_cap = np + 1;
+            caps.cap_str_off = m.cap_str_off.as_mut_ptr();
+            caps.cap_str_off_cap = ng + 1;
+            caps.cap_blob = m.cap_blob.as_mut_ptr();
+            caps.cap_blob_cap = m.cap_blob.len();
+            let mut enc = sys::zke_encoded_out { infos: infos.as_mut_ptr(), infos_cap: n, bytes: bytes.as_mut_ptr(), bytes_cap: bytes.len(), infos_need: 0, bytes_need: 0 };
+            // SAFETY: every pointer refers into the arguments, the tables, `m`, `infos` or `bytes`, alive and unmoved until the synchronous call returns.
+            let rc = unsafe {
+                sys::zke_extract_captures_encoded(self.raw, refs.as_ptr(), n as u32, hp.as_ptr(), hp.len() as u32, bp.as_ptr(), bp.len() as u32, m.records.as_mut_ptr(), &mut caps, ext_off.as_ptr(), ext_str_off.as_ptr(), ext_blob.as_ptr(), &mut enc)
+            };
+            if rc == sys::ZKE_E_NOMEM && attempt == 0 {
+                // the needs are exact: once more with the sizes the engine reports
+                if caps.cap_blob_need > m.cap_blob.len() {
+                    m.cap_blob = vec![0; caps.cap_blob_need];
+                }
+                if enc.bytes_need > bytes.len() {
+                    bytes = vec![0; enc.bytes_need];
+                }
+                continue;
+            }
+            if rc != 0 {
+                return Err(self.last_error(rc));
+            }
+            m.cap_str_off.truncate(caps.n_strings + 1);
+            m.cap_blob.truncate(caps.cap_blob_need);
+            break;
+        }
+        let outs = m
+            .records
+            .iter()
+            .zip(infos.iter())
+            .map(|(r, f)| {
+                if r.status == sys::ZKE_OK {
+                    Ok(EncodedOutput { bytes: bytes[f.off as usize..f.off as usize + f.len as usize].to_vec(), digest: f.digest })
+                } else {
+                    Err(Panic { status: r.status, detail: r.detail })
+                }
+            })
+            .collect();
+        Ok((m, outs))
+    }
+
     /// `zke_extract_captures_mapped` over a slice of e-mails that share one part list: verify_email, canonicalise, QP clean, exactly
     /// one match per part, the requested groups — and where each of them lies in the body as it was signed.
     pub fn extract_captures_mapped(&self, emails: &[Email], header_parts: &[CapturePart], body_parts: &[CapturePart]) -> Result<MappedCaptures, EngineError> {

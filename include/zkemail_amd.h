@@ -526,6 +526,21 @@ int zke_capture_batch(zke_engine* e, uint32_t dfa_id, uint32_t prog_id, const ui
 int zke_qp_clean_batch(zke_engine* e, const uint8_t* body_blob, const uint64_t* body_off, uint32_t n,
                        uint8_t* cleaned, uint32_t* index_map, uint32_t* clean_len);
 
+/* ---- String::from_utf8_lossy (helpers/src/regex.rs:35): the step between the bytes a capture group matched and the string the
+ * reference keeps in CompiledRegex.captures.  The rule is core::str::Utf8Chunks': every maximal prefix of a well-formed sequence
+ * (Unicode Table 3-7) that is not itself well-formed becomes one U+FFFD (EF BF BD), and so does every byte no sequence covers — a
+ * stray continuation byte, C0, C1, F5..FF — and a sequence cut short by the end of the string; well-formed bytes are copied
+ * (61 F1 80 80 E1 80 C2 62 80 63 80 BF 64 -> 61 FFFD FFFD FFFD 62 FFFD 63 FFFD FFFD 64).
+ * Building block: the function over n plain host strings blob[off[i] .. off[i+1]).  out_off[n + 1] is the CSR of the repaired
+ * strings (out_off[0] = 0), flags[i] bit 0 says string i was changed (it was not valid UTF-8), out_blob takes the repaired bytes:
+ * *out_blob_need is always written; when out_blob_cap is smaller the call returns ZKE_E_NOMEM, out_off and flags are delivered all
+ * the same, nothing is written into out_blob and a second call with *out_blob_need bytes suffices (three times the input always
+ * does).  The repaired offsets are 32-bit: strings of more than ZKE_UTF8_LOSSY_MAX_BYTES bytes in all, or offsets that decrease,
+ * are refused with ZKE_E_ARG before anything is staged.  Synchronous; runs in one slot, in buffers that only grow. */
+#define ZKE_UTF8_LOSSY_MAX_BYTES 1431655765u   /* (2^32 - 1) / 3 */
+int zke_utf8_lossy_batch(zke_engine* e, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t* out_off, uint8_t* out_blob,
+                         size_t out_blob_cap, size_t* out_blob_need, uint8_t* flags);
+
 /* zke_extract_captures that also says where each span lies BEFORE the QP filter.  Records, caps, statuses and the one fold are
  * those of zke_extract_captures on the same input; `org` is filled in addition (sizes known up front, the zke_capture_out
  * convention: too small fails at once with ZKE_E_NOMEM and the *_need fields set).  With im = the index map of the e-mail's regex
@@ -813,6 +828,44 @@ int zke_verify_emails_encoded(zke_engine* e, const zke_email_ref* emails, uint32
                               zke_encoded_out* enc);
 int zke_verify_emails_encoded_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_encode_in* in, zke_result* out,
                                     zke_encoded_out* enc, uint64_t* ticket);
+
+/* ---- extract, repair and encode in one call: from raw e-mails, keys and a part list to the public values.  The pipeline of
+ * zke_extract_captures (same records, spans, flags, the one fold), then on the device and on the batch's stream: the captured bytes
+ * repaired as String::from_utf8_lossy repairs them (zke_utf8_lossy_batch above has the rule) — the tables are the reference's
+ * CompiledRegex.captures, not raw bytes —, the encode plan, the encodings (kind 1, SolEmailWithRegexOutput, for every e-mail: its
+ * matches are all its strings in part order) and their SHA-256.  No table crosses the link twice and no second pipeline runs.
+ *   caps    as zke_extract_captures fills it, but cap_str_off / cap_blob hold the REPAIRED strings; flags keep ZKE_CAPF_NOT_UTF8
+ *           for the strings that were repaired; spans describe the haystack, not the string, and are unchanged.  May be NULL: the
+ *           caller wants the public values only (the tables then never leave the device).  Nobody names a capacity for the
+ *           strings then, so the slot's device blob is sized by what they cannot exceed, 3 * min(n * G * ZKE_CAP_MAX_SPAN,
+ *           G * (the raw e-mails' bytes + 64 n)) — a buffer that only grows and stays with the slot; a caller that minds the
+ *           memory passes a caps whose cap_blob_cap is its own guess and takes the ZKE_E_NOMEM path when it was short.
+ *   ext_*   the external inputs, as in zke_encode_in (ext_off NULL: none anywhere).
+ *   enc     infos (n entries: too small fails at once with ZKE_E_NOMEM and infos_need set) and bytes.  The plan is made on the device,
+ *           which knows the verdicts: an e-mail whose record is not ZKE_OK has len 0, a zero digest and NO place — off is the running
+ *           offset and its neighbours' places close up (zke_verify_emails_encoded, planned on the host, leaves such a place unused).
+ *           The sizes depend on the e-mails, so bytes follows the cap_blob protocol: when bytes is too small for the encodings, or
+ *           cap_blob for the strings, the call (zke_batch_wait for the asynchronous form) returns ZKE_E_NOMEM; records, infos, spans,
+ *           flags and both offset tables are delivered all the same, bytes_need and cap_blob_need are exact — one second call
+ *           suffices —, an e-mail that did not fit (its place would end beyond bytes_cap, or its strings beyond cap_blob_cap) is
+ *           not written and reports len 0 and a zero digest at its planned off — the caller's bytes stay as they were there —, and
+ *           nothing is written beyond a capacity.
+ * ZKE_E_ARG before anything is staged: what zke_extract_captures refuses; what zke_encode_in's external-input table is refused for;
+ * n * G * 3 * ZKE_CAP_MAX_SPAN >= 2^32 (offsets are 32-bit and a repaired string is at most three times its span: n * G >= 349 526);
+ * an e-mail whose external inputs, encoded, plus the largest matches its part list can yield (G strings of 3 * ZKE_CAP_MAX_SPAN
+ * bytes) would reach 2^32 bytes — so no encoding the device plans can reach that size, which the host plan refuses per call.
+ * Slots, tickets and zke_batch_wait are zke_extract_captures_async's; zke_timings has no new field (the launches count as the regex
+ * stage's).  Not built: a form over mixed configs (zke_extract_captures_mixed keeps raw bytes and the two-call path), a form over
+ * device-resident e-mails; zke_extract_captures* deliver raw bytes as before. */
+int zke_extract_captures_encoded(zke_engine* e, const zke_email_ref* emails, uint32_t n,
+                                 const zke_capture_part* header_parts, uint32_t n_header_parts,
+                                 const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out, zke_capture_out* caps,
+                                 const uint32_t* ext_off, const uint32_t* ext_str_off, const uint8_t* ext_blob, zke_encoded_out* enc);
+int zke_extract_captures_encoded_async(zke_engine* e, const zke_email_ref* emails, uint32_t n,
+                                       const zke_capture_part* header_parts, uint32_t n_header_parts,
+                                       const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out, zke_capture_out* caps,
+                                       const uint32_t* ext_off, const uint32_t* ext_str_off, const uint8_t* ext_blob, zke_encoded_out* enc,
+                                       uint64_t* ticket);
 
 /* Device-resident batch: every pointer in `in` and `out_dev` is device memory (the part-id lists stay host arrays);
  * `raw_total`, `domain_total`, `key_total` are the blob sizes (the CSR tails), which the

@@ -315,6 +315,82 @@ class Engine {
                                            const std::vector<CapturePart>& body_parts, CaptureTables& caps, CaptureOrigins& origins) {
     return extract(emails, header_parts, body_parts, caps, &origins);
   }
+  // zke_extract_captures_encoded: the extraction, String::from_utf8_lossy, abi_encode and SHA-256 in ONE batch — from raw e-mails,
+  // keys and a part list to the public values.  Per e-mail the record's verdict and, when that is ZKE_OK, the bytes of
+  // EmailWithRegexVerifierOutput.abi_encode() and their digest.  `caps`: nullptr, or the tables as zke_capture_out describes them,
+  // the strings REPAIRED (helpers/src/regex.rs:35) — CompiledRegex.captures as the reference holds them.  The external inputs are
+  // the e-mails' own, flattened [name, value, ...].  One call when the first guess of the two variable-size buffers holds, else a
+  // second with the exact needs the first reported.
+  std::vector<EncodedOutput> extract_captures_encoded(const std::vector<Email>& emails, const std::vector<CapturePart>& header_parts,
+                                                      const std::vector<CapturePart>& body_parts, CaptureTables* caps = nullptr) {
+    const uint32_t n = (uint32_t)emails.size();
+    std::vector<zke_email_ref> refs(n);
+    for (uint32_t i = 0; i < n; i++) refs[i] = ref_of(emails[i]);
+    std::vector<zke_capture_part> hp, bp;
+    size_t G = 0;
+    for (const auto& p : header_parts) { hp.push_back(zke_capture_part{p.dfa_id, p.prog_id, (uint32_t)p.groups.size(), p.groups.data()}); G += p.groups.size(); }
+    for (const auto& p : body_parts) { bp.push_back(zke_capture_part{p.dfa_id, p.prog_id, (uint32_t)p.groups.size(), p.groups.data()}); G += p.groups.size(); }
+    std::vector<uint32_t> ext_off{0}, ext_str_off{0};
+    std::vector<uint8_t> ext_blob;
+    for (const Email& em : emails) {
+      for (const auto& x : em.external_inputs)
+        for (const std::string* s : {&x.name, x.value ? &*x.value : nullptr}) {
+          if (s) ext_blob.insert(ext_blob.end(), s->begin(), s->end());
+          ext_str_off.push_back((uint32_t)ext_blob.size());
+        }
+      ext_off.push_back((uint32_t)ext_str_off.size() - 1);
+    }
+    if (ext_blob.empty()) ext_blob.push_back(0);
+    const size_t NP = (size_t)n * (hp.size() + bp.size()), NG = (size_t)n * G;
+    CaptureTables own;
+    CaptureTables& t = caps ? *caps : own;
+    if (caps) { t.spans.assign(NG * 2 + 1, 0); t.flags.assign(NG + 1, 0); t.cap_off.assign(NP + 1, 0); t.cap_str_off.assign(NG + 1, 0); t.cap_blob.assign(NG * 64 + 1, 0); }
+    std::vector<zke_result> recs(n);
+    std::vector<zke_encoded_info> infos(n + 1);
+    std::vector<uint8_t> bytes((size_t)n * 512 + 2 * ext_blob.size() + 64 * ext_str_off.size() + NG * 160 + 1);
+    zke_capture_out o{};
+    zke_encoded_out enc{};
+    for (int attempt = 0; attempt < 2; attempt++) {
+      if (caps) o = zke_capture_out{t.spans.data(), NG * 2, t.flags.data(), NG, t.cap_off.data(), NP + 1, t.cap_str_off.data(), NG + 1,
+                                    t.cap_blob.data(), t.cap_blob.size(), 0, 0, 0, 0, 0, 0};
+      enc = zke_encoded_out{infos.data(), n, bytes.data(), bytes.size(), 0, 0};
+      const int r = zke_extract_captures_encoded(e_, refs.data(), n, hp.data(), (uint32_t)hp.size(), bp.data(), (uint32_t)bp.size(), recs.data(),
+                                                 caps ? &o : nullptr, ext_off.data(), ext_str_off.data(), ext_blob.data(), &enc);
+      if (r == ZKE_E_NOMEM && attempt == 0) {      // the needs are exact: one second call suffices
+        if (caps && o.cap_blob_need > t.cap_blob.size()) t.cap_blob.resize(o.cap_blob_need);
+        if (enc.bytes_need > bytes.size()) bytes.resize(enc.bytes_need);
+        continue;
+      }
+      if (r) throw EngineError("zke_extract_captures_encoded failed: " + std::to_string(r) + " " + zke_last_error(e_));
+      break;
+    }
+    if (caps) { t.spans.resize(NG * 2); t.flags.resize(NG); t.cap_str_off.resize(o.n_strings + 1); t.cap_blob.resize(o.cap_blob_need); }
+    std::vector<EncodedOutput> out(n);
+    for (uint32_t i = 0; i < n; i++) {
+      out[i].status = recs[i].status; out[i].detail = recs[i].detail; out[i].kind = infos[i].kind;
+      out[i].bytes.assign(bytes.begin() + infos[i].off, bytes.begin() + infos[i].off + infos[i].len);
+      std::copy(infos[i].digest, infos[i].digest + 32, out[i].digest.begin());
+    }
+    return out;
+  }
+  // zke_utf8_lossy_batch: String::from_utf8_lossy over byte strings — every ill-formed chunk one U+FFFD.  `changed` (optional): per
+  // string whether it was not valid UTF-8.
+  std::vector<std::vector<uint8_t>> utf8_lossy(const std::vector<std::vector<uint8_t>>& strings, std::vector<uint8_t>* changed = nullptr) {
+    const uint32_t n = (uint32_t)strings.size();
+    std::vector<uint64_t> off{0};
+    std::vector<uint8_t> blob;
+    for (const auto& s : strings) { blob.insert(blob.end(), s.begin(), s.end()); off.push_back(blob.size()); }
+    std::vector<uint32_t> out_off(n + 1);
+    std::vector<uint8_t> out(blob.size() + blob.size() / 8 + 64), flags(n + 1);
+    size_t need = 0;
+    int r = zke_utf8_lossy_batch(e_, blob.data(), off.data(), n, out_off.data(), out.data(), out.size(), &need, flags.data());
+    if (r == ZKE_E_NOMEM) { out.resize(need); r = zke_utf8_lossy_batch(e_, blob.data(), off.data(), n, out_off.data(), out.data(), out.size(), &need, flags.data()); }
+    if (r) throw EngineError("zke_utf8_lossy_batch failed: " + std::to_string(r) + " " + zke_last_error(e_));
+    std::vector<std::vector<uint8_t>> res(n);
+    for (uint32_t i = 0; i < n; i++) res[i].assign(out.begin() + out_off[i], out.begin() + out_off[i + 1]);
+    if (changed) { changed->resize(n); for (uint32_t i = 0; i < n; i++) (*changed)[i] = flags[i] & 1; }
+    return res;
+  }
   // zke_extract_captures_mixed: the extraction over e-mails that carry different regex configs, in ONE batch.  `configs`: the
   // distinct configs (header parts, body parts); config_of[i]: e-mail i's, or ZKE_CONFIG_NONE (verify_email only).  `caps` is ragged:
   // cap_off has J + 1 entries, spans / flags / cap_str_off are indexed by column (the header's job_off / col_off) — the tables

@@ -174,6 +174,7 @@ class zke_capture_out(C.Structure):
 
 QP_NO_INDEX = 0xFFFFFFFF
 ORGF_SPLIT, ORGF_PADDING = 1, 2
+UTF8_LOSSY_MAX_BYTES = (2 ** 32 - 1) // 3     # zke_utf8_lossy_batch: the repaired offsets are 32-bit
 
 
 class zke_capture_origin(C.Structure):

@@ -74,6 +74,7 @@ CPP_QPMAP = os.path.join(ROOT, "tests", "cpp", "qpmap_test")
 CPP_BODY = os.path.join(ROOT, "tests", "cpp", "body_test")
 CPP_MIXED = os.path.join(ROOT, "tests", "cpp", "mixed_test")
 CPP_ENCODE = os.path.join(ROOT, "tests", "cpp", "encode_test")
+CPP_EXTRACT_ENCODED = os.path.join(ROOT, "tests", "cpp", "extract_encoded_test")
 ED_PROBE = os.path.join(ROOT, "tests", "cpp", "ed_probe")
 SHA_PROBE = os.path.join(ROOT, "tests", "cpp", "sha_probe")
 
@@ -107,6 +108,8 @@ def build_cpp_example(force: bool = False) -> str:
         build_cpp_mixed(force)
     if os.path.exists(CPP_ENCODE + ".cpp"):
         build_cpp_encode(force)
+    if os.path.exists(CPP_EXTRACT_ENCODED + ".cpp"):
+        build_cpp_extract_encoded(force)
     if os.path.exists(ED_PROBE + ".hip"):      # test infrastructure that lives in tests/: a tree whose tests/ does not carry the probe
         build_ed_probe(force)                   # has nothing that runs it, and the three programs below do not depend on it
     if os.path.exists(SHA_PROBE + ".hip"):
@@ -142,6 +145,11 @@ def build_cpp_mixed(force: bool = False) -> str:
 def build_cpp_encode(force: bool = False) -> str:
     """tests/cpp/encode_test: verify_emails_encoded / verify_emails_with_regex_encoded of the C++ mirror."""
     return _build_cpp(CPP_ENCODE, force)
+
+
+def build_cpp_extract_encoded(force: bool = False) -> str:
+    """tests/cpp/extract_encoded_test: extract_captures_encoded / utf8_lossy of the C++ mirror."""
+    return _build_cpp(CPP_EXTRACT_ENCODED, force)
 
 
 def build_ed_probe(force: bool = False) -> str:

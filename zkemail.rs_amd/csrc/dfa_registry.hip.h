@@ -234,7 +234,7 @@ uint32_t parse_capture_program(const uint8_t* b, size_t n, HostCapture& h) {
 }
 
 // One slot's capture buffer (device; everything in front of `blob` has a pinned twin and comes back as one copy):
-// hdr {strings, blob bytes needed} | codes | spans | flags | cap_off | cap_str_off | tmp | blob
+// hdr {strings, blob bytes needed, (capture_gather_lossy_kernel) encoding bytes needed} | codes | spans | flags | cap_off | cap_str_off | tmp | blob
 struct CapLayout {
   size_t hdr, codes, spans, flags, cap_off, cap_str_off, fixed_end, tmp, blob, total;
   size_t blob_cap;

@@ -47,6 +47,10 @@ struct EncodeArgs {
   ShaJob* sha;                        // [n] the digest launch's jobs
 };
 
+// EncodeJob.reserved of a job the device planned (capture_lossy.hip.h): the e-mail has no room — its place would end beyond the
+// blob, or its strings were not written — and encode_outputs_placed_kernel treats it like an e-mail that is not ZKE_OK
+constexpr uint32_t ENC_JOB_NO_ROOM = 1;
+
 typedef uint32_t enc_u4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void enc_store16(uint8_t* dst, enc_u4 v) { *reinterpret_cast<enc_u4*>(dst) = v; }
@@ -128,11 +132,13 @@ __device__ __forceinline__ uint32_t enc_string_array(uint8_t* __restrict__ dst, 
   return 32 + run;
 }
 
+// PLACED: the jobs are a device plan's (capture_lossy.hip.h), which marks the e-mails that have no room
+template <bool PLACED = false>
 __device__ __forceinline__ void encode_email(const EncodeArgs& A, const uint32_t i) {
   const uint32_t lane = threadIdx.x & 63;
   const EncodeJob J = A.jobs[i];
   const zke_result* R = A.records + i;
-  const bool ok = R->status == ZKE_OK;
+  const bool ok = R->status == ZKE_OK && !(PLACED && J.reserved == ENC_JOB_NO_ROOM);
   uint8_t* out = A.bytes + J.enc_off;
   uint32_t len = 0;
   if (ok) {
@@ -171,6 +177,13 @@ __global__ __launch_bounds__(64) void encode_outputs_kernel(EncodeArgs A) {
   const uint32_t email = blockIdx.x;
   if (email >= A.n) return;
   encode_email(A, email);
+}
+
+// the same over a device plan: an e-mail marked ENC_JOB_NO_ROOM writes nothing — len 0, a zero digest, an inactive hash job
+__global__ __launch_bounds__(64) void encode_outputs_placed_kernel(EncodeArgs A) {
+  const uint32_t email = blockIdx.x;
+  if (email >= A.n) return;
+  encode_email<true>(A, email);
 }
 
 }  // namespace zke

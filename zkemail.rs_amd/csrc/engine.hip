@@ -38,6 +38,8 @@
 #include "regex_mixed.hip.h"      // (behind the others: the earlier kernels keep their places in the code object)
 #include "capture_mixed.hip.h"
 #include "encode.hip.h"
+#include "utf8_lossy.hip.h"
+#include "capture_lossy.hip.h"
 
 using namespace zke;
 
@@ -92,12 +94,12 @@ struct Slot {
   // wave-routine job list's length); the host entry's packed input image and records, pinned and in HBM; and the buffers of the
   // side outputs, each a device buffer with its pinned twin, its extra device buffers and its layout (host_stage.hip.h):
   // cb capture extraction, sb signature scan, kb key records, ob origins of a mapped extraction, bb body extraction, eb output encoding;
-  // qb: zke_qp_clean_batch.
+  // qb: zke_qp_clean_batch; ub: zke_utf8_lossy_batch.
 #define ZKE_SLOT_BUFFERS(X)                                                                                                           \
   X(DevBuf, meta) X(DevBuf, rsa_jobs) X(DevBuf, sha_jobs) X(DevBuf, sha_order) X(DevBuf, rsa_ok) X(DevBuf, em_dbg)                    \
   X(DevBuf, scratch_off) X(DevBuf, scratch) X(DevBuf, clean) X(DevBuf, meta2) X(DevBuf, scratch2) X(DevBuf, parts) X(DevBuf, pending) \
   X(PinnedBuf, h_image) X(PinnedBuf, h_results) X(DevBuf, d_image) X(DevBuf, d_results)                                               \
-  X(CapBufs, cb) X(ScanBufs, sb) X(KeyrecBufs, kb) X(OriginBufs, ob) X(QpBufs, qb) X(BodyBufs, bb) X(EncBufs, eb)
+  X(CapBufs, cb) X(ScanBufs, sb) X(KeyrecBufs, kb) X(OriginBufs, ob) X(QpBufs, qb) X(BodyBufs, bb) X(EncBufs, eb) X(Utf8Bufs, ub)
 #define X(type, name) type name;
   ZKE_SLOT_BUFFERS(X)
 #undef X

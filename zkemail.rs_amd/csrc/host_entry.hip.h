@@ -95,7 +95,14 @@ struct EncodeReq {
   EncodePlan plan;
   const uint32_t* ext_str_off = nullptr;
   const uint8_t* ext_blob = nullptr;
-  EncImage image() const { return enc_image((uint32_t)plan.jobs.size(), plan.ext_strs, plan.ext_bytes); }
+  // zke_extract_captures_encoded: the plan is the device's (capture_lossy.hip.h).  `plan` then holds no jobs, only what the external
+  // inputs measure; ext_off[n + 1] rides in the image where the jobs would (a job is larger than a word: n jobs hold n + 1 words);
+  // bytes_cap: the capacity of the encodings on the device.
+  bool device_plan = false;
+  uint32_t n = 0;
+  const uint32_t* ext_off = nullptr;
+  uint64_t bytes_cap = 0;
+  EncImage image() const { return enc_image(device_plan ? n : (uint32_t)plan.jobs.size(), plan.ext_strs, plan.ext_bytes); }
 };
 
 // A slot's buffers for one side output of a batch of n: the layout, then the buffers it asks for (ensure_side_buffers).
@@ -112,6 +119,11 @@ int ensure_body_buffers(zke_engine* e, BodyBufs& b, uint32_t n, size_t raw_total
 int ensure_encode_buffers(zke_engine* e, EncBufs& b, uint32_t n, uint64_t blob, size_t staged) {
   b.L = enc_layout(n, blob);
   return ensure_side_buffers(e, b.t, b.L.total, b.L.prefix, staged ? &b.in : nullptr, staged, "output-encoding buffer allocation");
+}
+// a device-planned encoding: `cap` bytes of encodings, the jobs behind them, the infos alone pinned
+int ensure_encode_buffers_planned(zke_engine* e, EncBufs& b, uint32_t n, uint64_t cap) {
+  b.L = enc_layout_planned(n, cap, b.jobs_at);
+  return ensure_side_buffers(e, b.t, b.L.total, b.L.bytes, nullptr, 0, "output-encoding buffer allocation");
 }
 // max_sigs record slots per e-mail and the caller's sel_blob_cap bytes of selectors (a selector is at most ZKE_MAX_TAGBUF bytes: a
 // larger blob than that per record slot is never used)
@@ -246,6 +258,43 @@ int deliver_encoded(zke_engine* e, const EncBufs& b, zke_encoded_out* o) {
   return 0;
 }
 
+// The encodings of a device-planned batch (zke_extract_captures_encoded): the infos from the slot's pinned twin, the exact needs from
+// the gather launch's header (the capture buffer's twin), then the bytes from HBM in runs of written e-mails that follow each other,
+// as deliver_encoded copies them: a complete batch is ONE run from 0, of exactly its size; where an e-mail had no room (its place is
+// kept, nothing of it was written) the run ends, and the caller's bytes stay as they were there.  ZKE_E_NOMEM when bytes is too small for the
+// encodings (bytes_need says how much) or the strings did not fit their blob (the e-mails concerned have len 0): infos and needs
+// are delivered all the same.  An info that points outside the device blob is refused and nothing is read through it.
+int deliver_encoded_planned(zke_engine* e, const EncBufs& b, const CapBufs& cb, zke_encoded_out* o, hipStream_t s) {
+  const EncLayout& K = b.L;
+  const zke_encoded_info* src = reinterpret_cast<const zke_encoded_info*>(b.t.h.as<uint8_t>());
+  const uint64_t* hdr = reinterpret_cast<const uint64_t*>(cb.t.h.as<uint8_t>() + cb.L.hdr);
+  for (uint32_t i = 0; i < K.n; i++) {
+    if (!src[i].len) continue;          // (its off is the planned place, which may lie beyond a blob that is too small)
+    if (src[i].off > K.blob || src[i].len > K.blob - src[i].off) return fail(e, ZKE_E_DEVICE, "output encoding: an info points outside the blob");
+  }
+  if (K.n) memcpy(o->infos, src, (size_t)K.n * sizeof(zke_encoded_info));
+  o->infos_need = K.n; o->bytes_need = (size_t)hdr[2];
+  uint64_t r0 = 0, r1 = 0;
+  bool copied = false;
+  hipError_t he = hipSuccess;
+  auto flush = [&] {
+    if (r1 > r0 && he == hipSuccess) { he = hipMemcpyAsync(o->bytes + r0, b.t.d.as<uint8_t>() + K.bytes + r0, (size_t)(r1 - r0), hipMemcpyDeviceToHost, s); copied = true; }
+  };
+  for (uint32_t i = 0; i < K.n; i++) {
+    if (!src[i].len) continue;
+    if (src[i].off != r1) { flush(); r0 = src[i].off; }
+    r1 = src[i].off + src[i].len;
+  }
+  flush();
+  if (copied) {
+    const hipError_t hs = hipStreamSynchronize(s);      // also behind a failed copy: none outlives the caller's buffer
+    if (he != hipSuccess || hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "output encoding: copy", he != hipSuccess ? he : hs);
+  }
+  if (hdr[2] > K.blob) return fail(e, ZKE_E_NOMEM, "output encoding: bytes is smaller than the encodings (zke_encoded_out.bytes_need)");
+  if (hdr[1] > cb.L.blob_cap) return fail(e, ZKE_E_NOMEM, "output encoding: the capture strings did not fit cap_blob (zke_capture_out.cap_blob_need)");
+  return 0;
+}
+
 // A key selection's fold: the records of the (e-mail, candidate) pairs are in the pinned buffer; per e-mail the first ZKE_OK.
 void fold_selection(const zke_result* R, const std::vector<uint32_t>& off, zke_result* out, uint32_t* chosen) {
   for (size_t i = 0; i + 1 < off.size(); i++) {
@@ -286,6 +335,7 @@ int deliver_pending(zke_engine* e, Slot& w, const PendingDelivery& d, int* cap_r
   if (d.body && (r = settled(deliver_body(e, w.bb, d.body, w.stream)))) return r;
   if (d.caps && (r = settled(deliver_captures(e, w.cb, d.caps, w.stream)))) return r;
   if (d.org) deliver_origins(w.cb, w.ob, d.org);
+  if (d.enc && d.enc_planned) return settled(deliver_encoded_planned(e, w.eb, w.cb, d.enc, w.stream));
   if (d.enc && (r = deliver_encoded(e, w.eb, d.enc))) return r;
   return 0;
 }
@@ -413,7 +463,7 @@ PendingDelivery pending_delivery(const HostBatch& d, zke_result* out) {
   if (d.body) p.body = d.body->out;
   if (d.cap) { p.caps = d.cap->out; p.org = d.cap->org; }
   if (d.capmix) { p.caps = d.capmix->out; p.org = d.capmix->org; }
-  if (d.enc) p.enc = d.enc->out;
+  if (d.enc) { p.enc = d.enc->out; p.enc_planned = d.enc->device_plan; }
   return p;
 }
 
@@ -426,7 +476,7 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   int rc = 0;
   if ((rc = retire_host(e, w))) return rc;           // the pinned buffers are about to be overwritten
   if ((rc = ensure_host_buffers(e, w, L.total, n))) return rc;      // (a no-op: submit_host_batch has grown every slot's staging)
-  if (d.cap) w.cb.L = cap_layout(n, d.cap->P, d.cap->G, d.cap->out->cap_blob_cap);
+  if (d.cap) w.cb.L = cap_layout(n, d.cap->P, d.cap->G, d.cap->dev_blob_cap());
   if (d.cap && (rc = ensure_capture_buffers(e, w.cb, w.cb.L, d.cap->needs_work))) return rc;
   if (d.cap && d.cap->org && (rc = ensure_origin_buffers(e, w.ob, (size_t)n * d.cap->G, d.cap->origin_launch()))) return rc;
   if (d.capmix) w.cb.L = cap_layout_sized(d.capmix->plan.shape.J, d.capmix->plan.shape.Gt, d.capmix->out->cap_blob_cap);
@@ -435,7 +485,8 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   if (d.scan && (rc = ensure_scan_buffers(e, w.sb, n, d.scan->max_sigs, d.scan->out->sel_blob_cap))) return rc;
   if (d.keyrec && (rc = ensure_keyrec_buffers(e, w.kb, n, (size_t)(d.sel ? d.key_total : d.raw_total), d.sel != nullptr))) return rc;
   if (d.body && (rc = ensure_body_buffers(e, w.bb, n, (size_t)d.raw_total))) return rc;
-  if (d.enc && (rc = ensure_encode_buffers(e, w.eb, n, d.enc->plan.total, 0))) return rc;
+  if (d.enc && !d.enc->device_plan && (rc = ensure_encode_buffers(e, w.eb, n, d.enc->plan.total, 0))) return rc;
+  if (d.enc && d.enc->device_plan && (rc = ensure_encode_buffers_planned(e, w.eb, n, d.enc->bytes_cap))) return rc;
   uint8_t* hp = w.h_image.as<uint8_t>();
   if (d.refs) {
     // the CSR arrays are written where they will be read from (prefix sums over the lengths), and every e-mail's three buffers
@@ -495,7 +546,8 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   const size_t enc_at = d.enc ? L.mixed + enc_image_at(d) : 0;
   if (d.enc) {             // an encoding's jobs and its external-input table, the last of the plan sections
     const EncodePlan& P = d.enc->plan;
-    stage_copy(hp + enc_at + EL.jobs, P.jobs.data(), P.jobs.size() * sizeof(EncodeJob));
+    if (d.enc->device_plan) { if (P.ext_strs) stage_copy(hp + enc_at + EL.jobs, d.enc->ext_off, ((size_t)n + 1) * 4); }
+    else stage_copy(hp + enc_at + EL.jobs, P.jobs.data(), P.jobs.size() * sizeof(EncodeJob));
     if (P.ext_strs) stage_copy(hp + enc_at + EL.ext_str_off, d.enc->ext_str_off, ((size_t)P.ext_strs + 1) * 4);
     if (P.ext_bytes) stage_copy(hp + enc_at + EL.ext_blob, d.enc->ext_blob, P.ext_bytes);
   }
@@ -552,18 +604,29 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
                             d.capmix && d.capmix->origin_launch(),
                             CapMixedTables{ml.job_off, reinterpret_cast<const uint32_t*>(cp + CL.col_off), reinterpret_cast<const uint32_t*>(cp + CL.cap_cfg),
                                            reinterpret_cast<const CapMixedCfg*>(cp + CL.cfgs), reinterpret_cast<const CapPartDev*>(cp + CL.parts)}};
+    const bool planned = d.enc && d.enc->device_plan;
+    if (planned) {         // the gather launch of this extraction also plans the encoding: where it reads the external inputs, where the jobs go
+      d.cap->lossy_ext_off = d.enc->plan.ext_strs ? reinterpret_cast<const uint32_t*>(dp + enc_at + EL.jobs) : nullptr;
+      d.cap->lossy_ext_str_off = reinterpret_cast<const uint32_t*>(dp + enc_at + EL.ext_str_off);
+      d.cap->lossy_jobs = reinterpret_cast<EncodeJob*>(w.eb.t.d.as<uint8_t>() + w.eb.jobs_at);
+      d.cap->lossy_bytes_cap = d.enc->bytes_cap;
+    }
     if ((rc = run_device_pipeline(e, w, &dv, d.raw_total, key_hint, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap,
                                   d.mixed ? &ml : nullptr, d.capmix ? &cl : nullptr))) return rc;
     if (d.enc) {           // the encodings of the records just written and their digests, two more launches on the same stream
       EncodeArgs ea{};
       ea.records = w.d_results.as<zke_result>();
-      ea.jobs = reinterpret_cast<const EncodeJob*>(dp + enc_at + EL.jobs);
+      ea.jobs = planned ? d.cap->lossy_jobs : reinterpret_cast<const EncodeJob*>(dp + enc_at + EL.jobs);
       ea.ext_str_off = reinterpret_cast<const uint32_t*>(dp + enc_at + EL.ext_str_off); ea.ext_blob = dp + enc_at + EL.ext_blob;
       ea.match_str_off = dv.cap_str_off; ea.match_blob = dv.cap_blob;
-      if ((rc = launch_encode(e, w.eb, ea, s))) return rc;
+      if (planned) {       // the matches are the tables the gather launch has just written in the slot's capture buffer
+        ea.match_str_off = reinterpret_cast<const uint32_t*>(w.cb.t.d.as<uint8_t>() + w.cb.L.cap_str_off);
+        ea.match_blob = w.cb.t.d.as<uint8_t>() + w.cb.L.blob;
+      }
+      if ((rc = launch_encode(e, w.eb, ea, s, planned))) return rc;
     }
     HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
-    if (d.enc) HIPCHK(e, w.eb.t.fetch(w.eb.L.prefix, s));
+    if (d.enc) HIPCHK(e, w.eb.t.fetch(planned ? w.eb.L.bytes : w.eb.L.prefix, s));
     if (d.keyrec) HIPCHK(e, w.kb.t.fetch(w.kb.L.total, s));
   }
   if (rc) return rc;
@@ -1169,6 +1232,68 @@ int zke_extract_captures_mapped(zke_engine* e, const zke_email_ref* emails, uint
   });
 }
 
+// ---- extraction, UTF-8 repair and encoding in one batch (include/zkemail_amd.h; kernels: capture_lossy.hip.h, encode.hip.h).  The
+// extraction's request with the lossy gather launch, and an encoding whose plan is the device's: what can be refused is refused
+// here, from the part lists and the external-input table alone, before anything is staged.
+int zke_extract_captures_encoded_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
+                                       uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
+                                       zke_capture_out* caps, const uint32_t* ext_off, const uint32_t* ext_str_off, const uint8_t* ext_blob,
+                                       zke_encoded_out* enc, uint64_t* ticket) {
+  static const char who[] = "zke_extract_captures_encoded";
+  if (!e) return ZKE_E_ARG;
+  if (!ticket || !enc || (n_header_parts && !header_parts) || (n_body_parts && !body_parts)) return arg_error(who, "null pointer");
+  const uint32_t P = n_header_parts + n_body_parts;
+  if (P == 0 || P > ZKE_CAP_MAX_PARTS || n_header_parts > ZKE_CAP_MAX_PARTS) return arg_error(who, "1 .. ZKE_CAP_MAX_PARTS parts");
+  CaptureReq q;
+  q.P = P; q.n_header_parts = n_header_parts; q.out = caps; q.lossy = true;
+  q.dfa_ids.resize(P);
+  for (uint32_t p = 0; p < P; p++) {
+    const zke_capture_part& cp = p < n_header_parts ? header_parts[p] : body_parts[p - n_header_parts];
+    q.dfa_ids[p] = cp.dfa_id;
+    if (int r = capture_part_shape(q, p, cp.prog_id, cp.groups, cp.n_groups, who)) return r;
+  }
+  // a repaired string is at most three times its span: what n * G of those could not address in 32 bits is refused
+  const uint64_t str_worst = 3ull * ZKE_CAP_MAX_SPAN, blob_worst = (uint64_t)n * q.G * str_worst;
+  if (blob_worst > 0xFFFFFFFFull) return arg_error(who, "n x groups beyond what 32-bit string offsets address (n * G * 3 * ZKE_CAP_MAX_SPAN must stay below 4 GiB): split the batch");
+  if (caps) if (int r = check_capture_out(caps, n, P, q.G, who)) return r;
+  EncodeReq eq;
+  eq.device_plan = true; eq.n = n; eq.out = enc; eq.ext_off = ext_off; eq.ext_str_off = ext_str_off; eq.ext_blob = ext_blob;
+  if (const char* why = encode_table_check(ext_off, n, ext_str_off, ext_blob, eq.plan.ext_strs, eq.plan.ext_bytes)) return arg_error(who, why);
+  // the largest matches array the part lists can yield, and with it the largest encoding of every e-mail
+  const uint64_t match_worst = 32 + (uint64_t)q.G * (64 + str_worst);
+  uint64_t bytes_worst = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    uint64_t size = 32 + 96 + 64;
+    if (!enc_add_array(ext_str_off, eq.plan.ext_strs ? ext_off[i] : 0u, eq.plan.ext_strs ? ext_off[i + 1] : 0u, size) || size + match_worst >= ENC_MAX_LEN)
+      return arg_error(who, "an encoding could reach 2^32 bytes (the external inputs and the largest matches the part lists can yield)");
+    bytes_worst += size + match_worst;
+  }
+  enc->infos_need = n; enc->bytes_need = 0;
+  if (enc->infos_cap < n) return nomem_error(who, "zke_encoded_out.infos is smaller than infos_need");
+  if ((n && !enc->infos) || (enc->bytes_cap && !enc->bytes)) return arg_error(who, "null buffer in zke_encoded_out");
+  eq.bytes_cap = std::min<uint64_t>(enc->bytes_cap, bytes_worst);
+  zke_regex_lists lists{n_header_parts, q.dfa_ids.data(), n_body_parts, q.dfa_ids.data() + n_header_parts, nullptr, nullptr, nullptr};
+  HostBatch d;
+  if (int r = host_batch(d, who, out, emails, n, &lists)) return r;
+  // the strings' blob on the device: the caller's capacity; without `caps`, what the strings cannot exceed (a group lies in a
+  // canonical header or body, which is no longer than its e-mail but for a line end)
+  q.lossy_blob_cap = (size_t)std::min<uint64_t>(blob_worst, caps ? (uint64_t)caps->cap_blob_cap : 3ull * q.G * (d.raw_total + 64ull * n));
+  if (!n && caps) { caps->cap_off[0] = 0; caps->cap_str_off[0] = 0; }      // (nothing is launched: the empty tables are written here)
+  d.cap = &q; d.enc = &eq;
+  layout_host_batch(d);
+  return submit_host_batch(e, d, out, ticket);
+}
+
+int zke_extract_captures_encoded(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
+                                 uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
+                                 zke_capture_out* caps, const uint32_t* ext_off, const uint32_t* ext_str_off, const uint8_t* ext_blob,
+                                 zke_encoded_out* enc) {
+  return submit_and_wait(e, n, [&](uint64_t* t) {
+    return zke_extract_captures_encoded_async(e, emails, n, header_parts, n_header_parts, body_parts, n_body_parts, out, caps, ext_off,
+                                              ext_str_off, ext_blob, enc, t);
+  });
+}
+
 // ---- the extraction over `&[Email]` with a RegexConfig per e-mail (include/zkemail_amd.h): the checks, the plan's ragged half and the
 // sizes here, before anything is staged; the programs and the DFA pairs once the registry can be read (capmix_resolve, mixed_resolve).
 int zke_extract_captures_mixed_async(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_mixed* mixed, zke_result* out,
@@ -1330,6 +1455,60 @@ int zke_qp_clean_batch(zke_engine* e, const uint8_t* body_blob, const uint64_t* 
   const hipError_t hs = hipStreamSynchronize(s);      // also behind a failed enqueue: no copy outlives the caller's buffers
   if (r) return r;
   if (hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "zke_qp_clean_batch: sync", hs);
+  return 0;
+}
+
+// ---- String::from_utf8_lossy over plain strings (include/zkemail_amd.h; kernels: utf8_lossy.hip.h).  One slot, its stream and its
+// Utf8Bufs (grow only).  The repaired blob on the device holds min(out_blob_cap, 3 * the input) bytes — no string grows further — and
+// the write launch leaves out what would end beyond it; the offsets come back first, the bytes once the need is known to fit.
+int zke_utf8_lossy_batch(zke_engine* e, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t* out_off, uint8_t* out_blob,
+                         size_t out_blob_cap, size_t* out_blob_need, uint8_t* flags) {
+  static const char who[] = "zke_utf8_lossy_batch";
+  if (!e) return ZKE_E_ARG;
+  if (!out_off || !out_blob_need || (n && (!off || !flags)) || (out_blob_cap && !out_blob)) return arg_error(who, "null pointer");
+  if (n == 0) { out_off[0] = 0; *out_blob_need = 0; return 0; }
+  if (!rising(off, n)) return arg_error(who, "offset array is not non-decreasing");
+  const uint64_t base0 = off[0], total = off[n] - base0;
+  if (total > ZKE_UTF8_LOSSY_MAX_BYTES) return arg_error(who, "more than ZKE_UTF8_LOSSY_MAX_BYTES bytes of strings (the repaired offsets are 32-bit)");
+  if (total && !blob) return arg_error(who, "null pointer");
+  std::shared_lock<std::shared_mutex> sh(e->big);
+  HIPCHK(e, hipSetDevice(e->device));
+  uint32_t slot;
+  Slot& w = next_slot(e, slot);
+  std::lock_guard<std::mutex> g(w.mu);
+  Utf8Bufs& b = w.ub;
+  const uint64_t dev_cap = std::min<uint64_t>(out_blob_cap, 3 * total);
+  int r = 0;
+  if ((r = b.in.ensure((size_t)total + 16)) || (r = b.off.ensure((size_t)(n + 1) * 8)) || (r = b.out_off.ensure((size_t)(n + 1) * 4)) ||
+      (r = b.out.ensure((size_t)dev_cap + 16)) || (r = b.flags.ensure(n)))
+    return fail(e, r, "zke_utf8_lossy_batch: allocation");
+  hipStream_t s = w.stream;
+  SlotUse use(e, w, s);
+  if ((r = use.acquire())) return r;
+  auto enqueue = [&]() -> int {
+    if (total) HIPCHK(e, hipMemcpyAsync(b.in.p, blob + base0, (size_t)total, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(b.off.p, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));      // (as given: the kernels subtract off[0])
+    const Utf8LossyArgs ua{n, b.in.as<uint8_t>(), b.off.as<uint64_t>(), b.out_off.as<uint32_t>(), b.out.as<uint8_t>(), dev_cap, b.flags.as<uint8_t>()};
+    const dim3 grid(std::min<uint32_t>(n, 1u << 16));
+    hipLaunchKernelGGL(utf8_lossy_len_kernel, grid, dim3(64), 0, s, ua);
+    hipLaunchKernelGGL(utf8_lossy_scan_kernel, dim3(1), dim3(1024), 0, s, ua);
+    hipLaunchKernelGGL(utf8_lossy_write_kernel, grid, dim3(64), 0, s, ua);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(out_off, b.out_off.p, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(flags, b.flags.p, n, hipMemcpyDeviceToHost, s));
+    return use.release();
+  };
+  r = enqueue();
+  hipError_t hs = hipStreamSynchronize(s);      // also behind a failed enqueue: no copy outlives the caller's buffers
+  if (r) return r;
+  if (hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "zke_utf8_lossy_batch: sync", hs);
+  const size_t need = out_off[n];
+  *out_blob_need = need;
+  if (need > out_blob_cap) return fail(e, ZKE_E_NOMEM, "zke_utf8_lossy_batch: out_blob is smaller than the repaired strings (*out_blob_need)");
+  if (need) {
+    HIPCHK(e, hipMemcpyAsync(out_blob, b.out.p, need, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+  }
   return 0;
 }
 

@@ -393,10 +393,20 @@ inline EncLayout enc_layout(uint32_t n, uint64_t blob) {
   L.total = L.sha + (size_t)n * sizeof(ShaJob);
   return L;
 }
+// A device-planned encoding (zke_extract_captures_encoded): `blob` is the CAPACITY of the encodings — their size is known only
+// once the batch has run —, the plan's jobs lie behind the digest jobs, and the pinned twin holds the infos alone: the bytes come
+// back in a copy of their own, of exactly the size the infos name (deliver_encoded_planned).
+inline EncLayout enc_layout_planned(uint32_t n, uint64_t blob_cap, size_t& jobs_at) {
+  EncLayout L = enc_layout(n, blob_cap);
+  jobs_at = align_up(L.total, 64);
+  L.total = jobs_at + (size_t)n * sizeof(EncodeJob);
+  return L;
+}
 struct EncBufs {
   TwinBuf t;
   DevBuf in;
   EncLayout L{};
+  size_t jobs_at = 0;        // (a device-planned encoding)
 };
 template <class F> void each_buffer(EncBufs& b, F& f) { each_buffer(b.t, f); f(b.in); }
 // What the encode launch reads besides the records and the capture tables, as one section of a batch's input image: the jobs and the
@@ -415,6 +425,10 @@ inline EncImage enc_image(uint32_t n, uint32_t ext_strs, uint32_t ext_bytes) {
 struct QpBufs { DevBuf in, off, clean, map, len; };
 template <class F> void each_buffer(QpBufs& b, F& f) { for (DevBuf* x : {&b.in, &b.off, &b.clean, &b.map, &b.len}) f(*x); }
 
+// The buffers of zke_utf8_lossy_batch (a slot's): the strings and their offsets, the repaired offsets, bytes and flags.
+struct Utf8Bufs { DevBuf in, off, out_off, out, flags; };
+template <class F> void each_buffer(Utf8Bufs& b, F& f) { for (DevBuf* x : {&b.in, &b.off, &b.out_off, &b.out, &b.flags}) f(*x); }
+
 // What a slot owes the caller of its pending host batch: where each output goes once the batch's last copy has arrived.  A
 // default-constructed one owes nothing.  submit_host files it (pending_delivery), retire_host takes it out whole, deliver_pending
 // pays it (host_entry.hip.h).
@@ -430,6 +444,7 @@ struct PendingDelivery {
   zke_capture_out* caps = nullptr;
   zke_capture_origin* org = nullptr;   // (with caps only: a mapped extraction)
   zke_encoded_out* enc = nullptr;      // (beside the records: zke_verify_emails_encoded)
+  bool enc_planned = false;            // (with enc: the plan was the device's — zke_extract_captures_encoded; caps may then be null)
 };
 
 }  // namespace

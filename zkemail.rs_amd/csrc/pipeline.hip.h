@@ -64,6 +64,14 @@ struct CaptureReq {
   zke_capture_out* out = nullptr;
   zke_capture_origin* org = nullptr;     // zke_extract_captures_mapped: the spans' origins before the QP filter are wanted too
   bool origin_launch() const { return org && G > gbase[n_header_parts]; }      // some body part asks for a group
+  // zke_extract_captures_encoded: the gather launch is capture_gather_lossy_kernel (capture_lossy.hip.h) — repaired strings and the
+  // encode plan.  `out` may then be null (nobody wants the tables); blob_cap is the device blob's capacity, and submit_host fills in
+  // the device pointers once the slot's buffers exist.
+  bool lossy = false;
+  size_t lossy_blob_cap = 0;
+  uint64_t lossy_bytes_cap = 0;
+  const uint32_t* lossy_ext_off = nullptr; const uint32_t* lossy_ext_str_off = nullptr; EncodeJob* lossy_jobs = nullptr;
+  size_t dev_blob_cap() const { return lossy ? lossy_blob_cap : out->cap_blob_cap; }
 };
 constexpr uint32_t CAP_WORK_WAVES = 256;      // waves of a capture launch whose rows live in the slot's workspace (one slice each)
 
@@ -132,7 +140,12 @@ int launch_capture(zke_engine* e, CapBufs& b, const CaptureReq& q, uint32_t n, b
   ga.cap_blob = cb + L.blob; ga.blob_cap = L.blob_cap; ga.hdr = reinterpret_cast<uint64_t*>(cb + L.hdr);
   ga.tmp = reinterpret_cast<uint32_t*>(cb + L.tmp);
   for (uint32_t p = 0; p <= q.P; p++) ga.gbase[p] = q.gbase[p];
-  hipLaunchKernelGGL(capture_gather_kernel, dim3(1), dim3(1024), 0, s, ga);
+  if (q.lossy) {
+    const CapLossyArgs la{ga, ca.flags, q.lossy_ext_off, q.lossy_ext_str_off, q.lossy_jobs, q.lossy_bytes_cap};
+    hipLaunchKernelGGL(capture_gather_lossy_kernel, dim3(1), dim3(1024), 0, s, la);
+  } else {
+    hipLaunchKernelGGL(capture_gather_kernel, dim3(1), dim3(1024), 0, s, ga);
+  }
   HIPCHK(e, hipGetLastError());
   return 0;
 }
@@ -212,11 +225,13 @@ int launch_keyrec_prefix(zke_engine* e, KeyrecBufs& b, zke_batch& in, uint32_t m
 // ---- the output encoding behind a batch's records (zke_verify_emails_encoded, zke_encode_outputs; kernel: encode.hip.h): the encode
 // launch over records, jobs and tables (`a`: device pointers; the outputs are filled in here from the slot's buffer), then the SHA-256
 // of the encodings — the engine's hash launch over the job list the kernel left, the call sha256_batch_device_locked makes.
-int launch_encode(zke_engine* e, EncBufs& b, EncodeArgs a, hipStream_t s) {
+// `placed`: the jobs are a device plan's (capture_lossy.hip.h) and lie in the slot's buffer themselves.
+int launch_encode(zke_engine* e, EncBufs& b, EncodeArgs a, hipStream_t s, bool placed = false) {
   uint8_t* eo = b.t.d.as<uint8_t>();
   a.n = b.L.n;
   a.infos = reinterpret_cast<zke_encoded_info*>(eo); a.bytes = eo + b.L.bytes; a.sha = reinterpret_cast<ShaJob*>(eo + b.L.sha);
-  hipLaunchKernelGGL(encode_outputs_kernel, dim3(a.n), dim3(64), 0, s, a);
+  if (placed) hipLaunchKernelGGL(encode_outputs_placed_kernel, dim3(a.n), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(encode_outputs_kernel, dim3(a.n), dim3(64), 0, s, a);
   HIPCHK(e, hipGetLastError());
   return launch_sha(e, plan_sha(e->stage, a.n), a.sha, a.n, s);
 }

@@ -189,6 +189,14 @@ def load_library(path: Optional[str] = None):
         lib.zke_verify_emails_encoded_async.restype = C.c_int
         lib.zke_encode_outputs.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, eop]
         lib.zke_encode_outputs.restype = C.c_int
+    if hasattr(lib, "zke_utf8_lossy_batch"):        # (likewise)
+        lib.zke_utf8_lossy_batch.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
+        lib.zke_utf8_lossy_batch.restype = C.c_int
+        eop = C.POINTER(A.zke_encoded_out)
+        lib.zke_extract_captures_encoded.argtypes = [vp, erp, C.c_uint32, cpp, C.c_uint32, cpp, C.c_uint32, vp, cop, vp, vp, vp, eop]
+        lib.zke_extract_captures_encoded.restype = C.c_int
+        lib.zke_extract_captures_encoded_async.argtypes = lib.zke_extract_captures_encoded.argtypes + [C.POINTER(C.c_uint64)]
+        lib.zke_extract_captures_encoded_async.restype = C.c_int
     if hasattr(lib, "zke_engine_sha_ring"):         # (a ZKE_LIB build of an older tree, for an A/B run, has no such entry)
         lib.zke_engine_sha_ring.argtypes = [vp]
         lib.zke_engine_sha_ring.restype = C.c_int
@@ -233,6 +241,7 @@ EXPORTED_SYMBOLS = [
     "zke_extract_captures_mixed", "zke_extract_captures_mixed_async",
     "zke_verify_emails_encoded", "zke_verify_emails_encoded_async", "zke_encode_outputs",
     "zke_engine_queue_count", "zke_engine_slot_queue", "zke_engine_last_slot",
+    "zke_utf8_lossy_batch", "zke_extract_captures_encoded", "zke_extract_captures_encoded_async",
 ]
 
 
@@ -397,6 +406,36 @@ class _EncodedCall:
         return self.out[:self.refs.n]
 
 
+class ExtractEncoded:
+    """One zke_extract_captures_encoded call (Engine.extract_captures_encoded_call): its return code, everything it points to —
+    kept alive until the batch has been waited for — and the reading of what it delivered.  spans [n, G, 2], flags [n, G],
+    cap_off [n * P + 1], cap_str_off, blob: the zke_capture_out arrays as they lie (blob with its guard bytes behind blob_bytes);
+    enc: the ``_abi.EncodedBuffers``."""
+    rc = 0
+    ticket = 0
+
+    def strings(self) -> List[List[bytes]]:
+        """Per e-mail its capture strings in part order, as the device delivered them (repaired)."""
+        raw = self.blob.tobytes()
+        P, so = self.P, self.cap_str_off
+        return [[raw[int(so[k]):int(so[k + 1])] for k in range(int(self.cap_off[i * P]), int(self.cap_off[(i + 1) * P]))] for i in range(self.n)]
+
+    def regex_infos(self) -> List[Optional["A.RegexInfo"]]:
+        """What compile_regex_parts returns per e-mail (None where the record is not OK): the strings are valid UTF-8 as they come."""
+        raw, P, out = self.blob.tobytes(), self.P, []
+        nh = len(self.regex_config.header_parts or [])
+        for i in range(self.n):
+            if self.records[i]["status"] != A.ZKE_OK:
+                out.append(None)
+                continue
+            parts = [CompiledRegex(self.comp[p][0], [raw[int(self.cap_str_off[k]):int(self.cap_str_off[k + 1])].decode("utf-8")
+                                                      for k in range(int(self.cap_off[i * P + p]), int(self.cap_off[i * P + p + 1]))])
+                     for p in range(P)]
+            out.append(A.RegexInfo(parts[:nh] if self.regex_config.header_parts is not None else None,
+                                   parts[nh:] if self.regex_config.body_parts is not None else None))
+        return out
+
+
 class Engine:
     """One engine per GPU (``zke_engine``): owns the device workspace, the stream and the
     registered DFA tables."""
@@ -554,6 +593,27 @@ class Engine:
         raw = cleaned.tobytes()
         return ([raw[int(off[i]):int(off[i + 1])] for i in range(n)], [imap[int(off[i]):int(off[i + 1])].copy() for i in range(n)], clen[:n])
 
+    def utf8_lossy(self, strings: Sequence[bytes]):
+        """zke_utf8_lossy_batch: String::from_utf8_lossy (helpers/src/regex.rs:35) over a batch of byte strings.  Returns (repaired:
+        the strings as UTF-8 bytes, every ill-formed chunk one U+FFFD; changed: bool[n], the string was not valid UTF-8).  One
+        call when three times the input fits the first buffer's guess, else a second with the exact need."""
+        n = len(strings)
+        blob, off = A._csr(list(strings))
+        total = int(off[n]) if n else 0
+        out_off = np.zeros(n + 1, np.uint32)
+        flags = np.zeros(max(n, 1), np.uint8)
+        need = C.c_size_t(0)
+        out = np.zeros(max(total + total // 8, 64), np.uint8)
+        for _ in range(2):
+            rc = self.lib.zke_utf8_lossy_batch(self.h, blob.ctypes.data, off.ctypes.data, n, out_off.ctypes.data, out.ctypes.data, out.size,
+                                               C.byref(need), flags.ctypes.data)
+            if rc != -3:                                       # ZKE_E_NOMEM: the repaired strings need a larger blob
+                break
+            out = np.zeros(need.value, np.uint8)
+        self._check(rc, "zke_utf8_lossy_batch")
+        raw = out.tobytes()
+        return [raw[int(out_off[i]):int(out_off[i + 1])] for i in range(n)], (flags[:n] & 1).astype(bool)
+
     def remove_quoted_printable_soft_breaks(self, body: bytes):
         """The reference's function on one body (a batch of one): (cleaned, index_map) with usize::MAX = 2**64 - 1 over the padding."""
         cleaned, maps, _ = self.qp_clean_batch([bytes(body)])
@@ -608,6 +668,74 @@ class Engine:
         if origins:
             return out[:n], infos, (ospans[:n * G * 2].reshape(n, G, 2), oflags[:n * G].reshape(n, G))
         return out[:n], infos
+
+    def extract_captures_encoded_call(self, emails: Sequence[Email], regex_config, external_inputs=None, *, unicode: bool = True,
+                                      blob_bytes: Optional[int] = None, bytes_cap: Optional[int] = None, want_caps: bool = True,
+                                      guard: int = 0, fill: int = 0, ticket: bool = False):
+        """ONE zke_extract_captures_encoded with caller-sized buffers and no retry: returns an ``ExtractEncoded`` — rc (0, or -3 =
+        ZKE_E_NOMEM when `blob_bytes` / `bytes_cap` is too small: everything but the short buffer's bytes is delivered and the needs
+        are exact), the records, the capture tables (None with want_caps=False: caps is NULL) and the ``_abi.EncodedBuffers``.
+        `external_inputs`: per e-mail its list of ExternalInput (default: each Email's own), flattened as the reference does.
+        `guard` / `fill`: bytes behind both variable-size buffers and their initial value, for tests that watch what is written.
+        ticket=True: the asynchronous form; `.ticket` is to be waited for (``wait``) before anything is read, and rc is the submit's."""
+        from . import regex_compile as rc
+        if isinstance(regex_config, dict):
+            regex_config = rc.RegexConfig.from_json(regex_config)
+        hp, bp = list(regex_config.header_parts or []), list(regex_config.body_parts or [])
+        comp = [self.compile_pattern(p.pattern, unicode) for p in hp + bp]
+        groups = [np.array(list(p.capture_indices or []), np.uint32) for p in hp + bp]
+        arr = (A.zke_capture_part * max(len(comp), 1))()
+        for k, ((_, dfa_id, prog_id), g) in enumerate(zip(comp, groups)):
+            arr[k].dfa_id, arr[k].prog_id, arr[k].n_groups, arr[k].groups = dfa_id, prog_id, len(g), g.ctypes.data
+        body = C.cast(C.byref(arr, len(hp) * C.sizeof(A.zke_capture_part)), C.POINTER(A.zke_capture_part))
+        emails = list(emails)
+        refs = A.EmailRefs(emails)
+        n, P, G = refs.n, len(comp), sum(len(g) for g in groups)
+        ext_lists = [e.external_inputs for e in emails] if external_inputs is None else list(external_inputs)
+        ext = A.StringTable([A.flat_external_inputs(x) for x in ext_lists])
+        r = ExtractEncoded()
+        r.n, r.P, r.G, r.comp, r.regex_config = n, P, G, comp, regex_config
+        r.keep = (refs, arr, groups, ext)
+        r.records = np.zeros(max(n, 1), dtype=A.RESULT_DTYPE)[:n]
+        out_ptr = r.records.ctypes.data if n else None
+        r.blob_bytes = 64 * n * G if blob_bytes is None else blob_bytes
+        r.spans, r.flags = np.zeros(max(n * G * 2, 1), np.uint32), np.zeros(max(n * G, 1), np.uint8)
+        r.cap_off, r.cap_str_off = np.zeros(n * P + 1, np.uint32), np.zeros(n * G + 1, np.uint32)
+        r.blob = np.full(max(r.blob_bytes + guard, 1), fill, np.uint8)
+        o = r.caps = A.zke_capture_out()
+        o.spans, o.spans_cap, o.flags, o.flags_cap = r.spans.ctypes.data, n * G * 2, r.flags.ctypes.data, n * G
+        o.cap_off, o.cap_off_cap, o.cap_str_off, o.cap_str_off_cap = r.cap_off.ctypes.data, n * P + 1, r.cap_str_off.ctypes.data, n * G + 1
+        o.cap_blob, o.cap_blob_cap = r.blob.ctypes.data, r.blob_bytes
+        r.want_caps = want_caps
+        # an encoding: 192 bytes of head, the external inputs, per match 64 bytes and its padded bytes (_abi.encoded_len)
+        r.enc = A.EncodedBuffers(n, (256 * n + 2 * int(ext.str_off[-1]) + 64 * ext.n_strings + 160 * n * G) if bytes_cap is None else bytes_cap,
+                                 guard, fill)
+        args = (self.h, refs.arr, n, arr, len(hp), body, len(bp), out_ptr, C.byref(o) if want_caps else None,
+                ext.off.ctypes.data if ext.n_strings else None, ext.str_off.ctypes.data, ext.blob.ctypes.data, C.byref(r.enc.c))
+        r.args = args                            # (the synchronous entry's arguments: a caller that times it calls it again with these)
+        if ticket:
+            t = C.c_uint64()
+            r.rc = self.lib.zke_extract_captures_encoded_async(*args, C.byref(t))
+            r.ticket = t.value
+        else:
+            r.rc = self.lib.zke_extract_captures_encoded(*args)
+        return r
+
+    def extract_captures_encoded(self, emails: Sequence[Email], regex_config, external_inputs=None, *, unicode: bool = True):
+        """zke_extract_captures_encoded: from raw e-mails, keys and a regex config to the public values, one batch on the GPU —
+        verify_email, the extraction, String::from_utf8_lossy, abi_encode and SHA-256.  Returns (records, regex_infos, encodings,
+        digests): regex_infos[i] as ``extract_captures`` gives it, the strings taken from the device as they are (they are repaired
+        there); encodings[i] / digests[i] the bytes of EmailWithRegexVerifierOutput.abi_encode() and their SHA-256, b"" and 32 zero
+        bytes where the record is not OK.  One call when the first guess of the two variable-size buffers holds, else a second
+        with the exact needs."""
+        r = self.extract_captures_encoded_call(emails, regex_config, external_inputs, unicode=unicode)
+        if r.rc == -3:                                         # ZKE_E_NOMEM: the needs are exact
+            r = self.extract_captures_encoded_call(emails, regex_config, external_inputs, unicode=unicode,
+                                                   blob_bytes=max(int(r.caps.cap_blob_need), r.blob_bytes),
+                                                   bytes_cap=max(int(r.enc.c.bytes_need), r.enc.nbytes))
+        self._check(r.rc, "zke_extract_captures_encoded")
+        res = r.enc.result()
+        return r.records, r.regex_infos(), [x[0] for x in res], [x[1] for x in res]
 
     def pack_capture_mixed(self, regex_configs: Sequence, *, unicode: bool = True):
         """The tables of zke_extract_captures_mixed for one ``RegexConfig`` (or its JSON dict, or None: verify_email only) per
