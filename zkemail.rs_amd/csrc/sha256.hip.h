@@ -707,7 +707,23 @@ __global__ __launch_bounds__(128) void sha256_ring_kernel(const ShaJob* __restri
 //   U  = 0 | R3      A lanes only                    1   A: t1                 B: Σ0 + Maj
 //   N  = R3[partner] + U                             1   A: d + t1 = e'        B: t1 + Σ0 + Maj = a'
 //   R3 <- R2 <- R1 <- R0 <- N
-// 10 VALU instead of 14, and the Davies-Meyer add is 4 instead of 8.  The last three are DPP instructions (sha_twin_exchange).
+// 10 VALU instead of 14, and the Davies-Meyer add is 4 instead of 8.  The last three are DPP instructions (sha_twin_exchange),
+// and the third reads R3 through DPP two instructions behind its write: a wait state in every round, and a second one that the
+// compiler puts behind every asm statement.  On a wave that is alone on its SIMD an s_nop costs the issue slot of a VALU
+// instruction, so that is the round of the ZKE_SHA_TWIN_NOWAIT = 0 build only.  The default round hands t1 and d across the pair
+// so that no DPP operand is read sooner than three instructions behind its write, with Q = h + K + W on A lanes and 0 on B lanes:
+//   r1, r2, r3, S, D, F                              6   as above
+//   W  = add3(S, F, Q)                               1   A: h + Σ1 + Ch + K + W = t1   B: Σ0 + Maj
+//   N  = R3[partner] + W      all lanes              1   A: d + t1 = e'                B: (h + Σ0 + Maj: overwritten below)
+//   Q' = Q' + R2              A lanes only           1   the next round's Q, in place in its K + W register: R2 is that round's R3
+//   N  = W[partner] + W       B lanes only           1   B: t1 + Σ0 + Maj = a'
+//   R3 <- R2 <- R1 <- R0 <- N
+// W is the only register read through DPP soon after its write, and N and Q' stand between the two; R3 and R2 were written two
+// and more rounds ago; K + W comes from LDS.  B lanes read zeros for K + W and the masked add does not write them: their Q stays
+// 0.  N goes into the register of the dying R3, so after four rounds every value is in its own register again and a block is
+// ONE asm statement of 16 quads (sha_twin_block_nowait) with no move in it; the compiler's wait state follows the statement,
+// once per block.  Round 0's Q is made in front of its add3 (it reads R3 through DPP; the state was written by the block in
+// front), round 63 has no next K + W and an s_nop 0 in the slot.
 // Pairs: lane l and lane l ^ 7 (row_half_mirror: 7 - l within each eight); A lanes are those with (l & 4) == 0 (bank_mask 0x5 of an
 // identity quad_perm), so message p of the group sits in lanes 8 (p / 4) + p % 4 (A) and 8 (p / 4) + 7 - p % 4 (B).
 // The feeder wave's 64 lanes then serve two blocks of the 32 messages at once: lane l < 32 schedules block 2 j of message l, lane
@@ -737,6 +753,83 @@ __device__ __forceinline__ uint32_t sha_twin_exchange(uint32_t& r3, uint32_t u, 
       : "v"(zero));
   return n;
 }
+
+// ZKE_SHA_TWIN_NOWAIT (default 1): the round without wait states; 0 builds the round of sha_twin_exchange from the same source
+// (tools/build_variant.sh).
+#ifndef ZKE_SHA_TWIN_NOWAIT
+#define ZKE_SHA_TWIN_NOWAIT 1
+#endif
+
+// One round of the default build as asm text.  R0..R3: the registers in this round's roles; KW: the round's Q; PRE stands in front
+// of the add3 (round 0: its own Q), NEXT in the slot between N and the B lanes' N (the next round's Q, with the wait for its
+// quad where it is a quad's first word).
+#define ZKE_TW_Q(R, KW) "v_add_u32_dpp " KW ", " R ", " KW " quad_perm:[0,1,2,3] row_mask:0xf bank_mask:0x5\n\t"
+#define ZKE_TW_ROUND(R0, R1, R2, R3, KW, PRE, NEXT) \
+  "v_alignbit_b32 %[t0], " R0 ", " R0 ", %[sh0]\n\t" \
+  "v_alignbit_b32 %[t1], " R0 ", " R0 ", %[sh1]\n\t" \
+  "v_alignbit_b32 %[t2], " R0 ", " R0 ", %[sh2]\n\t" \
+  "v_bitop3_b32 %[t0], %[t0], %[t1], %[t2] bitop3:0x96\n\t" \
+  "v_bitop3_b32 %[t1], " R0 ", " R2 ", %[mb] bitop3:0x78\n\t" \
+  "v_bitop3_b32 %[t1], %[t1], " R1 ", " R2 " bitop3:0xca\n\t" \
+  PRE \
+  "v_add3_u32 %[t0], %[t0], %[t1], " KW "\n\t" \
+  "v_add_u32_dpp " R3 ", " R3 ", %[t0] row_half_mirror row_mask:0xf bank_mask:0xf\n\t" \
+  NEXT \
+  "v_add_u32_dpp " R3 ", %[t0], %[t0] row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+// Four rounds: the words of quad K0..K3, then NEXT3 (the first word of the quad behind it).  The roles rotate through the four
+// state registers and are back where they were.
+#define ZKE_TW_QUAD(K0, K1, K2, K3, PRE0, NEXT3) \
+  ZKE_TW_ROUND("%[r0]", "%[r1]", "%[r2]", "%[r3]", K0, PRE0, ZKE_TW_Q("%[r2]", K1)) \
+  ZKE_TW_ROUND("%[r3]", "%[r0]", "%[r1]", "%[r2]", K1, "", ZKE_TW_Q("%[r1]", K2)) \
+  ZKE_TW_ROUND("%[r2]", "%[r3]", "%[r0]", "%[r1]", K2, "", ZKE_TW_Q("%[r0]", K3)) \
+  ZKE_TW_ROUND("%[r1]", "%[r2]", "%[r3]", "%[r0]", K3, "", NEXT3)
+#define ZKE_TW_WAIT(N) "s_waitcnt lgkmcnt(" #N ")\n\t"
+#define ZKE_TW_READ(V, OFF) "ds_read_b128 " V ", %[src] offset:" #OFF "\n\t"
+
+// The 64 rounds of one block on r0..r3 (R0..R3), K + W from the 256 bytes at LDS address `src`.  The words go into v64..v127,
+// which the statement names itself: as components of operands the compiler would copy three words of every quad in front of the
+// statement, since the rounds add to them in place.  All 16 reads go out in front of round 0 and each quad is waited for alone, as
+// in the ring: lgkmcnt counts to 15, so the first wait (14) is for quads 0 and 1 and quad q >= 2 has arrived at 15 - q.  The
+// compiler does not see these counts, so the statement makes them its own with a wait in front of the reads: the wave's ds_write
+// of the zeros in front of block 0, and whatever else of LDS or scalar memory the code in front left counted, is done by then.
+// (Behind a block barrier its release fence has drained the counter already.)
+__device__ __forceinline__ void sha_twin_block_nowait(uint32_t& r0, uint32_t& r1, uint32_t& r2, uint32_t& r3, uint32_t src,
+                                                      uint32_t sh0, uint32_t sh1, uint32_t sh2, uint32_t maskb) {
+  uint32_t t0, t1, t2;
+  asm volatile(
+      "s_waitcnt lgkmcnt(0)\n\t"
+      ZKE_TW_READ("v[64:67]", 0) ZKE_TW_READ("v[68:71]", 16) ZKE_TW_READ("v[72:75]", 32) ZKE_TW_READ("v[76:79]", 48)
+      ZKE_TW_READ("v[80:83]", 64) ZKE_TW_READ("v[84:87]", 80) ZKE_TW_READ("v[88:91]", 96) ZKE_TW_READ("v[92:95]", 112)
+      ZKE_TW_READ("v[96:99]", 128) ZKE_TW_READ("v[100:103]", 144) ZKE_TW_READ("v[104:107]", 160) ZKE_TW_READ("v[108:111]", 176)
+      ZKE_TW_READ("v[112:115]", 192) ZKE_TW_READ("v[116:119]", 208) ZKE_TW_READ("v[120:123]", 224) ZKE_TW_READ("v[124:127]", 240)
+      ZKE_TW_QUAD("v64", "v65", "v66", "v67", ZKE_TW_WAIT(14) ZKE_TW_Q("%[r3]", "v64"), ZKE_TW_Q("%[r3]", "v68"))
+      ZKE_TW_QUAD("v68", "v69", "v70", "v71", "", ZKE_TW_WAIT(13) ZKE_TW_Q("%[r3]", "v72"))
+      ZKE_TW_QUAD("v72", "v73", "v74", "v75", "", ZKE_TW_WAIT(12) ZKE_TW_Q("%[r3]", "v76"))
+      ZKE_TW_QUAD("v76", "v77", "v78", "v79", "", ZKE_TW_WAIT(11) ZKE_TW_Q("%[r3]", "v80"))
+      ZKE_TW_QUAD("v80", "v81", "v82", "v83", "", ZKE_TW_WAIT(10) ZKE_TW_Q("%[r3]", "v84"))
+      ZKE_TW_QUAD("v84", "v85", "v86", "v87", "", ZKE_TW_WAIT(9) ZKE_TW_Q("%[r3]", "v88"))
+      ZKE_TW_QUAD("v88", "v89", "v90", "v91", "", ZKE_TW_WAIT(8) ZKE_TW_Q("%[r3]", "v92"))
+      ZKE_TW_QUAD("v92", "v93", "v94", "v95", "", ZKE_TW_WAIT(7) ZKE_TW_Q("%[r3]", "v96"))
+      ZKE_TW_QUAD("v96", "v97", "v98", "v99", "", ZKE_TW_WAIT(6) ZKE_TW_Q("%[r3]", "v100"))
+      ZKE_TW_QUAD("v100", "v101", "v102", "v103", "", ZKE_TW_WAIT(5) ZKE_TW_Q("%[r3]", "v104"))
+      ZKE_TW_QUAD("v104", "v105", "v106", "v107", "", ZKE_TW_WAIT(4) ZKE_TW_Q("%[r3]", "v108"))
+      ZKE_TW_QUAD("v108", "v109", "v110", "v111", "", ZKE_TW_WAIT(3) ZKE_TW_Q("%[r3]", "v112"))
+      ZKE_TW_QUAD("v112", "v113", "v114", "v115", "", ZKE_TW_WAIT(2) ZKE_TW_Q("%[r3]", "v116"))
+      ZKE_TW_QUAD("v116", "v117", "v118", "v119", "", ZKE_TW_WAIT(1) ZKE_TW_Q("%[r3]", "v120"))
+      ZKE_TW_QUAD("v120", "v121", "v122", "v123", "", ZKE_TW_WAIT(0) ZKE_TW_Q("%[r3]", "v124"))
+      ZKE_TW_QUAD("v124", "v125", "v126", "v127", "", "s_nop 0\n\t")
+      : [r0] "+v"(r0), [r1] "+v"(r1), [r2] "+v"(r2), [r3] "+v"(r3), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2)
+      : [src] "v"(src), [sh0] "v"(sh0), [sh1] "v"(sh1), [sh2] "v"(sh2), [mb] "v"(maskb)
+      : "memory", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79",
+        "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95",
+        "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111",
+        "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127");
+}
+#undef ZKE_TW_READ
+#undef ZKE_TW_WAIT
+#undef ZKE_TW_QUAD
+#undef ZKE_TW_ROUND
+#undef ZKE_TW_Q
 
 template <int T>
 __device__ __forceinline__ void sha256_twin_group(const ShaJob* __restrict__ jobs, uint32_t n, uint32_t group, uint8_t* lds_raw,
@@ -831,8 +924,10 @@ __device__ __forceinline__ void sha256_twin_group(const ShaJob* __restrict__ job
   }
   const uint32_t sh0 = is_b ? SHA_TWIN_SH[1][0] : SHA_TWIN_SH[0][0], sh1 = is_b ? SHA_TWIN_SH[1][1] : SHA_TWIN_SH[0][1];
   const uint32_t sh2 = is_b ? SHA_TWIN_SH[1][2] : SHA_TWIN_SH[0][2], maskb = is_b ? SHA_TWIN_MASKB[1] : SHA_TWIN_MASKB[0];
+#if !ZKE_SHA_TWIN_NOWAIT
   uint32_t zero = 0;
   asm volatile("" : "+v"(zero));                    // a register of its own, not a literal in the asm
+#endif
   if (lane < 16) ((uint4*)zeros)[lane] = make_uint4(0, 0, 0, 0);
   ZKE_SHA_WHERE();
   block_barrier();                                  // barrier -1 (the zeros are this wave's own: in order behind its store)
@@ -840,6 +935,10 @@ __device__ __forceinline__ void sha256_twin_group(const ShaJob* __restrict__ job
     ZKE_SHA_STAMP(kb, 0);
     const uint4* src = is_b ? (const uint4*)zeros
                             : (const uint4*)(kw + ((kb >> 1) & 1) * KW_BUF + ((kb & 1) * 32 + pos) * SHA_KW_ROW);
+#if ZKE_SHA_TWIN_NOWAIT
+    uint32_t r0 = st[0], r1 = st[1], r2 = st[2], r3 = st[3];
+    sha_twin_block_nowait(r0, r1, r2, r3, (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint4*)src, sh0, sh1, sh2, maskb);
+#else
     uint4 kq[16];                                   // all 16 reads go out here; each round group waits for its own quad only
 #pragma unroll
     for (int q = 0; q < 16; q++) kq[q] = src[q];
@@ -857,6 +956,7 @@ __device__ __forceinline__ void sha256_twin_group(const ShaJob* __restrict__ job
       const uint32_t nw = sha_twin_exchange(r3, u, zero);
       r3 = r2; r2 = r1; r1 = r0; r0 = nw;
     }
+#endif
     if (kb < J.nblk) { st[0] += r0; st[1] += r1; st[2] += r2; st[3] += r3; }
     ZKE_SHA_STAMP(kb, 1);
     if ((kb & 1) || kb + 1 == max_nblk) block_barrier();       // barrier kb / 2: the pass is read
