@@ -620,6 +620,100 @@ int main(int argc, char** argv) {
     for (int i = 1; i <= 1000; i++) off[i] = off[i - 1] + (rng() % 3 == 0 ? 0 : rng() % 100000);
     for (uint32_t w : {1u, 2u, 3u, 8u}) { if (zke_shard_bounds(off.data(), 1000, w, bounds) != 0 || bounds[w] != 1000) return 1; for (uint32_t r = 0; r < w; r++) if (bounds[r] > bounds[r + 1]) return 1; }
     (void)image_layout(0, 0, 0, 0, 0, 0, 0);
+    // ---- the plan sections of an image (host_stage.hip.h): {no plan, a mixed batch, a mixed batch + a mixed extraction} x {no encoding,
+    // a host-planned one, a device-planned one} over n = 0, 1, 2, 65, with and without external inputs; the mixed batch alone has a
+    // config without parts (an extraction's configs cannot).  The descriptor is built as the entries build it, laid out once, and then:
+    // the sections lie inside [L.mixed, L.raw) one behind the other, the encoding's starts 64-byte aligned, and what stage_* puts into a
+    // heap buffer of exactly the section's size, *_view on the same base hands back: equal to the plan's arrays.  The same through ONE
+    // buffer of exactly the sections' total, each section at its offset: no stage_* writes into a neighbour.
+    for (uint32_t n : {0u, 1u, 2u, 65u})
+      for (int plan_kind = 0; plan_kind < 3; plan_kind++)
+        for (int enc_kind = 0; enc_kind < 3; enc_kind++)
+          for (uint32_t ext_strs : {0u, 5u}) {
+            if ((!enc_kind || !n) && ext_strs) continue;                               // (the strings are the e-mails': ext_off[n] of them)
+            auto bad = [&](const char* what) { fprintf(stderr, "plan sections: n %u plan %d enc %d ext %u: %s\n", n, plan_kind, enc_kind, ext_strs, what); exit(1); };
+            // the e-mails, and configs of {2 header + 1 body parts, none (an extraction: 1 header part), 2 body parts}; every fourth e-mail has no config
+            std::vector<std::vector<uint8_t>> raw(n);
+            std::vector<zke_email_ref> refs(n);
+            std::vector<zke_result> out(n);
+            for (uint32_t i = 0; i < n; i++) { raw[i].assign(1 + rng() % 90, (uint8_t)i); refs[i] = zke_email_ref{raw[i].data(), raw[i].size(), nullptr, 0, nullptr, 0, ZKE_KEY_RSA, 0}; }
+            const std::vector<MixedConfigIn> counts{{2, 1}, {plan_kind == 2 ? 1u : 0u, 0}, {0, 2}};
+            const std::vector<uint32_t> ids{3, 1, 4, 1, 5, 9};
+            std::vector<zke_regex_config> cfgs;
+            for (size_t c = 0, at = 0; c < counts.size(); at += counts[c].n_header_parts + counts[c].n_body_parts, c++)
+              cfgs.push_back(zke_regex_config{counts[c].n_header_parts, ids.data() + at, counts[c].n_body_parts, ids.data() + at + counts[c].n_header_parts});
+            std::vector<uint32_t> config_of(n);
+            for (uint32_t i = 0; i < n; i++) config_of[i] = i % 4 == 3 ? ZKE_CONFIG_NONE : i % 3;
+            const zke_regex_mixed zm{(uint32_t)cfgs.size(), cfgs.data(), config_of.data(), nullptr, nullptr, nullptr};
+            zke_engine eng;                                                            // an empty registry: every part resolves to "not registered"
+            CapMixedReq cq;
+            MixedReq& mq = cq.verify;
+            if (plan_kind && (mixed_request("plan sections", &zm, n, mq) || mixed_resolve(&eng, mq))) bad(g_err.c_str());
+            if (plan_kind == 2) {
+              std::vector<uint32_t> groups(mq.shape.n_segs);
+              for (auto& g : groups) g = (uint32_t)(rng() % 4);
+              if (const char* why = capmix_plan_build(config_of.data(), n, counts.data(), zm.n_configs, groups.data(), cq.plan)) bad(why);
+              cq.lists = zm;
+              cq.part.resize(cq.plan.shape.n_parts);
+              for (auto& p : cq.part) { uint8_t* q = reinterpret_cast<uint8_t*>(&p); for (size_t k = 0; k < sizeof p; k++) q[k] = (uint8_t)rng(); }
+            }
+            // the encoding: five external strings in all (or none), n jobs of a host plan or ext_off[n + 1] of a device plan
+            EncodeReq eq;
+            std::vector<uint32_t> ext_off(n + 1, 0), ext_str_off(ext_strs + 1, 0);
+            for (uint32_t i = 0; i < n; i++) ext_off[i + 1] = i + 1 == n ? ext_strs : std::min(ext_strs, ext_off[i] + (uint32_t)(rng() % 3));
+            for (uint32_t k = 0; k < ext_strs; k++) ext_str_off[k + 1] = ext_str_off[k] + (uint32_t)(rng() % 40);
+            std::vector<uint8_t> ext_blob(ext_str_off[ext_strs]);
+            for (auto& c : ext_blob) c = (uint8_t)rng();
+            eq.ext_str_off = ext_str_off.data(); eq.ext_blob = ext_blob.data();
+            eq.plan.ext_strs = ext_strs; eq.plan.ext_bytes = (uint32_t)ext_blob.size();
+            eq.device_plan = enc_kind == 2; eq.n = n; eq.ext_off = ext_off.data();
+            if (enc_kind == 1) { eq.plan.jobs.resize(n); for (auto& j : eq.plan.jobs) { j = EncodeJob{}; j.enc_off = rng(); } }
+            HostBatch d;
+            // (an entry with an encoding lays the image out itself, once d.enc is set; every other one leaves that to host_batch)
+            if (host_batch(d, "plan sections", out.data(), refs.data(), n, nullptr, plan_kind ? &mq : nullptr, plan_kind == 2 ? &cq : nullptr, !enc_kind)) bad(g_err.c_str());
+            if (enc_kind) { d.enc = &eq; layout_host_batch(d); }
+            // where the sections lie
+            const PlanSections& S = d.S;
+            const ImageLayout& L = d.L;
+            if (L.mixed + S.total > L.raw || S.mixed.total > S.capmix_at || S.capmix_at + S.capmix.total > S.enc_at || S.enc_at + S.enc.total != S.total)
+              bad("a section leaves [L.mixed, L.raw) or overlaps its neighbour");
+            if ((L.mixed + S.enc_at) % 64) bad("the encoding's section does not start 64-byte aligned");
+            if ((!plan_kind && S.mixed.total) || (plan_kind != 2 && S.capmix.total) || (!enc_kind && S.enc.total)) bad("a section has bytes without a request");
+            const ImageLayout bare = image_layout(n, d.raw_total, 0, 0, 0, 0, 0);
+            if (!plan_kind && !enc_kind && (S.total || memcmp(&L, &bare, sizeof L))) bad("an image without a plan has plan bytes");
+            // the round trip: what *_view names from a section's base against the plan's arrays
+            auto same = [](const void* got, const auto& want) { return want.empty() || !memcmp(got, want.data(), want.size() * sizeof want[0]); };
+            auto mixed_back = [&](const uint8_t* base) {
+              const MixedLaunch ml = mixed_view(base, S.mixed, &mq.plan);
+              return ml.plan == &mq.plan && same(ml.job_off, mq.plan.job_off) && same(ml.email_cfg, mq.plan.email_cfg) && same(ml.perm, mq.plan.perm) &&
+                     same(ml.segs, mq.plan.segs) && mq.plan.job_off.size() == (size_t)n + 1 && mq.plan.segs.size() == mq.shape.n_segs;
+            };
+            auto capmix_back = [&](const uint8_t* base) {
+              const uint32_t* job_off = mq.plan.job_off.data();
+              const CapMixedTables t = capmix_view(base, S.capmix, job_off);
+              return t.job_off == job_off && same(t.col_off, cq.plan.col_off) && same(t.cap_cfg, cq.plan.cap_cfg) && same(t.cfgs, cq.plan.cfgs) && same(t.part, cq.part) &&
+                     cq.part.size() == mq.shape.n_segs;
+            };
+            auto enc_back = [&](const uint8_t* base) {
+              const EncodeArgs a = enc_view(base, S.enc);
+              return (enc_kind != 1 || (same(a.jobs, eq.plan.jobs) && eq.plan.jobs.size() == n)) && (enc_kind != 2 || !ext_strs || same(a.jobs, ext_off)) &&
+                     (!ext_strs || same(a.ext_str_off, ext_str_off)) && same(a.ext_blob, ext_blob);
+            };
+            auto stage_enc_of = [&](uint8_t* base) { stage_enc(base, S.enc, eq.plan, eq.device_plan, eq.ext_off, n, eq.ext_str_off, eq.ext_blob); };
+            // ... each section alone in a heap buffer of exactly its size (a write or a read past it trips ASan) ...
+            std::vector<uint8_t> bm(S.mixed.total, 0xEE), bc(S.capmix.total, 0xEE), be(S.enc.total, 0xEE);
+            if (plan_kind) { stage_mixed(bm.data(), S.mixed, mq.plan); if (!mixed_back(bm.data())) bad("the mixed plan's round trip"); }
+            if (plan_kind == 2) { stage_capmix(bc.data(), S.capmix, cq.plan, cq.part); if (!capmix_back(bc.data())) bad("the mixed extraction's round trip"); }
+            if (enc_kind) { stage_enc_of(be.data()); if (!enc_back(be.data())) bad("the encoding's round trip"); }
+            // ... and all of them in one buffer of exactly their total, each at its offset: first everything is staged, then everything is read
+            std::vector<uint8_t> all(S.total, 0xEE);
+            if (plan_kind) stage_mixed(all.data(), S.mixed, mq.plan);
+            if (plan_kind == 2) stage_capmix(all.data() + S.capmix_at, S.capmix, cq.plan, cq.part);
+            if (enc_kind) stage_enc_of(all.data() + S.enc_at);
+            if ((plan_kind && !mixed_back(all.data())) || (plan_kind == 2 && !capmix_back(all.data() + S.capmix_at)) || (enc_kind && !enc_back(all.data() + S.enc_at)))
+              bad("a section staged at its offset was overwritten by a neighbour");
+            cases++;
+          }
     (void)pair_hash(nullptr, 0, nullptr, 0);
     uint8_t x[17] = {1, 2, 3};
     if (pair_hash(x, 17, x, 3) == pair_hash(x, 16, x, 3)) return 1;

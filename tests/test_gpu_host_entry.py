@@ -502,3 +502,95 @@ def test_every_side_output_in_turn_on_one_slot():
             assert_records_equal(got["recs"], want["recs"], None, f"verify, {slots} slot(s)")
         finally:
             eng.close()
+
+
+def _capture_mixed(eng, refs, lists, ticket):
+    """zke_extract_captures_mixed[_async] with origins through the C entry, into buffers sized once (64 bytes of blob per column)."""
+    n, J, Gt = refs.n, lists.J, lists.Gt
+    st = dict(out=np.zeros(max(n, 1), dtype=A.RESULT_DTYPE), spans=np.zeros(max(Gt * 2, 1), np.uint32), flags=np.zeros(max(Gt, 1), np.uint8),
+              cap_off=np.zeros(J + 1, np.uint32), cap_str_off=np.zeros(Gt + 1, np.uint32), blob=np.zeros(max(64 * Gt, 1), np.uint8),
+              ospans=np.full(max(Gt * 2, 1), 0x55555555, np.uint32), oflags=np.full(max(Gt, 1), 0x55, np.uint8), keep=(refs, lists))
+    o, org = A.zke_capture_out(), A.zke_capture_origin()
+    o.spans, o.spans_cap, o.flags, o.flags_cap = st["spans"].ctypes.data, Gt * 2, st["flags"].ctypes.data, Gt
+    o.cap_off, o.cap_off_cap, o.cap_str_off, o.cap_str_off_cap = st["cap_off"].ctypes.data, J + 1, st["cap_str_off"].ctypes.data, Gt + 1
+    o.cap_blob, o.cap_blob_cap = st["blob"].ctypes.data, 64 * Gt
+    org.spans, org.spans_cap, org.flags, org.flags_cap = st["ospans"].ctypes.data, Gt * 2, st["oflags"].ctypes.data, Gt
+    st["o"], st["org"], st["ticket"] = o, org, C.c_uint64()
+    args = [eng.h, refs.arr, n, C.byref(lists.c), st["out"].ctypes.data, C.byref(o), C.byref(org)]
+    name = "zke_extract_captures_mixed" + ("_async" if ticket else "")
+    assert getattr(eng.lib, name)(*(args + ([C.byref(st["ticket"])] if ticket else []))) == 0, eng.lib.zke_last_error(None)
+    st["read"] = lambda: dict(out=st["out"][:n].tobytes(), spans=st["spans"][:Gt * 2].tolist(), flags=st["flags"][:Gt].tolist(), cap_off=st["cap_off"].tolist(),
+                              cap_str_off=st["cap_str_off"][:int(o.n_strings) + 1].tolist(), blob=st["blob"][:int(o.cap_blob_need)].tobytes(),
+                              ospans=st["ospans"][:Gt * 2].tolist(), oflags=st["oflags"][:Gt].tolist())
+    return st
+
+
+def test_every_plan_section_in_turn_on_one_slot():
+    """Every kind of plan section through ONE slot, one after the other, none waited for: a mixed verify (the mixed plan), a mixed
+    extraction with origins through the C entry (the plan and the extraction's tables), a plain verify — an image without a plan
+    section behind two with —, an encoded mixed verify (the plan and a host-planned encoding) and an extraction with a device-planned
+    encoding — each retired by the submission behind it, the last by its wait.  Every output equals what the synchronous entry
+    returns for the same call on a fresh engine.  Then the same sequence through two slots, waited for in reverse order.  A section
+    staged at the wrong offset of the image, or viewed from a stale one, shows here as wrong bytes.  Five e-mails of the case list,
+    the three signed ones in front; two regex configs and one e-mail without; every other e-mail has an external input."""
+    import dataclasses
+    import zkemail_rs_amd as z
+    from zkemail_rs_amd import regex_compile as rc
+    every = cases.build_cases()
+    good = [x for x in every if x.status == A.ZKE_OK and x.email.public_key.key_type == "rsa"][:3]
+    more = [x for x in every if all(x is not g for g in good)][:2]
+    assert len(good) == 3 and len(more) == 2
+    emails = [dataclasses.replace(x.email, external_inputs=[A.ExternalInput("order", "no-%d" % i, 16)] if i % 2 == 0 else [])
+              for i, x in enumerate(good + more)]
+    P = rc.RegexPattern
+    subject = P(*synth.HEADER_PATTERNS[1])
+    cfg_a, cfg_b = rc.RegexConfig([subject], [P(*_body_word_pattern(good[0]))]), rc.RegexConfig([subject], None)
+    configs = [cfg_a, cfg_b, None, cfg_a, cfg_b]
+    roomy = dict(unicode=False, blob_bytes=1 << 12, bytes_cap=1 << 14)
+
+    fresh = z.Engine()
+    try:
+        # the inputs of the verify entries: every e-mail with the RegexInfo its config extracts from it ("?" where it extracts nothing)
+        _, found = fresh.extract_captures_mixed(emails, configs, unicode=False)
+        def info(cfg, got):
+            side = lambda parts: None if parts is None else [A.CompiledRegex(fresh.compile_pattern(p.pattern, False)[0], ["?"] * len(p.capture_indices or []))
+                                                               for p in parts]
+            return got if got is not None else A.RegexInfo(side(cfg.header_parts), side(cfg.body_parts))
+        inputs = [e if cfg is None else A.EmailWithRegex(e, info(cfg, got)) for e, cfg, got in zip(emails, configs, found)]
+        xe = fresh.extract_captures_encoded_call(emails, cfg_b, **roomy)
+        assert xe.rc == 0
+        enc = fresh.verify_emails_encoded(inputs, form="mixed")
+        want = dict(mixed=fresh.verify_emails_mixed(inputs), capmix=_capture_mixed(fresh, A.EmailRefs(emails), fresh.pack_capture_mixed(configs, unicode=False)[0], False)["read"](),
+                    plain=fresh.verify_emails(emails), enc_recs=enc[0], enc=enc[1], xe_recs=xe.records, xe=xe.enc.result(), xe_strings=xe.strings(),
+                    xe_needs=(int(xe.caps.cap_blob_need), int(xe.enc.c.bytes_need)))
+    finally:
+        fresh.close()
+    # the inputs do what they are there for: an e-mail with a config and the one without verify, strings are captured, encodings come out
+    assert [int(want["mixed"]["status"][i]) for i in (0, 2)] == [A.ZKE_OK] * 2 and [int(s) for s in want["plain"]["status"][:3]] == [A.ZKE_OK] * 3
+    assert found[0] is not None and len(found[0].body_parts[0].captures) == 1 and found[2] is None
+    assert all(len(want[k][0][0]) > 0 for k in ("enc", "xe")) and len(want["enc"][2][0]) > 0 and len(want["xe_strings"][0]) == 1
+
+    for slots, reverse in ((1, False), (2, True)):
+        eng = z.Engine(slots=slots)
+        try:
+            lists = eng.pack_capture_mixed(configs, unicode=False)[0]
+            t1, mixed = eng.verify_emails_mixed_async(inputs)
+            capmix = _capture_mixed(eng, A.EmailRefs(emails), lists, True)
+            refs = A.EmailRefs(emails)
+            t3, plain = eng.verify_emails_async(refs)
+            t4, enc = eng.verify_emails_encoded_async(inputs, form="mixed")
+            xe = eng.extract_captures_encoded_call(emails, cfg_b, ticket=True, **roomy)
+            assert xe.rc == 0
+            tickets = [t1, capmix["ticket"].value, t3, t4, xe.ticket]
+            for t in (reversed(tickets) if reverse else tickets):
+                assert eng.lib.zke_batch_wait(eng.h, t) == 0, (slots, t)
+            assert_records_equal(mixed, want["mixed"], None, f"mixed verify, {slots} slot(s)")
+            assert capmix["read"]() == want["capmix"], slots
+            assert_records_equal(plain, want["plain"], None, f"plain verify, {slots} slot(s)")
+            assert_records_equal(enc.records, want["enc_recs"], None, f"encoded verify, {slots} slot(s)")
+            assert enc.enc.result() == want["enc"], slots
+            assert_records_equal(xe.records, want["xe_recs"], None, f"encoded extraction, {slots} slot(s)")
+            assert xe.enc.result() == want["xe"] and xe.strings() == want["xe_strings"], slots
+            assert (int(xe.caps.cap_blob_need), int(xe.enc.c.bytes_need)) == want["xe_needs"], slots
+        finally:
+            eng.close()

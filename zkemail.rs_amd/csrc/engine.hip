@@ -279,7 +279,9 @@ int set_kernel_attrs(zke_engine* e) {
 
 #include "pipeline.hip.h"
 #include "registry.hip.h"
+#include "host_deliver.hip.h"
 #include "host_entry.hip.h"
+#include "host_blocks.hip.h"
 #include "wire.hip.h"
 
 extern "C" {

@@ -1,7 +1,8 @@
 // host_entry.hip.h — the entries whose batch lies in host memory: the batch descriptor and its checks, the packed image into a
-// slot (host_stage.hip.h), upload, launches (pipeline.hip.h), delivery into the caller's buffers.  Stands for the reference's
-// callers, `&[Email]` into verify_email / verify_email_with_regex (core/src/circuits.rs:9-68), and for what comes before a key is
-// known: scan, key records, selection, captures.  Included by engine.hip behind pipeline.hip.h and registry.hip.h (one translation unit).
+// slot (host_stage.hip.h), upload, launches (pipeline.hip.h), and the slot's debt of a delivery into the caller's buffers
+// (host_deliver.hip.h).  Stands for the reference's callers, `&[Email]` into verify_email / verify_email_with_regex
+// (core/src/circuits.rs:9-68), and for what comes before a key is known: scan, key records, selection, captures.  Included by engine.hip
+// behind pipeline.hip.h, registry.hip.h and host_deliver.hip.h (one translation unit); the synchronous building blocks: host_blocks.hip.h.
 #pragma once
 
 #ifndef ZKE_HOST_COPY_STREAM
@@ -50,10 +51,7 @@ int mixed_resolve(zke_engine* e, MixedReq& q) {
     for (uint32_t c = 0; c < q.in->n_configs; c++) {
       const zke_regex_config& cf = q.in->configs[c];
       for (uint32_t p = 0; p < cf.n_header_parts + cf.n_body_parts; p++) {
-        const uint32_t id = p >= cf.n_header_parts ? cf.body_part_ids[p - cf.n_header_parts] : cf.header_part_ids[p];
-        const RegisteredDfa* rd = id < e->dfas.size() ? e->dfas[id] : nullptr;
-        PartInfo pi{};
-        if (rd) { pi.detail = rd->detail; pi.lds_bytes = rd->lds_bytes; pi.idle = rd->idle; pi.dev = rd->valid ? rd->dev.as<RegexDev>() : nullptr; }
+        const PartInfo pi = part_info(e, p >= cf.n_header_parts ? cf.body_part_ids[p - cf.n_header_parts] : cf.header_part_ids[p]);
         parts.push_back(MixedPartIn{(uint64_t)(uintptr_t)pi.dev, pi.lds_bytes, pi.idle, pi.detail});
       }
     }
@@ -105,241 +103,6 @@ struct EncodeReq {
   EncImage image() const { return enc_image(device_plan ? n : (uint32_t)plan.jobs.size(), plan.ext_strs, plan.ext_bytes); }
 };
 
-// A slot's buffers for one side output of a batch of n: the layout, then the buffers it asks for (ensure_side_buffers).
-// `pack`: zke_select_keys_from_records, the decoded keys are packed for the front end.
-int ensure_keyrec_buffers(zke_engine* e, KeyrecBufs& b, uint32_t m, size_t rec_total, bool pack) {
-  b.L = keyrec_layout(m, rec_total);
-  return ensure_side_buffers(e, b.t, b.L.total, b.L.total, pack ? &b.pack : nullptr, b.L.p_total, "key-record buffer allocation");
-}
-int ensure_body_buffers(zke_engine* e, BodyBufs& b, uint32_t n, size_t raw_total) {
-  b.L = body_layout(n, raw_total);
-  return ensure_side_buffers(e, b.t, b.L.total, b.L.total, &b.ovf, (size_t)n * HDR_OVF_BYTES, "body-extraction buffer allocation");
-}
-// `staged`: bytes of the building block's input (zke_encode_outputs), 0 where the batch's image carries it
-int ensure_encode_buffers(zke_engine* e, EncBufs& b, uint32_t n, uint64_t blob, size_t staged) {
-  b.L = enc_layout(n, blob);
-  return ensure_side_buffers(e, b.t, b.L.total, b.L.prefix, staged ? &b.in : nullptr, staged, "output-encoding buffer allocation");
-}
-// a device-planned encoding: `cap` bytes of encodings, the jobs behind them, the infos alone pinned
-int ensure_encode_buffers_planned(zke_engine* e, EncBufs& b, uint32_t n, uint64_t cap) {
-  b.L = enc_layout_planned(n, cap, b.jobs_at);
-  return ensure_side_buffers(e, b.t, b.L.total, b.L.bytes, nullptr, 0, "output-encoding buffer allocation");
-}
-// max_sigs record slots per e-mail and the caller's sel_blob_cap bytes of selectors (a selector is at most ZKE_MAX_TAGBUF bytes: a
-// larger blob than that per record slot is never used)
-int ensure_scan_buffers(zke_engine* e, ScanBufs& b, uint32_t n, uint32_t max_sigs, size_t sel_blob_cap) {
-  b.L = scan_layout(n, max_sigs, std::min<size_t>(sel_blob_cap, (size_t)n * max_sigs * ZKE_MAX_TAGBUF));
-  return ensure_side_buffers(e, b.t, b.L.total, b.L.total, &b.ovf, (size_t)n * HDR_OVF_BYTES, "signature-scan buffer allocation");
-}
-// `launched`: capture_origin_kernel runs for this batch; where it does not, nothing is allocated
-int ensure_origin_buffers(zke_engine* e, OriginBufs& b, size_t NG, bool launched) {
-  b.L = origin_layout_sized(NG);
-  b.launched = launched;
-  return b.launched ? ensure_side_buffers(e, b.t, b.L.total, b.L.total, nullptr, 0, "capture-origin buffer allocation") : 0;
-}
-
-// An extraction's tables from the slot's pinned twin (and the blob from HBM) into the caller's zke_capture_out.  Returns
-// ZKE_E_NOMEM when the caller's cap_blob is too small for the strings (everything else is delivered; cap_blob_need says how much).
-int deliver_captures(zke_engine* e, CapBufs& b, zke_capture_out* o, hipStream_t s) {
-  const CapLayout& L = b.L;
-  const uint8_t* hp = b.t.h.as<uint8_t>();
-  const uint64_t* hdr = reinterpret_cast<const uint64_t*>(hp + L.hdr);
-  const size_t strings = (size_t)hdr[0], bytes = (size_t)hdr[1];
-  memcpy(o->spans, hp + L.spans, o->spans_need * 4);
-  memcpy(o->flags, hp + L.flags, o->flags_need);
-  memcpy(o->cap_off, hp + L.cap_off, o->cap_off_need * 4);
-  memcpy(o->cap_str_off, hp + L.cap_str_off, (strings + 1) * 4);
-  o->n_strings = strings;
-  o->cap_blob_need = bytes;
-  const size_t take = std::min(bytes, L.blob_cap);
-  if (take) {
-    HIPCHK(e, hipMemcpyAsync(o->cap_blob, b.t.d.as<uint8_t>() + L.blob, take, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-  }
-  if (bytes > L.blob_cap) return fail(e, ZKE_E_NOMEM, "capture extraction: cap_blob is smaller than the strings (zke_capture_out.cap_blob_need)");
-  return 0;
-}
-
-// A mapped extraction's origins into the caller's zke_capture_origin: from the slot's pinned twin where capture_origin_kernel ran,
-// else (no body part asks for a group) the spans themselves, which the capture buffer's pinned twin holds, and no flag.
-void deliver_origins(const CapBufs& b, const OriginBufs& ob, zke_capture_origin* o) {
-  const OriginLayout& L = ob.L;
-  if (!L.NG) return;
-  if (ob.launched) {
-    const uint8_t* hp = ob.t.h.as<uint8_t>();
-    memcpy(o->spans, hp, L.NG * 8);
-    memcpy(o->flags, hp + L.flags, L.NG);
-  } else {
-    memcpy(o->spans, b.t.h.as<uint8_t>() + b.L.spans, L.NG * 8);
-    memset(o->flags, 0, L.NG);
-  }
-}
-
-// A scan from the slot's pinned twin into the caller's zke_sig_scan: statuses, the CSR over the record slots in use (the
-// compaction: one memcpy per e-mail), the selector bytes.  ZKE_E_NOMEM when sigs or sel_blob is too small (*_need says how much).
-int deliver_scan(zke_engine* e, const ScanBufs& b, zke_sig_scan* o) {
-  const ScanLayout& S = b.L;
-  const uint8_t* hp = b.t.h.as<uint8_t>();
-  const uint32_t* st = reinterpret_cast<const uint32_t*>(hp + S.status);
-  const zke_sig_info* recs = reinterpret_cast<const zke_sig_info*>(hp + S.recs);
-  const size_t used = *reinterpret_cast<const uint32_t*>(hp);
-  memcpy(o->scan_status, st, (size_t)S.n * 16);
-  size_t total = 0;
-  for (uint32_t i = 0; i < S.n; i++) { o->sig_off[i] = (uint32_t)total; total += std::min(st[4 * (size_t)i + 2], S.max_sigs); }
-  o->sig_off[S.n] = (uint32_t)total;
-  o->sigs_need = total; o->sel_blob_need = used; o->n_sigs = 0;
-  if (total > o->sigs_cap) return fail(e, ZKE_E_NOMEM, "signature scan: sigs is smaller than the records (zke_sig_scan.sigs_need)");
-  for (uint32_t i = 0; i < S.n; i++)
-    if (const uint32_t c = o->sig_off[i + 1] - o->sig_off[i]) memcpy(o->sigs + o->sig_off[i], recs + (size_t)i * S.max_sigs, (size_t)c * sizeof(zke_sig_info));
-  o->n_sigs = total;
-  if (used > S.blob_cap) return fail(e, ZKE_E_NOMEM, "signature scan: sel_blob is smaller than the selectors (zke_sig_scan.sel_blob_need)");
-  if (used) memcpy(o->sel_blob, hp + S.blob, used);
-  return 0;
-}
-
-// A decode from the slot's pinned twin into the caller's zke_keyrec_out: the infos with key_off rewritten to the packed offsets,
-// the key bytes compacted (one memcpy per key).  ZKE_E_NOMEM when keys is too small (keys_need says how much).
-int deliver_keyrec(zke_engine* e, const KeyrecBufs& b, zke_keyrec_out* o) {
-  const KeyrecLayout& K = b.L;
-  const uint8_t* hp = b.t.h.as<uint8_t>();
-  const zke_key_info* src = reinterpret_cast<const zke_key_info*>(hp);
-  size_t total = 0;
-  for (uint32_t i = 0; i < K.m; i++) {
-    zke_key_info f = src[i];
-    if (f.code) f.key_len = 0;
-    f.key_off = (uint32_t)total;
-    total += f.key_len;
-    o->infos[i] = f;
-  }
-  o->keys_need = total;
-  if (total > o->keys_cap) return fail(e, ZKE_E_NOMEM, "key records: keys is smaller than the decoded keys (zke_keyrec_out.keys_need)");
-  for (uint32_t i = 0; i < K.m; i++)
-    if (o->infos[i].key_len) memcpy(o->keys + o->infos[i].key_off, hp + K.keys + src[i].key_off, o->infos[i].key_len);
-  return 0;
-}
-
-// An extraction from the slot's pinned twin into the caller's zke_body_out (host_stage.hip.h: body_measure, body_compact): the infos
-// with body_off rewritten to the packed offsets, the bodies compacted.  The second places (bodies that outgrew their e-mail) are
-// fetched only when one is in use.  ZKE_E_NOMEM when bytes is too small (bytes_need says how much).
-int deliver_body(zke_engine* e, const BodyBufs& b, zke_body_out* o, hipStream_t s) {
-  const BodyLayout& K = b.L;
-  uint8_t* hp = b.t.h.as<uint8_t>();
-  bool spilled = false;
-  const int r = body_measure(K, hp, o, spilled);
-  if (r == ZKE_E_DEVICE) return fail(e, r, "body extraction: an info points outside its e-mail's place");
-  if (r) return fail(e, r, "body extraction: bytes is smaller than the decoded bodies (zke_body_out.bytes_need)");
-  if (spilled) {
-    HIPCHK(e, hipMemcpyAsync(hp + K.first_copy, b.t.d.as<uint8_t>() + K.first_copy, K.region, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-  }
-  body_compact(K, hp, o);
-  return 0;
-}
-
-// The encodings from the slot's pinned twin into the caller's zke_encoded_out (both buffers were checked against the plan's exact
-// sizes before the batch was staged): the infos as they are, the bytes in runs of encoded e-mails that follow each other — the place
-// of an e-mail that was not encoded holds whatever the slot's buffer held, and the caller's bytes stay as they were there.  An info
-// that points outside the blob is refused and nothing is read through it.
-int deliver_encoded(zke_engine* e, const EncBufs& b, zke_encoded_out* o) {
-  const EncLayout& K = b.L;
-  const uint8_t* hp = b.t.h.as<uint8_t>();
-  const zke_encoded_info* src = reinterpret_cast<const zke_encoded_info*>(hp);
-  for (uint32_t i = 0; i < K.n; i++)
-    if (src[i].off > K.blob || src[i].len > K.blob - src[i].off) return fail(e, ZKE_E_DEVICE, "output encoding: an info points outside the blob");
-  if (K.n) memcpy(o->infos, src, (size_t)K.n * sizeof(zke_encoded_info));
-  uint64_t r0 = 0, r1 = 0;
-  auto flush = [&] { if (r1 > r0) memcpy(o->bytes + r0, hp + K.bytes + r0, (size_t)(r1 - r0)); };
-  for (uint32_t i = 0; i < K.n; i++) {
-    if (!src[i].len) continue;
-    if (src[i].off != r1) { flush(); r0 = src[i].off; }
-    r1 = src[i].off + src[i].len;
-  }
-  flush();
-  return 0;
-}
-
-// The encodings of a device-planned batch (zke_extract_captures_encoded): the infos from the slot's pinned twin, the exact needs from
-// the gather launch's header (the capture buffer's twin), then the bytes from HBM in runs of written e-mails that follow each other,
-// as deliver_encoded copies them: a complete batch is ONE run from 0, of exactly its size; where an e-mail had no room (its place is
-// kept, nothing of it was written) the run ends, and the caller's bytes stay as they were there.  ZKE_E_NOMEM when bytes is too small for the
-// encodings (bytes_need says how much) or the strings did not fit their blob (the e-mails concerned have len 0): infos and needs
-// are delivered all the same.  An info that points outside the device blob is refused and nothing is read through it.
-int deliver_encoded_planned(zke_engine* e, const EncBufs& b, const CapBufs& cb, zke_encoded_out* o, hipStream_t s) {
-  const EncLayout& K = b.L;
-  const zke_encoded_info* src = reinterpret_cast<const zke_encoded_info*>(b.t.h.as<uint8_t>());
-  const uint64_t* hdr = reinterpret_cast<const uint64_t*>(cb.t.h.as<uint8_t>() + cb.L.hdr);
-  for (uint32_t i = 0; i < K.n; i++) {
-    if (!src[i].len) continue;          // (its off is the planned place, which may lie beyond a blob that is too small)
-    if (src[i].off > K.blob || src[i].len > K.blob - src[i].off) return fail(e, ZKE_E_DEVICE, "output encoding: an info points outside the blob");
-  }
-  if (K.n) memcpy(o->infos, src, (size_t)K.n * sizeof(zke_encoded_info));
-  o->infos_need = K.n; o->bytes_need = (size_t)hdr[2];
-  uint64_t r0 = 0, r1 = 0;
-  bool copied = false;
-  hipError_t he = hipSuccess;
-  auto flush = [&] {
-    if (r1 > r0 && he == hipSuccess) { he = hipMemcpyAsync(o->bytes + r0, b.t.d.as<uint8_t>() + K.bytes + r0, (size_t)(r1 - r0), hipMemcpyDeviceToHost, s); copied = true; }
-  };
-  for (uint32_t i = 0; i < K.n; i++) {
-    if (!src[i].len) continue;
-    if (src[i].off != r1) { flush(); r0 = src[i].off; }
-    r1 = src[i].off + src[i].len;
-  }
-  flush();
-  if (copied) {
-    const hipError_t hs = hipStreamSynchronize(s);      // also behind a failed copy: none outlives the caller's buffer
-    if (he != hipSuccess || hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "output encoding: copy", he != hipSuccess ? he : hs);
-  }
-  if (hdr[2] > K.blob) return fail(e, ZKE_E_NOMEM, "output encoding: bytes is smaller than the encodings (zke_encoded_out.bytes_need)");
-  if (hdr[1] > cb.L.blob_cap) return fail(e, ZKE_E_NOMEM, "output encoding: the capture strings did not fit cap_blob (zke_capture_out.cap_blob_need)");
-  return 0;
-}
-
-// A key selection's fold: the records of the (e-mail, candidate) pairs are in the pinned buffer; per e-mail the first ZKE_OK.
-void fold_selection(const zke_result* R, const std::vector<uint32_t>& off, zke_result* out, uint32_t* chosen) {
-  for (size_t i = 0; i + 1 < off.size(); i++) {
-    const uint32_t a = off[i], b = off[i + 1];
-    if (a == b) {
-      memset(&out[i], 0, sizeof(zke_result));
-      out[i].status = ZKE_DKIM_NOT_PASS; out[i].detail = ZKE_D_NEUTRAL;
-      chosen[i] = ZKE_SEL_NONE;
-      continue;
-    }
-    uint32_t pick = ZKE_SEL_NONE, flag = 0;
-    for (uint32_t k = a; k < b; k++) {
-      if (R[k].status == ZKE_OK) { pick = k - a; break; }
-      if (R[k].status == ZKE_UNSUPPORTED) flag = ZKE_SEL_AFTER_UNSUPPORTED;
-    }
-    out[i] = R[pick == ZKE_SEL_NONE ? b - 1 : a + pick];
-    chosen[i] = pick == ZKE_SEL_NONE ? ZKE_SEL_NONE : (pick | flag);
-  }
-}
-
-// Pay what a slot owes for a batch whose last copy has arrived, from the slot's pinned buffers into the caller's.  The order: the
-// records, the selection fold, the scan, the key records, the bodies, the captures, the origins, the encodings.  Needs no device where
-// nothing is left in HBM (a body that did not spill, no capture strings).
-// The shortfall rule: an output whose variable-size buffer is too small is ZKE_E_NOMEM to whoever waits — `cap_rc` (zke_batch_wait,
-// the synchronous entries) — and nobody's business otherwise: a slot that retires a batch nobody waited for has nobody to tell, and
-// zke_last_error stays what it was.  Everything of fixed size and every *_need is delivered either way; any other error ends the delivery.
-int deliver_pending(zke_engine* e, Slot& w, const PendingDelivery& d, int* cap_rc) {
-  if (d.records && d.n) memcpy(d.records, w.h_results.p, (size_t)d.n * sizeof(zke_result));
-  if (!d.sel_off.empty()) fold_selection(w.h_results.as<zke_result>(), d.sel_off, d.sel_out, d.sel_chosen);
-  const std::string keep = cap_rc ? std::string() : g_err;
-  auto settled = [&](int r) {      // the shortfall rule
-    if (r == ZKE_E_NOMEM) { if (cap_rc) *cap_rc = r; else g_err = keep; }
-    return r == ZKE_E_NOMEM ? 0 : r;
-  };
-  int r = 0;
-  if (d.scan && (r = settled(deliver_scan(e, w.sb, d.scan)))) return r;
-  if (d.keyrec && (r = settled(deliver_keyrec(e, w.kb, d.keyrec)))) return r;
-  if (d.body && (r = settled(deliver_body(e, w.bb, d.body, w.stream)))) return r;
-  if (d.caps && (r = settled(deliver_captures(e, w.cb, d.caps, w.stream)))) return r;
-  if (d.org) deliver_origins(w.cb, w.ob, d.org);
-  if (d.enc && d.enc_planned) return settled(deliver_encoded_planned(e, w.eb, w.cb, d.enc, w.stream));
-  if (d.enc && (r = deliver_encoded(e, w.eb, d.enc))) return r;
-  return 0;
-}
-
 // Deliver a host batch that was enqueued in this slot and not waited for yet: wait for its last D2H, pay what is owed for it.
 // Caller holds the slot's lock.
 int retire_host(zke_engine* e, Slot& w, int* cap_rc = nullptr) {
@@ -367,7 +130,8 @@ int check_batch_pointers(const zke_batch* in, const void* out, bool host, const 
   return check_part_ids(*in, who);
 }
 
-// A host batch, checked and measured for the staging image by host_batch(): packed (zke_batch) or gathered (zke_email_ref[n]).
+// A host batch, checked and measured for the staging image by host_batch(): packed (zke_batch) or gathered (zke_email_ref[n]).  The requests say
+// what is asked; the three that are not const are completed against the registry by submit_host_batch, under `big`; submit_host writes through none.
 struct HostBatch {
   zke_batch b{};                        // n, the regex section, (packed) the caller's blobs and offsets; capture tables only if any
   const zke_email_ref* refs = nullptr;  // the gathered shape's e-mails (nullptr: packed)
@@ -381,20 +145,18 @@ struct HostBatch {
   const EncodeReq* enc = nullptr;       // zke_verify_emails_encoded: the encode and digest launches behind this batch's records
   uint64_t raw_total = 0, dom_total = 0, key_total = 0, raw_base = 0, dom_base = 0, key_base = 0;   // blob bytes; off[0] of packed offsets
   size_t cap_words = 0, cap_strs = 0, cap_bytes = 0;      // entries of cap_off and cap_str_off, bytes of cap_blob (0: no tables)
+  PlanSections S{};                     // the plan sections behind L.mixed and the image: layout_host_batch, once
   ImageLayout L{};
 };
-// The plan sections of a batch's image, one behind the other: a mixed batch's plan, a mixed extraction's tables, an encoding's jobs
-// and external inputs (which start 64-byte aligned: a blob lies in them).
-size_t enc_image_at(const HostBatch& d) {
-  return align_up((d.mixed ? mixed_image(d.b.n, d.mixed->shape).total : 0) + (d.capmix ? d.capmix->image(d.b.n).total : 0), 64);
-}
+// The image of a batch that has been measured and whose plan sections are all known: the sections (host_stage.hip.h), then the image
+// around them.  Once per batch: host_batch() ends with it, unless the entry has an encoding to add first and calls it itself (`lay_out`).
 void layout_host_batch(HostBatch& d) {
-  const size_t plans = d.enc ? enc_image_at(d) + d.enc->image().total
-                             : (d.mixed ? mixed_image(d.b.n, d.mixed->shape).total : 0) + (d.capmix ? d.capmix->image(d.b.n).total : 0);
-  d.L = image_layout(d.b.n, d.raw_total, d.dom_total, d.key_total, d.cap_words, d.cap_strs, d.cap_bytes, plans);
+  d.S = plan_sections(d.mixed ? mixed_image(d.b.n, d.mixed->shape) : MixedImage{}, d.capmix ? d.capmix->image(d.b.n) : CapMixedImage{},
+                      d.enc ? d.enc->image() : EncImage{});
+  d.L = image_layout(d.b.n, d.raw_total, d.dom_total, d.key_total, d.cap_words, d.cap_strs, d.cap_bytes, d.S.total);
 }
 // Both shapes.  Capture tables: a cap_off whose last entry is 0 holds no string and is no table (cap_str_off, cap_blob unread).
-int measure_host_batch(HostBatch& d, const char* who) {
+int measure_host_batch(HostBatch& d, const char* who, bool lay_out = true) {
   zke_batch& b = d.b;
   if (d.raw_total > (1ull << 40)) return arg_error(who, "raw e-mails beyond 1 TiB");
   const size_t NP = d.mixed ? (size_t)d.mixed->shape.J : b.with_regex ? (size_t)b.n * (b.n_header_parts + b.n_body_parts) : 0;
@@ -407,7 +169,7 @@ int measure_host_batch(HostBatch& d, const char* who) {
     }
   }
   if (!d.cap_words) b.cap_off = nullptr, b.cap_str_off = nullptr, b.cap_blob = nullptr;
-  layout_host_batch(d);
+  if (lay_out) layout_host_batch(d);
   return 0;
 }
 // The packed shape.  Its offsets are in host memory here, so they are checked (three passes over n + 1 words): a negative length
@@ -423,9 +185,9 @@ int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_b
   return measure_host_batch(d, who);
 }
 // The gathered shape: the e-mails one by one, lists == nullptr for verify_email; `mixed` (checked and measured by its entry) instead
-// of lists: the capture tables are its; `capmix`: the mixed extraction whose regex stage `mixed` is.
+// of lists: the capture tables are its; `capmix`: its mixed extraction.  lay_out = false: the entry sets d.enc, then lays the image out itself.
 int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_email_ref* refs, uint32_t n, const zke_regex_lists* lists,
-               MixedReq* mixed = nullptr, CapMixedReq* capmix = nullptr) {
+               MixedReq* mixed = nullptr, CapMixedReq* capmix = nullptr, bool lay_out = true) {
   if (n && (!refs || !out)) return arg_error(who, "null pointer");
   d = HostBatch{zke_batch{n}, refs};
   d.capmix = capmix;
@@ -446,7 +208,7 @@ int host_batch(HostBatch& d, const char* who, const zke_result* out, const zke_e
     if (m.raw_len > (1ull << 40) || m.domain_len > (1ull << 32) || m.key_len > (1ull << 32)) return arg_error(who, "implausible length");
     d.raw_total += m.raw_len; d.dom_total += m.domain_len; d.key_total += m.key_len;
   }
-  return measure_host_batch(d, who);
+  return measure_host_batch(d, who, lay_out);
 }
 
 // What the slot will owe for the batch d: only a batch that is nothing but a verify hands the records over as they are.
@@ -467,15 +229,12 @@ PendingDelivery pending_delivery(const HostBatch& d, zke_result* out) {
   return p;
 }
 
-// One host batch into slot w (caller holds its lock): the side outputs' buffers, then pack -> one H2D -> the launches (one stand-alone
-// side launch, or the verify pipeline, behind the key-record prefix if the keys come as records) -> the D2H of every twin -> event, and
-// the slot owes the delivery.
-int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, bool want_em, bool want_clean) {
+// ---- One host batch into a slot, stage by stage (submit_host below is the list); every stage reads the descriptor and writes the slot.
+// 1. The buffers of every output the batch asks for (grow only; the layouts of the batch at hand).
+int ensure_output_buffers(zke_engine* e, Slot& w, const HostBatch& d) {
   const uint32_t n = d.b.n;
-  const ImageLayout& L = d.L;
   int rc = 0;
-  if ((rc = retire_host(e, w))) return rc;           // the pinned buffers are about to be overwritten
-  if ((rc = ensure_host_buffers(e, w, L.total, n))) return rc;      // (a no-op: submit_host_batch has grown every slot's staging)
+  if ((rc = ensure_host_buffers(e, w, d.L.total, n))) return rc;      // (a no-op: submit_host_batch has grown every slot's staging)
   if (d.cap) w.cb.L = cap_layout(n, d.cap->P, d.cap->G, d.cap->dev_blob_cap());
   if (d.cap && (rc = ensure_capture_buffers(e, w.cb, w.cb.L, d.cap->needs_work))) return rc;
   if (d.cap && d.cap->org && (rc = ensure_origin_buffers(e, w.ob, (size_t)n * d.cap->G, d.cap->origin_launch()))) return rc;
@@ -487,76 +246,66 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   if (d.body && (rc = ensure_body_buffers(e, w.bb, n, (size_t)d.raw_total))) return rc;
   if (d.enc && !d.enc->device_plan && (rc = ensure_encode_buffers(e, w.eb, n, d.enc->plan.total, 0))) return rc;
   if (d.enc && d.enc->device_plan && (rc = ensure_encode_buffers_planned(e, w.eb, n, d.enc->bytes_cap))) return rc;
-  uint8_t* hp = w.h_image.as<uint8_t>();
-  if (d.refs) {
-    // the CSR arrays are written where they will be read from (prefix sums over the lengths), and every e-mail's three buffers
-    // go to their places in the blobs — the pool takes runs of consecutive e-mails (CopyPool::gather)
-    uint64_t* ro = reinterpret_cast<uint64_t*>(hp + L.raw_off), *dofs = reinterpret_cast<uint64_t*>(hp + L.dom_off), *ko = reinterpret_cast<uint64_t*>(hp + L.key_off);
-    uint8_t* kt = hp + L.key_type, *xn = hp + L.ext_null;
-    w.gather.resize((size_t)3 * n);
-    uint64_t r = 0, dd = 0, k = 0;
-    for (uint32_t i = 0; i < n; i++) {
-      const zke_email_ref& m = d.refs[i];
-      ro[i] = r; dofs[i] = dd; ko[i] = k;
-      kt[i] = (uint8_t)(m.key_type > ZKE_KEY_OTHER ? ZKE_KEY_OTHER : m.key_type);
-      xn[i] = m.external_input_null ? 1 : 0;
-      w.gather[i] = CopyPool::Piece{hp + L.raw + r, m.raw, m.raw_len};                       // three runs, each contiguous in the image
-      w.gather[(size_t)n + i] = CopyPool::Piece{hp + L.dom + dd, m.from_domain, m.domain_len};
-      w.gather[2 * (size_t)n + i] = CopyPool::Piece{hp + L.key + k, m.key, m.key_len};
-      r += m.raw_len; dd += m.domain_len; k += m.key_len;
-    }
-    ro[n] = r; dofs[n] = dd; ko[n] = k;
-    if (e->pool) e->pool->gather(w.gather.data(), w.gather.size());
-    else for (const auto& p : w.gather) if (p.n) stage_copy(p.dst, p.src, p.n, ZKE_GATHER_STREAM_FROM);
-  } else {
-    // the offsets are copied as they are (the kernels subtract off[0] themselves and the device pointers below are biased
-    // by -off[0]): nothing is rebased, nothing is allocated, every byte is written once
-    CopyPool::Piece pc[8] = {
-        {hp + L.raw_off, d.b.raw_off, (size_t)(n + 1) * 8}, {hp + L.dom_off, d.b.domain_off, (size_t)(n + 1) * 8},
-        {hp + L.key_off, d.b.key_off, (size_t)(n + 1) * 8}, {hp + L.key_type, d.b.key_type, n},
-        {hp + L.ext_null, d.b.ext_null, d.b.ext_null ? n : 0u}, {hp + L.raw, d.b.raw_blob + d.raw_base, (size_t)d.raw_total},
-        {hp + L.dom, d.b.domain_blob + d.dom_base, (size_t)d.dom_total}, {hp + L.key, d.b.key_blob + d.key_base, (size_t)d.key_total}};
-    if (e->pool) e->pool->copy(pc, 8);
-    else for (const auto& p : pc) if (p.n) stage_copy(p.dst, p.src, p.n);
+  return 0;
+}
+
+// 2. The image in the slot's pinned buffer.  The gathered shape: the CSR arrays are written where they will be read from (prefix sums over
+// the lengths), and every e-mail's three buffers go to their places in the blobs — the pool takes runs of consecutive e-mails (CopyPool::gather).
+void pack_gathered(zke_engine* e, Slot& w, const HostBatch& d, uint8_t* hp) {
+  const uint32_t n = d.b.n;
+  const ImageLayout& L = d.L;
+  uint64_t* ro = reinterpret_cast<uint64_t*>(hp + L.raw_off), *dofs = reinterpret_cast<uint64_t*>(hp + L.dom_off), *ko = reinterpret_cast<uint64_t*>(hp + L.key_off);
+  uint8_t* kt = hp + L.key_type, *xn = hp + L.ext_null;
+  w.gather.resize((size_t)3 * n);
+  uint64_t r = 0, dd = 0, k = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const zke_email_ref& m = d.refs[i];
+    ro[i] = r; dofs[i] = dd; ko[i] = k;
+    kt[i] = (uint8_t)(m.key_type > ZKE_KEY_OTHER ? ZKE_KEY_OTHER : m.key_type);
+    xn[i] = m.external_input_null ? 1 : 0;
+    w.gather[i] = CopyPool::Piece{hp + L.raw + r, m.raw, m.raw_len};                       // three runs, each contiguous in the image
+    w.gather[(size_t)n + i] = CopyPool::Piece{hp + L.dom + dd, m.from_domain, m.domain_len};
+    w.gather[2 * (size_t)n + i] = CopyPool::Piece{hp + L.key + k, m.key, m.key_len};
+    r += m.raw_len; dd += m.domain_len; k += m.key_len;
   }
-  if (d.cap_words) {       // the capture tables of a regex batch (small)
+  ro[n] = r; dofs[n] = dd; ko[n] = k;
+  if (e->pool) e->pool->gather(w.gather.data(), w.gather.size());
+  else for (const auto& p : w.gather) if (p.n) stage_copy(p.dst, p.src, p.n, ZKE_GATHER_STREAM_FROM);
+}
+// The packed shape: the offsets are copied as they are (the kernels subtract off[0] themselves and the device pointers of
+// device_view are biased by -off[0]): nothing is rebased, nothing is allocated, every byte is written once.
+void pack_packed(zke_engine* e, const HostBatch& d, uint8_t* hp) {
+  const uint32_t n = d.b.n;
+  const ImageLayout& L = d.L;
+  CopyPool::Piece pc[8] = {
+      {hp + L.raw_off, d.b.raw_off, (size_t)(n + 1) * 8}, {hp + L.dom_off, d.b.domain_off, (size_t)(n + 1) * 8},
+      {hp + L.key_off, d.b.key_off, (size_t)(n + 1) * 8}, {hp + L.key_type, d.b.key_type, n},
+      {hp + L.ext_null, d.b.ext_null, d.b.ext_null ? n : 0u}, {hp + L.raw, d.b.raw_blob + d.raw_base, (size_t)d.raw_total},
+      {hp + L.dom, d.b.domain_blob + d.dom_base, (size_t)d.dom_total}, {hp + L.key, d.b.key_blob + d.key_base, (size_t)d.key_total}};
+  if (e->pool) e->pool->copy(pc, 8);
+  else for (const auto& p : pc) if (p.n) stage_copy(p.dst, p.src, p.n);
+}
+// Either shape, then the capture tables of a regex batch (small) and the plan sections: they ride in the same image, the batch is
+// still ONE copy.
+void pack_image(zke_engine* e, Slot& w, const HostBatch& d) {
+  uint8_t* hp = w.h_image.as<uint8_t>();
+  const ImageLayout& L = d.L;
+  if (d.refs) pack_gathered(e, w, d, hp);
+  else pack_packed(e, d, hp);
+  if (d.cap_words) {
     stage_copy(hp + L.cap_off, d.b.cap_off, d.cap_words * 4);
     stage_copy(hp + L.cap_str_off, d.b.cap_str_off, d.cap_strs * 4);
     stage_copy(hp + L.cap_blob, d.b.cap_blob, d.cap_bytes);
   }
-  const MixedImage ML = d.mixed ? mixed_image(n, d.mixed->shape) : MixedImage{};
-  if (d.mixed) {           // the plan of a mixed batch rides in the same image: the batch is still ONE copy
-    const MixedPlan& P = d.mixed->plan;
-    uint8_t* mp = hp + L.mixed;
-    stage_copy(mp + ML.job_off, P.job_off.data(), P.job_off.size() * 4);
-    stage_copy(mp + ML.email_cfg, P.email_cfg.data(), P.email_cfg.size() * 4);
-    stage_copy(mp + ML.perm, P.perm.data(), P.perm.size() * 4);
-    stage_copy(mp + ML.segs, P.segs.data(), P.segs.size() * sizeof(MixedSeg));
-  }
-  const CapMixedImage CL = d.capmix ? d.capmix->image(n) : CapMixedImage{};
-  if (d.capmix) {          // a mixed extraction's columns and its part table, one more section behind the plan
-    const CapMixedPlan& P = d.capmix->plan;
-    uint8_t* cp = hp + L.mixed + ML.total;
-    stage_copy(cp + CL.col_off, P.col_off.data(), P.col_off.size() * 4);
-    stage_copy(cp + CL.cap_cfg, P.cap_cfg.data(), P.cap_cfg.size() * 4);
-    stage_copy(cp + CL.cfgs, P.cfgs.data(), P.cfgs.size() * sizeof(CapMixedCfg));
-    stage_copy(cp + CL.parts, d.capmix->part.data(), d.capmix->part.size() * sizeof(CapPartDev));
-  }
-  const EncImage EL = d.enc ? d.enc->image() : EncImage{};
-  const size_t enc_at = d.enc ? L.mixed + enc_image_at(d) : 0;
-  if (d.enc) {             // an encoding's jobs and its external-input table, the last of the plan sections
-    const EncodePlan& P = d.enc->plan;
-    if (d.enc->device_plan) { if (P.ext_strs) stage_copy(hp + enc_at + EL.jobs, d.enc->ext_off, ((size_t)n + 1) * 4); }
-    else stage_copy(hp + enc_at + EL.jobs, P.jobs.data(), P.jobs.size() * sizeof(EncodeJob));
-    if (P.ext_strs) stage_copy(hp + enc_at + EL.ext_str_off, d.enc->ext_str_off, ((size_t)P.ext_strs + 1) * 4);
-    if (P.ext_bytes) stage_copy(hp + enc_at + EL.ext_blob, d.enc->ext_blob, P.ext_bytes);
-  }
-  hipStream_t s = w.stream;
-  SlotUse use(e, w, s);
-  if ((rc = use.acquire())) return rc;
-  StageTimer tm(e, &w, s);
-  tm.mark(MK_START);
-  if (ZKE_HOST_COPY_STREAM && L.total >= (256u << 10)) {
+  uint8_t* sp = hp + L.mixed;
+  if (d.mixed) stage_mixed(sp, d.S.mixed, d.mixed->plan);
+  if (d.capmix) stage_capmix(sp + d.S.capmix_at, d.S.capmix, d.capmix->plan, d.capmix->part);
+  if (d.enc) stage_enc(sp + d.S.enc_at, d.S.enc, d.enc->plan, d.enc->device_plan, d.enc->ext_off, d.b.n, d.enc->ext_str_off, d.enc->ext_blob);
+}
+
+// 3. ONE H2D of the image.
+int upload_image(zke_engine* e, Slot& w, size_t bytes, hipStream_t s) {
+  if (ZKE_HOST_COPY_STREAM && bytes >= (256u << 10)) {
     // The image crosses PCIe on one of the engine's TWO copy streams, taken in turn, and the slot's stream waits for it.  Issued
     // on the slots' own 22 streams the input copies moved 31 GB/s in aggregate — one DMA engine's rate —, on one copy stream the
     // same; on two, 48 GB/s = 84 % of the link (122 us per 1 024-e-mail batch instead of 186; three streams: 141 us, four: worse).
@@ -565,13 +314,18 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
     // single e-mail 16 us of latency and buys nothing.)
     std::lock_guard<std::mutex> cg(e->copy_mu);
     hipStream_t cs = e->copy_stream[e->copy_turn++ % ZKE_COPY_STREAMS];
-    HIPCHK(e, hipMemcpyAsync(w.d_image.p, hp, L.total, hipMemcpyHostToDevice, cs));
+    HIPCHK(e, hipMemcpyAsync(w.d_image.p, w.h_image.p, bytes, hipMemcpyHostToDevice, cs));
     HIPCHK(e, hipEventRecord(w.h2d_done, cs));
     HIPCHK(e, hipStreamWaitEvent(s, w.h2d_done, 0));
   } else {
-    HIPCHK(e, hipMemcpyAsync(w.d_image.p, hp, L.total, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(w.d_image.p, w.h_image.p, bytes, hipMemcpyHostToDevice, s));
   }
-  tm.mark(MK_H2D);
+  return 0;
+}
+
+// 4. The batch as the kernels see it: the descriptor with its pointers into the slot's image in HBM.
+zke_batch device_view(const Slot& w, const HostBatch& d) {
+  const ImageLayout& L = d.L;
   uint8_t* dp = w.d_image.as<uint8_t>();
   zke_batch dv = d.b;
   dv.raw_off = reinterpret_cast<const uint64_t*>(dp + L.raw_off);
@@ -585,57 +339,84 @@ int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, boo
   dv.cap_off = d.cap_words ? reinterpret_cast<const uint32_t*>(dp + L.cap_off) : nullptr;
   dv.cap_str_off = d.cap_words ? reinterpret_cast<const uint32_t*>(dp + L.cap_str_off) : nullptr;
   dv.cap_blob = d.cap_words ? dp + L.cap_blob : nullptr;
-  if (d.scan) rc = launch_scan(e, w.sb, dv, batch_clock(e), tm, s);
-  else if (d.body) rc = launch_body(e, w.bb, dv, d.body->flags, tm, s);
-  else if (d.keyrec && !d.sel) rc = launch_keyrec(e, w.kb, dv, d.keyrec->mode, tm, s);
-  else {
-    uint64_t key_hint = d.key_total;
-    if (d.keyrec) {
-      if ((rc = launch_keyrec_prefix(e, w.kb, dv, d.keyrec->mode, s))) return rc;
-      // (run_device_pipeline reads "the keys average more than an RSA-2048 key's 270 bytes" from the total: a 2048-bit
-      // SubjectPublicKeyInfo record is about 410 characters, a 3072-bit one 580)
-      key_hint = d.key_total > (uint64_t)n * 480 ? (uint64_t)n * 273 : 0;
-    }
-    const uint8_t* mp = dp + L.mixed;
-    const MixedLaunch ml{d.mixed ? &d.mixed->plan : nullptr, reinterpret_cast<const uint32_t*>(mp + ML.job_off), reinterpret_cast<const uint32_t*>(mp + ML.email_cfg),
-                         reinterpret_cast<const uint32_t*>(mp + ML.perm), reinterpret_cast<const MixedSeg*>(mp + ML.segs)};
-    const uint8_t* cp = mp + ML.total;
-    const CapMixedLaunch cl{d.capmix ? d.capmix->plan.shape.J : 0u, d.capmix ? d.capmix->plan.shape.Gt : 0u, d.capmix && d.capmix->needs_work,
-                            d.capmix && d.capmix->origin_launch(),
-                            CapMixedTables{ml.job_off, reinterpret_cast<const uint32_t*>(cp + CL.col_off), reinterpret_cast<const uint32_t*>(cp + CL.cap_cfg),
-                                           reinterpret_cast<const CapMixedCfg*>(cp + CL.cfgs), reinterpret_cast<const CapPartDev*>(cp + CL.parts)}};
+  return dv;
+}
+
+// 5. The launches.  A batch that is ONE stand-alone side launch instead of the verify pipeline (its twin's copy back is the launch's own) ...
+bool side_launch_alone(const HostBatch& d) { return d.scan || d.body || (d.keyrec && !d.sel); }
+// ... or the pipeline: behind the key-record prefix if the keys come as records, the plan sections viewed in HBM, the encode launches behind it.
+int launch_verify(zke_engine* e, Slot& w, const HostBatch& d, zke_batch& dv, bool want_em, bool want_clean, hipStream_t s) {
+  const uint32_t n = d.b.n;
+  int rc = 0;
+  uint64_t key_hint = d.key_total;
+  if (d.keyrec) {
+    if ((rc = launch_keyrec_prefix(e, w.kb, dv, d.keyrec->mode, s))) return rc;
+    // (run_device_pipeline reads "the keys average more than an RSA-2048 key's 270 bytes" from the total: a 2048-bit
+    // SubjectPublicKeyInfo record is about 410 characters, a 3072-bit one 580)
+    key_hint = d.key_total > (uint64_t)n * 480 ? (uint64_t)n * 273 : 0;
+  }
+  const uint8_t* sp = w.d_image.as<uint8_t>() + d.L.mixed;      // the plan sections, as pack_image staged them
+  const MixedLaunch ml = mixed_view(sp, d.S.mixed, d.mixed ? &d.mixed->plan : nullptr);
+  const CapMixedLaunch cl{d.capmix ? d.capmix->plan.shape.J : 0u, d.capmix ? d.capmix->plan.shape.Gt : 0u, d.capmix && d.capmix->needs_work,
+                          d.capmix && d.capmix->origin_launch(), capmix_view(sp + d.S.capmix_at, d.S.capmix, ml.job_off)};
+  EncodeArgs ea = enc_view(sp + d.S.enc_at, d.S.enc);
+  const bool planned = d.enc && d.enc->device_plan;
+  LossyLaunch ll{};
+  if (planned)             // the gather launch of this extraction also plans the encoding: where it reads the external inputs, where the jobs go
+    ll = LossyLaunch{d.enc->plan.ext_strs ? reinterpret_cast<const uint32_t*>(ea.jobs) : nullptr, ea.ext_str_off,
+                     reinterpret_cast<EncodeJob*>(w.eb.t.d.as<uint8_t>() + w.eb.jobs_at), d.enc->bytes_cap};
+  if ((rc = run_device_pipeline(e, w, &dv, d.raw_total, key_hint, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap,
+                                d.mixed ? &ml : nullptr, d.capmix ? &cl : nullptr, planned ? &ll : nullptr))) return rc;
+  if (!d.enc) return 0;
+  // the encodings of the records just written and their digests, two more launches on the same stream
+  ea.records = w.d_results.as<zke_result>();
+  ea.match_str_off = dv.cap_str_off; ea.match_blob = dv.cap_blob;
+  if (planned) {           // the jobs are the gather launch's, the matches the tables it has just written in the slot's capture buffer
+    ea.jobs = ll.jobs;
+    ea.match_str_off = reinterpret_cast<const uint32_t*>(w.cb.t.d.as<uint8_t>() + w.cb.L.cap_str_off);
+    ea.match_blob = w.cb.t.d.as<uint8_t>() + w.cb.L.blob;
+  }
+  return launch_encode(e, w.eb, ea, s, planned);
+}
+int launch_host_batch(zke_engine* e, Slot& w, const HostBatch& d, zke_batch& dv, bool want_em, bool want_clean, StageTimer& tm, hipStream_t s) {
+  if (d.scan) return launch_scan(e, w.sb, dv, batch_clock(e), tm, s);
+  if (d.body) return launch_body(e, w.bb, dv, d.body->flags, tm, s);
+  if (d.keyrec && !d.sel) return launch_keyrec(e, w.kb, dv, d.keyrec->mode, tm, s);
+  return launch_verify(e, w, d, dv, want_em, want_clean, s);
+}
+
+// 6. The D2H of every twin still in HBM (behind the pipeline: records, encodings, key records; captures, origins), the event, the debt.
+int fetch_and_file(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, StageTimer& tm, hipStream_t s) {
+  if (!side_launch_alone(d)) {
     const bool planned = d.enc && d.enc->device_plan;
-    if (planned) {         // the gather launch of this extraction also plans the encoding: where it reads the external inputs, where the jobs go
-      d.cap->lossy_ext_off = d.enc->plan.ext_strs ? reinterpret_cast<const uint32_t*>(dp + enc_at + EL.jobs) : nullptr;
-      d.cap->lossy_ext_str_off = reinterpret_cast<const uint32_t*>(dp + enc_at + EL.ext_str_off);
-      d.cap->lossy_jobs = reinterpret_cast<EncodeJob*>(w.eb.t.d.as<uint8_t>() + w.eb.jobs_at);
-      d.cap->lossy_bytes_cap = d.enc->bytes_cap;
-    }
-    if ((rc = run_device_pipeline(e, w, &dv, d.raw_total, key_hint, w.d_results.as<zke_result>(), s, want_em, batch_clock(e), want_clean, d.cap,
-                                  d.mixed ? &ml : nullptr, d.capmix ? &cl : nullptr))) return rc;
-    if (d.enc) {           // the encodings of the records just written and their digests, two more launches on the same stream
-      EncodeArgs ea{};
-      ea.records = w.d_results.as<zke_result>();
-      ea.jobs = planned ? d.cap->lossy_jobs : reinterpret_cast<const EncodeJob*>(dp + enc_at + EL.jobs);
-      ea.ext_str_off = reinterpret_cast<const uint32_t*>(dp + enc_at + EL.ext_str_off); ea.ext_blob = dp + enc_at + EL.ext_blob;
-      ea.match_str_off = dv.cap_str_off; ea.match_blob = dv.cap_blob;
-      if (planned) {       // the matches are the tables the gather launch has just written in the slot's capture buffer
-        ea.match_str_off = reinterpret_cast<const uint32_t*>(w.cb.t.d.as<uint8_t>() + w.cb.L.cap_str_off);
-        ea.match_blob = w.cb.t.d.as<uint8_t>() + w.cb.L.blob;
-      }
-      if ((rc = launch_encode(e, w.eb, ea, s, planned))) return rc;
-    }
-    HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(w.h_results.p, w.d_results.p, (size_t)d.b.n * sizeof(zke_result), hipMemcpyDeviceToHost, s));
     if (d.enc) HIPCHK(e, w.eb.t.fetch(planned ? w.eb.L.bytes : w.eb.L.prefix, s));
     if (d.keyrec) HIPCHK(e, w.kb.t.fetch(w.kb.L.total, s));
   }
-  if (rc) return rc;
   if (d.cap || d.capmix) HIPCHK(e, w.cb.t.fetch(w.cb.L.fixed_end, s));
   if (((d.cap && d.cap->org) || (d.capmix && d.capmix->org)) && w.ob.launched) HIPCHK(e, w.ob.t.fetch(w.ob.L.total, s));
   tm.mark(MK_D2H);
   HIPCHK(e, hipEventRecord(w.host_done, s));
   w.host_gen++;
   w.owed = pending_delivery(d, out);
+  return 0;
+}
+
+// One host batch into slot w (caller holds its lock): the stages above in order.  The slot's use ends on every way out (SlotUse).
+int submit_host(zke_engine* e, Slot& w, const HostBatch& d, zke_result* out, bool want_em, bool want_clean) {
+  if (int rc = retire_host(e, w)) return rc;         // the pinned buffers are about to be overwritten
+  if (int rc = ensure_output_buffers(e, w, d)) return rc;
+  pack_image(e, w, d);
+  hipStream_t s = w.stream;
+  SlotUse use(e, w, s);
+  if (int rc = use.acquire()) return rc;
+  StageTimer tm(e, &w, s);
+  tm.mark(MK_START);
+  if (int rc = upload_image(e, w, d.L.total, s)) return rc;
+  tm.mark(MK_H2D);
+  zke_batch dv = device_view(w, d);
+  if (int rc = launch_host_batch(e, w, d, dv, want_em, want_clean, tm, s)) return rc;
+  if (int rc = fetch_and_file(e, w, d, out, tm, s)) return rc;
   return use.release();
 }
 
@@ -822,10 +603,15 @@ int zke_verify_emails_async(zke_engine* e, const zke_email_ref* emails, uint32_t
 // `&[EmailWithRegex]` with a RegexInfo per value (include/zkemail_amd.h): the checks and the sizes here, before anything is staged;
 // the plan once the registry can be read (mixed_resolve); its tables in the slot's image (submit_host).
 namespace {
+// What a mixed verify and a mixed extraction check of their configs before they look at one: the count and the two arrays.
+int check_mixed_configs(const char* who, uint32_t n_configs, const void* configs, const uint32_t* config_of, uint32_t n) {
+  if (n_configs > ZKE_MIXED_MAX_CONFIGS) return arg_error(who, "more than ZKE_MIXED_MAX_CONFIGS configs");
+  if ((n_configs && !configs) || (n && !config_of)) return arg_error(who, "null pointer");
+  return 0;
+}
 // The request of a mixed batch from the caller's zke_regex_mixed: the checks that need no registry, the configs' part counts, the shape.
 int mixed_request(const char* who, const zke_regex_mixed* mixed, uint32_t n, MixedReq& q) {
-  if (mixed->n_configs > ZKE_MIXED_MAX_CONFIGS) return arg_error(who, "more than ZKE_MIXED_MAX_CONFIGS configs");
-  if ((mixed->n_configs && !mixed->configs) || (n && !mixed->config_of)) return arg_error(who, "null pointer");
+  if (int r = check_mixed_configs(who, mixed->n_configs, mixed->configs, mixed->config_of, n)) return r;
   q.in = mixed; q.n = n;
   q.counts.resize(mixed->n_configs);
   for (uint32_t c = 0; c < mixed->n_configs; c++) {
@@ -1061,7 +847,7 @@ int zke_verify_emails_encoded_async(zke_engine* e, const zke_email_ref* emails, 
   MixedReq mq;
   if (in->mixed) if (int r = mixed_request(who, in->mixed, n, mq)) return r;
   HostBatch d;
-  if (int r = host_batch(d, who, out, emails, n, in->lists, in->mixed ? &mq : nullptr)) return r;
+  if (int r = host_batch(d, who, out, emails, n, in->lists, in->mixed ? &mq : nullptr, nullptr, false)) return r;
   std::vector<uint32_t> kinds(n, in->lists ? ENC_KIND_WITH_REGEX : ENC_KIND_EMAIL), row_off;
   EncodeTables t;
   t.ext_off = in->ext_off; t.ext_str_off = in->ext_str_off; t.ext_blob = in->ext_blob;
@@ -1094,63 +880,6 @@ int zke_verify_emails_encoded(zke_engine* e, const zke_email_ref* emails, uint32
   return submit_and_wait(e, n, [&](uint64_t* t) { return zke_verify_emails_encoded_async(e, emails, n, in, out, enc, t); });
 }
 
-// The two launches alone over the caller's records and tables (host pointers), beside zke_sha256_batch: one staged input
-// {records | jobs | the two tables}, the slot's encoding buffer — the one the entry above uses —, one copy back.  Synchronous.
-int zke_encode_outputs(zke_engine* e, const zke_result* records, uint32_t n, const uint32_t* kinds, const uint32_t* ext_off,
-                       const uint32_t* ext_str_off, const uint8_t* ext_blob, const uint32_t* match_off, const uint32_t* match_str_off,
-                       const uint8_t* match_blob, zke_encoded_out* enc) {
-  static const char who[] = "zke_encode_outputs";
-  if (!e) return ZKE_E_ARG;
-  if (!enc || (n && (!records || !kinds))) return arg_error(who, "null pointer");
-  EncodeTables t;
-  t.ext_off = ext_off; t.ext_str_off = ext_str_off; t.ext_blob = ext_blob;
-  t.match_off = match_off; t.match_str_off = match_str_off; t.match_blob = match_blob;
-  EncodePlan P;
-  if (const char* why = encode_plan_build(n, kinds, t, P)) return arg_error(who, why);
-  if (int r = check_encoded_out(enc, n, P.total, who)) return r;
-  if (n == 0) return 0;
-  size_t o = 0;
-  auto put = [&](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 64); return at; };
-  const size_t at_rec = put((size_t)n * sizeof(zke_result)), at_jobs = put((size_t)n * sizeof(EncodeJob));
-  const size_t at_eso = put(P.ext_strs ? ((size_t)P.ext_strs + 1) * 4 : 0), at_eb = put(P.ext_bytes);
-  const size_t at_mso = put(P.match_strs ? ((size_t)P.match_strs + 1) * 4 : 0), at_mb = put(P.match_bytes);
-  std::vector<uint8_t> img(o);
-  memcpy(img.data() + at_rec, records, (size_t)n * sizeof(zke_result));
-  memcpy(img.data() + at_jobs, P.jobs.data(), (size_t)n * sizeof(EncodeJob));
-  if (P.ext_strs) memcpy(img.data() + at_eso, ext_str_off, ((size_t)P.ext_strs + 1) * 4);
-  if (P.ext_bytes) memcpy(img.data() + at_eb, ext_blob, P.ext_bytes);
-  if (P.match_strs) memcpy(img.data() + at_mso, match_str_off, ((size_t)P.match_strs + 1) * 4);
-  if (P.match_bytes) memcpy(img.data() + at_mb, match_blob, P.match_bytes);
-  std::shared_lock<std::shared_mutex> sh(e->big);
-  HIPCHK(e, hipSetDevice(e->device));
-  uint32_t slot;
-  Slot& w = next_slot(e, slot);
-  std::lock_guard<std::mutex> g(w.mu);
-  int r = 0;
-  if ((r = retire_host(e, w))) return r;             // the buffer's pinned twin may hold encodings nobody has waited for yet
-  if ((r = ensure_encode_buffers(e, w.eb, n, P.total, img.size()))) return r;
-  hipStream_t s = w.stream;
-  SlotUse use(e, w, s);
-  if ((r = use.acquire())) return r;
-  auto enqueue = [&]() -> int {
-    HIPCHK(e, hipMemcpyAsync(w.eb.in.p, img.data(), img.size(), hipMemcpyHostToDevice, s));
-    const uint8_t* ip = w.eb.in.as<uint8_t>();
-    EncodeArgs ea{};
-    ea.records = reinterpret_cast<const zke_result*>(ip + at_rec);
-    ea.jobs = reinterpret_cast<const EncodeJob*>(ip + at_jobs);
-    ea.ext_str_off = reinterpret_cast<const uint32_t*>(ip + at_eso); ea.ext_blob = ip + at_eb;
-    ea.match_str_off = reinterpret_cast<const uint32_t*>(ip + at_mso); ea.match_blob = ip + at_mb;
-    if (int lr = launch_encode(e, w.eb, ea, s)) return lr;
-    HIPCHK(e, w.eb.t.fetch(w.eb.L.prefix, s));
-    return use.release();
-  };
-  r = enqueue();
-  const hipError_t hs = hipStreamSynchronize(s);      // also behind a failed enqueue: no copy outlives `img`
-  if (r) return r;
-  if (hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "zke_encode_outputs: sync", hs);
-  return deliver_encoded(e, w.eb, enc);
-}
-
 namespace {
 // the sizes an extraction over n e-mails needs, written back; ZKE_E_NOMEM when a buffer of known size is too small
 // (NP jobs and NG columns: n * P and n * G of one part list per batch, J and Gt of a mixed extraction)
@@ -1176,23 +905,31 @@ int check_capture_origin_sized(zke_capture_origin* o, size_t NG, const char* who
 }
 int check_capture_origin(zke_capture_origin* o, uint32_t n, uint32_t G, const char* who) { return check_capture_origin_sized(o, (size_t)n * G, who); }
 
-// zke_extract_captures_async and its mapped form (`mapped`: org is wanted, and checked behind caps)
-int extract_captures_submit(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
-                            uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
-                            zke_capture_out* caps, bool mapped, zke_capture_origin* org, uint64_t* ticket, const char* who) {
-  if (!e) return ZKE_E_ARG;
-  if (!ticket || !caps || (mapped && !org) || (n_header_parts && !header_parts) || (n_body_parts && !body_parts)) return arg_error(who, "null pointer");
+// The request of an extraction over one pair of part lists (non-null where they have entries): the parts' shapes, no registry
+// involved.  `lossy`: the gather launch repairs the strings and plans the encoding (zke_extract_captures_encoded).
+int capture_request(CaptureReq& q, const zke_capture_part* header_parts, uint32_t n_header_parts, const zke_capture_part* body_parts,
+                    uint32_t n_body_parts, zke_capture_out* caps, bool lossy, const char* who) {
   const uint32_t P = n_header_parts + n_body_parts;
   if (P == 0 || P > ZKE_CAP_MAX_PARTS || n_header_parts > ZKE_CAP_MAX_PARTS) return arg_error(who, "1 .. ZKE_CAP_MAX_PARTS parts");
-  CaptureReq q;
-  q.P = P; q.n_header_parts = n_header_parts; q.out = caps;
+  q.P = P; q.n_header_parts = n_header_parts; q.out = caps; q.lossy = lossy;
   q.dfa_ids.resize(P);
   for (uint32_t p = 0; p < P; p++) {
     const zke_capture_part& cp = p < n_header_parts ? header_parts[p] : body_parts[p - n_header_parts];
     q.dfa_ids[p] = cp.dfa_id;
     if (int r = capture_part_shape(q, p, cp.prog_id, cp.groups, cp.n_groups, who)) return r;
   }
-  if (int r = check_capture_out(caps, n, P, q.G, who)) return r;
+  return 0;
+}
+
+// zke_extract_captures_async and its mapped form (`mapped`: org is wanted, and checked behind caps)
+int extract_captures_submit(zke_engine* e, const zke_email_ref* emails, uint32_t n, const zke_capture_part* header_parts,
+                            uint32_t n_header_parts, const zke_capture_part* body_parts, uint32_t n_body_parts, zke_result* out,
+                            zke_capture_out* caps, bool mapped, zke_capture_origin* org, uint64_t* ticket, const char* who) {
+  if (!e) return ZKE_E_ARG;
+  if (!ticket || !caps || (mapped && !org) || (n_header_parts && !header_parts) || (n_body_parts && !body_parts)) return arg_error(who, "null pointer");
+  CaptureReq q;
+  if (int r = capture_request(q, header_parts, n_header_parts, body_parts, n_body_parts, caps, false, who)) return r;
+  if (int r = check_capture_out(caps, n, q.P, q.G, who)) return r;
   if (mapped) { if (int r = check_capture_origin(org, n, q.G, who)) return r; q.org = org; }
   zke_regex_lists lists{n_header_parts, q.dfa_ids.data(), n_body_parts, q.dfa_ids.data() + n_header_parts, nullptr, nullptr, nullptr};
   HostBatch d;
@@ -1242,20 +979,12 @@ int zke_extract_captures_encoded_async(zke_engine* e, const zke_email_ref* email
   static const char who[] = "zke_extract_captures_encoded";
   if (!e) return ZKE_E_ARG;
   if (!ticket || !enc || (n_header_parts && !header_parts) || (n_body_parts && !body_parts)) return arg_error(who, "null pointer");
-  const uint32_t P = n_header_parts + n_body_parts;
-  if (P == 0 || P > ZKE_CAP_MAX_PARTS || n_header_parts > ZKE_CAP_MAX_PARTS) return arg_error(who, "1 .. ZKE_CAP_MAX_PARTS parts");
   CaptureReq q;
-  q.P = P; q.n_header_parts = n_header_parts; q.out = caps; q.lossy = true;
-  q.dfa_ids.resize(P);
-  for (uint32_t p = 0; p < P; p++) {
-    const zke_capture_part& cp = p < n_header_parts ? header_parts[p] : body_parts[p - n_header_parts];
-    q.dfa_ids[p] = cp.dfa_id;
-    if (int r = capture_part_shape(q, p, cp.prog_id, cp.groups, cp.n_groups, who)) return r;
-  }
+  if (int r = capture_request(q, header_parts, n_header_parts, body_parts, n_body_parts, caps, true, who)) return r;
   // a repaired string is at most three times its span: what n * G of those could not address in 32 bits is refused
   const uint64_t str_worst = 3ull * ZKE_CAP_MAX_SPAN, blob_worst = (uint64_t)n * q.G * str_worst;
   if (blob_worst > 0xFFFFFFFFull) return arg_error(who, "n x groups beyond what 32-bit string offsets address (n * G * 3 * ZKE_CAP_MAX_SPAN must stay below 4 GiB): split the batch");
-  if (caps) if (int r = check_capture_out(caps, n, P, q.G, who)) return r;
+  if (caps) if (int r = check_capture_out(caps, n, q.P, q.G, who)) return r;
   EncodeReq eq;
   eq.device_plan = true; eq.n = n; eq.out = enc; eq.ext_off = ext_off; eq.ext_str_off = ext_str_off; eq.ext_blob = ext_blob;
   if (const char* why = encode_table_check(ext_off, n, ext_str_off, ext_blob, eq.plan.ext_strs, eq.plan.ext_bytes)) return arg_error(who, why);
@@ -1274,7 +1003,7 @@ int zke_extract_captures_encoded_async(zke_engine* e, const zke_email_ref* email
   eq.bytes_cap = std::min<uint64_t>(enc->bytes_cap, bytes_worst);
   zke_regex_lists lists{n_header_parts, q.dfa_ids.data(), n_body_parts, q.dfa_ids.data() + n_header_parts, nullptr, nullptr, nullptr};
   HostBatch d;
-  if (int r = host_batch(d, who, out, emails, n, &lists)) return r;
+  if (int r = host_batch(d, who, out, emails, n, &lists, nullptr, nullptr, false)) return r;
   // the strings' blob on the device: the caller's capacity; without `caps`, what the strings cannot exceed (a group lies in a
   // canonical header or body, which is no longer than its e-mail but for a line end)
   q.lossy_blob_cap = (size_t)std::min<uint64_t>(blob_worst, caps ? (uint64_t)caps->cap_blob_cap : 3ull * q.G * (d.raw_total + 64ull * n));
@@ -1301,8 +1030,7 @@ int zke_extract_captures_mixed_async(zke_engine* e, const zke_email_ref* emails,
   static const char who[] = "zke_extract_captures_mixed";
   if (!e) return ZKE_E_ARG;
   if (!mixed || !ticket || !caps) return arg_error(who, "null pointer");
-  if (mixed->n_configs > ZKE_MIXED_MAX_CONFIGS) return arg_error(who, "more than ZKE_MIXED_MAX_CONFIGS configs");
-  if ((mixed->n_configs && !mixed->configs) || (n && !mixed->config_of)) return arg_error(who, "null pointer");
+  if (int r = check_mixed_configs(who, mixed->n_configs, mixed->configs, mixed->config_of, n)) return r;
   CapMixedReq q;
   q.out = caps; q.org = org;
   q.verify.counts.resize(mixed->n_configs);
@@ -1347,169 +1075,4 @@ int zke_extract_captures_mixed(zke_engine* e, const zke_email_ref* emails, uint3
                                zke_capture_out* caps, zke_capture_origin* org) {
   return submit_and_wait(e, n, [&](uint64_t* t) { return zke_extract_captures_mixed_async(e, emails, n, mixed, out, caps, org, t); });
 }
-
-// ---- capture extraction over haystacks of the caller's (registry.hip.h), with the checks and the delivery of the entries above
-int zke_capture_batch(zke_engine* e, uint32_t dfa_id, uint32_t prog_id, const uint32_t* groups, uint32_t n_groups,
-                      const uint8_t* hay_blob, const uint64_t* hay_off, uint32_t n, uint32_t* matches, zke_capture_out* caps) {
-  static const char who[] = "zke_capture_batch";
-  if (!e) return ZKE_E_ARG;
-  if (!caps || (n && (!hay_off || !matches)) || (n && hay_off[n] > hay_off[0] && !hay_blob)) return arg_error(who, "null pointer");
-  if (n && (!rising(hay_off, n) || hay_off[n] - hay_off[0] > (1ull << 32))) return arg_error(who, "offset array is not non-decreasing, or the haystacks exceed 4 GiB");
-  for (uint32_t i = 0; i < n; i++) if (hay_off[i + 1] - hay_off[i] >= (1ull << 31)) return arg_error(who, "haystack of 2 GiB or more");
-  CaptureReq q;
-  q.P = 1; q.n_header_parts = 1; q.out = caps;
-  if (int r = capture_part_shape(q, 0, prog_id, groups, n_groups, who)) return r;
-  if (int r = check_capture_out(caps, n, 1, q.G, who)) return r;
-  if (n == 0) return 0;
-  std::shared_lock<std::shared_mutex> sh(e->big);      // from the registry lookups to the last launch: no table is freed meanwhile
-  std::lock_guard<std::mutex> g(e->misc_mu);
-  HIPCHK(e, hipSetDevice(e->device));
-  capture_resolve(e, q);
-  PartInfo pi{};
-  {
-    std::shared_lock<std::shared_mutex> rl(e->reg_mu);
-    const RegisteredDfa* rd = dfa_id < e->dfas.size() ? e->dfas[dfa_id] : nullptr;
-    if (rd) { pi.detail = rd->detail; pi.dev = rd->valid ? rd->dev.as<RegexDev>() : nullptr; }
-  }
-  // the building blocks run in buffers of their own on slot 0's stream
-  const uint64_t base0 = hay_off[0], total = hay_off[n] - base0;
-  Scoped<CapBufs> tmp;
-  Scoped<DevBuf> dhay, doff, dparts;
-  std::vector<uint8_t> fixed;
-  int r = 0;
-  hipError_t he = hipSuccess;
-  tmp.L = cap_layout(n, 1, q.G, caps->cap_blob_cap);
-  const CapLayout& L = tmp.L;
-  hipStream_t s = e->stream;
-  if ((r = dhay.ensure((size_t)total + 64)) || (r = doff.ensure((size_t)(n + 1) * 8)) || (r = dparts.ensure((size_t)n * sizeof(PartRes))) ||
-      (r = ensure_capture_buffers(e, tmp, L, q.needs_work)))
-    return fail(e, r, "zke_capture_batch: allocation");
-  std::vector<uint64_t> rel(n + 1);
-  for (uint32_t i = 0; i <= n; i++) rel[i] = hay_off[i] - base0;
-  if (total) he = hipMemcpyAsync(dhay.p, hay_blob + base0, (size_t)total, hipMemcpyHostToDevice, s);
-  if (he == hipSuccess) he = hipMemsetAsync(dhay.as<uint8_t>() + total, 0, 64, s);         // the DFA walk loads 16 bytes at a time
-  if (he == hipSuccess) he = hipMemcpyAsync(doff.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s);
-  if (he != hipSuccess) { (void)hipStreamSynchronize(s); return fail(e, ZKE_E_DEVICE, "zke_capture_batch: copy", he); }
-  CapFindArgs fa{};
-  fa.d.re = pi.dev; fa.d.P = 1; fa.d.out = dparts.as<PartRes>(); fa.d.idle = 0xFFFFFFFFu; fa.d.decode_detail = pi.detail;
-  fa.hay_blob = dhay.as<uint8_t>(); fa.hay_off = doff.as<uint64_t>(); fa.n = n;
-  hipLaunchKernelGGL(capture_find_kernel, dim3((n + 255) / 256), dim3(256), 1024, s, fa);
-  r = launch_capture(e, tmp, q, n, true, DfaArgs{}, fa.hay_blob, fa.hay_off, dparts.as<PartRes>(), nullptr, s);
-  std::vector<PartRes> prs(n);
-  if (!r) {
-    he = tmp.t.fetch(L.fixed_end, s);
-    if (he == hipSuccess) he = hipMemcpyAsync(prs.data(), dparts.p, (size_t)n * sizeof(PartRes), hipMemcpyDeviceToHost, s);
-  }
-  const hipError_t hs = hipStreamSynchronize(s);
-  if (r) return r;
-  if (he != hipSuccess || hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "zke_capture_batch", he != hipSuccess ? he : hs);
-  const uint32_t* codes = reinterpret_cast<const uint32_t*>(tmp.t.h.as<uint8_t>() + L.codes);
-  for (uint32_t i = 0; i < n; i++) {
-    const PartRes& pr = prs[i];
-    const bool undecodable = pr.code == PART_DECODE_FAIL;
-    matches[4 * i] = undecodable ? pr.count : (pr.code ? pr.code : codes[i]);
-    matches[4 * i + 1] = undecodable ? 0 : pr.count; matches[4 * i + 2] = pr.start; matches[4 * i + 3] = pr.end;
-  }
-  return deliver_captures(e, tmp, caps, s);
-}
-
-// ---- remove_quoted_printable_soft_breaks with its index map over plain bodies (include/zkemail_amd.h; kernel: qpmap.hip.h).  One
-// slot, its stream and its QpBufs (grow only); the caller's buffers are read and written by the copies themselves.
-int zke_qp_clean_batch(zke_engine* e, const uint8_t* body_blob, const uint64_t* body_off, uint32_t n,
-                       uint8_t* cleaned, uint32_t* index_map, uint32_t* clean_len) {
-  static const char who[] = "zke_qp_clean_batch";
-  if (!e) return ZKE_E_ARG;
-  if (!cleaned && !index_map && !clean_len) return arg_error(who, "all three outputs are null");
-  if (n == 0) return 0;
-  if (!body_off) return arg_error(who, "null pointer");
-  if (!rising(body_off, n)) return arg_error(who, "offset array is not non-decreasing");
-  for (uint32_t i = 0; i < n; i++) if (body_off[i + 1] - body_off[i] >= 0xFFFFFFFFull) return arg_error(who, "body of 2^32 - 1 bytes or more");
-  const uint64_t base0 = body_off[0], total = body_off[n] - base0;
-  if (total && !body_blob) return arg_error(who, "null pointer");
-  std::shared_lock<std::shared_mutex> sh(e->big);
-  HIPCHK(e, hipSetDevice(e->device));
-  uint32_t slot;
-  Slot& w = next_slot(e, slot);
-  std::lock_guard<std::mutex> g(w.mu);
-  QpBufs& b = w.qb;
-  int r = 0;
-  if ((r = b.in.ensure((size_t)total + 16)) || (r = b.off.ensure((size_t)(n + 1) * 8)) || (cleaned && (r = b.clean.ensure((size_t)total + 16))) ||
-      (index_map && (r = b.map.ensure(((size_t)total + 4) * 4))) || (clean_len && (r = b.len.ensure((size_t)n * 4))))
-    return fail(e, r, "zke_qp_clean_batch: allocation");
-  hipStream_t s = w.stream;
-  SlotUse use(e, w, s);
-  if ((r = use.acquire())) return r;
-  auto enqueue = [&]() -> int {
-    if (total) HIPCHK(e, hipMemcpyAsync(b.in.p, body_blob + base0, (size_t)total, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(b.off.p, body_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));      // (as given: the kernel subtracts off[0])
-    const QpIndexArgs qa{n, b.in.as<uint8_t>(), b.off.as<uint64_t>(), cleaned ? b.clean.as<uint8_t>() : nullptr,
-                         index_map ? b.map.as<uint32_t>() : nullptr, clean_len ? b.len.as<uint32_t>() : nullptr};
-    hipLaunchKernelGGL(qp_index_kernel, dim3(std::min<uint32_t>(n, 1u << 16)), dim3(64), 0, s, qa);
-    HIPCHK(e, hipGetLastError());
-    if (cleaned && total) HIPCHK(e, hipMemcpyAsync(cleaned, b.clean.p, (size_t)total, hipMemcpyDeviceToHost, s));
-    if (index_map && total) HIPCHK(e, hipMemcpyAsync(index_map, b.map.p, (size_t)total * 4, hipMemcpyDeviceToHost, s));
-    if (clean_len) HIPCHK(e, hipMemcpyAsync(clean_len, b.len.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    return use.release();
-  };
-  r = enqueue();
-  const hipError_t hs = hipStreamSynchronize(s);      // also behind a failed enqueue: no copy outlives the caller's buffers
-  if (r) return r;
-  if (hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "zke_qp_clean_batch: sync", hs);
-  return 0;
-}
-
-// ---- String::from_utf8_lossy over plain strings (include/zkemail_amd.h; kernels: utf8_lossy.hip.h).  One slot, its stream and its
-// Utf8Bufs (grow only).  The repaired blob on the device holds min(out_blob_cap, 3 * the input) bytes — no string grows further — and
-// the write launch leaves out what would end beyond it; the offsets come back first, the bytes once the need is known to fit.
-int zke_utf8_lossy_batch(zke_engine* e, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t* out_off, uint8_t* out_blob,
-                         size_t out_blob_cap, size_t* out_blob_need, uint8_t* flags) {
-  static const char who[] = "zke_utf8_lossy_batch";
-  if (!e) return ZKE_E_ARG;
-  if (!out_off || !out_blob_need || (n && (!off || !flags)) || (out_blob_cap && !out_blob)) return arg_error(who, "null pointer");
-  if (n == 0) { out_off[0] = 0; *out_blob_need = 0; return 0; }
-  if (!rising(off, n)) return arg_error(who, "offset array is not non-decreasing");
-  const uint64_t base0 = off[0], total = off[n] - base0;
-  if (total > ZKE_UTF8_LOSSY_MAX_BYTES) return arg_error(who, "more than ZKE_UTF8_LOSSY_MAX_BYTES bytes of strings (the repaired offsets are 32-bit)");
-  if (total && !blob) return arg_error(who, "null pointer");
-  std::shared_lock<std::shared_mutex> sh(e->big);
-  HIPCHK(e, hipSetDevice(e->device));
-  uint32_t slot;
-  Slot& w = next_slot(e, slot);
-  std::lock_guard<std::mutex> g(w.mu);
-  Utf8Bufs& b = w.ub;
-  const uint64_t dev_cap = std::min<uint64_t>(out_blob_cap, 3 * total);
-  int r = 0;
-  if ((r = b.in.ensure((size_t)total + 16)) || (r = b.off.ensure((size_t)(n + 1) * 8)) || (r = b.out_off.ensure((size_t)(n + 1) * 4)) ||
-      (r = b.out.ensure((size_t)dev_cap + 16)) || (r = b.flags.ensure(n)))
-    return fail(e, r, "zke_utf8_lossy_batch: allocation");
-  hipStream_t s = w.stream;
-  SlotUse use(e, w, s);
-  if ((r = use.acquire())) return r;
-  auto enqueue = [&]() -> int {
-    if (total) HIPCHK(e, hipMemcpyAsync(b.in.p, blob + base0, (size_t)total, hipMemcpyHostToDevice, s));
-    HIPCHK(e, hipMemcpyAsync(b.off.p, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));      // (as given: the kernels subtract off[0])
-    const Utf8LossyArgs ua{n, b.in.as<uint8_t>(), b.off.as<uint64_t>(), b.out_off.as<uint32_t>(), b.out.as<uint8_t>(), dev_cap, b.flags.as<uint8_t>()};
-    const dim3 grid(std::min<uint32_t>(n, 1u << 16));
-    hipLaunchKernelGGL(utf8_lossy_len_kernel, grid, dim3(64), 0, s, ua);
-    hipLaunchKernelGGL(utf8_lossy_scan_kernel, dim3(1), dim3(1024), 0, s, ua);
-    hipLaunchKernelGGL(utf8_lossy_write_kernel, grid, dim3(64), 0, s, ua);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(out_off, b.out_off.p, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipMemcpyAsync(flags, b.flags.p, n, hipMemcpyDeviceToHost, s));
-    return use.release();
-  };
-  r = enqueue();
-  hipError_t hs = hipStreamSynchronize(s);      // also behind a failed enqueue: no copy outlives the caller's buffers
-  if (r) return r;
-  if (hs != hipSuccess) return fail(e, ZKE_E_DEVICE, "zke_utf8_lossy_batch: sync", hs);
-  const size_t need = out_off[n];
-  *out_blob_need = need;
-  if (need > out_blob_cap) return fail(e, ZKE_E_NOMEM, "zke_utf8_lossy_batch: out_blob is smaller than the repaired strings (*out_blob_need)");
-  if (need) {
-    HIPCHK(e, hipMemcpyAsync(out_blob, b.out.p, need, hipMemcpyDeviceToHost, s));
-    HIPCHK(e, hipStreamSynchronize(s));
-  }
-  return 0;
-}
-
 }  // extern "C"

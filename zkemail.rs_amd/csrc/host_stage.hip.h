@@ -71,6 +71,7 @@ __attribute__((target("avx2"))) inline void stream_copy_avx2(uint8_t* dst, const
 }
 inline void stage_copy(void* dst, const void* src, size_t n, size_t stream_from = 64u << 10) {
   static const bool avx2 = __builtin_cpu_supports("avx2");
+  if (!n) return;          // (an empty table may have no address at all: nothing for memcpy to be handed)
   if (avx2 && n >= stream_from) stream_copy_avx2((uint8_t*)dst, (const uint8_t*)src, n);
   else memcpy(dst, src, n);
 }
@@ -419,6 +420,76 @@ inline EncImage enc_image(uint32_t n, uint32_t ext_strs, uint32_t ext_bytes) {
   L.ext_blob = align_up(L.ext_str_off + (ext_strs ? (size_t)ext_strs + 1 : 0) * 4, 64);
   L.total = align_up(L.ext_blob + ext_bytes, 64);
   return L;
+}
+
+// ---- The plan sections of a batch's image: tables built on the host that ride behind ImageLayout::mixed, one behind the other — a
+// mixed batch's plan, a mixed extraction's tables, an encoding's jobs and external inputs (which start 64-byte aligned: a blob lies
+// in them).  A section is a layout (mixed_image, capmix_image, enc_image), a stage_* that copies the plan's arrays to their places
+// from the section's base in the pinned image, and a *_view that names the same places from its base in HBM: a section's offsets are
+// used by those two and nobody else.  Plain C++ like the layouts: no HIP call, no engine.  A section that is not there has no bytes.
+struct PlanSections {
+  MixedImage mixed{}; CapMixedImage capmix{}; EncImage enc{};
+  size_t capmix_at = 0, enc_at = 0, total = 0;      // mixed lies at 0; offsets from ImageLayout::mixed
+};
+inline PlanSections plan_sections(const MixedImage& mixed, const CapMixedImage& capmix, const EncImage& enc) {
+  PlanSections S{mixed, capmix, enc};
+  S.capmix_at = mixed.total;
+  S.enc_at = align_up(S.capmix_at + capmix.total, 64);
+  S.total = S.enc_at + enc.total;
+  return S;
+}
+
+// The plan of a mixed batch and where its tables lie in the slot's staged image (device pointers).
+struct MixedLaunch {
+  const MixedPlan* plan;
+  const uint32_t* job_off; const uint32_t* email_cfg; const uint32_t* perm; const MixedSeg* segs;
+};
+inline void stage_mixed(uint8_t* base, const MixedImage& L, const MixedPlan& P) {
+  stage_copy(base + L.job_off, P.job_off.data(), P.job_off.size() * 4);
+  stage_copy(base + L.email_cfg, P.email_cfg.data(), P.email_cfg.size() * 4);
+  stage_copy(base + L.perm, P.perm.data(), P.perm.size() * 4);
+  stage_copy(base + L.segs, P.segs.data(), P.segs.size() * sizeof(MixedSeg));
+}
+inline MixedLaunch mixed_view(const uint8_t* base, const MixedImage& L, const MixedPlan* plan) {
+  return MixedLaunch{plan, reinterpret_cast<const uint32_t*>(base + L.job_off), reinterpret_cast<const uint32_t*>(base + L.email_cfg),
+                     reinterpret_cast<const uint32_t*>(base + L.perm), reinterpret_cast<const MixedSeg*>(base + L.segs)};
+}
+
+// The shape of a mixed extraction and where its tables lie in the slot's staged image (device pointers).
+struct CapMixedLaunch {
+  uint32_t J, Gt;
+  bool needs_work;              // some part of some config keeps its rows in the slot's workspace: the grid is bounded by CAP_WORK_WAVES
+  bool origin;                  // the origin launch runs (org is wanted and some body part asks for a group)
+  CapMixedTables t;
+};
+// `part`: the config-major part table as the registry resolved it (the plan's shape.n_parts entries)
+inline void stage_capmix(uint8_t* base, const CapMixedImage& L, const CapMixedPlan& P, const std::vector<CapPartDev>& part) {
+  stage_copy(base + L.col_off, P.col_off.data(), P.col_off.size() * 4);
+  stage_copy(base + L.cap_cfg, P.cap_cfg.data(), P.cap_cfg.size() * 4);
+  stage_copy(base + L.cfgs, P.cfgs.data(), P.cfgs.size() * sizeof(CapMixedCfg));
+  stage_copy(base + L.parts, part.data(), part.size() * sizeof(CapPartDev));
+}
+// job_off: the mixed plan's, in its own section (mixed_view)
+inline CapMixedTables capmix_view(const uint8_t* base, const CapMixedImage& L, const uint32_t* job_off) {
+  return CapMixedTables{job_off, reinterpret_cast<const uint32_t*>(base + L.col_off), reinterpret_cast<const uint32_t*>(base + L.cap_cfg),
+                        reinterpret_cast<const CapMixedCfg*>(base + L.cfgs), reinterpret_cast<const CapPartDev*>(base + L.parts)};
+}
+
+// An encoding's section.  A host plan stages its jobs; a device plan (zke_extract_captures_encoded) has none yet, and ext_off[n + 1]
+// rides in their place when there are external inputs at all.  The external-input table is the caller's either way.
+inline void stage_enc(uint8_t* base, const EncImage& L, const EncodePlan& P, bool device_plan, const uint32_t* ext_off, uint32_t n,
+                      const uint32_t* ext_str_off, const uint8_t* ext_blob) {
+  if (!device_plan) stage_copy(base + L.jobs, P.jobs.data(), P.jobs.size() * sizeof(EncodeJob));
+  else if (P.ext_strs) stage_copy(base + L.jobs, ext_off, ((size_t)n + 1) * 4);
+  if (P.ext_strs) stage_copy(base + L.ext_str_off, ext_str_off, ((size_t)P.ext_strs + 1) * 4);
+  if (P.ext_bytes) stage_copy(base + L.ext_blob, ext_blob, P.ext_bytes);
+}
+// The input half of the encode launch's arguments that the section holds (a device plan: `jobs` points to ext_off, see above).
+inline EncodeArgs enc_view(const uint8_t* base, const EncImage& L) {
+  EncodeArgs a{};
+  a.jobs = reinterpret_cast<const EncodeJob*>(base + L.jobs);
+  a.ext_str_off = reinterpret_cast<const uint32_t*>(base + L.ext_str_off); a.ext_blob = base + L.ext_blob;
+  return a;
 }
 
 // The buffers of zke_qp_clean_batch (a slot's): the bodies and their offsets, cleaned bytes, index map, kept lengths.

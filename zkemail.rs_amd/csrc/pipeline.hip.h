@@ -48,6 +48,17 @@ int ensure_workspace(zke_engine* e, Slot& w, uint32_t n, uint64_t raw_total, boo
   return 0;
 }
 
+// The DFA pair `id` as the registry holds it, copied out (the caller holds reg_mu; the entry itself stays put until the engine is idle).
+PartInfo part_info(const zke_engine* e, uint32_t id) {
+  PartInfo pi{};
+  const RegisteredDfa* rd = id < e->dfas.size() ? e->dfas[id] : nullptr;
+  if (rd) {
+    pi.detail = rd->detail; pi.lds_bytes = rd->lds_bytes; pi.idle = rd->idle;
+    pi.dev = rd->valid ? rd->dev.as<RegexDev>() : nullptr;
+  }
+  return pi;
+}
+
 int arg_error(const char* who, const char* what);      // (these three: host_entry.hip.h, behind this file)
 int check_batch_pointers(const zke_batch* in, const void* out, bool host, const char* who);
 int ensure_host_buffers(zke_engine* e, Slot& w, size_t image_bytes, uint32_t n);
@@ -65,13 +76,17 @@ struct CaptureReq {
   zke_capture_origin* org = nullptr;     // zke_extract_captures_mapped: the spans' origins before the QP filter are wanted too
   bool origin_launch() const { return org && G > gbase[n_header_parts]; }      // some body part asks for a group
   // zke_extract_captures_encoded: the gather launch is capture_gather_lossy_kernel (capture_lossy.hip.h) — repaired strings and the
-  // encode plan.  `out` may then be null (nobody wants the tables); blob_cap is the device blob's capacity, and submit_host fills in
-  // the device pointers once the slot's buffers exist.
+  // encode plan.  `out` may then be null (nobody wants the tables); lossy_blob_cap is the device blob's capacity.
   bool lossy = false;
   size_t lossy_blob_cap = 0;
-  uint64_t lossy_bytes_cap = 0;
-  const uint32_t* lossy_ext_off = nullptr; const uint32_t* lossy_ext_str_off = nullptr; EncodeJob* lossy_jobs = nullptr;
   size_t dev_blob_cap() const { return lossy ? lossy_blob_cap : out->cap_blob_cap; }
+};
+// Where the lossy gather launch of a request finds things in the slot (device pointers): the external inputs it reads from the staged
+// image (ext_off: nullptr without external inputs), where the jobs it plans go, the capacity of the encodings behind them.
+struct LossyLaunch {
+  const uint32_t* ext_off; const uint32_t* ext_str_off;
+  EncodeJob* jobs;
+  uint64_t bytes_cap;
 };
 constexpr uint32_t CAP_WORK_WAVES = 256;      // waves of a capture launch whose rows live in the slot's workspace (one slice each)
 
@@ -85,6 +100,39 @@ int ensure_side_buffers(zke_engine* e, TwinBuf& t, size_t device_bytes, size_t p
 // (b.L is the caller's to set: zke_engine_reserve grows a slot's capture buffers without touching the layout of a pending extraction)
 int ensure_capture_buffers(zke_engine* e, CapBufs& b, const CapLayout& L, bool work) {
   return ensure_side_buffers(e, b.t, L.total, L.fixed_end, work ? &b.work : nullptr, (size_t)CAP_WORK_WAVES * CAP_WORK_WORDS * 8, "capture workspace allocation");
+}
+
+// A slot's buffers for one side output of a batch of n: the layout, then the buffers it asks for (ensure_side_buffers).
+// `pack`: zke_select_keys_from_records, the decoded keys are packed for the front end.
+int ensure_keyrec_buffers(zke_engine* e, KeyrecBufs& b, uint32_t m, size_t rec_total, bool pack) {
+  b.L = keyrec_layout(m, rec_total);
+  return ensure_side_buffers(e, b.t, b.L.total, b.L.total, pack ? &b.pack : nullptr, b.L.p_total, "key-record buffer allocation");
+}
+int ensure_body_buffers(zke_engine* e, BodyBufs& b, uint32_t n, size_t raw_total) {
+  b.L = body_layout(n, raw_total);
+  return ensure_side_buffers(e, b.t, b.L.total, b.L.total, &b.ovf, (size_t)n * HDR_OVF_BYTES, "body-extraction buffer allocation");
+}
+// `staged`: bytes of the building block's input (zke_encode_outputs), 0 where the batch's image carries it
+int ensure_encode_buffers(zke_engine* e, EncBufs& b, uint32_t n, uint64_t blob, size_t staged) {
+  b.L = enc_layout(n, blob);
+  return ensure_side_buffers(e, b.t, b.L.total, b.L.prefix, staged ? &b.in : nullptr, staged, "output-encoding buffer allocation");
+}
+// a device-planned encoding: `cap` bytes of encodings, the jobs behind them, the infos alone pinned
+int ensure_encode_buffers_planned(zke_engine* e, EncBufs& b, uint32_t n, uint64_t cap) {
+  b.L = enc_layout_planned(n, cap, b.jobs_at);
+  return ensure_side_buffers(e, b.t, b.L.total, b.L.bytes, nullptr, 0, "output-encoding buffer allocation");
+}
+// max_sigs record slots per e-mail and the caller's sel_blob_cap bytes of selectors (a selector is at most ZKE_MAX_TAGBUF bytes: a
+// larger blob than that per record slot is never used)
+int ensure_scan_buffers(zke_engine* e, ScanBufs& b, uint32_t n, uint32_t max_sigs, size_t sel_blob_cap) {
+  b.L = scan_layout(n, max_sigs, std::min<size_t>(sel_blob_cap, (size_t)n * max_sigs * ZKE_MAX_TAGBUF));
+  return ensure_side_buffers(e, b.t, b.L.total, b.L.total, &b.ovf, (size_t)n * HDR_OVF_BYTES, "signature-scan buffer allocation");
+}
+// `launched`: capture_origin_kernel runs for this batch; where it does not, nothing is allocated
+int ensure_origin_buffers(zke_engine* e, OriginBufs& b, size_t NG, bool launched) {
+  b.L = origin_layout_sized(NG);
+  b.launched = launched;
+  return b.launched ? ensure_side_buffers(e, b.t, b.L.total, b.L.total, nullptr, 0, "capture-origin buffer allocation") : 0;
 }
 
 // Part p of a request: the requested groups (no registry involved: the sizes of the output follow from these alone) ...
@@ -121,7 +169,8 @@ void capture_resolve(zke_engine* e, CaptureReq& q) {
 
 // The two launches of an extraction: the walk per (e-mail, part), then verdict + tables.  `parts`: the PartRes the search left.
 int launch_capture(zke_engine* e, CapBufs& b, const CaptureReq& q, uint32_t n, bool plain, const DfaArgs& base,
-                   const uint8_t* hay_blob, const uint64_t* hay_off, const PartRes* parts, zke_result* results, hipStream_t s) {
+                   const uint8_t* hay_blob, const uint64_t* hay_off, const PartRes* parts, zke_result* results, hipStream_t s,
+                   const LossyLaunch* lossy = nullptr) {
   const CapLayout& L = b.L;
   uint8_t* cb = b.t.d.as<uint8_t>();
   CapArgs ca{};
@@ -141,7 +190,7 @@ int launch_capture(zke_engine* e, CapBufs& b, const CaptureReq& q, uint32_t n, b
   ga.tmp = reinterpret_cast<uint32_t*>(cb + L.tmp);
   for (uint32_t p = 0; p <= q.P; p++) ga.gbase[p] = q.gbase[p];
   if (q.lossy) {
-    const CapLossyArgs la{ga, ca.flags, q.lossy_ext_off, q.lossy_ext_str_off, q.lossy_jobs, q.lossy_bytes_cap};
+    const CapLossyArgs la{ga, ca.flags, lossy->ext_off, lossy->ext_str_off, lossy->jobs, lossy->bytes_cap};
     hipLaunchKernelGGL(capture_gather_lossy_kernel, dim3(1), dim3(1024), 0, s, la);
   } else {
     hipLaunchKernelGGL(capture_gather_kernel, dim3(1), dim3(1024), 0, s, ga);
@@ -236,12 +285,19 @@ int launch_encode(zke_engine* e, EncBufs& b, EncodeArgs a, hipStream_t s, bool p
   return launch_sha(e, plan_sha(e->stage, a.n), a.sha, a.n, s);
 }
 
+// The canonicalize_signed_email pass's view of a batch whose verify pass sees B: the slot's second meta and scratch, the verify pass's
+// meta to compare with, no length buckets.
+BatchDev canon_pass_view(const Slot& w, const BatchDev& B) {
+  BatchDev B2 = B;
+  B2.meta = w.meta2.as<EmailMeta>();
+  B2.scratch = w.scratch2.as<uint8_t>();
+  B2.meta_verify = B.meta;
+  B2.order = nullptr;
+  return B2;
+}
+
 // ---- the regex stage of a mixed batch (zke_verify_emails_mixed; kernels: regex_mixed.hip.h, plan: mixed_plan.hip.h)
-// The plan of the batch and where its tables lie in the slot's staged image (device pointers).
-struct MixedLaunch {
-  const MixedPlan* plan;
-  const uint32_t* job_off; const uint32_t* email_cfg; const uint32_t* perm; const MixedSeg* segs;
-};
+// (MixedLaunch, the plan of the batch and where its tables lie in the slot's staged image: host_stage.hip.h)
 // Behind the verify launches: the preparation (e-mails without a config left out), ONE lane-mapped and ONE wave-mapped DFA launch
 // over the plan's segments, the fold.  B: the verify pass's view of the batch; `in`: its capture tables (indexed by job).
 // base_out: the launches' common DfaArgs, for the capture launches of a mixed extraction behind this stage.
@@ -249,11 +305,7 @@ int run_mixed_regex_stage(zke_engine* e, Slot& w, const BatchDev& B, const zke_b
                           bool want_clean, StageTimer& tm, hipStream_t s, DfaArgs* base_out = nullptr) {
   const MixedPlan& P = *mx.plan;
   const uint32_t n = B.n;
-  BatchDev B2 = B;
-  B2.meta = w.meta2.as<EmailMeta>();
-  B2.scratch = w.scratch2.as<uint8_t>();
-  B2.meta_verify = B.meta;
-  B2.order = nullptr;
+  const BatchDev B2 = canon_pass_view(w, B);
   // want_clean stays what a parity buffer asks for: whether a config has body parts is decided per e-mail (email_cfg)
   PrepMixedArgs pr{PrepArgs{ParseArgs{B2, 0, 1, 0, e->strict, now, nullptr, 0, nullptr, nullptr},
                             QpArgs{B2, B.meta, w.clean.as<uint8_t>(), clean_off, B.scratch, B.scratch_off}, want_clean ? 1u : 0u},
@@ -284,13 +336,7 @@ int run_mixed_regex_stage(zke_engine* e, Slot& w, const BatchDev& B, const zke_b
 }
 
 // ---- capture extraction behind the mixed regex stage (zke_extract_captures_mixed; kernels: capture_mixed.hip.h)
-// The shape of the extraction and where its tables lie in the slot's staged image (device pointers).
-struct CapMixedLaunch {
-  uint32_t J, Gt;
-  bool needs_work;              // some part of some config keeps its rows in the slot's workspace: the grid is bounded by CAP_WORK_WAVES
-  bool origin;                  // the origin launch runs (org is wanted and some body part asks for a group)
-  CapMixedTables t;
-};
+// (CapMixedLaunch, the shape of the extraction and where its tables lie in the slot's staged image: host_stage.hip.h)
 // The walk per job, then verdict + tables, as launch_capture; b.L is laid out for J jobs and Gt columns.
 int launch_capture_mixed(zke_engine* e, CapBufs& b, const CapMixedLaunch& cm, uint32_t n, const DfaArgs& base, const PartRes* parts,
                          zke_result* results, hipStream_t s) {
@@ -330,7 +376,7 @@ int launch_capture_origin_mixed(zke_engine* e, const CapBufs& b, OriginBufs& ob,
 // Caller holds the slot's lock; everything the call needs is in its arguments or in the slot.
 int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t raw_total, uint64_t key_total, zke_result* out_dev,
                         hipStream_t s, bool want_em, uint64_t now, bool want_clean = false, const CaptureReq* cap = nullptr,
-                        const MixedLaunch* mixed = nullptr, const CapMixedLaunch* capmix = nullptr) {
+                        const MixedLaunch* mixed = nullptr, const CapMixedLaunch* capmix = nullptr, const LossyLaunch* lossy = nullptr) {
   const uint32_t n = in->n;
   if (n == 0) return 0;
   const uint32_t n_pad = (n + 63) & ~63u;
@@ -410,25 +456,13 @@ int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t ra
     if (P > 16) { parts_big.resize(P); parts = parts_big.data(); }
     {
       std::shared_lock<std::shared_mutex> rl(e->reg_mu);
-      for (uint32_t p = 0; p < P; p++) {
-        const uint32_t id = p >= in->n_header_parts ? in->body_part_ids[p - in->n_header_parts] : in->header_part_ids[p];
-        PartInfo pi{};
-        const RegisteredDfa* rd = id < e->dfas.size() ? e->dfas[id] : nullptr;
-        if (rd) {
-          pi.detail = rd->detail; pi.lds_bytes = rd->lds_bytes; pi.idle = rd->idle;
-          pi.dev = rd->valid ? rd->dev.as<RegexDev>() : nullptr;
-        }
-        parts[p] = pi;
-      }
+      for (uint32_t p = 0; p < P; p++)
+        parts[p] = part_info(e, p >= in->n_header_parts ? in->body_part_ids[p - in->n_header_parts] : in->header_part_ids[p]);
     }
     // canonicalize_signed_email (circuits.rs:34-35: first DKIM-Signature header, own scratch unless it is the verified one) and
     // remove_quoted_printable_soft_breaks (circuits.rs:37), one launch (regex.hip.h, regex_prep_kernel).  The cleaned body is
     // unobservable without body parts (circuits.rs:48-56): it is then only produced when a parity buffer asks for it.
-    BatchDev B2 = B;
-    B2.meta = w.meta2.as<EmailMeta>();
-    B2.scratch = w.scratch2.as<uint8_t>();
-    B2.meta_verify = B.meta;
-    B2.order = nullptr;
+    const BatchDev B2 = canon_pass_view(w, B);
     PrepArgs pr{ParseArgs{B2, 0, 1, 0, e->strict, now, nullptr, 0, nullptr, nullptr},
                 QpArgs{B2, B.meta, w.clean.as<uint8_t>(), clean_off, B.scratch, B.scratch_off},
                 (in->n_body_parts || want_clean) ? 1u : 0u};
@@ -484,7 +518,7 @@ int run_device_pipeline(zke_engine* e, Slot& w, const zke_batch* in, uint64_t ra
     }
     // capture extraction (zke_extract_captures): two more launches behind the regex verdict, in the slot's capture buffer
     if (cap)
-      if ((r = launch_capture(e, w.cb, *cap, n, false, base, nullptr, nullptr, w.parts.as<PartRes>(), out_dev, s))) return r;
+      if ((r = launch_capture(e, w.cb, *cap, n, false, base, nullptr, nullptr, w.parts.as<PartRes>(), out_dev, s, lossy))) return r;
     if (cap && cap->origin_launch())
       if ((r = launch_capture_origin(e, w.cb, w.ob, *cap, n, base, out_dev, s))) return r;
     tm.mark(MK_DFA);
