@@ -327,6 +327,11 @@ __device__ __forceinline__ void canon_body_wave(const BatchDev& B, uint32_t i, u
 }
 
 // ---- verdict of one signature round, by the wave that ran the e-mail's RSA job -----------------------
+#ifndef ZKE_VERDICT_ONE_TRIP
+#define ZKE_VERDICT_ONE_TRIP 1   // the verdict launch (verdict.hip.h, ed_verdict_kernel): its first verdicts from loads requested at kernel entry,
+                                 // the Ed25519 stage and the later signature rounds behind one call that RSA waves never make, base64 without
+                                 // branches (verdict_lane); 0: the loop as the kernel's body, the verdict behind a call of its own
+#endif
 struct FinArgs { BatchDev b; uint32_t round, max_rounds; uint32_t* pending; uint32_t debug_skip_rsa; };   // debug_skip_rsa: ablation experiments only
 
 // Everything the verdict of e-mail i is decided from, fetched by its lane in ONE go: the e-mail's EmailMeta as 16-byte loads, the
@@ -394,9 +399,17 @@ __device__ __forceinline__ bool verdict_lane(const FinArgs& A, uint32_t round, E
       const bool sha1 = (flags & ZKE_F_SHA1) != 0;
       const uint32_t hl = sha1 ? 20u : 32u, nch = sha1 ? 28u : 44u;
       bool bad = V.m[ZKE_MW(bh_len)] != nch;
+#if ZKE_VERDICT_ONE_TRIP
+      // the alphabet's five runs as steps added to 'A' + six, no branch: as a chain of conditions each character compiled to some
+      // 45 instructions around four branches, two thousand of them in a launch that decides one status per e-mail
+      auto b64c = [](uint32_t six) -> uint32_t {
+        return 'A' + six + (six >= 26 ? 6u : 0u) - (six >= 52 ? 75u : 0u) - (six >= 62 ? 15u : 0u) + (six >= 63 ? 3u : 0u);
+      };
+#else
       auto b64c = [](uint32_t six) -> uint32_t {
         return six < 26 ? 'A' + six : (six < 52 ? 'a' + (six - 26) : (six < 62 ? '0' + (six - 52) : (six == 62 ? '+' : '/')));
       };
+#endif
       auto hbyte = [&](uint32_t j) -> uint32_t { return (V.hash[j >> 2] >> (8 * (j & 3))) & 0xFFu; };      // j: a constant, once unrolled
 #pragma unroll
       for (uint32_t g = 0; g < 11; g++) {

@@ -105,27 +105,12 @@ __device__ __noinline__ bool verdict_round(const EdVerdictArgs& A, uint32_t roun
 #endif
 constexpr uint32_t VERDICT_EMAILS_PER_WAVE = 16;      // a DPP quad per e-mail in the Ed25519 stage
 
-// One wave: the Ed25519 stage and the verdicts of 16 e-mails, then — for the rare e-mail whose candidate signature failed
-// while another same-domain signature is untried — the next signature round of those e-mails right here: cfdkim's
-// verify_email_with_key tries the candidates one after the other until one passes (behind core/src/email.rs:31-33).
-// Round 0 of every e-mail runs in the batch's three launches; giving the later rounds launches of their own would charge
-// every batch for them, here they cost a ballot per wave.  The loop body is the round: Ed25519 stage (a quad per e-mail),
-// verdict (a lane per e-mail), and for the e-mails still pending the next round's front end, hashes and RSA by the
-// whole wave, one e-mail after the other.
-__global__ __launch_bounds__(64, ZKE_VERDICT_WAVES) void ed_verdict_kernel(EdVerdictArgs A) {
+// The rounds of one wave from signature round `round` on, for the e-mails base + (bits of active).  The loop body is the round:
+// Ed25519 stage (a quad per e-mail), verdict (a lane per e-mail), and for the e-mails still pending the next round's front end,
+// hashes and RSA by the whole wave, one e-mail after the other.
+__device__ __forceinline__ void verdict_rounds(const EdVerdictArgs& A, uint32_t round, uint64_t active, uint32_t base) {
   const BatchDev& B = A.fin.b;
   const int lane = threadIdx.x & 63;
-  const uint32_t base = blockIdx.x * VERDICT_EMAILS_PER_WAVE;
-  if (blockIdx.x == 0 && lane == 0 && A.wave_count) {
-    if (A.wave_feedback) __hip_atomic_store(A.wave_feedback, *A.wave_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    *A.wave_count = 0;
-  }
-  if (blockIdx.x == 0 && B.order)              // the hash stage has consumed the length buckets: counters back to zero for the slot's next batch
-    for (uint32_t k = 0; k < 2; k++)
-      for (uint32_t c = (uint32_t)lane; c < SHA_CLASSES; c += 64) B.order[sha_order_cnt(k) + c] = 0;
-  uint32_t round = A.fin.round;
-  uint64_t active = 0;                                  // verdict lanes (= e-mails base + lane) this wave still works on
-  for (uint32_t j = 0; j < VERDICT_EMAILS_PER_WAVE; j++) if (base + j < B.n) active |= 1ull << j;
   for (;;) {
     // ---- Ed25519 stage, four lanes per e-mail (quad j = e-mail base + j): the curve-point check of every 32-byte key in
     // round 0 (DkimPublicKey::try_from_bytes, core/src/email.rs:28-29), the verification of a=ed25519-sha256 candidates
@@ -180,6 +165,92 @@ __global__ __launch_bounds__(64, ZKE_VERDICT_WAVES) void ed_verdict_kernel(EdVer
     next_round(A, round, active, base);
     wave_publish();
   }
+}
+
+#if ZKE_VERDICT_ONE_TRIP
+// The one call of the launch, made by the waves that RSA batches do not have: one with Ed25519 work (from_next = false: the whole of
+// round `round`, every load again) or with e-mails left pending (from_next = true).  A: the kernel's argument where the dispatch
+// packet put it (verdict_args_in_place), not a copy: a by-value kernel argument whose address leaves the kernel is copied to
+// scratch at kernel entry, by every wave, and the callee is compiled for the kernel's whole register budget either way.
+__device__ __noinline__ void verdict_rounds_call(const EdVerdictArgs& A, uint32_t round, uint64_t active, uint32_t base, bool from_next) {
+  if (from_next) {
+    round++;
+    next_round(A, round, active, base);
+    wave_publish();
+  }
+  verdict_rounds(A, round, active, base);
+}
+// ed_verdict_kernel's one argument in the kernel-argument segment: explicit arguments start at offset 0 of it
+__device__ __forceinline__ const EdVerdictArgs& verdict_args_in_place() {
+  return *(const EdVerdictArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+}
+#endif
+
+// One wave: the Ed25519 stage and the verdicts of 16 e-mails, then — for the rare e-mail whose candidate signature failed
+// while another same-domain signature is untried — the next signature round of those e-mails right here: cfdkim's
+// verify_email_with_key tries the candidates one after the other until one passes (behind core/src/email.rs:31-33).
+// Round 0 of every e-mail runs in the batch's three launches; giving the later rounds launches of their own would charge
+// every batch for them, here they cost a ballot per wave (verdict_rounds).
+//
+// ZKE_VERDICT_ONE_TRIP: a wave of an RSA batch has no Ed25519 work and, almost always, no e-mail left pending.  What it does is
+// one trip to memory and back: every load its 16 verdicts need — the key type, EmailMeta, the two hashes and the ext flag, by the
+// e-mail's verdict lane (verdict_load) — is requested at kernel entry before anything waits; workgroup 0's resets are issued behind
+// them.  The words a quad would decide its Ed25519 work by (key type, key_ok, state, flags) are among them, so the verdict lanes say
+// whether the wave has any: no second round of loads that waits for the first.
+// It has none: the verdicts are decided right here from what is in registers, without a call and without scratch (`mine` = 3: the
+// stage wrote nothing, so the copy of EmailMeta is current; ed_key_bad in it is round 0's).  It has some: the wave leaves for
+// verdict_rounds_call, which runs the stage and then loads EmailMeta AGAIN for its verdicts — the stage writes ed_key_bad and ed_ok,
+// and nothing of the copy fetched at entry is used behind it, those two fields included.  Later signature rounds load again, as ever.
+__global__ __launch_bounds__(64, ZKE_VERDICT_WAVES) void ed_verdict_kernel(EdVerdictArgs A) {
+  const BatchDev& B = A.fin.b;
+  const int lane = threadIdx.x & 63;
+  const uint32_t base = blockIdx.x * VERDICT_EMAILS_PER_WAVE;
+  const bool lead = blockIdx.x == 0 && lane == 0 && A.wave_count;
+#if ZKE_VERDICT_ONE_TRIP
+  // ---- every load of the wave, requested before anything waits: the job-list length (workgroup 0), key type and verdict inputs
+  const uint32_t round = A.fin.round;
+  uint32_t n_wave_jobs = 0;
+  if (lead) n_wave_jobs = *A.wave_count;
+  const bool vlane = lane < (int)VERDICT_EMAILS_PER_WAVE && base + (uint32_t)lane < B.n;      // verdict lane of e-mail base + lane
+  const uint32_t vi = base + (uint32_t)lane;
+  uint32_t key_type = 0;
+  VerdictIn V;
+  if (vlane) {
+    key_type = B.key_type[vi];
+    verdict_load(B.meta + vi, B.results + vi, B.ext_null ? B.ext_null + vi : nullptr, V);
+  }
+  if (lead) {
+    if (A.wave_feedback) __hip_atomic_store(A.wave_feedback, n_wave_jobs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    *A.wave_count = 0;
+  }
+#else
+  if (lead) {
+    if (A.wave_feedback) __hip_atomic_store(A.wave_feedback, *A.wave_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    *A.wave_count = 0;
+  }
+#endif
+  if (blockIdx.x == 0 && B.order)              // the hash stage has consumed the length buckets: counters back to zero for the slot's next batch
+    for (uint32_t k = 0; k < 2; k++)
+      for (uint32_t c = (uint32_t)lane; c < SHA_CLASSES; c += 64) B.order[sha_order_cnt(k) + c] = 0;
+  uint64_t active = 0;                                  // verdict lanes (= e-mails base + lane) this wave still works on
+  for (uint32_t j = 0; j < VERDICT_EMAILS_PER_WAVE; j++) if (base + j < B.n) active |= 1ull << j;
+#if ZKE_VERDICT_ONE_TRIP
+  // (the condition of the Ed25519 stage in verdict_rounds, taken by the e-mail's verdict lane from the words it has: whether ANY
+  // quad of the wave would have work is all that is asked here; the key itself is checked in round 0)
+  const bool work = vlane && !A.skip_ed && key_type == ZKE_KEY_ED25519 && V.m[ZKE_MW(key_ok)] == 2 &&
+                    (round == 0 || (V.m[ZKE_MW(state)] == ST_CAND && (V.m[ZKE_MW(flags)] & ZKE_F_ED25519)));
+  bool from_next = false;
+  if (!__ballot(work)) {
+    bool again = false;
+    if (vlane) again = verdict_lane(A.fin, round, B.meta + vi, B.results + vi, V, verdict_rsa_ok(V), false, V.m[ZKE_MW(ed_key_bad)] != 0);
+    active = __ballot(again);
+    if (!active) return;
+    from_next = true;
+  }
+  verdict_rounds_call(verdict_args_in_place(), round, active, base, from_next);
+#else
+  verdict_rounds(A, A.fin.round, active, base);
+#endif
 }
 
 }  // namespace zke
